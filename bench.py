@@ -2,6 +2,7 @@
 """Throughput of the EmotiVoice hot path (JETSGenerator.forward = acoustic model + HiFi-GAN) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--mode am_vocoder|ragged|vocoder|style|pipeline] [--precision mx|fast|strict]
+                    [--full] [--dump-outputs DIR]
         N > 1: one rank per GPU.  Started by a launcher (torch.distributed.run: WORLD_SIZE set) it is a rank and requires
         WORLD_SIZE == N; started bare it becomes the launcher itself (spawn_command) -- `python bench.py --gpus 8` runs 8 ranks.
 
@@ -17,8 +18,12 @@ One "step" = one pass of the rank's batch (all its sub-batches) with the inputs 
 sharded (weak scaling, per-GPU work fixed); the only collective is the start-up broadcast of the packed weight blob over RCCL.
 Precision (--precision): "mx" (default, the contract mode: waveform within 1e-3 of the reference on every fixture) = fp32-class activations,
 a product as one fp16 MFMA + two block-scaled fp4 MFMAs; "fast" = fp16 MFMA operands / activations (the precision BASELINE.json names, 2.4e-3
-on zero-mean audio); "strict" = split precision (three fp16 MFMAs per product, ~1e-6).  At N = 1 the other two precisions are timed as well
-and reported under "other_precision".  --mode pipeline times the host pipeline (text line -> int16 wav).  Prints ONE JSON line on rank 0.
+on zero-mean audio); "strict" = split precision (three fp16 MFMAs per product, ~1e-6).  --mode pipeline times the host pipeline (text line -> int16 wav).
+Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, ...).  --full adds everything that takes runs of its
+own: B = 1 latency, the profiled step (roofline, stage_ms, kernels_ms, --dump-launches), clock / power, at N = 1 the other two precisions
+("other_precision") and the CPU baseline (--mode style: single-text latency, CPU baseline and parity against the oracle).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all: see dump_outputs).
 """
 import argparse
 import json
@@ -211,8 +216,15 @@ class Workload:
     def step(self):
         frames = 0
         for c in self.calls:
-            frames += int(c().total_frames)
+            self.last = c()
+            frames += int(self.last.total_frames)
         return frames
+
+    def outputs(self):
+        """What the caller of the timed path receives from the last call of the last step (ev_result -> host arrays; for more than one
+        sub-batch per step that is the last sub-batch: they share the engine's output buffers)."""
+        out = self.eng.result_to_numpy(self.last)
+        return {k: out[k] for k in ("wav", "mel", "mel_lens", "durations", "log_durations", "pitch", "energy") if k in out}
 
 
 def power_sample(work, torch, seconds=2.5):
@@ -284,6 +296,32 @@ def b1_latency(eng, phonemes=(64, 256)):
                 # (a committed timing from ANOTHER machine -- the build container's 8 cores -- over this box's live GPU latency: named for what it is)
                 lat["b1_%dph_speedup_vs_build_container_reference" % nph] = round(r["ms_per_utterance"] / lat["b1_%dph_ms" % nph], 1)
     return lat
+
+
+DUMP_BYTES = 60 << 20        # --dump-outputs budget (under 64 MB with the .npy headers)
+DUMP_WHOLE_BYTES = 1 << 20   # arrays up to this size are always written whole
+
+
+def dump_outputs(outdir, arrays):
+    """Write arrays as <outdir>/<name>.npy: floating point as float32 (float64 stays), integers as float64 (exact).  When the arrays exceed
+    DUMP_BYTES, each one larger than DUMP_WHOLE_BYTES is replaced by a fixed sample of its flattened elements (seed 0, sorted positions,
+    the same count for the same size) so that two builds given the same arguments write comparable files."""
+    conv = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        conv[k] = v.astype(np.float64 if v.dtype == np.float64 or not np.issubdtype(v.dtype, np.floating) else np.float32)
+    total = sum(v.nbytes for v in conv.values())
+    if total > DUMP_BYTES:
+        small = sum(v.nbytes for v in conv.values() if v.nbytes <= DUMP_WHOLE_BYTES)
+        keep = (DUMP_BYTES - small) / float(total - small)
+        for k, v in conv.items():
+            if v.nbytes > DUMP_WHOLE_BYTES:
+                n = int(v.size * keep)
+                idx = np.sort(np.random.default_rng(0).choice(v.size, n, replace=False))
+                conv[k] = v.ravel()[idx]
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in conv.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
 
 
 def timed(work, steps, warmup, sync):
@@ -422,16 +460,20 @@ def bench_style(args, torch):
     for _ in range(args.steps):
         out = eng.style_embed(ids)
     dt = time.perf_counter() - t0
-    one = [ids[0]]
-    best = 1e9
-    for _ in range(10):
-        t1 = time.perf_counter(); eng.style_embed(one); best = min(best, time.perf_counter() - t1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out})
     line = {"metric": "style_embeddings_per_sec", "value": round(nb * args.steps / dt, 1), "unit": "texts/s", "n_gpus": 1, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16x3 (split precision, fp32-class)", "data": "synthetic",
+            "dtype": "f16x3 (split precision, fp32-class)", "data": "synthetic", "full": args.full,
             "config": {"workload": "SimBERT (BERT-base 12 x 768) pooled_output of %d texts x 64 tokens per step, host ids in / host embeddings out" % nb},
-            "latency": {"one_text_64_tokens_ms": round(best * 1e3, 3)}, "roofline": None}
-    if args.cpu_utts > 0:
+            "latency": None, "roofline": None}
+    if args.full:
+        one = [ids[0]]
+        best = 1e9
+        for _ in range(10):
+            t1 = time.perf_counter(); eng.style_embed(one); best = min(best, time.perf_counter() - t1)
+        line["latency"] = {"one_text_64_tokens_ms": round(best * 1e3, 3)}
+    if args.full and args.cpu_utts > 0:
         from oracle.bert_oracle import bert_pooled_output
         torch.set_num_threads(min(os.cpu_count() or 1, 16))
         bert_pooled_output(sd, ids[0])
@@ -511,10 +553,12 @@ def bench_pipeline(args, torch):
         pool.close()
     os.unlink(vpath)
     assert wav.size == int(res.total_samples) and np.abs(wav).max() > 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"wav_i16": wav, "mel_lens": np.array([res.mel_lens[b] for b in range(res.batch)], np.int32)})
     print(json.dumps({
         "metric": "host_pipeline_utterances_per_sec", "value": round(utts / dt, 1), "unit": "utterances/s", "mel_frames_per_sec": round(frames / dt, 1),
         "x_realtime": round(frames / dt * 256 / 16000, 1), "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "data": "synthetic", "precision": args.precision,
+        "higher_is_better": True, "data": "synthetic", "precision": args.precision, "full": args.full,
         "config": {"workload": "text line -> int16 wav on the host, B = %d lines of 14 words (~%d phonemes) per step, one process" % (nb, int(np.mean([len(x) for x in ling]))),
                    "frontend_workers": args.frontend_workers},
         "host_ms_per_step": {k: round(v / args.steps * 1e3, 3) for k, v in parts.items()},
@@ -564,9 +608,14 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="utterances per GPU per (sub-)batch (default: 32 / 256 / 128 by mode)")
     ap.add_argument("--sub-batches", type=int, default=0, help="am_vocoder: sub-batches per step (default 1 at N = 1, 8 at N > 1 = configs[3])")
     ap.add_argument("--phonemes", type=int, default=256)
-    ap.add_argument("--cpu-utts", type=int, default=12, help="utterances for the CPU baseline sample (0 = skip); 12 x 256 phonemes = 12-15 s of host work on 16 threads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: B = 1 latency, the profiled step (roofline, stage / kernel times), clock / power, "
+                         "the other precisions (N = 1) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; rank 0)")
+    ap.add_argument("--cpu-utts", type=int, default=12, help="--full: utterances for the CPU baseline sample (0 = skip); 12 x 256 phonemes = 12-15 s of host work on 16 threads")
     ap.add_argument("--cpu-threads", type=int, default=16, help="torch threads of the CPU baseline (more are slower on the 2 x 64-core box)")
-    ap.add_argument("--dump-launches", default=None, help="write the per-launch table of the profiled step to this path (+ .<mode> for the other precisions)")
+    ap.add_argument("--dump-launches", default=None, help="--full: write the per-launch table of the profiled step to this path (+ .<mode> for the other precisions)")
     ap.add_argument("--chunk-mb", type=int, default=0, help="ev_config.vocoder_chunk_mb (tuning; 0 = whole tensors)")
     ap.add_argument("--voc-streams", type=int, default=0, help="ev_config.vocoder_streams (tuning; 0 = engine default)")
     ap.add_argument("--mx-residual", default="planes", choices=["planes", "fp32"], help="ev_config.mx_residual (A/B: round 3's fp32 residual stream)")
@@ -579,12 +628,14 @@ def main():
                          "two block-scaled fp4 MFMAs per product; fast = fp16 MFMA operands / fp16 activations (2.4e-3 on zero-mean audio); "
                          "strict = split precision (3 fp16 MFMAs per product, ~1e-6)")
     ap.add_argument("--decoder-precision", default=None, choices=["f16", "f32", "x3"])
-    ap.add_argument("--no-other-precision", action="store_true", help="skip the extra timed passes in the other precisions (N = 1)")
+    ap.add_argument("--no-other-precision", action="store_true", help="--full: skip the extra timed passes in the other precisions (N = 1)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU smoke tests)")
     ap.add_argument("--force-device", type=int, default=-1, help="debug: put every rank on this device (with --backend gloo)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch check: the ranks meet (gloo), rank 0 prints n_gpus / ranks_seen, nothing touches a GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: become the launcher of N ranks (one per GPU) running this same command line
@@ -638,7 +689,7 @@ def main():
         return e
 
     eng = make_engine(args.precision, args.decoder_precision)
-    lat0 = b1_latency(eng) if rank == 0 and args.mode == "am_vocoder" else {}
+    lat0 = b1_latency(eng) if args.full and rank == 0 and args.mode == "am_vocoder" else {}
     work = Workload(args, eng, rank, dev, torch, _ffi)
 
     def sync():
@@ -659,8 +710,11 @@ def main():
         frames = sum(r["frames"] for r in per_rank)
         dt = max(r["s"] for r in per_rank)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, work.outputs())
+
     roof, stages, kernels, lat, other, power = None, {}, {}, lat0, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         roof, stages, kernels = roofline_block(eng, work, torch, args.dump_launches)
         # (behind the profiled step: 2.5 s of sustained load in front of it cost its per-launch numbers 5-10 % -- the chip throttles further as it warms)
         power = power_sample(work, torch) if world == 1 else None
@@ -696,7 +750,7 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": DTYPE_NAME[eng.vocoder_precision], "precision": args.precision, "waveform_rel_l2_vs_reference": PARITY_LEVEL[args.precision],
-        "data": "synthetic", "ranks_seen": ranks_seen, "ranks": per_rank, "config": cfg,
+        "data": "synthetic", "full": args.full, "ranks_seen": ranks_seen, "ranks": per_rank, "config": cfg,
         "latency": lat, "roofline": roof, "stage_ms": {k: round(v, 3) for k, v in stages.items()}, "kernels_ms": kernels,
         "other_precision": other,
     }
@@ -706,7 +760,7 @@ def main():
         roof["frac_at_measured_clock"] = round(roof["frac"] / clk, 4)
         roof["measured_clock_note"] = ("the forward runs power-limited: sclk %d MHz at %d W under load (line.power); frac_at_measured_clock = frac x 2400 / sclk -- "
                                        "what the dominant family reaches of its arithmetic's roof at the clock the chip actually sustains" % (power["sclk_MHz"], int(power["socket_W"])))
-    if world == 1 and args.cpu_utts > 0:
+    if args.full and world == 1 and args.cpu_utts > 0:
         line["cpu_baseline"] = cpu_baseline(args.cpu_utts, args.phonemes, args.cpu_threads)
     else:
         line["cpu_baseline"] = None

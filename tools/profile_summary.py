@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 outputs of `tools/gpu_check.sh prof pmc pmcsq pmccal bench` (under gpurun_out/) into the committed summaries
+"""Turn the rocprofv3 outputs of `tools/gpu_check.sh prof pmc pmcsq pmccal bench` (under $EV_OUT, default out/) into the committed summaries
 under profiles/:
 
     python tools/profile_summary.py --tag r2_d
@@ -21,7 +21,7 @@ import os
 import shutil
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, os.environ.get("EV_OUT", "out"))          # where tools/gpu_check.sh wrote them (same default)
 N_DEC = 17          # decoder launches of the same template in front of the vocoder's (4 layers x 4 GEMMs + to_mel)
 N_DEC_MX = 8        # "mx" precision: the decoder's conv-FFN launches (4 layers x 2) of conv_gemm_mx_kernel in front of the generator's
 GIB = float(1 << 30)
@@ -162,7 +162,7 @@ def main():
                                                             "resblock_pair_c64_mx", "resblock_pair_c32_mx", "mx_planes_kernel") if k in fam)
         dom = "conv_gemm_mx_vocoder" if args.mode == "mx" else "conv_gemm_f16_vocoder"
         doc = {
-            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) on `python bench.py --steps 1 --warmup 1 --cpu-utts 0 --no-other-precision`, the B=32 x 1024-frame forward",
+            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) on `python bench.py --full --steps 1 --warmup 1 --cpu-utts 0 --no-other-precision`, the B=32 x 1024-frame forward",
             "correction": dict(fetch_factor=f_corr, write_factor=w_corr, calibration=cal,
                                note="bytes = counter x 1024 x factor; factors = 2^30 / (counter x 1024) measured on dispatches that read and write exactly 1 GiB "
                                     "(tools/pmc_calibrate.py); without a calibration run: FETCH_SIZE x 2 (MI355X_MICROARCH.md section HBM), WRITE_SIZE x 1"),
