@@ -547,21 +547,29 @@ int run_predictor(ev_handle* h, const char* name, int layers, const RowCtx& rc, 
     return 0;
 }
 
+// Generator schedule of one call (make_voc_plan, before the arena passes): per up stage the kernel of the up-conv and of every ResBlock pair, how
+// the running MRF sum travels and how the stage's ResBlocks are issued.  plan_vocoder sizes the workspace from it and run_vocoder executes it.
+enum class UpKind { F16, Split, MxPlanes, MxScratch };   // MX up-conv: operand planes written by the previous stage / by the planes kernel into the scratch
+enum class MrfMode { F16Branches, Planes, F32 };         // rb0, rb1 as fp16 branches added by rb2 / a partial plane set / an fp32 running sum
+enum class Issue { Serial, Streams, Grouped };           // ResBlock after ResBlock / three streams / same-level convs as grouped launches
+enum class PairKind { FusedC64Mx, FusedC32Mx, Fused, MxLayers, Layers };
+struct VocStage {
+    int cin, cout, s, U_in, rows_in, rows_out;           // U_in: the upsampling factor in front of the stage
+    UpKind up; bool stage_mx, rpl, next_up_mx; MrfMode mrf; Issue issue;
+    PairKind pair[3][4];                                 // [ResBlock][dilation]
+};
+struct VocPlan { bool mx, x3, keep; int Rf, U; size_t scratch_bytes; VocStage st[4]; };
+
 struct VocBufs {
     Buf pre, xu[4], tmp[3], rba[3], rbb[3], nxt[4], mrf32, mrf16a, mrf16b, wavrows; Buf mrf_tap[4]; Buf pre_tap;
     // EV_PREC_MX: plane sets of the up-conv output, conv1's output, the two alternating ResBlock states and the stage output; the
     // planes-kernel scratch of the one fp32 tensor an MX launch reads (conv_pre's output)
-    // (pl_t / pl_a / pl_b: one set per ResBlock of a stage when the three run concurrently -- small batches, voc_small_batch -- else only [0])
+    // (tmp / rba / rbb: one set per ResBlock of a stage when the plan issues them on three streams; pl_t / pl_a / pl_b: also when it issues an MX stage
+    // as grouped levels; else only [0])
     // pl_mrf: the running MRF sum of a stage as a PARTIAL plane set (hi plane, remainder codes, their scales; ev_config.mx_mrf == 0)
-    PlaneBuf pl_xu, pl_t[3], pl_a[3], pl_b[3], pl_nxt, pl_mrf; char* mx_scratch = nullptr; size_t mx_scratch_bytes = 0;
+    PlaneBuf pl_xu, pl_t[3], pl_a[3], pl_b[3], pl_nxt, pl_mrf; char* mx_scratch = nullptr;
+    float* wav = nullptr; int16_t* wav_i16 = nullptr;    // the packed waveform
 };
-
-// Small batches (single utterances: the reference's own call pattern): a generator launch is a handful of tiles whose K loops are sequential chains
-// (tools/probe_b1.py: 39 conv launches of ~35 us each for 64 phonemes while 240 of 256 CUs idle), so the three ResBlocks of a stage -- independent until
-// their scaled outputs meet in the MRF sum -- run on three streams there, also in the mx mode (each with its own intermediates; the running fp32 sum
-// keeps its order rb0, rb1, rb2 through events, so the result has the same bits as the serial order).  At full batches a launch fills the chip and
-// streams only reorder the same work (measured in round 3: 54.99 vs 54.56 ms), so large batches stay serial and allocate one set of intermediates.
-static bool voc_small_batch(int Rf) { return Rf <= 2048; }
 
 // weights of one generator conv: fp16 (also the "hi" part of the split) and, in the split-precision mode, the "lo" part
 int voc_weights(ev_handle* h, const std::string& base /* e.g. "voc.rb3.c1.0" */, bool x3, ConvGemmParams& p, bool mx = false) {
@@ -584,358 +592,355 @@ int voc_weights(ev_handle* h, const std::string& base /* e.g. "voc.rb3.c1.0" */,
     return 0;
 }
 
-// HiFi-GAN generator (reference models/hifigan/models.py:115-131) on channels-last rows.
-// vocoder_precision F16: fp16 activations, every leaky-relu fused into the producer (post_lrelu) or the consumer's staging.
-// vocoder_precision X3:  fp32 activations, split-precision products; every stored tensor is the RAW module output of the
-// reference (so the Appendix-C taps are the buffers themselves) and each consumer applies its leaky-relu while staging.
-int run_vocoder(ev_handle* h, const Buf& melin, int Rf, double n_frames, VocBufs& vb, bool keep) {
+int make_voc_plan(ev_handle* h, int Rf, VocPlan& vp) {
     const ev_config& c = h->cfg;
     // EV_PREC_MX: the split-precision data flow (fp32 raw module outputs), but every layer with N, K % 128 == 0 evaluates its products as
     // one fp16 MFMA + two block-scaled fp4 MFMAs (conv_gemm_mx_kernel) and reads its operand as the plane set its producer's epilogue wrote.
-    const bool mx = c.vocoder_precision == EV_PREC_MX;
-    const bool x3 = c.vocoder_precision == EV_PREC_X3 || mx;
-    const size_t ves = x3 ? 4 : 2;
-    auto set_out = [&](ConvGemmParams& q, void* dst) { if (x3) q.out32 = (float*)dst; else q.out16 = dst; };
+    const bool mx = c.vocoder_precision == EV_PREC_MX, x3 = c.vocoder_precision == EV_PREC_X3 || mx, keep = c.keep_stages != 0;
     auto has_wt = [&](const std::string& name) { return h->wt.find(name) != h->wt.end(); };
     auto has_mx = [&](const std::string& base) { return mx && (has_wt(base + ".wmx") || has_wt(base + ".wcmx")); };
-    bool prev_planes = false;           // vb.pl_nxt holds the plane set of lrelu(prev)
-    ConvGemmParams p = gemm_defaults();
-    if (voc_weights(h, "voc.pre", x3, p)) return -1;
-    p.A = melin.p; p.lda = MEL_PAD; p.M = Rf; p.N = c.up_init_ch; p.K = MEL_PAD;
-    p.taps = 7; p.center = 3; p.row_valid = h->d_frm_valid; p.valid_shift = 0; p.ldo = c.up_init_ch;
-    set_out(p, vb.pre.p);
-    if (!x3) {
-        p.post_lrelu = 1; p.post_slope = 0.1f;      // leaky_relu(0.1) of models.py:118 fused into the producer
-        if (keep) { p.out32 = (float*)vb.pre_tap.p; p.out32_before_post = 1; }
-    }
-    if (gemm(h, x3 ? "voc_conv_gemm_x3" : "voc_conv_gemm_f16", p, n_frames)) return -1;
-    const char* gname = x3 ? "voc_conv_gemm_x3" : "voc_conv_gemm_f16";
-    const void* prev = vb.pre.p;
+    auto k3711 = [](int k) { return k == 3 || k == 7 || k == 11; };
+    int seen = 0;          // the ResBlocks' kernel sizes as a set: {3, 7, 11} is what the grouped launches take
+    for (int j = 0; j < c.n_rb; ++j) seen |= c.rb_kernels[j] == 3 ? 1 : (c.rb_kernels[j] == 7 ? 2 : (c.rb_kernels[j] == 11 ? 4 : 8));
+    vp.mx = mx; vp.x3 = x3; vp.keep = keep; vp.Rf = Rf;
+    vp.scratch_bytes = (mx && c.up_init_ch % 128 == 0) ? mx_scratch_bytes(Rf, c.up_init_ch) : 0;
+    bool prev_planes = false;           // the previous stage's epilogue writes the plane set of lrelu(its output)
     int ch = c.up_init_ch, U = 1;
     for (int i = 0; i < c.n_up; ++i) {
+        VocStage& st = vp.st[i];
         const int s = c.up_rates[i], cout = ch / 2;
-        const int rows_in = Rf * U, rows_out = rows_in * s;
-        const double valid_in = n_frames * U, valid_out = valid_in * s;
-        // ConvTranspose1d(k = 2s, pad = s/2) == 3-tap conv with N = s * C_out, viewed as [rows_in*s][C_out] (models.py:119)
-        p = gemm_defaults();
-        if (voc_weights(h, "voc.up" + std::to_string(i), x3, p, mx)) return -1;
-        p.A = prev; p.lda = ch; p.M = rows_in; p.N = s * cout; p.K = ch; p.taps = 3; p.center = 1;
-        if (cout % 64 == 0 && s % 2 == 0) p.polyphase_cout = cout;          // (conv_gemm_mx_kernel skips the zero tap of each output phase; other kernels ignore the hint)
-        p.row_valid = h->d_frm_valid; p.valid_shift = ilog2(U); p.ldo = s * cout;
-        if (x3) { p.pro_lrelu = 1; p.pro_slope = 0.1f; }          // models.py:118 (the fp16 path has it in the producer's epilogue)
-        set_out(p, vb.xu[i].p);
-        // the ResBlocks of this stage run on the MX kernel iff all their convs have fp4 planes (shape rule of the packer)
-        bool stage_mx = mx && cout % 64 == 0;            // (C = 64: conv_c64_mx_kernel, the same plane-set data flow)
-        for (int j = 0; stage_mx && j < c.n_rb; ++j) stage_mx = has_mx("voc.rb" + std::to_string(i * c.n_rb + j) + ".c1.0");
-        if (p.dtype == DT_MX) {
-            if (prev_planes) mx_in(p, mx_view(vb.pl_nxt, rows_in, ch), ch);            // the previous stage's epilogue wrote lrelu(prev) as planes
-            else if (vb.mx_scratch && vb.mx_scratch_bytes >= mx_scratch_bytes(rows_in, ch)) { p.mx_scratch = vb.mx_scratch; p.mx_scratch_size = vb.mx_scratch_bytes; }
-            else p.dtype = DT_F32S;
-        }
-        if (p.dtype == DT_MX && stage_mx) mx_out(p, mx_view(vb.pl_xu, (size_t)rows_out, cout), 0.1f);      // lrelu(x) of models.py:51, shared by the three ResBlocks
-        else stage_mx = false;
+        st.cin = ch; st.cout = cout; st.s = s; st.U_in = U; st.rows_in = Rf * U; st.rows_out = st.rows_in * s;
+        auto rb = [&](int j) { return "voc.rb" + std::to_string(i * c.n_rb + j); };
+        if (!x3) st.up = UpKind::F16;
+        else if (!has_mx("voc.up" + std::to_string(i))) st.up = UpKind::Split;
+        else if (prev_planes) st.up = UpKind::MxPlanes;
+        else if (vp.scratch_bytes && vp.scratch_bytes >= mx_scratch_bytes(st.rows_in, ch)) st.up = UpKind::MxScratch;
+        else st.up = UpKind::Split;
+        // the ResBlocks of this stage run on the MX kernel iff the up-conv does and all their convs have fp4 planes (shape rule of the packer)
+        st.stage_mx = (st.up == UpKind::MxPlanes || st.up == UpKind::MxScratch) && cout % 64 == 0;     // (C = 64: conv_c64_mx_kernel, the same plane-set data flow)
+        for (int j = 0; st.stage_mx && j < c.n_rb; ++j) st.stage_mx = has_mx(rb(j) + ".c1.0");
         // MX stage: the residual stream of a ResBlock exists only as the plane set of lrelu(x, .1) its conv1 reads -- conv2's epilogue rebuilds x from
         // the fp16 hi plane + the fp4 remainder codes (ConvGemmParams::res_x4), so neither the up-conv nor a conv2 inside a ResBlock writes an fp32
         // copy (tools/precision_study_mx.py: 3.4e-4 -> 4.4e-4; 8.7 instead of 14.1 bytes per element and conv2 launch).  Default since round 4 (the
         // round-3 driver run XPASSed every reference fixture through it); ev_config.mx_residual = 1 restores the separate fp32 residual tensor.
-        const bool rpl = stage_mx && c.mx_residual == 0;
-        if (rpl && !keep) p.out32 = nullptr;                   // (kept stages still get the raw up-conv output: the voc_up tap)
-        if (gemm(h, p.dtype == DT_MX ? (p.N == 64 && p.K == 64 ? "voc_conv_c64_mx" : "voc_conv_gemm_mx") : gname, p, valid_in, nullptr, 2.0 / 3.0)) return -1;
-        const bool next_up_mx = stage_mx && i + 1 < c.n_up && has_mx("voc.up" + std::to_string(i + 1));
+        st.rpl = st.stage_mx && c.mx_residual == 0;
+        st.next_up_mx = st.stage_mx && i + 1 < c.n_up && has_mx("voc.up" + std::to_string(i + 1));
         // MRF sum as partial plane sets (conv_gemm_mx_kernel stages, i.e. >= 128 channels): rb0's last conv writes out_scale * x as fp16 hi plane + fp4 remainder
         // codes, rb1's adds that to its own and rewrites it in place, rb2's adds it and writes the next up-conv's plane set: 2.53 instead of 4 bytes per element
         // and transfer (16 -> 10.1 bytes per stage-output element; tools/precision_study_mx.py: 4.17e-4 -> 4.22e-4 on the zero-mean recipe)
         // (round 6: also at C = 64 -- conv_gemm_mx64_kernel has the same epilogue variants, the fused k = 3 pair writes the partial set itself)
-        bool mrf_pl = rpl && !keep && c.mx_mrf == 0 && c.n_rb == 3 && cout % 64 == 0 && next_up_mx && vb.pl_mrf.h;
+        bool mrf_pl = st.rpl && !keep && c.mx_mrf == 0 && c.n_rb == 3 && cout % 64 == 0 && st.next_up_mx;
         for (int j = 0; mrf_pl && j < c.n_rb; ++j) {
             const int k = c.rb_kernels[j];
-            mrf_pl = k == 3 || k == 7 || k == 11;
+            mrf_pl = k3711(k);
             // C = 64, k = 3: only the fused pair kernel writes / the streamed k = 7 / 11 kernel reads partial sets (conv_c64_mx_kernel does neither), and the pair
             // kernel has no plane-set accumulate-in: the k = 3 ResBlock must be the first of the stage and run fused
             if (mrf_pl && cout == 64 && k == 3)
-                mrf_pl = j == 0 && c.fused_pairs == 0 && c.rb_dils[j][c.n_rb_dils - 1] <= 8 && has_wt("voc.rb" + std::to_string(i * c.n_rb + j) + ".c2." + std::to_string(c.n_rb_dils - 1) + ".wcmx");
+                mrf_pl = j == 0 && c.fused_pairs == 0 && c.rb_dils[j][c.n_rb_dils - 1] <= 8 && has_wt(rb(j) + ".c2." + std::to_string(c.n_rb_dils - 1) + ".wcmx");
         }
-        U *= s;
-        const int shift = ilog2(U);
-        const bool last_stage = (i == c.n_up - 1);
-        // Optional (ev_config.vocoder_chunk_mb > 0): the ResBlocks of a stage run on row chunks sized for the 256 MB Infinity
-        // Cache, so that a chunk's intermediates (xt, the running x of a ResBlock, the fp16 MRF branches) are re-read from the
-        // memory-side cache instead of HBM.  The isolated probe (tools/bench_chunked.py) gains 10-15 % on the HBM-bound chains
-        // with 2-4 chunks, but in the full forward every chunk size measured LOSES 1-4 % (more launches, each with its own
-        // tail: 113-251 instead of 53 conv launches), so the default is whole tensors.
-        // Overlapped tiling keeps the result bit-identical: op q of a ResBlock's 6-conv chain runs on the chunk extended by
-        // (5 - q) x 256 rows per side, more than any conv's halo (<= 25 rows; the fused pair kernels get the tensor's true
-        // bounds so that they zero-pad only at real sequence edges), so the last op's rows [a, b) only ever read
-        // rows that were recomputed from valid inputs inside this chunk; what the extensions write outside [a, b) is dead or
-        // rewritten by the neighbouring chunk.
-        int nchunks = 1;
-        if (!keep && !x3 && c.vocoder_chunk_mb > 0) {
-            const double tensor_mb = (double)rows_out * cout * 2.0 / 1e6;
-            nchunks = (int)(tensor_mb / c.vocoder_chunk_mb + 0.5);
-            if (nchunks < 1) nchunks = 1;
-            if (nchunks > 64) nchunks = 64;
-        }
-        const int chunk_rows = ((rows_out + nchunks - 1) / nchunks + 255) / 256 * 256;
-        // shift every row-indexed operand of a conv call to the row range [lo, hi)
-        auto sub = [&](ConvGemmParams q, int lo, int hi) {
-            q.A = (const char*)q.A + (size_t)lo * q.lda * ves;
-            if (q.res) q.res = (const char*)q.res + (size_t)lo * q.ldres * (q.res_dtype == DT_F16 ? 2 : 4);
-            if (q.acc32) q.acc32 = q.acc32 + (size_t)lo * q.ldacc;
-            if (q.add16_a) { q.add16_a = (const char*)q.add16_a + (size_t)lo * q.ldadd * 2; q.add16_b = (const char*)q.add16_b + (size_t)lo * q.ldadd * 2; }
-            if (q.out16) q.out16 = (char*)q.out16 + (size_t)lo * q.ldo * 2;
-            if (q.out32) q.out32 = q.out32 + (size_t)lo * q.ldo;
-            if (q.row_valid) q.row_valid = q.row_valid + (lo >> q.valid_shift);
-            q.M = hi - lo;
-            return q;
-        };
+        // MRF: fp16 mode with three ResBlocks (the reference config): the first two scaled branches are kept in fp16 and the third adds them in its
+        // fp32 epilogue (half the HBM traffic of an fp32 running sum; the two extra fp16 roundings are of the size of the one the stage output gets
+        // anyway).  Any other count, and the split-precision mode, use the fp32 running sum.
+        st.mrf = (c.n_rb == 3 && !x3) ? MrfMode::F16Branches : mrf_pl ? MrfMode::Planes : MrfMode::F32;
         // The three ResBlocks of a stage only share the stage input and meet again in the MRF sum: the first two run on
         // auxiliary streams beside the third (its last conv waits for both).  A k = 3 chain is HBM-bound and a k = 11 chain
         // MFMA-bound, so their workgroups complement each other on a CU and fill each other's launch tails.  Profiled steps
-        // (per-launch events) and chunked execution stay on one stream.  (Split-precision mode: the MRF sum is a running fp32
-        // accumulator shared by the three ResBlocks, so they run in order on the handle's stream.)
-        const bool conc = c.n_rb == 3 && nchunks == 1 && (!x3 || (mx && !keep && voc_small_batch(Rf))) && !h->profiling && c.vocoder_streams != 1 &&
-                          h->aux[0] && h->aux[1];
+        // (per-launch events) stay on one stream.  (Split-precision mode: the MRF sum is a running fp32 accumulator shared
+        // by the three ResBlocks, so they run in order on the handle's stream.)
+        // In the mx mode only small batches (Rf <= 2048 rows; single utterances: the reference's own call pattern) do so: there a generator launch is a
+        // handful of tiles whose K loops are sequential chains (tools/probe_b1.py: 39 conv launches of ~35 us each for 64 phonemes while 240 of 256 CUs
+        // idle); the running fp32 sum keeps its order rb0, rb1, rb2 through events, so the result has the same bits as the serial order.  At full batches a
+        // launch fills the chip and streams only reorder the same work (measured in round 3: 54.99 vs 54.56 ms).
+        const bool conc = c.n_rb == 3 && (!x3 || (mx && !keep && Rf <= 2048)) && !h->profiling && c.vocoder_streams != 1 && h->aux[0] && h->aux[1];
         // Large batches on the conv_gemm_mx_kernel stages (round 6, ev_config.mx_group == 0): the three ResBlocks advance level by level -- the three conv1 of a
         // pair position, then the three conv2 -- each level ONE grouped launch (launch_conv_gemm_group3: a launch of its own costs every conv 30-50 us of ramp and
         // tail); the last conv2 of each ResBlock stays a launch of its own (the running MRF sum orders them).  Each ResBlock has its own intermediates; descriptors
-        // are built in the usual ResBlock order and issued level by level.  Same kernels' code on the same data: the same bits.
-        bool grp = stage_mx && rpl && !keep && !conc && nchunks == 1 && c.mx_group == 0 && c.n_rb == 3 && cout % 128 == 0 && vb.pl_t[2].h && vb.pl_a[2].h && vb.pl_b[2].h;
-        {
-            int seen = 0;
-            for (int j = 0; j < c.n_rb; ++j) seen |= c.rb_kernels[j] == 3 ? 1 : (c.rb_kernels[j] == 7 ? 2 : (c.rb_kernels[j] == 11 ? 4 : 8));
-            if (seen != 7) grp = false;
-        }
-        std::vector<ConvGemmParams> pend(grp ? (size_t)c.n_rb * 2 * c.n_rb_dils : 0);
-        if (conc) {
-            (void)hipEventRecord(h->ev_fork, h->stream);
-            (void)hipStreamWaitEvent(h->aux[0], h->ev_fork, 0);
-            (void)hipStreamWaitEvent(h->aux[1], h->ev_fork, 0);
-        }
-        for (int a0 = 0; a0 < rows_out; a0 += chunk_rows) {
-        const int b0 = std::min(rows_out, a0 + chunk_rows);
-        const double frac = (double)(b0 - a0) / rows_out;
+        // are built in the usual ResBlock order and issued level by level.  Same kernels' code on the same data: the same bits.  A small batch that may not
+        // use the streams (profiled, vocoder_streams = 1) is issued this way too.
+        const bool grp = st.rpl && !keep && !conc && c.mx_group == 0 && c.n_rb == 3 && cout % 128 == 0 && seen == 7;
+        st.issue = conc ? Issue::Streams : grp ? Issue::Grouped : Issue::Serial;
         for (int j = 0; j < c.n_rb; ++j) {
             const int k = c.rb_kernels[j];
-            const std::string rb = "voc.rb" + std::to_string(i * c.n_rb + j);
-            const void* xcur = vb.xu[i].p;
-            const int bj = (conc || grp) ? j : 0;
-            hipStream_t sj = (conc && j < 2) ? h->aux[j] : h->stream;
             for (int d = 0; d < c.n_rb_dils; ++d) {
                 const int dil = c.rb_dils[j][d];
-                const std::string c1 = rb + ".c1." + std::to_string(d), c2 = rb + ".c2." + std::to_string(d);
-                // fused pair kernels: C = 32 (every k) and C = 64 with k = 3 (the HBM-bound end of the generator; fp16 mode only)
-                const bool fused = !x3 && ((cout == 32 && (k == 3 || k == 7 || k == 11)) || (cout == 64 && k == 3)) && c.fused_pairs == 0;
+                const std::string c1 = rb(j) + ".c1." + std::to_string(d), c2 = rb(j) + ".c2." + std::to_string(d);
+                PairKind& pk = st.pair[j][d];
+                // EV_PREC_MX at C = 64, k = 3 with the residual in the planes: the pair in one persistent kernel (ev_pair64_mx.h), plane sets in / out -- xt
+                // never reaches HBM and the residual comes from the slab conv1 reads (6.1 instead of 14.8 bytes per element; the k = 3 chain of stage 2 is HBM-bound)
+                if (st.rpl && cout == 64 && k == 3 && dil <= 8 && c.fused_pairs == 0 && has_wt(c1 + ".wcmx") && has_wt(c2 + ".wcmx")) pk = PairKind::FusedC64Mx;
                 // EV_PREC_MX at C = 32: the whole pair in one persistent kernel (ev_pair_mx.h), x fp32 in, fp32 out
-                const bool fused_mx = mx && cout == 32 && (k == 3 || k == 7 || k == 11) && (k - 1) * (dil + 1) <= 64 && has_wt(c1 + ".wpmx") && has_wt(c2 + ".wpmx") &&
-                                      c.fused_pairs == 0;
-                // the plane set of lrelu(x, .1) this pair starts from: conv1's operand and, with rpl, conv2's residual
-                const PlaneBuf& xin = d == 0 ? vb.pl_xu : ((d - 1) % 2 == 0 ? vb.pl_a[bj] : vb.pl_b[bj]);
-                // EV_PREC_MX at C = 64, k = 3 with the residual in the planes: the pair in one persistent kernel (ev_pair64_mx.h), plane sets in / out -- xt never
-                // reaches HBM and the residual comes from the slab conv1 reads (6.1 instead of 14.8 bytes per element; the k = 3 chain of stage 2 is HBM-bound)
-                const bool fused_c64 = stage_mx && rpl && cout == 64 && k == 3 && dil <= 8 && c.fused_pairs == 0 && has_wt(c1 + ".wcmx") && has_wt(c2 + ".wcmx");
-                if (fused_mx || fused_c64) {
-                } else if (stage_mx) {
-                    // MX stage: xt only ever exists as conv2's operand planes; x travels as fp32 (the residual) + the planes of lrelu(x); with EV_MX_RESPL=1 as the planes only
-                    p = gemm_defaults();
-                    if (voc_weights(h, c1, x3, p, true) || p.dtype != DT_MX) return fail(h, "MX stage: %s has no fp4 planes", c1.c_str());
-                    mx_in(p, mx_view(xin, (size_t)rows_out, cout), cout);
-                    p.M = rows_out; p.N = cout; p.K = cout; p.taps = k; p.dil = dil; p.center = (k - 1) / 2;
-                    p.row_valid = h->d_frm_valid; p.valid_shift = shift; p.act = ACT_LRELU; p.act_slope = 0.1f; p.ldo = cout;
-                    mx_out(p, mx_view(vb.pl_t[bj], (size_t)rows_out, cout), 1.0f);
-                    if (grp) pend[((size_t)j * c.n_rb_dils + d) * 2] = p;
-                    else if (gemm(h, cout == 64 ? "voc_conv_c64_mx" : "voc_conv_gemm_mx", p, valid_out, sj)) return -1;
-                } else if (!fused) {
-                    // xt = lrelu(c1(lrelu(x)))  (models.py:51-53)
-                    p = gemm_defaults();
-                    if (voc_weights(h, c1, x3, p, false)) return -1;      // (no plane-set input here: DT_MX would only fall back to the split kernel)
-                    p.A = xcur; p.lda = cout; p.M = rows_out; p.N = cout; p.K = cout;
-                    p.taps = k; p.dil = dil; p.center = (k - 1) / 2; p.row_valid = h->d_frm_valid; p.valid_shift = shift;
-                    p.pro_lrelu = 1; p.pro_slope = 0.1f; p.act = ACT_LRELU; p.act_slope = 0.1f; p.ldo = cout;
-                    set_out(p, vb.tmp[bj].p);
-                    const int e1 = (2 * (c.n_rb_dils - 1 - d) + 1) * 256, lo1 = std::max(0, a0 - e1), hi1 = std::min(rows_out, b0 + e1);
-                    if (gemm(h, gname, sub(p, lo1, hi1), valid_out * frac, sj)) return -1;
-                }
-                // x = c2(xt) + x  (models.py:54-56)
-                p = gemm_defaults();
-                if (voc_weights(h, c2, x3, p, stage_mx)) return -1;
-                p.A = vb.tmp[bj].p; p.lda = cout; p.M = rows_out; p.N = cout; p.K = cout;
-                if (stage_mx) {
-                    if (p.dtype != DT_MX) return fail(h, "MX stage: %s has no fp4 planes", c2.c_str());
-                    mx_in(p, mx_view(vb.pl_t[bj], (size_t)rows_out, cout), cout);
-                }
-                p.taps = k; p.dil = 1; p.center = (k - 1) / 2; p.row_valid = h->d_frm_valid; p.valid_shift = shift;
-                p.res = xcur; p.res_dtype = x3 ? DT_F32 : DT_F16; p.ldres = cout; p.ldo = cout;
-                if (rpl) {
-                    const MxView xv = mx_view(xin, (size_t)rows_out, cout);
-                    p.res = xv.h; p.res_dtype = DT_MX; p.res_x4 = xv.q4[1]; p.res_xs = xv.qs[1]; p.res_xs_stride = xv.qs_stride; p.res_inv_slope = 10.0f;
-                }
-                if (d + 1 < c.n_rb_dils) {
-                    void* dst = (d % 2 == 0) ? vb.rba[bj].p : vb.rbb[bj].p;
-                    if (!rpl || keep) set_out(p, dst);          // (rpl: the next pair reads the planes below; the fp32 copy only feeds stage taps)
-                    xcur = dst;
-                    if (stage_mx) mx_out(p, mx_view(d % 2 == 0 ? vb.pl_a[bj] : vb.pl_b[bj], (size_t)rows_out, cout), 0.1f);     // the next conv1's operand
-                } else {
-                    // MRF: xs += resblock(x); x = xs / num_kernels (models.py:121-126), then the next leaky_relu
-                    // fp16 mode with three ResBlocks (the reference config): the first two scaled branches are kept in fp16 and the
-                    // third adds them in its fp32 epilogue (half the HBM traffic of an fp32 running sum; the two extra fp16
-                    // roundings are of the size of the one the stage output gets anyway).  Any other count, and the
-                    // split-precision mode, use the fp32 running sum.
-                    p.out_scale = 1.0f / (float)c.n_rb;
-                    const bool mrf16 = (c.n_rb == 3) && !x3;
-                    const MxView mv = mrf_pl ? mx_view(vb.pl_mrf, (size_t)rows_out, cout) : MxView{};
-                    if (mrf16) {
-                        if (j == 2) { p.add16_a = vb.mrf16a.p; p.add16_b = vb.mrf16b.p; p.ldadd = cout; }
-                    } else if (mrf_pl) {
-                        if (j > 0) { p.acc_h = mv.h; p.acc_x4 = mv.q4[1]; p.acc_xs = mv.qs[1]; p.acc_xs_stride = mv.qs_stride; p.ldacc = cout; }
-                    } else if (j > 0) { p.acc32 = (const float*)vb.mrf32.p; p.ldacc = cout; }
-                    if (j + 1 < c.n_rb) {
-                        if (mrf16) p.out16 = (j == 0) ? vb.mrf16a.p : vb.mrf16b.p;
-                        else if (mrf_pl) { mx_out(p, mv, 1.0f); p.mxo_partial = 1; }
-                        else p.out32 = (float*)vb.mrf32.p;
-                    } else if (x3) {
-                        p.out32 = (float*)vb.nxt[i].p;               // raw MRF mean (= the voc_mrf tap); consumers apply the leaky-relu
-                        if (next_up_mx) {
-                            mx_out(p, mx_view(vb.pl_nxt, (size_t)rows_out, cout), 0.1f);      // ... or read these planes (models.py:118)
-                            if (rpl && !keep) p.out32 = nullptr;                              // the next up-conv reads only the planes: no fp32 copy of the stage output
-                        }
-                    } else {
-                        p.post_lrelu = 1; p.post_slope = last_stage ? 0.01f : 0.1f;   // models.py:118 / :127
-                        p.out16 = vb.nxt[i].p;
-                        if (keep) { p.out32 = (float*)vb.mrf_tap[i].p; p.out32_before_post = 1; }
-                    }
-                }
-                const int e2 = 2 * (c.n_rb_dils - 1 - d) * 256, lo2 = std::max(0, a0 - e2), hi2 = std::min(rows_out, b0 + e2);
-                p = sub(p, lo2, hi2);
-                if (conc && j == 2 && d + 1 == c.n_rb_dils) {      // the MRF sum reads the other two branches
-                    (void)hipStreamWaitEvent(h->stream, h->ev_join[0], 0);
-                    (void)hipStreamWaitEvent(h->stream, h->ev_join[1], 0);
-                }
-                // fp32 running sum (split-precision / mx modes): rb1's last conv adds onto what rb0's wrote (the sum keeps the serial order's bits)
-                if (conc && x3 && j == 1 && d + 1 == c.n_rb_dils) (void)hipStreamWaitEvent(h->aux[1], h->ev_join[0], 0);
-                if (fused_c64) {
-                    WPTR(w1, char, c1 + ".w16"); WPTR(b1, float, c1 + ".b"); WPTR(w1m, char, c1 + ".wcmx");
-                    const MxView xv = mx_view(xin, (size_t)rows_out, cout);
-                    ResPairParams rp;
-                    memset(&rp, 0, sizeof rp);
-                    rp.x = xv.h; rp.ldx = cout; rp.w1 = w1; rp.b1 = b1; rp.w2 = p.W; rp.w1_mx = w1m; rp.w2_mx = p.W_mx;
-                    rp.M = p.M; rp.k = k; rp.dil = dil; rp.epi = p;
-                    rp.epi.mx_x4[0] = xv.q4[0]; rp.epi.mx_x4[1] = xv.q4[1]; rp.epi.mx_xs[0] = xv.qs[0]; rp.epi.mx_xs[1] = xv.qs[1]; rp.epi.mx_xs_stride = xv.qs_stride;
-                    const double fl = 2.0 * 2.0 * valid_out * cout * (double)cout * k;
-                    ConvGemmParams shape = p; shape.dil = dil;
-                    KScope ks(h, "voc_resblock_pair_c64_mx", fl, valid_out * cout * 3.0625 * 2.0, sj, &shape);
-                    if (launch_resblock_pair_c64_mx(rp, sj)) return fail(h, "fused MX pair (C = 64): unsupported call (k %d, dil %d)", k, dil);
-                } else if (fused_mx) {
-                    WPTR(w1, char, c1 + ".w16"); WPTR(b1, float, c1 + ".b"); WPTR(w1m, char, c1 + ".wpmx"); WPTR(w2m, char, c2 + ".wpmx");
-                    ResPairParams rp;
-                    memset(&rp, 0, sizeof rp);
-                    rp.x = p.res; rp.ldx = cout; rp.w1 = w1; rp.b1 = b1; rp.w2 = p.W; rp.w1_mx = w1m; rp.w2_mx = w2m;
-                    rp.M = p.M; rp.k = k; rp.dil = dil; rp.gmin = 0; rp.gmax = rows_out; rp.epi = p;
-                    if (c.mx_act_format != 0) rp.epi.reserved0 |= 16;          // block-scaled fp4 activation operands (rounds 3-5) instead of E5M2
-                    const double fl = 2.0 * 2.0 * valid_out * cout * (double)cout * k;
-                    ConvGemmParams shape = p; shape.dil = dil;
-                    KScope ks(h, "voc_resblock_pair_c32_mx", fl, valid_out * cout * 4.0 * 2.0, sj, &shape);
-                    if (launch_resblock_pair_c32_mx(rp, sj)) return fail(h, "fused MX pair: unsupported call (k %d, dil %d)", k, dil);
-                } else if (fused) {
-                    // conv1 -> LDS -> conv2 + residual / MRF epilogue in one persistent kernel (ev_gemm.hip)
-                    WPTR(w1, char, c1 + ".w16"); WPTR(b1, float, c1 + ".b");
-                    ResPairParams rp;
-                    memset(&rp, 0, sizeof rp);
-                    rp.x = p.res; rp.ldx = cout; rp.w1 = w1; rp.b1 = b1; rp.w2 = p.W; rp.M = p.M; rp.k = k; rp.dil = dil; rp.gmin = -lo2; rp.gmax = rows_out - lo2; rp.epi = p;
-                    const double fl = 2.0 * 2.0 * valid_out * frac * cout * (double)cout * k;
-                    ConvGemmParams shape = p; shape.dil = dil;
-                    KScope ks(h, cout == 32 ? "voc_resblock_pair_c32" : "voc_resblock_pair_c64", fl, valid_out * frac * cout * 2.0 * 2.0, sj, &shape);
-                    if (cout == 32) launch_resblock_pair_c32(rp, sj);
-                    else launch_resblock_pair_c64(rp, sj);
-                } else if (grp) pend[((size_t)j * c.n_rb_dils + d) * 2 + 1] = p;
-                else if (gemm(h, p.dtype == DT_MX ? (cout == 64 ? "voc_conv_c64_mx" : "voc_conv_gemm_mx") : gname, p, valid_out * frac, sj)) return -1;
-            }
-            if (conc && j < 2) (void)hipEventRecord(h->ev_join[j], h->aux[j]);
-        }
-        if (grp) {
-            for (int lvl = 0; lvl < 2 * c.n_rb_dils; ++lvl) {
-                ConvGemmParams ps[3];
-                for (int j = 0; j < 3; ++j) ps[j] = pend[((size_t)j * c.n_rb_dils) * 2 + lvl];
-                if (lvl + 1 < 2 * c.n_rb_dils) {
-                    if (gemm_group3(h, "voc_conv_gemm_mx", ps, valid_out)) return -1;
-                } else {
-                    for (int j = 0; j < 3; ++j)
-                        if (gemm(h, "voc_conv_gemm_mx", ps[j], valid_out)) return -1;
-                }
+                else if (mx && cout == 32 && k3711(k) && (k - 1) * (dil + 1) <= 64 && has_wt(c1 + ".wpmx") && has_wt(c2 + ".wpmx") && c.fused_pairs == 0) pk = PairKind::FusedC32Mx;
+                // fused fp16 pair kernels: C = 32 (every k) and C = 64 with k = 3 (the HBM-bound end of the generator)
+                else if (!st.stage_mx) pk = !x3 && ((cout == 32 && k3711(k)) || (cout == 64 && k == 3)) && c.fused_pairs == 0 ? PairKind::Fused : PairKind::Layers;
+                else if (!has_mx(c1) || !has_mx(c2)) return fail(h, "MX stage: %s has no fp4 planes", (has_mx(c1) ? c2 : c1).c_str());
+                else pk = PairKind::MxLayers;
             }
         }
-        }   // row chunks
-        prev = vb.nxt[i].p;
-        prev_planes = next_up_mx;
-        ch = cout;
+        prev_planes = st.next_up_mx;
+        ch = cout; U *= s;
     }
-    WPTR(wpost, float, "voc.post.w");
-    float bpv;
-    if (get_scalar(h, "voc.post.b", &bpv)) return -1;
-    {
-        KScope ks(h, "voc_conv_post", 2.0 * n_frames * U * ch * 7, n_frames * U * (ch * (double)ves + 4.0));
-        launch_conv_post(prev, x3 ? 1 : 0, ch, wpost, bpv, 7, x3 ? 0.01f : 1.0f, h->d_frm_valid, ilog2(U), (float*)vb.wavrows.p, Rf * U, ch, h->stream);
+    vp.U = U;
+    return 0;
+}
+
+// ConvTranspose1d(k = 2s, pad = s/2) of stage i == 3-tap conv with N = s * C_out, viewed as [rows_in*s][C_out] (models.py:119)
+int voc_up(ev_handle* h, const VocPlan& vp, int i, const void* prev, VocBufs& vb, double n_frames) {
+    const VocStage& st = vp.st[i];
+    ConvGemmParams p = gemm_defaults();
+    if (voc_weights(h, "voc.up" + std::to_string(i), vp.x3, p, vp.mx)) return -1;
+    p.A = prev; p.lda = st.cin; p.M = st.rows_in; p.N = st.s * st.cout; p.K = st.cin; p.taps = 3; p.center = 1;
+    if (st.cout % 64 == 0 && st.s % 2 == 0) p.polyphase_cout = st.cout;          // (conv_gemm_mx_kernel skips the zero tap of each output phase; other kernels ignore the hint)
+    p.row_valid = h->d_frm_valid; p.valid_shift = ilog2(st.U_in); p.ldo = st.s * st.cout;
+    if (vp.x3) { p.pro_lrelu = 1; p.pro_slope = 0.1f; p.out32 = (float*)vb.xu[i].p; }     // models.py:118 (the fp16 path has it in the producer's epilogue)
+    else p.out16 = vb.xu[i].p;
+    if (st.up == UpKind::MxPlanes) mx_in(p, mx_view(vb.pl_nxt, st.rows_in, st.cin), st.cin);            // the previous stage's epilogue wrote lrelu(prev) as planes
+    else if (st.up == UpKind::MxScratch) { p.mx_scratch = vb.mx_scratch; p.mx_scratch_size = vp.scratch_bytes; }
+    else if (vp.x3) p.dtype = DT_F32S;                  // (an up-conv with planes but no plane-set input: the split kernel)
+    if (st.stage_mx) mx_out(p, mx_view(vb.pl_xu, (size_t)st.rows_out, st.cout), 0.1f);      // lrelu(x) of models.py:51, shared by the three ResBlocks
+    if (st.rpl && !vp.keep) p.out32 = nullptr;                   // (kept stages still get the raw up-conv output: the voc_up tap)
+    const char* name = p.dtype == DT_MX ? (p.N == 64 && p.K == 64 ? "voc_conv_c64_mx" : "voc_conv_gemm_mx") : vp.x3 ? "voc_conv_gemm_x3" : "voc_conv_gemm_f16";
+    return gemm(h, name, p, n_frames * st.U_in, nullptr, 2.0 / 3.0);
+}
+
+// MRF: xs += resblock(x); x = xs / num_kernels (models.py:121-126), then the next leaky_relu -- the outputs of ResBlock j's last conv in stage i
+void voc_mrf_epilogue(ConvGemmParams& p, const ev_config& c, const VocPlan& vp, int i, int j, VocBufs& vb) {
+    const VocStage& st = vp.st[i];
+    p.out_scale = 1.0f / (float)c.n_rb;
+    const MxView mv = st.mrf == MrfMode::Planes ? mx_view(vb.pl_mrf, (size_t)st.rows_out, st.cout) : MxView{};
+    if (st.mrf == MrfMode::F16Branches && j == 2) { p.add16_a = vb.mrf16a.p; p.add16_b = vb.mrf16b.p; p.ldadd = st.cout; }
+    if (st.mrf == MrfMode::Planes && j > 0) { p.acc_h = mv.h; p.acc_x4 = mv.q4[1]; p.acc_xs = mv.qs[1]; p.acc_xs_stride = mv.qs_stride; p.ldacc = st.cout; }
+    if (st.mrf == MrfMode::F32 && j > 0) { p.acc32 = (const float*)vb.mrf32.p; p.ldacc = st.cout; }
+    if (j + 1 < c.n_rb) {
+        if (st.mrf == MrfMode::F16Branches) p.out16 = (j == 0) ? vb.mrf16a.p : vb.mrf16b.p;
+        else if (st.mrf == MrfMode::Planes) { mx_out(p, mv, 1.0f); p.mxo_partial = 1; }
+        else p.out32 = (float*)vb.mrf32.p;
+    } else if (vp.x3) {
+        p.out32 = (float*)vb.nxt[i].p;               // raw MRF mean (= the voc_mrf tap); consumers apply the leaky-relu
+        if (st.next_up_mx) {
+            mx_out(p, mx_view(vb.pl_nxt, (size_t)st.rows_out, st.cout), 0.1f);      // ... or read these planes (models.py:118)
+            if (st.rpl && !vp.keep) p.out32 = nullptr;                              // the next up-conv reads only the planes: no fp32 copy of the stage output
+        }
+    } else {
+        p.post_lrelu = 1; p.post_slope = i == c.n_up - 1 ? 0.01f : 0.1f;   // models.py:118 / :127
+        p.out16 = vb.nxt[i].p;
+        if (vp.keep) { p.out32 = (float*)vb.mrf_tap[i].p; p.out32_before_post = 1; }
+    }
+}
+
+// One (ResBlock j, dilation d) pair of stage i, as the plan's kind says: xt = lrelu(c1(lrelu(x))), x = c2(xt) + x (models.py:51-56).  pend (grouped
+// levels): receives the two descriptors instead of launching them.
+int voc_pair(ev_handle* h, const VocPlan& vp, int i, int j, int d, VocBufs& vb, double valid_out, ConvGemmParams* pend) {
+    const ev_config& c = h->cfg;
+    const VocStage& st = vp.st[i];
+    const PairKind kind = st.pair[j][d];
+    const int k = c.rb_kernels[j], dil = c.rb_dils[j][d], cout = st.cout, shift = ilog2(st.U_in * st.s);
+    const size_t rows = st.rows_out;
+    const bool conc = st.issue == Issue::Streams;
+    const int bj = st.issue == Issue::Serial ? 0 : j;
+    hipStream_t sj = (conc && j < 2) ? h->aux[j] : h->stream;
+    const std::string rb = "voc.rb" + std::to_string(i * c.n_rb + j), c1 = rb + ".c1." + std::to_string(d), c2 = rb + ".c2." + std::to_string(d);
+    const char* gname = vp.x3 ? "voc_conv_gemm_x3" : "voc_conv_gemm_f16";
+    const char* mxname = cout == 64 ? "voc_conv_c64_mx" : "voc_conv_gemm_mx";
+    // x of this pair (fp32 / fp16) and the plane set of lrelu(x, .1): conv1's operand and, with rpl, conv2's residual
+    const void* xcur = d == 0 ? vb.xu[i].p : ((d - 1) % 2 == 0 ? vb.rba[bj].p : vb.rbb[bj].p);
+    const PlaneBuf& xin = d == 0 ? vb.pl_xu : ((d - 1) % 2 == 0 ? vb.pl_a[bj] : vb.pl_b[bj]);
+    ConvGemmParams p = gemm_defaults();
+    if (kind == PairKind::MxLayers) {
+        // MX stage: xt only ever exists as conv2's operand planes; x travels as fp32 (the residual) + the planes of lrelu(x); with rpl as the planes only
+        if (voc_weights(h, c1, vp.x3, p, true)) return -1;
+        mx_in(p, mx_view(xin, rows, cout), cout);
+        p.M = st.rows_out; p.N = cout; p.K = cout; p.taps = k; p.dil = dil; p.center = (k - 1) / 2;
+        p.row_valid = h->d_frm_valid; p.valid_shift = shift; p.act = ACT_LRELU; p.act_slope = 0.1f; p.ldo = cout;
+        mx_out(p, mx_view(vb.pl_t[bj], rows, cout), 1.0f);
+        if (pend) pend[0] = p;
+        else if (gemm(h, mxname, p, valid_out, sj)) return -1;
+    } else if (kind == PairKind::Layers) {
+        if (voc_weights(h, c1, vp.x3, p, false)) return -1;      // (no plane-set input here: DT_MX would only fall back to the split kernel)
+        p.A = xcur; p.lda = cout; p.M = st.rows_out; p.N = cout; p.K = cout;
+        p.taps = k; p.dil = dil; p.center = (k - 1) / 2; p.row_valid = h->d_frm_valid; p.valid_shift = shift;
+        p.pro_lrelu = 1; p.pro_slope = 0.1f; p.act = ACT_LRELU; p.act_slope = 0.1f; p.ldo = cout;
+        if (vp.x3) p.out32 = (float*)vb.tmp[bj].p; else p.out16 = vb.tmp[bj].p;
+        if (gemm(h, gname, p, valid_out, sj)) return -1;
+    }
+    // conv2 (the fused kinds: the epilogue of the pair kernel)
+    p = gemm_defaults();
+    if (voc_weights(h, c2, vp.x3, p, st.stage_mx)) return -1;
+    p.A = vb.tmp[bj].p; p.lda = cout; p.M = st.rows_out; p.N = cout; p.K = cout;
+    if (st.stage_mx) mx_in(p, mx_view(vb.pl_t[bj], rows, cout), cout);
+    p.taps = k; p.dil = 1; p.center = (k - 1) / 2; p.row_valid = h->d_frm_valid; p.valid_shift = shift;
+    p.res = xcur; p.res_dtype = vp.x3 ? DT_F32 : DT_F16; p.ldres = cout; p.ldo = cout;
+    if (st.rpl) {
+        const MxView xv = mx_view(xin, rows, cout);
+        p.res = xv.h; p.res_dtype = DT_MX; p.res_x4 = xv.q4[1]; p.res_xs = xv.qs[1]; p.res_xs_stride = xv.qs_stride; p.res_inv_slope = 10.0f;
+    }
+    if (d + 1 < c.n_rb_dils) {
+        void* dst = (d % 2 == 0) ? vb.rba[bj].p : vb.rbb[bj].p;
+        if (!st.rpl || vp.keep) { if (vp.x3) p.out32 = (float*)dst; else p.out16 = dst; }     // (rpl: the next pair reads the planes below; the fp32 copy only feeds stage taps)
+        if (st.stage_mx) mx_out(p, mx_view(d % 2 == 0 ? vb.pl_a[bj] : vb.pl_b[bj], rows, cout), 0.1f);     // the next conv1's operand
+    } else {
+        voc_mrf_epilogue(p, c, vp, i, j, vb);
+        if (conc && j == 2) {               // the MRF sum reads the other two branches
+            (void)hipStreamWaitEvent(h->stream, h->ev_join[0], 0);
+            (void)hipStreamWaitEvent(h->stream, h->ev_join[1], 0);
+        }
+        // fp32 running sum (split-precision / mx modes): rb1's last conv adds onto what rb0's wrote (the sum keeps the serial order's bits)
+        if (conc && vp.x3 && j == 1) (void)hipStreamWaitEvent(h->aux[1], h->ev_join[0], 0);
+    }
+    if (pend) { pend[1] = p; return 0; }
+    if (kind == PairKind::MxLayers || kind == PairKind::Layers) return gemm(h, kind == PairKind::MxLayers ? mxname : gname, p, valid_out, sj);
+    // conv1 -> LDS -> conv2 + residual / MRF epilogue in one persistent kernel
+    WPTR(w1, char, c1 + ".w16"); WPTR(b1, float, c1 + ".b");
+    ResPairParams rp;
+    memset(&rp, 0, sizeof rp);
+    rp.x = p.res; rp.ldx = cout; rp.w1 = w1; rp.b1 = b1; rp.w2 = p.W; rp.M = p.M; rp.k = k; rp.dil = dil; rp.epi = p;
+    const double fl = 2.0 * 2.0 * valid_out * cout * (double)cout * k;
+    ConvGemmParams shape = p; shape.dil = dil;
+    if (kind == PairKind::FusedC64Mx) {
+        WPTR(w1m, char, c1 + ".wcmx");
+        const MxView xv = mx_view(xin, rows, cout);
+        rp.w1_mx = w1m; rp.w2_mx = p.W_mx;
+        rp.epi.mx_x4[0] = xv.q4[0]; rp.epi.mx_x4[1] = xv.q4[1]; rp.epi.mx_xs[0] = xv.qs[0]; rp.epi.mx_xs[1] = xv.qs[1]; rp.epi.mx_xs_stride = xv.qs_stride;
+        KScope ks(h, "voc_resblock_pair_c64_mx", fl, valid_out * cout * 3.0625 * 2.0, sj, &shape);
+        if (launch_resblock_pair_c64_mx(rp, sj)) return fail(h, "fused MX pair (C = 64): unsupported call (k %d, dil %d)", k, dil);
+    } else if (kind == PairKind::FusedC32Mx) {
+        WPTR(w1m, char, c1 + ".wpmx"); WPTR(w2m, char, c2 + ".wpmx");
+        rp.w1_mx = w1m; rp.w2_mx = w2m; rp.gmax = st.rows_out;
+        if (c.mx_act_format != 0) rp.epi.reserved0 |= 16;          // block-scaled fp4 activation operands (rounds 3-5) instead of E5M2
+        KScope ks(h, "voc_resblock_pair_c32_mx", fl, valid_out * cout * 4.0 * 2.0, sj, &shape);
+        if (launch_resblock_pair_c32_mx(rp, sj)) return fail(h, "fused MX pair: unsupported call (k %d, dil %d)", k, dil);
+    } else {
+        rp.gmax = st.rows_out;
+        KScope ks(h, cout == 32 ? "voc_resblock_pair_c32" : "voc_resblock_pair_c64", fl, valid_out * cout * 2.0 * 2.0, sj, &shape);
+        if (cout == 32) launch_resblock_pair_c32(rp, sj);
+        else launch_resblock_pair_c64(rp, sj);
     }
     return 0;
 }
 
-int total_up(const ev_config& c) { int u = 1; for (int i = 0; i < c.n_up; ++i) u *= c.up_rates[i]; return u; }
+// The ResBlocks of stage i and their MRF sum into vb.nxt[i], issued as the plan says
+int voc_resblocks(ev_handle* h, const VocPlan& vp, int i, VocBufs& vb, double n_frames) {
+    const ev_config& c = h->cfg;
+    const VocStage& st = vp.st[i];
+    const double valid_out = n_frames * st.U_in * st.s;
+    const bool conc = st.issue == Issue::Streams, grp = st.issue == Issue::Grouped;
+    std::vector<ConvGemmParams> pend(grp ? (size_t)c.n_rb * 2 * c.n_rb_dils : 0);
+    if (conc) {
+        (void)hipEventRecord(h->ev_fork, h->stream);
+        (void)hipStreamWaitEvent(h->aux[0], h->ev_fork, 0);
+        (void)hipStreamWaitEvent(h->aux[1], h->ev_fork, 0);
+    }
+    for (int j = 0; j < c.n_rb; ++j) {
+        for (int d = 0; d < c.n_rb_dils; ++d)
+            if (voc_pair(h, vp, i, j, d, vb, valid_out, grp ? &pend[((size_t)j * c.n_rb_dils + d) * 2] : nullptr)) return -1;
+        if (conc && j < 2) (void)hipEventRecord(h->ev_join[j], h->aux[j]);
+    }
+    for (int lvl = 0; grp && lvl < 2 * c.n_rb_dils; ++lvl) {
+        ConvGemmParams ps[3];
+        for (int j = 0; j < 3; ++j) ps[j] = pend[((size_t)j * c.n_rb_dils) * 2 + lvl];
+        if (lvl + 1 < 2 * c.n_rb_dils) {
+            if (gemm_group3(h, "voc_conv_gemm_mx", ps, valid_out)) return -1;
+        } else {
+            for (int j = 0; j < 3; ++j)
+                if (gemm(h, "voc_conv_gemm_mx", ps[j], valid_out)) return -1;
+        }
+    }
+    return 0;
+}
 
-void plan_vocoder(ArenaPlan& ap, const ev_config& c, int Rf, bool keep, VocBufs& vb) {
-    const bool mx = c.vocoder_precision == EV_PREC_MX;
-    const bool x3 = c.vocoder_precision == EV_PREC_X3 || mx;
+// HiFi-GAN generator (reference models/hifigan/models.py:115-131) on channels-last rows.
+// vocoder_precision F16: fp16 activations, every leaky-relu fused into the producer (post_lrelu) or the consumer's staging.
+// vocoder_precision X3:  fp32 activations, split-precision products; every stored tensor is the RAW module output of the
+// reference (so the Appendix-C taps are the buffers themselves) and each consumer applies its leaky-relu while staging.
+int run_vocoder(ev_handle* h, const VocPlan& vp, const Buf& melin, double n_frames, VocBufs& vb) {
+    const ev_config& c = h->cfg;
+    const bool x3 = vp.x3;
+    ConvGemmParams p = gemm_defaults();
+    if (voc_weights(h, "voc.pre", x3, p)) return -1;
+    p.A = melin.p; p.lda = MEL_PAD; p.M = vp.Rf; p.N = c.up_init_ch; p.K = MEL_PAD;
+    p.taps = 7; p.center = 3; p.row_valid = h->d_frm_valid; p.valid_shift = 0; p.ldo = c.up_init_ch;
+    if (x3) p.out32 = (float*)vb.pre.p;
+    else {
+        p.out16 = vb.pre.p;
+        p.post_lrelu = 1; p.post_slope = 0.1f;      // leaky_relu(0.1) of models.py:118 fused into the producer
+        if (vp.keep) { p.out32 = (float*)vb.pre_tap.p; p.out32_before_post = 1; }
+    }
+    if (gemm(h, x3 ? "voc_conv_gemm_x3" : "voc_conv_gemm_f16", p, n_frames)) return -1;
+    for (int i = 0; i < c.n_up; ++i)
+        if (voc_up(h, vp, i, i ? vb.nxt[i - 1].p : vb.pre.p, vb, n_frames) || voc_resblocks(h, vp, i, vb, n_frames)) return -1;
+    const void* prev = vb.nxt[c.n_up - 1].p;
+    const int ch = vp.st[c.n_up - 1].cout;
+    WPTR(wpost, float, "voc.post.w");
+    float bpv;
+    if (get_scalar(h, "voc.post.b", &bpv)) return -1;
+    {
+        KScope ks(h, "voc_conv_post", 2.0 * n_frames * vp.U * ch * 7, n_frames * vp.U * (ch * (double)(x3 ? 4 : 2) + 4.0));
+        launch_conv_post(prev, x3 ? 1 : 0, ch, wpost, bpv, 7, x3 ? 0.01f : 1.0f, h->d_frm_valid, ilog2(vp.U), (float*)vb.wavrows.p, vp.Rf * vp.U, ch, h->stream);
+    }
+    return 0;
+}
+
+// the generator's share of the frame arena, as far as the plan uses it, and the packed waveform behind it
+void plan_vocoder(ArenaPlan& ap, const VocPlan& vp, VocBufs& vb) {
+    const ev_config& c = ap.h->cfg;
+    const bool x3 = vp.x3, keep = vp.keep;
+    const int Rf = vp.Rf;
     const size_t ves = x3 ? 4 : 2;
     vb.pre = ap.rows(Rf, c.up_init_ch, ves);
     if (keep && !x3) vb.pre_tap = ap.rows(Rf, c.up_init_ch, 4);
-    int ch = c.up_init_ch, U = 1;
     size_t max_elems = 0;
+    bool streams = false, planes_per_rb = false, mrf16 = false, mrf32 = false, pl_mrf = false, scratch = false;
     for (int i = 0; i < c.n_up; ++i) {
-        U *= c.up_rates[i]; ch /= 2;
-        max_elems = std::max(max_elems, (size_t)Rf * U * ch);
+        const VocStage& st = vp.st[i];
+        max_elems = std::max(max_elems, (size_t)st.rows_out * st.cout);
+        streams |= st.issue == Issue::Streams;
+        planes_per_rb |= st.stage_mx && st.issue != Issue::Serial;
+        mrf16 |= st.mrf == MrfMode::F16Branches; mrf32 |= st.mrf == MrfMode::F32; pl_mrf |= st.mrf == MrfMode::Planes;
+        scratch |= st.up == UpKind::MxScratch;
     }
     // stage buffers are re-used across stages unless taps are kept
-    ch = c.up_init_ch; U = 1;
-    Buf shared_xu{}, shared_nxt[2];
-    for (int i = 0; i < c.n_up; ++i) {
-        U *= c.up_rates[i]; ch /= 2;
-        if (keep) {
-            vb.xu[i] = ap.rows((size_t)Rf * U, ch, ves);
-            vb.nxt[i] = ap.rows((size_t)Rf * U, ch, ves);
-            if (!x3) vb.mrf_tap[i] = ap.rows((size_t)Rf * U, ch, 4);
-        }
+    for (int i = 0; keep && i < c.n_up; ++i) {
+        vb.xu[i] = ap.rows((size_t)vp.st[i].rows_out, vp.st[i].cout, ves);
+        vb.nxt[i] = ap.rows((size_t)vp.st[i].rows_out, vp.st[i].cout, ves);
+        if (!x3) vb.mrf_tap[i] = ap.rows((size_t)vp.st[i].rows_out, vp.st[i].cout, 4);
     }
     // row pitch differs per stage, so size by elements with the largest pad (C = 256 rows of slack)
     auto mk2 = [&](size_t es) { Buf b; const size_t pad = (size_t)PAD_ROWS * 512 * es; b.bytes = max_elems * es; b.base = ap.take(pad + b.bytes + pad); b.p = ap.dry ? nullptr : b.base + pad; return b; };
     if (!keep) {
-        shared_xu = mk2(ves); shared_nxt[0] = mk2(ves); shared_nxt[1] = mk2(ves);
+        const Buf shared_xu = mk2(ves), shared_nxt[2] = {mk2(ves), mk2(ves)};
         for (int i = 0; i < c.n_up; ++i) { vb.xu[i] = shared_xu; vb.nxt[i] = shared_nxt[i & 1]; }
     }
-    // fp16 mode, and small batches in the mx mode: the three ResBlocks of a stage run concurrently, each with its own intermediates
-    const bool per_rb = (c.n_rb == 3) && (!x3 || (mx && !keep && voc_small_batch(Rf)));
-    for (int j = 0; j < (per_rb ? 3 : 1); ++j) { vb.tmp[j] = mk2(ves); vb.rba[j] = mk2(ves); vb.rbb[j] = mk2(ves); }
-    if (per_rb && !x3) { vb.mrf16a = mk2(2); vb.mrf16b = mk2(2); } else vb.mrf32 = mk2(4);
-    vb.wavrows = ap.rows((size_t)Rf * total_up(c), 1, 4);
-    if (mx) {
-        // plane sets, re-used across the stages that run on the MX kernel (C % 128 == 0): sized by the largest
+    for (int j = 0; j < (streams ? 3 : 1); ++j) { vb.tmp[j] = mk2(ves); vb.rba[j] = mk2(ves); vb.rbb[j] = mk2(ves); }
+    if (mrf16) { vb.mrf16a = mk2(2); vb.mrf16b = mk2(2); }
+    if (mrf32) vb.mrf32 = mk2(4);
+    vb.wavrows = ap.rows((size_t)Rf * vp.U, 1, 4);
+    if (vp.mx) {
+        // plane sets, re-used across the stages that run on the MX kernel (C % 64 == 0): sized by the largest
         size_t hb = 0, qb = 0, sb = 0;
-        ch = c.up_init_ch; U = 1;
         for (int i = 0; i < c.n_up; ++i) {
-            U *= c.up_rates[i]; ch /= 2;
+            const int ch = vp.st[i].cout;
             if (ch % 64) continue;
-            const size_t R = (size_t)Rf * U + 2 * MX_PAD;
+            const size_t R = (size_t)vp.st[i].rows_out + 2 * MX_PAD;
             hb = std::max(hb, R * ch * 2); qb = std::max(qb, R * (ch / 2)); sb = std::max(sb, (size_t)std::max(1, ch / 128) * R * 4);
         }
-        std::vector<PlaneBuf*> sets = {&vb.pl_xu, &vb.pl_nxt, &vb.pl_mrf};
-        // (one set of intermediates per ResBlock also for large batches when their same-level convs are launched grouped: ev_config.mx_group == 0)
-        const bool per_rb_planes = per_rb || (c.n_rb == 3 && !keep && c.mx_group == 0 && c.mx_residual == 0);
-        for (int j = 0; j < (per_rb_planes ? 3 : 1); ++j) { sets.push_back(&vb.pl_t[j]); sets.push_back(&vb.pl_a[j]); sets.push_back(&vb.pl_b[j]); }
+        std::vector<PlaneBuf*> sets = {&vb.pl_xu, &vb.pl_nxt};
+        if (pl_mrf) sets.push_back(&vb.pl_mrf);
+        for (int j = 0; j < (planes_per_rb ? 3 : 1); ++j) { sets.push_back(&vb.pl_t[j]); sets.push_back(&vb.pl_a[j]); sets.push_back(&vb.pl_b[j]); }
         for (PlaneBuf* b : sets) {
             if (!hb) break;
             b->h = ap.take(hb);
             for (int i = 0; i < 2; ++i) { b->q4[i] = ap.take(qb); b->qs[i] = ap.take(sb); }
         }
-        vb.mx_scratch_bytes = (c.up_init_ch % 128 == 0) ? mx_scratch_bytes(Rf, c.up_init_ch) : 0;
-        vb.mx_scratch = vb.mx_scratch_bytes ? ap.take(vb.mx_scratch_bytes) : nullptr;
+        vb.mx_scratch = scratch ? ap.take(vp.scratch_bytes) : nullptr;
     }
+    vb.wav = ap.arr<float>((size_t)ap.h->total_frames * vp.U);
+    vb.wav_i16 = ap.arr<int16_t>((size_t)ap.h->total_frames * vp.U);
+}
+
+// frame rows of a batch: GAP rows before every utterance and after the last, padded to ROW_ALIGN
+int frame_rows(const int32_t* mel_lens, int B) {
+    int64_t rows = GAP;
+    for (int b = 0; b < B; ++b) rows += mel_lens[b] + GAP;
+    return (int)align_up((size_t)rows, ROW_ALIGN);
 }
 
 // frame layout from mel lengths (host) -> device maps; returns Rf
@@ -949,7 +954,7 @@ int build_frame_layout(ev_handle* h, ArenaPlan& ap, bool dry, int B) {
         h->mel_offs[b + 1] = h->mel_offs[b] + h->mel_lens[b];
     }
     h->total_frames = h->mel_offs[B];
-    const int Rf = (int)align_up((size_t)rows, ROW_ALIGN);
+    const int Rf = frame_rows(h->mel_lens.data(), B);
     h->d_frm_seq = ap.arr<int32_t>(Rf); h->d_frm_pos = ap.arr<int32_t>(Rf); h->d_frm_valid = ap.arr<uint8_t>(Rf);
     h->d_frm_off = ap.arr<int32_t>(B);
     h->d_frm_len = ap.arr<int32_t>(B);
@@ -1181,25 +1186,24 @@ int ev_get_kernel_stat(ev_handle* h, int idx, ev_kernel_stat* out) {
 }
 
 // ------------------------------------------------------------------- vocoder-only entry
-static int finish_wav(ev_handle* h, VocBufs& vb, float* d_wav, int16_t* d_i16, int64_t* d_scr, uint32_t flags, ev_result* out) {
-    const int U = total_up(h->cfg);
-    if (pack_level(h, vb.wavrows.p, DT_F32, 1, 1, ilog2(U), false, d_wav, d_scr)) return -1;
-    if (flags & EV_FLAG_WANT_INT16) launch_wav_to_i16(d_wav, d_i16, h->total_frames * U, h->stream);
-    out->wav = d_wav;
-    out->wav_i16 = (flags & EV_FLAG_WANT_INT16) ? d_i16 : nullptr;
+static int finish_wav(ev_handle* h, const VocPlan& vp, VocBufs& vb, int64_t* d_scr, uint32_t flags, ev_result* out) {
+    const int U = vp.U;
+    if (pack_level(h, vb.wavrows.p, DT_F32, 1, 1, ilog2(U), false, vb.wav, d_scr)) return -1;
+    if (flags & EV_FLAG_WANT_INT16) launch_wav_to_i16(vb.wav, vb.wav_i16, h->total_frames * U, h->stream);
+    out->wav = vb.wav;
+    out->wav_i16 = (flags & EV_FLAG_WANT_INT16) ? vb.wav_i16 : nullptr;
     out->total_samples = h->total_frames * U;
     return 0;
 }
 
-static void register_voc_taps(ev_handle* h, VocBufs& vb) {
+static void register_voc_taps(ev_handle* h, const VocPlan& vp, VocBufs& vb) {
     const ev_config& c = h->cfg;
-    const bool x3 = c.vocoder_precision != EV_PREC_F16;     // split-precision / MX modes: the stored tensors ARE the raw module outputs
+    const bool x3 = vp.x3;     // split-precision / MX modes: the stored tensors ARE the raw module outputs
     add_tap(h, "voc_pre", x3 ? vb.pre.p : vb.pre_tap.p, DT_F32, c.up_init_ch, c.up_init_ch, 1, 0);
-    int ch = c.up_init_ch, U = 1;
     for (int i = 0; i < c.n_up; ++i) {
-        U *= c.up_rates[i]; ch /= 2;
-        add_tap(h, ("voc_up" + std::to_string(i)).c_str(), vb.xu[i].p, x3 ? DT_F32 : DT_F16, ch, ch, 2 + i, ilog2(U));
-        add_tap(h, ("voc_mrf" + std::to_string(i)).c_str(), x3 ? vb.nxt[i].p : vb.mrf_tap[i].p, DT_F32, ch, ch, 2 + i, ilog2(U));
+        const int ch = vp.st[i].cout, shift = ilog2(vp.st[i].U_in * vp.st[i].s);
+        add_tap(h, ("voc_up" + std::to_string(i)).c_str(), vb.xu[i].p, x3 ? DT_F32 : DT_F16, ch, ch, 2 + i, shift);
+        add_tap(h, ("voc_mrf" + std::to_string(i)).c_str(), x3 ? vb.nxt[i].p : vb.mrf_tap[i].p, DT_F32, ch, ch, 2 + i, shift);
     }
 }
 
@@ -1208,9 +1212,7 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
     if (!h->wt.count("voc.post.w")) return fail(h, "ev_vocoder: weights not loaded");
     HIPCHK(h, hipSetDevice(h->device));
     const ev_config& c = h->cfg;
-    const bool keep = c.keep_stages != 0;
     const bool voc_x3 = c.vocoder_precision != EV_PREC_F16;      // X3 and MX: fp32 mel rows
-    const int U = total_up(c);
     profiling_reset(h);
     h->taps.clear();
     h->B = B; h->total_tokens = 0;
@@ -1221,9 +1223,11 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
     for (int b = 0; b < B; ++b) { elem_off[b] = eo; eo += (int64_t)c.n_mels * mel_lens[b]; }
     const size_t es = mel_is_f16 ? 2 : 4;
 
-    Buf mel16; VocBufs vb; float* d_wav = nullptr; int16_t* d_i16 = nullptr; int64_t* d_scr = nullptr; int64_t* d_eoff = nullptr;
-    void* d_melin = nullptr; int Rf = 0;
-    { int64_t rows = GAP; for (int b = 0; b < B; ++b) rows += mel_lens[b] + GAP; Rf = (int)align_up((size_t)rows, ROW_ALIGN); }
+    Buf mel16; VocBufs vb; int64_t* d_scr = nullptr; int64_t* d_eoff = nullptr;
+    void* d_melin = nullptr;
+    const int Rf = frame_rows(mel_lens, B);
+    VocPlan vp;
+    if (make_voc_plan(h, Rf, vp)) return -1;
     if ((size_t)B > PIN_MAX_B) return fail(h, "at most %zu utterances per call", PIN_MAX_B);
     if (pinned_reserve(h, PIN_BYTES)) return -1;
     size_t need = 0;
@@ -1236,9 +1240,7 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
         d_scr = ap.arr<int64_t>(3 * (size_t)B + 8);
         if (!(flags & EV_FLAG_DEVICE_INPUTS)) d_melin = ap.take((size_t)eo * es);
         mel16 = ap.rows(Rf, MEL_PAD, voc_x3 ? 4 : 2);      // the generator's input rows (fp32 in the split-precision mode)
-        plan_vocoder(ap, c, Rf, keep, vb);
-        d_wav = ap.arr<float>((size_t)h->total_frames * U);
-        d_i16 = ap.arr<int16_t>((size_t)h->total_frames * U);
+        plan_vocoder(ap, vp, vb);
         need = ap.off;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_mel_len, mel_lens, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
@@ -1249,16 +1251,16 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
     region_begin(h, "total");
     launch_mel_to_rows(melsrc, mel_is_f16, d_eoff, h->d_frm_seq, h->d_frm_pos, h->d_mel_len, mel16.p, voc_x3 ? 1 : 0, Rf, c.n_mels, MEL_PAD, h->stream);
     region_begin(h, "vocoder");
-    if (run_vocoder(h, mel16, Rf, (double)h->total_frames, vb, keep)) return -1;
+    if (run_vocoder(h, vp, mel16, (double)h->total_frames, vb)) return -1;
     HIPCHK(h, hipGetLastError());       // a rejected launch (bad configuration, missing LDS opt-in) must not return stale audio
     region_end(h, "vocoder");
     memset(out, 0, sizeof *out);
-    if (finish_wav(h, vb, d_wav, d_i16, d_scr, flags, out)) return -1;
+    if (finish_wav(h, vp, vb, d_scr, flags, out)) return -1;
     HIPCHK(h, hipGetLastError());
     region_end(h, "total");
     HIPCHK(h, hipStreamSynchronize(h->stream));
     profiling_collect(h);
-    if (keep) register_voc_taps(h, vb);
+    if (vp.keep) register_voc_taps(h, vp, vb);
     out->batch = B; out->total_frames = h->total_frames; out->mel_lens = h->mel_lens.data(); out->mel_offsets = h->mel_offs.data();
     return 0;
 }
@@ -1271,7 +1273,7 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
     if (cu[0] != 0) return fail(h, "ev_synthesize: cu_seqlens[0] must be 0");
     HIPCHK(h, hipSetDevice(h->device));
     const ev_config& c = h->cfg;
-    const int C = c.hidden, U = total_up(c);
+    const int C = c.hidden;
     const bool keep = c.keep_stages != 0;
     const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
     const int dec_prec = c.decoder_precision == EV_PREC_F16 ? DT_F16 : DT_F32;      // X3 and F32 both keep fp32 activations
@@ -1414,15 +1416,14 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
     const float* pe = h->pe_dev;
 
     // ---------------- phase 2: frame-rate arena (placed after the token arena)
-    struct FrmBufs { Buf x, hb, qkv, ctx, ffn, y, mel32, mel16, up_tap, y_tap; std::vector<Buf> ltaps; float* d_mel; float* d_wav; int16_t* d_i16; } fb;
+    struct FrmBufs { Buf x, hb, qkv, ctx, ffn, y, mel32, mel16, up_tap, y_tap; std::vector<Buf> ltaps; float* d_mel; } fb;
     VocBufs vb;
-    int Rf = 0;
+    const int Rf = frame_rows(h->mel_lens.data(), B);
+    VocPlan vp;
+    if (!(flags & EV_FLAG_NO_VOCODER) && make_voc_plan(h, Rf, vp)) return -1;
     const size_t esd = dec_prec == DT_F16 ? 2 : 4;
     const bool dec_mx = c.decoder_precision == EV_PREC_MX && C % 128 == 0;
     DecMx dmx{};
-    { int64_t r = GAP; for (int b = 0; b < B; ++b) r += h->mel_lens[b] + GAP; Rf = (int)align_up((size_t)r, ROW_ALIGN); }
-    if ((size_t)B > PIN_MAX_B) return fail(h, "at most %zu utterances per call", PIN_MAX_B);
-    if (pinned_reserve(h, PIN_BYTES)) return -1;
     size_t frm_need = 0;
     for (int pass = 0; pass < 2; ++pass) {
         ArenaPlan ap{h, 1, pass == 0};
@@ -1439,11 +1440,7 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         }
         if (keep) { fb.ltaps.resize(c.dec_layers); for (auto& b : fb.ltaps) b = ap.rows(Rf, C, 4); fb.up_tap = ap.rows(Rf, C, 4); fb.y_tap = ap.rows(Rf, C, 4); }
         fb.d_mel = ap.arr<float>((size_t)h->total_frames * c.n_mels);
-        if (!(flags & EV_FLAG_NO_VOCODER)) {
-            plan_vocoder(ap, c, Rf, keep, vb);
-            fb.d_wav = ap.arr<float>((size_t)h->total_frames * U);
-            fb.d_i16 = ap.arr<int16_t>((size_t)h->total_frames * U);
-        }
+        if (!(flags & EV_FLAG_NO_VOCODER)) plan_vocoder(ap, vp, vb);
         frm_need = ap.off;
     }
     h->Rf = Rf;
@@ -1473,10 +1470,10 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
     memset(out, 0, sizeof *out);
     if (!(flags & EV_FLAG_NO_VOCODER)) {
         region_begin(h, "vocoder");
-        if (run_vocoder(h, voc_x3 ? fb.mel32 : fb.mel16, Rf, (double)h->total_frames, vb, keep)) return -1;
+        if (run_vocoder(h, vp, voc_x3 ? fb.mel32 : fb.mel16, (double)h->total_frames, vb)) return -1;
         HIPCHK(h, hipGetLastError());
         region_end(h, "vocoder");
-        if (finish_wav(h, vb, fb.d_wav, fb.d_i16, tb.d_scr, flags, out)) return -1;
+        if (finish_wav(h, vp, vb, tb.d_scr, flags, out)) return -1;
         HIPCHK(h, hipGetLastError());
     }
     region_end(h, "total");
@@ -1493,7 +1490,7 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         if (dec_prec == DT_F16) add_tap(h, "dec_out", fb.y_tap.p, DT_F32, C, C, 1, 0);
         else add_tap(h, "dec_out", fb.y.p, DT_F32, C, C, 1, 0);
         add_tap(h, "mel", fb.mel32.p, DT_F32, MEL_PAD, c.n_mels, 1, 0);
-        if (!(flags & EV_FLAG_NO_VOCODER)) register_voc_taps(h, vb);
+        if (!(flags & EV_FLAG_NO_VOCODER)) register_voc_taps(h, vp, vb);
     }
     out->batch = B; out->total_tokens = NT; out->total_frames = h->total_frames;
     out->mel = fb.d_mel; out->durations = tb.d_dur; out->log_durations = tb.d_logd_packed; out->pitch = tb.d_pitch_packed;

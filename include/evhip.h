@@ -75,10 +75,9 @@ typedef struct ev_config {
     int32_t keep_stages;        /* !=0: keep every Appendix-C stage tap retrievable by ev_get_stage */
     int32_t token_rate_split;   /* 1 (default): fp32 token-rate GEMMs as 3 fp16 MFMAs on hi/lo splits (fp32-level accuracy,
                                    ~4x faster); 0: exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
-    int32_t vocoder_chunk_mb;   /* EV_PREC_F16 generator only (accepted and without effect in the other precisions); > 0: the ResBlocks of a generator stage run on row chunks of about this many MB per fp16 tensor so
-                                   that a chunk's intermediates stay in the 256 MB Infinity Cache (bit-identical results for any
-                                   value; measured slower than whole tensors in the full forward, hence off); 0 (default): whole
-                                   tensors */
+    int32_t vocoder_chunk_mb;   /* accepted and without effect in every precision (the field keeps the layout).  It selected row chunks sized for the
+                                   Infinity Cache for the fp16 generator's ResBlocks: bit-identical, but 1-4 % slower than whole tensors in the full
+                                   forward at every size measured, so that schedule was removed */
     int32_t vocoder_streams;    /* 0 (default): the three ResBlocks of a generator stage run concurrently (two internal streams beside
                                    the handle's); 1: everything on the handle's stream.  The pitch / energy predictors use the same two streams beside the
                                    duration predictor. */

@@ -574,10 +574,9 @@ def test_chunked_vocoding_is_bit_identical(gpu, prec):
 
 @pytest.mark.parametrize("prec", [None, "fast"], ids=["default", "fast"])
 def test_chunked_stage_execution_is_bit_identical(gpu, prec):
-    """The generator's ResBlocks run on row chunks sized for the Infinity Cache (ev_config.vocoder_chunk_mb, overlapped
-    tiling over the 6-conv chain of a ResBlock): any chunk size must give the same bits as whole-tensor execution, with chunk
-    borders falling inside utterances and next to the zero gaps between them.  The chunked schedule exists for the fp16 flow ("fast");
-    in the ABI's default precision (the plane-set flow) the field is accepted and must not change a bit either."""
+    """ev_config.vocoder_chunk_mb once selected row chunks sized for the Infinity Cache for the fp16 generator's ResBlocks (bit-identical,
+    but slower than whole tensors, and removed); the field is still accepted in every precision and must not change a bit of the
+    waveform, in the fp16 flow ("fast") as in the ABI's default precision (the plane-set flow)."""
     from emotivoice_amd.engine import EVEngine
     from oracle import synth_inputs
     _, blob, man = _weights("parity")
