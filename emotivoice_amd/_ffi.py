@@ -41,6 +41,17 @@ class ev_result(C.Structure):
     ]
 
 
+EV_PROSODY_MAX_DURATION = 1024
+
+
+class ev_prosody(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("alpha", C.c_void_p), ("pitch_scale", C.c_void_p),
+        ("pitch_shift", C.c_void_p), ("energy_scale", C.c_void_p), ("energy_shift", C.c_void_p), ("pitch", C.c_void_p),
+        ("energy", C.c_void_p), ("durations", C.c_void_p),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -95,6 +106,7 @@ SIGNATURES = {
     "ev_load_weights": (C.c_int, [_P, _P, C.c_size_t, C.c_char_p]),
     "ev_load_weights_device": (C.c_int, [_P, _P, C.c_size_t, C.c_char_p]),
     "ev_synthesize": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_uint32, C.POINTER(ev_result)]),
+    "ev_synthesize_prosody": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.POINTER(ev_prosody), C.c_uint32, C.POINTER(ev_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

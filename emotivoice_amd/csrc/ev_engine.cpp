@@ -37,6 +37,8 @@ constexpr int MEL_PAD = 96;       // n_mels padded to a multiple of 32 (MFMA K g
 constexpr size_t PIN_MAX_B = 1 << 16;                // utterances per call the pinned staging area is laid out for
 constexpr size_t PIN_FRAME = 4 * PIN_MAX_B * 4;      // byte offset of the frame-layout region (after the token-layout region)
 constexpr size_t PIN_BYTES = PIN_FRAME + 2 * PIN_MAX_B * 4;
+constexpr size_t PIN_PROSODY = PIN_BYTES;                  // ev_synthesize_prosody: its per-utterance controls, 5 floats per utterance
+constexpr size_t PIN_BYTES_PROSODY = PIN_PROSODY + 5 * PIN_MAX_B * 4;
 
 thread_local std::string g_create_error;
 
@@ -84,6 +86,7 @@ struct ev_handle {
     std::vector<int32_t> tok_off, tok_len, frm_off;
     std::map<std::string, Tap> taps;
     const int64_t* last_dur = nullptr; const int32_t* last_mel_len_dev = nullptr;
+    const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1266,8 +1269,37 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
 }
 
 // ------------------------------------------------------------------- full synthesis
-int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const int64_t* speaker, const float* style,
-                  const float* content, float alpha, uint32_t flags, ev_result* out) {
+// ev_synthesize_prosody's host-side checks (include/evhip.h): everything that can be validated without touching the device, before anything
+// is launched.  Per-token device arrays are left to the kernels (non-finite / negative = predicted, durations clamped).
+static int check_prosody(ev_handle* h, const ev_prosody* p, int B, int NT, float alpha, uint32_t flags) {
+    // one layout exists so far: a smaller size is no earlier version but a truncated struct, a larger one carries fields this library does
+    // not know.  The change that appends fields keeps accepting this size, with the missing fields read as NULL.
+    if (p->struct_size != sizeof(ev_prosody)) return fail(h, "ev_synthesize_prosody: prosody.struct_size %u != sizeof(ev_prosody) %zu", p->struct_size, sizeof(ev_prosody));
+    if (p->reserved0 != 0) return fail(h, "ev_synthesize_prosody: prosody.reserved0 must be 0");
+    if (flags & EV_FLAG_FORCED_DURATIONS) return fail(h, "ev_synthesize_prosody: prosody cannot be combined with EV_FLAG_FORCED_DURATIONS (use prosody.durations)");
+    if (!p->alpha && !(alpha > 0.f && std::isfinite(alpha))) return fail(h, "ev_synthesize_prosody: alpha %g must be > 0 and finite", (double)alpha);
+    const struct { const float* v; const char* name; } per_utt[] = {
+        {p->pitch_scale, "pitch_scale"}, {p->pitch_shift, "pitch_shift"}, {p->energy_scale, "energy_scale"}, {p->energy_shift, "energy_shift"}};
+    for (int b = 0; b < B; ++b) {
+        if (p->alpha && !(p->alpha[b] > 0.f && std::isfinite(p->alpha[b])))
+            return fail(h, "ev_synthesize_prosody: prosody.alpha[%d] = %g must be > 0 and finite", b, (double)p->alpha[b]);
+        for (const auto& f : per_utt)
+            if (f.v && !std::isfinite(f.v[b])) return fail(h, "ev_synthesize_prosody: prosody.%s[%d] = %g is not finite", f.name, b, (double)f.v[b]);
+    }
+    if (!(flags & EV_FLAG_DEVICE_INPUTS)) {
+        for (int j = 0; j < NT; ++j) {
+            if (p->pitch && std::isinf(p->pitch[j])) return fail(h, "ev_synthesize_prosody: prosody.pitch[%d] is infinite (NaN = predicted)", j);
+            if (p->energy && std::isinf(p->energy[j])) return fail(h, "ev_synthesize_prosody: prosody.energy[%d] is infinite (NaN = predicted)", j);
+            if (p->durations && (p->durations[j] < -1 || p->durations[j] > EV_PROSODY_MAX_DURATION))
+                return fail(h, "ev_synthesize_prosody: prosody.durations[%d] = %lld outside [-1, %d]", j, (long long)p->durations[j], EV_PROSODY_MAX_DURATION);
+        }
+    }
+    return 0;
+}
+
+// ev_synthesize and ev_synthesize_prosody: pros == NULL is the plain call (the launches and bits of ev_synthesize)
+static int synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const int64_t* speaker, const float* style,
+                      const float* content, float alpha, const ev_prosody* pros, uint32_t flags, ev_result* out) {
     if (!h || !ling || !cu || !speaker || !style || !content || !out || B <= 0) return fail(h, "ev_synthesize: bad argument");
     if (!h->wt.count("tok_emb")) return fail(h, "ev_synthesize: weights not loaded");
     if (cu[0] != 0) return fail(h, "ev_synthesize: cu_seqlens[0] must be 0");
@@ -1300,6 +1332,7 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         for (int b = 0; b < B; ++b)
             if (speaker[b] < 0 || speaker[b] >= c.n_speaker) return fail(h, "ev_synthesize: speaker id %lld of utterance %d outside [0, %d)", (long long)speaker[b], b, c.n_speaker);
     }
+    if (pros && check_prosody(h, pros, B, NT, alpha, flags)) return -1;
     if (ensure_pe(h, max_tok)) return -1;
 
     // ---------------- phase 1: token-rate arena
@@ -1308,7 +1341,9 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         std::vector<Buf> ltaps; Buf tokemb_tap;
         int64_t* d_ling; int64_t* d_spk; float* d_style; float* d_content; float* d_u;
         int64_t* d_dur; float* d_logd_packed; float* d_pitch_packed; float* d_energy_packed; int64_t* d_forced; int64_t* d_scr;
-    } tb;
+        // ev_synthesize_prosody only: per-utterance controls (SoA [5][B]), per-token overrides, effective durations and track rows
+        float* d_pctrl; float* d_povr_pitch; float* d_povr_energy; int64_t* d_povr_dur; int64_t* d_dur_eff; Buf pitch_eff, energy_eff;
+    } tb{};
     size_t tok_arena_end = 0;
     for (int pass = 0; pass < 2; ++pass) {
         ArenaPlan ap{h, 0, pass == 0};
@@ -1326,6 +1361,14 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         tb.t1b = ap.rows(Rt, C, 4); tb.t2b = ap.rows(Rt, C, 4); tb.t1c = ap.rows(Rt, C, 4); tb.t2c = ap.rows(Rt, C, 4);
         tb.pitch = ap.rows(Rt, 1, 4); tb.energy = ap.rows(Rt, 1, 4); tb.logd = ap.rows(Rt, 1, 4); tb.centre = ap.rows(Rt, 1, 4);
         if (keep) { tb.ltaps.resize(c.enc_layers); for (auto& b : tb.ltaps) b = ap.rows(Rt, C, 4); tb.tokemb_tap = ap.rows(Rt, C, 4); }
+        if (pros) {
+            tb.d_pctrl = ap.arr<float>(5 * (size_t)B);
+            tb.d_povr_pitch = pros->pitch ? ap.arr<float>(NT) : nullptr;
+            tb.d_povr_energy = pros->energy ? ap.arr<float>(NT) : nullptr;
+            tb.d_povr_dur = pros->durations ? ap.arr<int64_t>(NT) : nullptr;
+            tb.d_dur_eff = ap.arr<int64_t>(NT);
+            tb.pitch_eff = ap.rows(Rt, 1, 4); tb.energy_eff = ap.rows(Rt, 1, 4);
+        }
         {          // split-K partial sums (tok_splitk): 4 ranges x hidden columns
             const Buf kb = (c.token_splitk == 0 && c.token_rate_split != 0) ? ap.rows(Rt, 4 * C, 4) : Buf{};
             h->tok_ks = kb.p; h->tok_ks_bytes = kb.p ? (size_t)Rt * 4 * C * 4 : 0;
@@ -1334,7 +1377,7 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
     }
     // token layout: B offsets / lengths / cu_seqlens through the pinned token region, per-row maps built on the device
     if ((size_t)B > PIN_MAX_B) return fail(h, "ev_synthesize: at most %zu utterances per call", PIN_MAX_B);
-    if (pinned_reserve(h, PIN_BYTES)) return -1;
+    if (pinned_reserve(h, pros ? PIN_BYTES_PROSODY : PIN_BYTES)) return -1;
     {
         int32_t* off = (int32_t*)h->pinned; int32_t* len = off + B; int32_t* pcu = len + B;
         for (int b = 0; b < B; ++b) { off[b] = h->tok_off[b]; len[b] = h->tok_len[b]; }
@@ -1352,6 +1395,17 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         HIPCHK(h, hipMemcpyAsync(tb.d_content, content, (size_t)B * c.bert_dim * 4, kind, h->stream));
         if (flags & EV_FLAG_FORCED_DURATIONS)
             HIPCHK(h, hipMemcpyAsync(tb.d_forced, h->forced_dur.data(), (size_t)NT * 8, hipMemcpyHostToDevice, h->stream));
+        if (pros) {         // per-utterance controls through the pinned prosody region, per-token overrides like ling
+            float* ctrl = (float*)(h->pinned + PIN_PROSODY);
+            const float* src[5] = {pros->alpha, pros->pitch_scale, pros->pitch_shift, pros->energy_scale, pros->energy_shift};
+            const float dflt[5] = {alpha, 1.0f, 0.0f, 1.0f, 0.0f};
+            for (int i = 0; i < 5; ++i)
+                for (int b = 0; b < B; ++b) ctrl[(size_t)i * B + b] = src[i] ? src[i][b] : dflt[i];
+            HIPCHK(h, hipMemcpyAsync(tb.d_pctrl, ctrl, (size_t)5 * B * 4, hipMemcpyHostToDevice, h->stream));
+            if (pros->pitch) HIPCHK(h, hipMemcpyAsync(tb.d_povr_pitch, pros->pitch, (size_t)NT * 4, kind, h->stream));
+            if (pros->energy) HIPCHK(h, hipMemcpyAsync(tb.d_povr_energy, pros->energy, (size_t)NT * 4, kind, h->stream));
+            if (pros->durations) HIPCHK(h, hipMemcpyAsync(tb.d_povr_dur, pros->durations, (size_t)NT * 8, kind, h->stream));
+        }
     }
     region_begin(h, "total");
     region_begin(h, "am");
@@ -1392,13 +1446,27 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         if (run_predictor(h, "dur", c.dur_layers, trc, tb.xp, tb.t1, tb.t2, (float*)tb.logd.p)) return -1;
         if (conc) { (void)hipStreamWaitEvent(h->stream, h->ev_join[0], 0); (void)hipStreamWaitEvent(h->stream, h->ev_join[1], 0); }
     }
+    // prosody (after the join, on the handle's stream): the effective tracks replace the predictions as the embeddings' input
+    const float* pitch_in = (const float*)tb.pitch.p;
+    const float* energy_in = (const float*)tb.energy.p;
+    if (pros) {
+        KScope ks(h, "prosody_tracks", 0, (double)NT * 16.0);
+        launch_prosody_tracks((const float*)tb.pitch.p, (const float*)tb.energy.p, h->d_tok_seq, h->d_tok_pos, h->d_cu, tb.d_povr_pitch, tb.d_povr_energy,
+                              tb.d_pctrl, B, (float*)tb.pitch_eff.p, (float*)tb.energy_eff.p, Rt, h->stream);
+        pitch_in = (const float*)tb.pitch_eff.p; energy_in = (const float*)tb.energy_eff.p;
+    }
     {
         WPTR(wp, float, "pitch_emb.w"); WPTR(bp, float, "pitch_emb.b"); WPTR(we, float, "energy_emb.w"); WPTR(be, float, "energy_emb.b");
         KScope ks(h, "var_embed_add", 0, (double)NT * C * 8.0);
-        launch_var_embed_add((const float*)tb.xp.p, (const float*)tb.pitch.p, (const float*)tb.energy.p, wp, bp, we, be, h->d_tok_valid,
+        launch_var_embed_add((const float*)tb.xp.p, pitch_in, energy_in, wp, bp, we, be, h->d_tok_valid,
                              (float*)tb.xvar.p, Rt, C, c.var_embed_kernel, h->stream);
     }
-    { KScope ks(h, "durations", 0, 0);
+    if (pros) {
+        KScope ks(h, "durations_prosody", 0, 0);
+        launch_durations_prosody((const float*)tb.logd.p, h->d_tok_off, h->d_tok_len, B, alpha, pros->alpha ? tb.d_pctrl : nullptr, tb.d_povr_dur,
+                                 EV_PROSODY_MAX_DURATION, h->d_cu, tb.d_dur, tb.d_dur_eff, tb.d_logd_packed, (float*)tb.centre.p, h->d_mel_len, h->stream);
+    } else {
+      KScope ks(h, "durations", 0, 0);
       launch_durations((const float*)tb.logd.p, h->d_tok_off, h->d_tok_len, B, alpha, (flags & EV_FLAG_FORCED_DURATIONS) ? tb.d_forced : nullptr,
                        h->d_cu, tb.d_dur, tb.d_logd_packed, (float*)tb.centre.p, h->d_mel_len, h->stream); }
     HIPCHK(h, hipGetLastError());
@@ -1484,6 +1552,8 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
         for (int i = 0; i < c.enc_layers; ++i) add_tap(h, ("enc_l" + std::to_string(i)).c_str(), tb.ltaps[i].p, DT_F32, C, C, 0, 0);
         add_tap(h, "enc_out", tb.y.p, DT_F32, C, C, 0, 0);
         add_tap(h, "x_proj", tb.xp.p, DT_F32, C, C, 0, 0);
+        add_tap(h, "pitch_eff", pros ? tb.pitch_eff.p : tb.pitch.p, DT_F32, 1, 1, 0, 0);      // the tracks pitch_embed / energy_embed read
+        add_tap(h, "energy_eff", pros ? tb.energy_eff.p : tb.energy.p, DT_F32, 1, 1, 0, 0);
         add_tap(h, "x_var", tb.xvar.p, DT_F32, C, C, 0, 0);
         add_tap(h, "upsampled", fb.up_tap.p, DT_F32, C, C, 1, 0);
         for (int i = 0; i < c.dec_layers; ++i) add_tap(h, ("dec_l" + std::to_string(i)).c_str(), fb.ltaps[i].p, DT_F32, C, C, 1, 0);
@@ -1496,7 +1566,18 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, c
     out->mel = fb.d_mel; out->durations = tb.d_dur; out->log_durations = tb.d_logd_packed; out->pitch = tb.d_pitch_packed;
     out->energy = tb.d_energy_packed; out->mel_lens = h->mel_lens.data(); out->mel_offsets = h->mel_offs.data();
     h->last_dur = tb.d_dur;
+    h->last_dur_eff = pros ? tb.d_dur_eff : tb.d_dur;
     return 0;
+}
+
+int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const int64_t* speaker, const float* style,
+                  const float* content, float alpha, uint32_t flags, ev_result* out) {
+    return synthesize(h, B, ling, cu, speaker, style, content, alpha, nullptr, flags, out);
+}
+
+int ev_synthesize_prosody(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const int64_t* speaker, const float* style,
+                          const float* content, float alpha, const ev_prosody* prosody, uint32_t flags, ev_result* out) {
+    return synthesize(h, B, ling, cu, speaker, style, content, alpha, prosody, flags, out);
 }
 
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
@@ -1630,6 +1711,13 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
         if (!host_dst) return (int64_t)need;
         if (cap < need || !h->last_dur) return fail(h, "ev_get_stage(dur): buffer too small or no synthesis yet");
         HIPCHK(h, hipMemcpy(host_dst, h->last_dur, need, hipMemcpyDeviceToHost));
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "dur_eff")) {
+        const size_t need = (size_t)h->total_tokens * 8;
+        if (!host_dst) return (int64_t)need;
+        if (cap < need || !h->last_dur_eff) return fail(h, "ev_get_stage(dur_eff): buffer too small or no synthesis yet");
+        HIPCHK(h, hipMemcpy(host_dst, h->last_dur_eff, need, hipMemcpyDeviceToHost));
         return (int64_t)need;
     }
     if (!strcmp(name, "mel_len")) {

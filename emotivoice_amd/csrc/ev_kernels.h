@@ -180,6 +180,18 @@ void launch_var_embed_add(const float* x, const float* pitch, const float* energ
 void launch_durations(const float* log_d /* token rows */, const int32_t* tok_off, const int32_t* tok_len, int B,
                       float alpha, const int64_t* forced /* packed or null */, const int32_t* cu_seqlens_dev,
                       int64_t* dur_packed, float* logd_packed, float* centre_rows, int32_t* mel_len, hipStream_t s);
+// ev_synthesize_prosody: the same, with per-utterance duration scales alpha_b (B,) (NULL = alpha) and per-token overrides partial
+// (packed, >= 0 forced and clamped to dur_cap, negative = predicted; NULL = all predicted).  dur_packed keeps the predictions, dur_eff
+// receives the durations that are scanned.
+void launch_durations_prosody(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const float* alpha_b,
+                              const int64_t* partial, int64_t dur_cap, const int32_t* cu_seqlens_dev, int64_t* dur_packed, int64_t* dur_eff,
+                              float* logd_packed, float* centre_rows, int32_t* mel_len, hipStream_t s);
+
+// ev_synthesize_prosody: effective pitch / energy token rows = per-utterance affine transform of (override if finite, else prediction);
+// ctrl is SoA [5][B] (alpha, pitch_scale, pitch_shift, energy_scale, energy_shift); gap rows = 0.
+void launch_prosody_tracks(const float* pitch, const float* energy, const int32_t* row_seq, const int32_t* row_pos, const int32_t* cu_seqlens_dev,
+                           const float* pitch_ovr /* packed or null */, const float* energy_ovr /* packed or null */, const float* ctrl, int B,
+                           float* pitch_out, float* energy_out, int rows, hipStream_t s);
 
 // Gaussian upsampling (alignment.py:204-210) + decoder positional encoding (encoder.py:257-261).
 void launch_gauss_upsample(const float* xvar, const float* centre_rows, const int32_t* tok_off, const int32_t* tok_len,

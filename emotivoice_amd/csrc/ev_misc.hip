@@ -995,18 +995,56 @@ void launch_var_embed_add(const float* x, const float* pitch, const float* energ
                        rows, C, k);
 }
 
+// ------------------------------------------------------------------ prosody: effective pitch / energy tracks (ev_synthesize_prosody)
+// One thread per token row.  src = the caller's override where one is given and finite (NaN = "predicted"; device inputs: any
+// non-finite value), else the prediction (the last predictor LayerNorm's Linear(C, 1) head); then scale * src + shift per utterance
+// (ctrl: SoA [5][B] = alpha, pitch_scale, pitch_shift, energy_scale, energy_shift).  An identity transform copies src through
+// untouched (fmaf(1, -0, 0) would turn -0 into +0).  Gap rows are written as exact zeros: they are the k = 9 embedding conv's halo.
+__global__ __launch_bounds__(256) void prosody_tracks_kernel(const float* pitch, const float* energy, const int32_t* row_seq,
+                                                             const int32_t* row_pos, const int32_t* cu, const float* pitch_ovr,
+                                                             const float* energy_ovr, const float* ctrl, int B, float* pitch_out,
+                                                             float* energy_out, int rows) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int b = row_seq[r];
+    if (b < 0) { pitch_out[r] = 0.f; energy_out[r] = 0.f; return; }
+    const int j = cu[b] + row_pos[r];
+    float p = pitch[r], e = energy[r];
+    if (pitch_ovr) { const float v = pitch_ovr[j]; if (isfinite(v)) p = v; }
+    if (energy_ovr) { const float v = energy_ovr[j]; if (isfinite(v)) e = v; }
+    const float ps = ctrl[B + b], psh = ctrl[2 * B + b], es = ctrl[3 * B + b], esh = ctrl[4 * B + b];
+    if (!(ps == 1.0f && psh == 0.0f)) p = fmaf(ps, p, psh);
+    if (!(es == 1.0f && esh == 0.0f)) e = fmaf(es, e, esh);
+    pitch_out[r] = p;
+    energy_out[r] = e;
+}
+void launch_prosody_tracks(const float* pitch, const float* energy, const int32_t* row_seq, const int32_t* row_pos, const int32_t* cu,
+                           const float* pitch_ovr, const float* energy_ovr, const float* ctrl, int B, float* pitch_out, float* energy_out,
+                           int rows, hipStream_t s) {
+    hipLaunchKernelGGL(prosody_tracks_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, pitch, energy, row_seq, row_pos, cu, pitch_ovr,
+                       energy_ovr, ctrl, B, pitch_out, energy_out, rows);
+}
+
 // ------------------------------------------------------------------ durations + prefix sum
 // reference modules/variance.py:47-51: d = clamp(round(exp(x) - 1), 0) (round-half-even);
 // modules/alignment.py:183-202: ds*alpha, all-zero guard, mel_len = int(sum), c = cumsum(ds) - ds/2.
 // One 256-thread block per utterance; inclusive scan = wave shuffle scan + cross-wave carry in LDS.
+// PROS (ev_synthesize_prosody only; the plain call runs the <false> instantiation, i.e. the code above this extension): alpha_b = the
+// per-utterance duration scales (each block takes the integer-scan or the float path by ITS OWN alpha, so that an utterance gets the
+// same bits alone and in a mixed batch), partial = per-token overrides (>= 0 forced, clamped to dur_cap; negative = predicted).
+// dur_packed keeps the predictions; the durations the length regulator uses go to dur_eff, which the scan below reads.
+template <bool PROS>
 __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, const int32_t* tok_off, const int32_t* tok_len,
                                                         float alpha, const int64_t* forced, const int32_t* cu, int64_t* dur_packed,
-                                                        float* logd_packed, float* centre_rows, int32_t* mel_len) {
+                                                        float* logd_packed, float* centre_rows, int32_t* mel_len,
+                                                        const float* alpha_b, const int64_t* partial, int64_t dur_cap, int64_t* dur_eff) {
     __shared__ int wsum[4];
     __shared__ int carry_s;
     __shared__ int total_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int off = tok_off[b], n = tok_len[b], c0 = cu[b];
+    if (PROS && alpha_b) alpha = alpha_b[b];
+    int64_t* const dur_scan = PROS ? dur_eff : dur_packed;
     // pass 1: integer durations + total
     int local = 0;
     for (int j = tid; j < n; j += 256) {
@@ -1016,6 +1054,10 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, cons
         else d = (long)fmaxf(rintf(expf(ld) - 1.0f), 0.0f);
         dur_packed[c0 + j] = d;
         logd_packed[c0 + j] = ld;
+        if (PROS) {
+            if (partial && partial[c0 + j] >= 0) d = min((long)partial[c0 + j], (long)dur_cap);
+            dur_eff[c0 + j] = d;
+        }
         local += (int)d;
     }
     int ws = local;
@@ -1031,7 +1073,7 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, cons
         for (int base = 0; base < n; base += 256) {
             const int j = base + tid;
             int d = 0;
-            if (j < n) d = all_zero ? 1 : (int)dur_packed[c0 + j];
+            if (j < n) d = all_zero ? 1 : (int)dur_scan[c0 + j];
             int x = d;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
@@ -1057,7 +1099,7 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, cons
             float cs = 0.f;
             double tot = 0.0;
             for (int j = 0; j < n; ++j) {
-                const float d = all_zero ? 1.0f : (float)dur_packed[c0 + j] * alpha;
+                const float d = all_zero ? 1.0f : (float)dur_scan[c0 + j] * alpha;
                 cs += d;
                 tot += (double)d;
                 centre_rows[off + j] = cs - d / 2.0f;
@@ -1069,8 +1111,14 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, cons
 void launch_durations(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const int64_t* forced,
                       const int32_t* cu, int64_t* dur_packed, float* logd_packed, float* centre_rows, int32_t* mel_len,
                       hipStream_t s) {
-    hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, s, log_d, tok_off, tok_len, alpha, forced, cu, dur_packed,
-                       logd_packed, centre_rows, mel_len);
+    hipLaunchKernelGGL(durations_kernel<false>, dim3(B), dim3(256), 0, s, log_d, tok_off, tok_len, alpha, forced, cu, dur_packed,
+                       logd_packed, centre_rows, mel_len, nullptr, nullptr, (int64_t)0, nullptr);
+}
+void launch_durations_prosody(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const float* alpha_b,
+                              const int64_t* partial, int64_t dur_cap, const int32_t* cu, int64_t* dur_packed, int64_t* dur_eff,
+                              float* logd_packed, float* centre_rows, int32_t* mel_len, hipStream_t s) {
+    hipLaunchKernelGGL(durations_kernel<true>, dim3(B), dim3(256), 0, s, log_d, tok_off, tok_len, alpha, (const int64_t*)nullptr, cu,
+                       dur_packed, logd_packed, centre_rows, mel_len, alpha_b, partial, dur_cap, dur_eff);
 }
 
 // ------------------------------------------------------------------ Gaussian upsampling

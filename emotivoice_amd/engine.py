@@ -163,6 +163,22 @@ class EVEngine:
         self.last = res
         return res
 
+    def synthesize_prosody_raw(self, B: int, ling_ptr: int, cu_seqlens: np.ndarray, speaker_ptr: int, style_ptr: int,
+                               content_ptr: int, alpha: float = 1.0, prosody=None, flags: int = 0) -> _ffi.ev_result:
+        """ev_synthesize_prosody.  ``prosody``: a PackedProsody (emotivoice_amd.prosody.pack_prosody, packed with device=True when
+        ``flags`` has EV_FLAG_DEVICE_INPUTS) or None (= ev_synthesize)."""
+        if prosody is not None and prosody.device != bool(flags & _ffi.EV_FLAG_DEVICE_INPUTS):
+            raise ValueError("the prosody arrays were packed for %s inputs, the call passes %s inputs"
+                             % ("device" if prosody.device else "host", "device" if flags & _ffi.EV_FLAG_DEVICE_INPUTS else "host"))
+        cu = np.ascontiguousarray(cu_seqlens, np.int32)
+        res = _ffi.ev_result()
+        self._check(self._lib.ev_synthesize_prosody(self._h, B, C.c_void_p(ling_ptr), cu.ctypes.data_as(C.c_void_p),
+                                                    C.c_void_p(speaker_ptr), C.c_void_p(style_ptr), C.c_void_p(content_ptr),
+                                                    C.c_float(alpha), C.byref(prosody.struct) if prosody is not None else None,
+                                                    flags, C.byref(res)))
+        self.last = res
+        return res
+
     def vocoder_raw(self, B: int, mel_ptr: int, mel_is_f16: bool, mel_lens: np.ndarray, flags: int = 0) -> _ffi.ev_result:
         ml = np.ascontiguousarray(mel_lens, np.int32)
         res = _ffi.ev_result()
@@ -205,10 +221,16 @@ class EVEngine:
 
     # -- numpy convenience API
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
-        reference builds per input line (inference_am_vocoder_joint.py:113-119)."""
+        reference builds per input line (inference_am_vocoder_joint.py:113-119).
+        prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
+        for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way."""
         B = len(utts)
+        packed = None
+        if prosody is not None:
+            from .prosody import pack_prosody
+            packed = pack_prosody(prosody, [len(u["ling"]) for u in utts], alpha, forced=forced_durations is not None)
         ling = np.ascontiguousarray(np.concatenate([np.asarray(u["ling"], np.int64) for u in utts]))
         cu = np.zeros(B + 1, np.int32)
         cu[1:] = np.cumsum([len(u["ling"]) for u in utts])
@@ -223,7 +245,11 @@ class EVEngine:
         if forced_durations is not None:
             self.set_forced_durations(forced_durations)
             flags |= _ffi.EV_FLAG_FORCED_DURATIONS
-        res = self.synthesize_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, alpha, flags)
+        if packed is None:
+            res = self.synthesize_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, alpha, flags)
+        else:
+            res = self.synthesize_prosody_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, alpha,
+                                              packed, flags)
         out = self.result_to_numpy(res, want_int16)
         out["cu_seqlens"] = cu
         return out
@@ -261,7 +287,7 @@ class EVEngine:
         need = self._lib.ev_get_stage(self._h, name.encode(), None, 0)
         if need < 0:
             raise EVError(self._lib.ev_last_error(self._h).decode())
-        if name in ("dur", "mel_len"):
+        if name in ("dur", "dur_eff", "mel_len"):
             out = np.empty(need // 8, np.int64)
         else:
             out = np.empty(need // 4, np.float32)

@@ -6,7 +6,9 @@ pyrubberband time-stretching (:170-171).  Here:
     ``max_tokens``) and synthesised in ONE ev_synthesize call -- the engine evaluates every utterance with B = 1 semantics, so
     batching changes latency and throughput, never the audio (tests/test_gpu_parity.py::test_batch_invariance_bit_exact);
   * ``speed`` maps to the model's own duration scale alpha = 1 / speed (GaussianUpsampling's alpha, modules/alignment.py:183)
-    instead of a time-stretch of the finished waveform; requests with different speeds form separate batches;
+    instead of a time-stretch of the finished waveform; requests with different speeds form separate batches -- unless the
+    batcher is built with ``mixed_prosody=True``: then every request's speed / pitch / energy controls travel with it into one
+    ev_synthesize_prosody call (``engine_prosody_synth_fn``), whatever the mix;
   * the text front-end (G2P) and the tokenizer are host-side callables supplied by the caller (the reference's frontend.py /
     AutoTokenizer), the style encoder is the device SimBERT (emotivoice_amd/simbert.py) or any ``text -> 768-vector`` callable.
 Response formats: ``wav`` (16-bit PCM in a RIFF container) and ``pcm`` (raw little-endian int16); mp3 needs pydub / ffmpeg,
@@ -14,6 +16,7 @@ which are not part of this package.
 """
 from __future__ import annotations
 
+import dataclasses
 import io
 import logging
 import queue
@@ -26,6 +29,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .prosody import Prosody
 from .text_io import wav_float_to_int16
 
 
@@ -40,6 +44,7 @@ class SynthesisRequest:
     content: object                  # (768,) array, or the content text
     alpha: float = 1.0               # duration scale (1 / speed)
     future: Future = field(default_factory=Future)
+    prosody: Optional[Prosody] = None     # per-utterance controls (mixed_prosody batchers only); its speed / alpha, if set, wins over ``alpha``
     t_submit: float = field(default_factory=time.perf_counter)
 
 
@@ -48,11 +53,14 @@ class DynamicBatcher:
     One worker thread owns the engine handle (the handle is not thread-safe, include/evhip.h): everything that touches the
     handle runs on that thread -- including the style / content embedding when the embedder lives on the same handle
     (``embed_batch_fn(texts) -> (len(texts), 768)``: requests then carry the TEXTS and the worker embeds a whole batch at once,
-    which also batches the BERT forward)."""
+    which also batches the BERT forward).
+    ``mixed_prosody=True``: requests are no longer grouped by ``alpha``; ``synth_fn(utts, prosodies)`` then receives one Prosody per
+    utterance (speed folded in as its alpha) -- ``engine_prosody_synth_fn``."""
 
     def __init__(self, synth_fn: Callable[[List[dict], float], Sequence[np.ndarray]], max_batch: int = 32, max_wait_ms: float = 5.0,
                  max_tokens: int = 16384, embed_batch_fn: Optional[Callable[[List[str]], np.ndarray]] = None,
-                 n_vocab: Optional[int] = None, n_speaker: Optional[int] = None, max_len: int = 4096):
+                 n_vocab: Optional[int] = None, n_speaker: Optional[int] = None, max_len: int = 4096, mixed_prosody: bool = False):
+        self.mixed_prosody = mixed_prosody
         self.synth_fn, self.max_batch, self.max_wait, self.max_tokens = synth_fn, max_batch, max_wait_ms * 1e-3, max_tokens
         self.embed_batch_fn, self.n_vocab, self.n_speaker, self.max_len = embed_batch_fn, n_vocab, n_speaker, max_len
         self._q: "queue.Queue[Optional[SynthesisRequest]]" = queue.Queue()
@@ -65,7 +73,7 @@ class DynamicBatcher:
         self._thread = threading.Thread(target=self._loop, name="ev-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, ling, speaker: int, style, content, alpha: float = 1.0) -> Future:
+    def submit(self, ling, speaker: int, style, content, alpha: float = 1.0, prosody: Optional[Prosody] = None) -> Future:
         """Validation happens HERE (ValueError -> the handler's 400), so that one malformed request cannot take the requests
         batched with it down: the reference serves every request on its own (openaiapi.py:159-184)."""
         ling = np.asarray(ling, np.int64).reshape(-1)
@@ -79,6 +87,11 @@ class DynamicBatcher:
             raise ValueError("speaker id out of range")
         if not (alpha > 0 and np.isfinite(alpha)):
             raise ValueError("alpha must be positive")
+        if prosody is not None:
+            if not self.mixed_prosody:
+                raise ValueError("prosody controls need a batcher with mixed_prosody=True")
+            from .prosody import pack_prosody
+            pack_prosody([prosody], [ling.size], alpha)        # validation only: a bad control fails its own request, not the batch
 
         def emb(x):
             if isinstance(x, str):
@@ -89,7 +102,7 @@ class DynamicBatcher:
             if not np.isfinite(x).all():
                 raise ValueError("embedding is not finite")
             return x
-        req = SynthesisRequest(ling, int(speaker), emb(style), emb(content), float(alpha))
+        req = SynthesisRequest(ling, int(speaker), emb(style), emb(content), float(alpha), prosody=prosody)
         with self._lock:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -140,7 +153,7 @@ class DynamicBatcher:
             keep = []
             for r in self._carry:                           # carried requests first (they have waited longest)
                 cur = r
-                if r.alpha == first.alpha and len(batch) < self.max_batch and tokens + len(r.ling) <= self.max_tokens:
+                if (self.mixed_prosody or r.alpha == first.alpha) and len(batch) < self.max_batch and tokens + len(r.ling) <= self.max_tokens:
                     batch.append(r); tokens += len(r.ling)
                 else:
                     keep.append(r)
@@ -158,7 +171,7 @@ class DynamicBatcher:
                     break
                 batch.append(r)                             # (taken off the queue: from here on it is somebody's responsibility)
                 cur = r
-                if r.alpha == first.alpha and tokens + len(r.ling) <= self.max_tokens:
+                if (self.mixed_prosody or r.alpha == first.alpha) and tokens + len(r.ling) <= self.max_tokens:
                     tokens += len(r.ling)
                 else:
                     batch.pop()
@@ -183,7 +196,11 @@ class DynamicBatcher:
                 for r in batch:
                     r.style = table[r.style] if isinstance(r.style, str) else r.style
                     r.content = table[r.content] if isinstance(r.content, str) else r.content
-        wavs = self.synth_fn([dict(ling=r.ling, speaker=r.speaker, style=r.style, content=r.content) for r in batch], batch[0].alpha)
+        utts = [dict(ling=r.ling, speaker=r.speaker, style=r.style, content=r.content) for r in batch]
+        if self.mixed_prosody:
+            wavs = self.synth_fn(utts, [_request_prosody(r) for r in batch])
+        else:
+            wavs = self.synth_fn(utts, batch[0].alpha)
         if len(wavs) != len(batch):
             raise RuntimeError("synth_fn returned %d waveforms for %d requests" % (len(wavs), len(batch)))
         for r, w in zip(batch, wavs):
@@ -240,6 +257,14 @@ class DynamicBatcher:
                 time.sleep(min(0.5, 0.01 * consecutive))      # a persistent failure (e.g. in _take_batch) must not spin a core
 
 
+def _request_prosody(r: SynthesisRequest) -> Prosody:
+    """The controls a request travels with: its Prosody, with the request's alpha where the Prosody sets no speed of its own."""
+    p = r.prosody if r.prosody is not None else Prosody()
+    if p.speed is None and p.alpha is None:
+        p = dataclasses.replace(p, alpha=r.alpha)
+    return p
+
+
 def _resolve(future: Future, result=None, exception: Optional[BaseException] = None):
     """set_result / set_exception that tolerates a Future its client has cancelled or that was resolved already."""
     try:
@@ -256,6 +281,11 @@ def _resolve(future: Future, result=None, exception: Optional[BaseException] = N
 def engine_synth_fn(engine) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
     """``synth_fn`` of a DynamicBatcher for an EVEngine."""
     return lambda utts, alpha: engine.synthesize(utts, alpha=alpha)["wav_list"]
+
+
+def engine_prosody_synth_fn(engine) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch."""
+    return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies)["wav_list"]
 
 
 def engine_embed_batch_fn(engine, tokenize: Callable[[str], Sequence[int]]) -> Callable[[List[str]], np.ndarray]:
@@ -292,18 +322,26 @@ class TTSService:
         if embed is None and batcher.embed_batch_fn is None:
             raise ValueError("TTSService needs embed= or a batcher with embed_batch_fn=")
 
-    def submit(self, text: str, voice: str, prompt: str = "", speed: float = 1.0) -> Future:
+    def submit(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, pitch_shift: float = 0.0, pitch_scale: float = 1.0,
+               energy_scale: float = 1.0) -> Future:
+        """``pitch_shift`` / ``pitch_scale`` / ``energy_scale`` (extension fields, in the predictor's normalised units; include/evhip.h
+        ev_prosody): anything but the identity needs a batcher with ``mixed_prosody=True``."""
         if not (0.25 <= speed <= 4.0):
             raise ValueError("speed must be within [0.25, 4]")
+        prosody = None
+        if (pitch_shift, pitch_scale, energy_scale) != (0.0, 1.0, 1.0):
+            prosody = Prosody(pitch_shift=float(pitch_shift), pitch_scale=float(pitch_scale), energy_scale=float(energy_scale))
         ling = np.array([self.token2id[ph] for ph in self.g2p(text).split()], np.int64)       # KeyError like openaiapi.py:128
         if ling.size == 0:
             raise ValueError("input has no phonemes")
         if self.embed is None:
-            return self.batcher.submit(ling, self.speaker2id[voice], prompt, text, alpha=1.0 / speed)
-        return self.batcher.submit(ling, self.speaker2id[voice], self.embed(prompt), self.embed(text), alpha=1.0 / speed)
+            return self.batcher.submit(ling, self.speaker2id[voice], prompt, text, alpha=1.0 / speed, prosody=prosody)
+        return self.batcher.submit(ling, self.speaker2id[voice], self.embed(prompt), self.embed(text), alpha=1.0 / speed, prosody=prosody)
 
-    def speech(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, response_format: str = "wav", timeout: float = 120.0) -> bytes:
-        return encode_audio(self.submit(text, voice, prompt, speed).result(timeout=timeout), response_format, self.sample_rate)
+    def speech(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, response_format: str = "wav", timeout: float = 120.0,
+               pitch_shift: float = 0.0, pitch_scale: float = 1.0, energy_scale: float = 1.0) -> bytes:
+        fut = self.submit(text, voice, prompt, speed, pitch_shift, pitch_scale, energy_scale)
+        return encode_audio(fut.result(timeout=timeout), response_format, self.sample_rate)
 
 
 try:          # the request schema lives at module level: FastAPI resolves the handler's annotations in the module namespace
@@ -318,6 +356,10 @@ try:          # the request schema lives at module level: FastAPI resolves the h
         model: Optional[str] = "emoti-voice"
         response_format: Optional[str] = "wav"
         speed: Optional[float] = 1.0
+        # extensions (not in the reference schema): prosody controls in the predictor's normalised units, identity by default
+        pitch_shift: Optional[float] = 0.0
+        pitch_scale: Optional[float] = 1.0
+        energy_scale: Optional[float] = 1.0
 except ImportError:          # pydantic / fastapi are only needed by create_app
     SpeechRequest = None
 
@@ -331,7 +373,10 @@ def create_app(service: TTSService):
     @app.post("/v1/audio/speech")
     def text_to_speech(req: SpeechRequest):
         try:
-            data = service.speech(req.input, req.voice, req.prompt or "", req.speed or 1.0, req.response_format or "wav")
+            data = service.speech(req.input, req.voice, req.prompt or "", req.speed or 1.0, req.response_format or "wav",
+                                  pitch_shift=req.pitch_shift if req.pitch_shift is not None else 0.0,
+                                  pitch_scale=req.pitch_scale if req.pitch_scale is not None else 1.0,
+                                  energy_scale=req.energy_scale if req.energy_scale is not None else 1.0)
         except KeyError as e:
             raise HTTPException(status_code=400, detail="unknown voice or phoneme: %s" % e)
         except ValueError as e:

@@ -10,6 +10,9 @@
  *   ev_load_weights[_device] <- .load_state_dict(ckpt['generator'])           (inference_am_vocoder_joint.py:72-73)
  *   ev_synthesize        <- JETSGenerator.forward, inference branch           (jets.py:50-71 ->
  *                           model_open_source.py:102-163 -> models/hifigan/models.py:115-131)
+ *   ev_synthesize_prosody <- the same, with per-utterance speed / pitch / energy controls and per-token prosody overrides
+ *                           fed through the embeddings and the length regulator exactly where the teacher-forced branch
+ *                           feeds ps / es / ds (model_open_source.py:113-139); an extension, not part of the reference call
  *   ev_vocoder           <- HiFiGANGenerator.forward on pre-computed mels     (models/hifigan/models.py:115-131)
  *   ev_get_stage         <- register_forward_hook taps used by the parity tests
  *   ev_last_error        <- Python exceptions (no exceptions cross the ABI)
@@ -187,6 +190,48 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_se
                   const int64_t* speaker, const float* style, const float* content,
                   float alpha, uint32_t flags, ev_result* out);
 
+/* Per-utterance prosody control (ev_synthesize_prosody).  For utterance b and its token j (packed index cu_seqlens[b] + j):
+ *   p_src[j] = pitch[j] if pitch is given and pitch[j] is not NaN, else the predicted pitch;  e_src[j] likewise from energy;
+ *   d_src[j] = durations[j] if durations is given and durations[j] >= 0, else the predicted clamp(round(exp(logd) - 1), 0);
+ *   p[j] = pitch_scale[b] * p_src[j] + pitch_shift[b],  e[j] = energy_scale[b] * e_src[j] + energy_shift[b]
+ *          (one fmaf; an utterance whose scale is 1 and shift 0 gets p_src unchanged, -0.0 included) -- p / e go into pitch_embed /
+ *          energy_embed where the predictions go in ev_synthesize.  Units are the predictor's own: the checkpoint's normalised tracks;
+ *   d_src is scaled by alpha[b] in the Gaussian upsampling exactly as ev_synthesize's alpha scales every utterance (float scale,
+ *          mel_len = int(sum), all-zero guard); alpha == NULL: the call's alpha for every utterance.
+ * ev_result.pitch / .energy / .durations / .log_durations keep returning the PREDICTIONS, so that a caller can edit them and send them back.
+ * Identity controls (every pointer NULL, or scale 1, shift 0, all-NaN pitch / energy, all -1 durations, alpha[b] == alpha) give the
+ * bits of ev_synthesize.  What was used can be read back with ev_get_stage: "dur_eff" (int64, every call) and, with keep_stages,
+ * "pitch_eff" / "energy_eff" (the tracks the embeddings read).
+ * Ordering of device per-token arrays: like ling, they are read in the order of the handle's stream (ev_set_stream), which the internal
+ * stream gives no ordering against any other stream, the null stream included.  The caller makes sure they are written before the call:
+ * produce them on the stream set with ev_set_stream, or synchronise the producing stream first (emotivoice_amd.prosody.pack_prosody does).
+ * The per-utterance arrays are always HOST memory and are validated: alpha[b] > 0 and finite, scales / shifts finite.  The per-token arrays
+ * follow EV_FLAG_DEVICE_INPUTS like ling.  Host per-token values are validated too: pitch / energy must not be +-inf, durations must lie
+ * in [-1, EV_PROSODY_MAX_DURATION].  Device per-token values cannot be checked without a sync; the kernels treat a non-finite pitch /
+ * energy as "predicted", a negative duration as "predicted" and clamp durations at EV_PROSODY_MAX_DURATION. */
+#define EV_PROSODY_MAX_DURATION 1024      /* frames per token (~16 s at 16 kHz / 256) */
+typedef struct ev_prosody {
+    uint32_t struct_size;            /* sizeof(ev_prosody): lets the struct grow later without a new entry point (a version that appends
+                                        fields keeps accepting this size; today any other size is rejected) */
+    uint32_t reserved0;              /* 0 */
+    const float*   alpha;            /* (B,) HOST, duration scale per utterance (> 0, finite) or NULL = the call's alpha */
+    const float*   pitch_scale;      /* (B,) HOST or NULL = 1 */
+    const float*   pitch_shift;      /* (B,) HOST or NULL = 0 */
+    const float*   energy_scale;     /* (B,) HOST or NULL = 1 */
+    const float*   energy_shift;     /* (B,) HOST or NULL = 0 */
+    const float*   pitch;            /* (total_tokens,) packed like ling, NaN = predicted; NULL = all predicted */
+    const float*   energy;           /* same */
+    const int64_t* durations;        /* (total_tokens,) >= 0 forced, -1 predicted; NULL = all predicted */
+} ev_prosody;
+
+/* ev_synthesize with prosody controls (semantics above).  prosody == NULL is exactly ev_synthesize.  Rejected (negative return, message
+ * naming the field, nothing launched): struct_size != sizeof(ev_prosody), reserved0 != 0, an invalid control value, and prosody combined
+ * with EV_FLAG_FORCED_DURATIONS.  Costs one small token-rate launch (prosody_tracks) more than ev_synthesize, and the durations kernel
+ * runs its prosody instantiation (durations_prosody). */
+int ev_synthesize_prosody(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_seqlens, const int64_t* speaker,
+                          const float* style, const float* content, float alpha, const ev_prosody* prosody,
+                          uint32_t flags, ev_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 
@@ -224,7 +269,8 @@ int ev_style_embed(ev_handle* h, int B, const int64_t* input_ids, const int64_t*
 /* Copy a named stage tap (SURVEY.md Appendix C names) of the LAST call to host memory as fp32
  * (integer taps as int64), in the packed utterance-major layout (rows x channels, valid rows only).
  * Returns the number of bytes written, or a negative error (e.g. cap too small, unknown name,
- * keep_stages disabled).  With host_dst == NULL returns the required size. */
+ * keep_stages disabled).  With host_dst == NULL returns the required size.  "dur" / "dur_eff" (int64, always available): the durations
+ * ev_result.durations holds / the durations the length regulator used (they differ only where ev_synthesize_prosody overrides them). */
 int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap);
 
 /* Convenience for callers without a HIP runtime binding (numpy/ctypes): synchronous device -> host copy
