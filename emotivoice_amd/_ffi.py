@@ -52,6 +52,17 @@ class ev_prosody(C.Structure):
     ]
 
 
+EV_ALIGN_MAX_TOKENS, EV_ALIGN_MAX_FRAMES = 2048, 16384
+
+
+class ev_align_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_tokens", C.c_int32), ("reserved0", C.c_int32), ("total_frames", C.c_int64),
+        ("durations", C.c_void_p), ("pitch", C.c_void_p), ("energy", C.c_void_p), ("score", C.c_void_p),
+        ("mel_lens", C.POINTER(C.c_int32)), ("mel_offsets", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -107,6 +118,7 @@ SIGNATURES = {
     "ev_load_weights_device": (C.c_int, [_P, _P, C.c_size_t, C.c_char_p]),
     "ev_synthesize": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_uint32, C.POINTER(ev_result)]),
     "ev_synthesize_prosody": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.POINTER(ev_prosody), C.c_uint32, C.POINTER(ev_result)]),
+    "ev_align": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_uint32, C.POINTER(ev_align_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

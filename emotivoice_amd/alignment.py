@@ -1,0 +1,75 @@
+"""Forced alignment helpers on top of ``EVEngine.align`` (ev_align, include/evhip.h).
+
+``timestamps`` turns durations into per-phoneme times, ``prosody_from_alignment`` turns an alignment into per-token overrides for
+``ev_synthesize_prosody`` (the values the reference's teacher-forced branch feeds as ds / ps / es, model_open_source.py:113-139), and
+``transfer`` re-voices recordings: align them with their own conditioning, then synthesise the same phonemes with another speaker /
+prompt and the recording's timing (and, optionally, its intonation and energy).
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .prosody import MAX_DURATION, Prosody
+
+
+def timestamps(durations, hop: int = 256, sr: int = 16000) -> List[Tuple[float, float]]:
+    """(start_s, end_s) of every token of one utterance from its durations in mel frames (hop samples per frame at ``sr``)."""
+    d = np.asarray(durations, np.int64).reshape(-1)
+    if (d < 0).any():
+        raise ValueError("durations must be >= 0")
+    ends = np.cumsum(d)
+    starts = ends - d
+    f = float(hop) / float(sr)
+    return [(float(a) * f, float(b) * f) for a, b in zip(starts, ends)]
+
+
+def _split(aligned: Dict[str, object], key: str):
+    cu = np.asarray(aligned["cu_seqlens"])
+    v = aligned.get(key)
+    if v is None:
+        return None
+    v = np.asarray(v)
+    return [v[cu[b]:cu[b + 1]] for b in range(len(cu) - 1)]
+
+
+def prosody_from_alignment(aligned: Dict[str, object], pitch: bool = True, energy: bool = True) -> List[Prosody]:
+    """One Prosody per utterance of an ``EVEngine.align`` result: the aligned durations, and the per-token pitch / energy means where
+    ``pitch`` / ``energy`` ask for them (an alignment made without frame tracks has none: asking for them is an error).  A duration above
+    EV_PROSODY_MAX_DURATION is an error that names the utterance and token."""
+    durs = _split(aligned, "durations")
+    ps = _split(aligned, "pitch") if pitch else None
+    es = _split(aligned, "energy") if energy else None
+    if pitch and ps is None:
+        raise ValueError("the alignment has no pitch: align with per-frame pitch tracks, or pass pitch=False")
+    if energy and es is None:
+        raise ValueError("the alignment has no energy: align with per-frame energy tracks, or pass energy=False")
+    out = []
+    for b, d in enumerate(durs):
+        big = np.nonzero(d > MAX_DURATION)[0]
+        if big.size:
+            j = int(big[0])
+            raise ValueError("utterance %d, token %d: aligned duration %d frames > EV_PROSODY_MAX_DURATION %d" % (b, j, int(d[j]), MAX_DURATION))
+        out.append(Prosody(durations=np.asarray(d, np.int64), pitch=None if ps is None else np.asarray(ps[b], np.float32),
+                           energy=None if es is None else np.asarray(es[b], np.float32)))
+    return out
+
+
+def transfer(engine, src_utts: Sequence[dict], mels: Sequence[np.ndarray], dst_utts: Sequence[dict],
+             pitch_frames: Optional[Sequence[np.ndarray]] = None, energy_frames: Optional[Sequence[np.ndarray]] = None,
+             pitch: bool = True, energy: bool = True, vocoder: bool = True) -> Dict[str, object]:
+    """Re-voice recordings: align ``mels`` (one (n_mels, T_b) array per utterance) with the SOURCE conditioning of ``src_utts``, then
+    synthesise ``dst_utts`` -- the same phonemes with the target speaker / style / content -- with the recording's durations, and its
+    per-token pitch / energy where frame tracks are given and ``pitch`` / ``energy`` ask for them.  Utterance b of both lists must carry the
+    same ``ling``.  Returns the synthesis result with the alignment under "alignment"."""
+    if len(src_utts) != len(dst_utts):
+        raise ValueError("%d source and %d target utterances" % (len(src_utts), len(dst_utts)))
+    for b, (s, d) in enumerate(zip(src_utts, dst_utts)):
+        if not np.array_equal(np.asarray(s["ling"], np.int64), np.asarray(d["ling"], np.int64)):
+            raise ValueError("utterance %d: source and target phonemes (ling) differ" % b)
+    aligned = engine.align(src_utts, mels, pitch=pitch_frames, energy=energy_frames)
+    pros = prosody_from_alignment(aligned, pitch=pitch and pitch_frames is not None, energy=energy and energy_frames is not None)
+    out = engine.synthesize(dst_utts, prosody=pros, vocoder=vocoder)
+    out["alignment"] = aligned
+    return out

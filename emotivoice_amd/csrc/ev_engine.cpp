@@ -73,7 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[3] = {nullptr, nullptr, nullptr}; size_t arena_bytes[3] = {0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT
+    char* arena[4] = {nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[4] = {0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -87,6 +88,9 @@ struct ev_handle {
     std::map<std::string, Tap> taps;
     const int64_t* last_dur = nullptr; const int32_t* last_mel_len_dev = nullptr;
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
+    // ev_align: host halves of its result (kept apart from the synthesis' mel_lens / mel_offs) and the "log_p_attn" stage of the last call
+    std::vector<int32_t> aln_mel_lens; std::vector<int64_t> aln_mel_offs; std::vector<AlignSeq> aln_seqs;
+    const float* aln_lp = nullptr; int64_t aln_lp_elems = 0;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1099,7 +1103,7 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 3; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 4; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->sblob) (void)hipFree(h->sblob);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->pe_dev) (void)hipFree(h->pe_dev);
@@ -1217,7 +1221,7 @@ int ev_vocoder(ev_handle* h, int B, const void* mel, int mel_is_f16, const int32
     const ev_config& c = h->cfg;
     const bool voc_x3 = c.vocoder_precision != EV_PREC_F16;      // X3 and MX: fp32 mel rows
     profiling_reset(h);
-    h->taps.clear();
+    h->taps.clear(); h->aln_lp = nullptr;
     h->B = B; h->total_tokens = 0;
     h->mel_lens.assign(mel_lens, mel_lens + B);
     for (int b = 0; b < B; ++b) if (mel_lens[b] <= 0) return fail(h, "ev_vocoder: mel_lens[%d] = %d", b, mel_lens[b]);
@@ -1311,7 +1315,7 @@ static int synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* c
     const int dec_prec = c.decoder_precision == EV_PREC_F16 ? DT_F16 : DT_F32;      // X3 and F32 both keep fp32 activations
     const bool voc_x3 = c.vocoder_precision != EV_PREC_F16;      // X3 and MX: fp32 mel rows
     profiling_reset(h);
-    h->taps.clear();
+    h->taps.clear(); h->aln_lp = nullptr;
     h->B = B;
     const int NT = cu[B];
     h->total_tokens = NT;
@@ -1580,6 +1584,181 @@ int ev_synthesize_prosody(ev_handle* h, int B, const int64_t* ling, const int32_
     return synthesize(h, B, ling, cu, speaker, style, content, alpha, prosody, flags, out);
 }
 
+// ------------------------------------------------------------------- forced alignment (include/evhip.h: ev_align)
+int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const int64_t* speaker, const float* style, const float* content,
+             const void* mel, int mel_is_f16, const int32_t* mel_lens, const float* pitch_frames, const float* energy_frames, uint32_t flags,
+             ev_align_result* out) {
+    if (!h) return -1;
+    if (!ling || !cu || !speaker || !style || !content || !mel || !mel_lens || !out || B <= 0) return fail(h, "ev_align: bad argument");
+    if (out->struct_size != sizeof(ev_align_result))
+        return fail(h, "ev_align: out->struct_size %u != sizeof(ev_align_result) %zu", out->struct_size, sizeof(ev_align_result));
+    if (!h->wt.count("tok_emb")) return fail(h, "ev_align: weights not loaded");
+    if (!h->wt.count("aln.t1.b")) return fail(h, "ev_align: the weight blob has no aligner (aln.*): pack a state dict that carries am.alignment_module.*");
+    if (cu[0] != 0) return fail(h, "ev_align: cu_seqlens[0] must be 0");
+    if ((size_t)B > PIN_MAX_B) return fail(h, "ev_align: at most %zu utterances per call", PIN_MAX_B);
+    const ev_config& c = h->cfg;
+    const int C = c.hidden;
+    const bool keep = c.keep_stages != 0;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    const int NT = cu[B];
+    int max_tok = 0, max_frames = 0;
+    int64_t rows = GAP, lp_elems = 0, total_frames = 0;
+    std::vector<int32_t> tok_off(B), tok_len(B);
+    for (int b = 0; b < B; ++b) {
+        const int n = cu[b + 1] - cu[b], T = mel_lens[b];
+        if (n <= 0) return fail(h, "ev_align: utterance %d has %d tokens", b, n);
+        if (n > EV_ALIGN_MAX_TOKENS) return fail(h, "ev_align: utterance %d has %d tokens > EV_ALIGN_MAX_TOKENS %d", b, n, EV_ALIGN_MAX_TOKENS);
+        if (T > EV_ALIGN_MAX_FRAMES) return fail(h, "ev_align: mel_lens[%d] = %d > EV_ALIGN_MAX_FRAMES %d", b, T, EV_ALIGN_MAX_FRAMES);
+        if (T < n) return fail(h, "ev_align: mel_lens[%d] = %d < its %d tokens: no monotonic path gives every token a frame", b, T, n);
+        tok_off[b] = (int32_t)rows; tok_len[b] = n; rows += n + GAP; max_tok = std::max(max_tok, n); max_frames = std::max(max_frames, T);
+        lp_elems += (int64_t)T * n; total_frames += T;
+    }
+    if (!dev_in) {
+        for (int j = 0; j < NT; ++j)
+            if (ling[j] < 0 || ling[j] >= c.n_vocab) return fail(h, "ev_align: phoneme id %lld at position %d outside [0, %d)", (long long)ling[j], j, c.n_vocab);
+        for (int b = 0; b < B; ++b)
+            if (speaker[b] < 0 || speaker[b] >= c.n_speaker) return fail(h, "ev_align: speaker id %lld of utterance %d outside [0, %d)", (long long)speaker[b], b, c.n_speaker);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (ensure_pe(h, max_tok)) return -1;
+    // the state of the last call: this one (ev_get_stage reads it); no synthesis' durations survive it
+    profiling_reset(h);
+    h->taps.clear(); h->aln_lp = nullptr;
+    h->last_dur = nullptr; h->last_dur_eff = nullptr;
+    h->B = B; h->total_tokens = NT;
+    h->tok_off = tok_off; h->tok_len = tok_len;
+    h->mel_lens.assign(mel_lens, mel_lens + B);
+    const int Rt = (int)align_up((size_t)rows, ROW_ALIGN);
+    const int Rf = frame_rows(mel_lens, B);
+    h->Rt = Rt; h->Rf = Rf;
+    std::vector<int64_t> elem_off(B);
+    for (int b = 0, e = 0; b < B; ++b) { elem_off[b] = (int64_t)e * c.n_mels; e += mel_lens[b]; }
+    const size_t mel_es = mel_is_f16 ? 2 : 4;
+
+    struct {
+        Buf x, hb, qkv, ctx, ffn, y, xp, t1, t2, melrows, f1, f2, f3;
+        int64_t *d_ling, *d_spk, *d_eoff, *d_dur; float *d_style, *d_content, *d_u, *d_pf, *d_ef, *d_pitch, *d_energy, *d_score, *d_lp;
+        void* d_mel; AlignSeq* d_seqs; uint32_t* d_bits;
+    } ab{};
+    if (pinned_reserve(h, PIN_BYTES)) return -1;      // (build_frame_layout stages through the pinned frame region)
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 3, pass == 0};
+        if (pass == 1 && arena_reserve(h, 3, need)) return -1;
+        h->d_tok_seq = ap.arr<int32_t>(Rt); h->d_tok_pos = ap.arr<int32_t>(Rt); h->d_tok_valid = ap.arr<uint8_t>(Rt);
+        h->d_tok_off = ap.arr<int32_t>(B); h->d_tok_len = ap.arr<int32_t>(B); h->d_cu = ap.arr<int32_t>(B + 1);
+        h->d_mel_len = ap.arr<int32_t>(B);
+        build_frame_layout(h, ap, pass == 0, B);
+        ab.d_ling = ap.arr<int64_t>(NT); ab.d_spk = ap.arr<int64_t>(B); ab.d_style = ap.arr<float>((size_t)B * c.bert_dim);
+        ab.d_content = ap.arr<float>((size_t)B * c.bert_dim); ab.d_u = ap.arr<float>((size_t)B * C); ab.d_eoff = ap.arr<int64_t>(B);
+        ab.d_mel = dev_in ? nullptr : ap.take((size_t)total_frames * c.n_mels * mel_es);
+        ab.d_pf = (pitch_frames && !dev_in) ? ap.arr<float>(total_frames) : nullptr;
+        ab.d_ef = (energy_frames && !dev_in) ? ap.arr<float>(total_frames) : nullptr;
+        ab.d_seqs = ap.arr<AlignSeq>(B); ab.d_bits = ap.arr<uint32_t>((size_t)total_frames * 64);
+        ab.d_dur = ap.arr<int64_t>(NT); ab.d_pitch = pitch_frames ? ap.arr<float>(NT) : nullptr; ab.d_energy = energy_frames ? ap.arr<float>(NT) : nullptr;
+        ab.d_score = ap.arr<float>(B); ab.d_lp = ap.arr<float>((size_t)lp_elems);
+        ab.x = ap.rows(Rt, C, 4); ab.hb = ap.rows(Rt, C, 4); ab.qkv = ap.rows(Rt, 3 * C, 4); ab.ctx = ap.rows(Rt, C, 4);
+        ab.ffn = ap.rows(Rt, 4 * C, 4); ab.y = ap.rows(Rt, C, 4); ab.xp = ap.rows(Rt, C, 4); ab.t1 = ap.rows(Rt, C, 4); ab.t2 = ap.rows(Rt, C, 4);
+        ab.melrows = ap.rows(Rf, MEL_PAD, 4); ab.f1 = ap.rows(Rf, C, 4); ab.f2 = ap.rows(Rf, C, 4); ab.f3 = ap.rows(Rf, C, 4);
+        {          // split-K partial sums of the encoder (tok_splitk), as in ev_synthesize
+            const Buf kb = (c.token_splitk == 0 && c.token_rate_split != 0) ? ap.rows(Rt, 4 * C, 4) : Buf{};
+            h->tok_ks = kb.p; h->tok_ks_bytes = kb.p ? (size_t)Rt * 4 * C * 4 : 0;
+        }
+        need = ap.off;
+    }
+    h->aln_mel_lens.assign(mel_lens, mel_lens + B);
+    h->aln_mel_offs = h->mel_offs;
+    h->aln_seqs.resize(B);
+    {
+        int64_t lo = 0;
+        for (int b = 0; b < B; ++b) {
+            AlignSeq& q = h->aln_seqs[b];
+            q.tok_row = tok_off[b]; q.tokens = tok_len[b]; q.frm_row = h->frm_off[b]; q.frames = mel_lens[b];
+            q.lp_off = lo; q.tok_packed = cu[b]; q.frm_packed = h->mel_offs[b]; q.bits_off = h->mel_offs[b] * 64;
+            lo += (int64_t)q.frames * q.tokens;
+        }
+    }
+    {
+        int32_t* poff = (int32_t*)h->pinned; int32_t* plen = poff + B; int32_t* pcu = plen + B;
+        for (int b = 0; b < B; ++b) { poff[b] = tok_off[b]; plen[b] = tok_len[b]; }
+        memcpy(pcu, cu, (size_t)(B + 1) * 4);
+        HIPCHK(h, hipMemcpyAsync(h->d_tok_off, poff, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_tok_len, plen, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_cu, pcu, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, h->stream));
+        launch_row_maps(h->d_tok_off, h->d_tok_len, B, h->d_tok_seq, h->d_tok_pos, h->d_tok_valid, Rt, h->stream);
+        const hipMemcpyKind kind = dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        HIPCHK(h, hipMemcpyAsync(ab.d_ling, ling, (size_t)NT * 8, kind, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ab.d_spk, speaker, (size_t)B * 8, kind, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ab.d_style, style, (size_t)B * c.bert_dim * 4, kind, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ab.d_content, content, (size_t)B * c.bert_dim * 4, kind, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_mel_len, mel_lens, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ab.d_eoff, elem_off.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ab.d_seqs, h->aln_seqs.data(), (size_t)B * sizeof(AlignSeq), hipMemcpyHostToDevice, h->stream));
+        if (!dev_in) {
+            HIPCHK(h, hipMemcpyAsync(ab.d_mel, mel, (size_t)total_frames * c.n_mels * mel_es, hipMemcpyHostToDevice, h->stream));
+            if (pitch_frames) HIPCHK(h, hipMemcpyAsync(ab.d_pf, pitch_frames, (size_t)total_frames * 4, hipMemcpyHostToDevice, h->stream));
+            if (energy_frames) HIPCHK(h, hipMemcpyAsync(ab.d_ef, energy_frames, (size_t)total_frames * 4, hipMemcpyHostToDevice, h->stream));
+        }
+    }
+    const void* melsrc = dev_in ? mel : ab.d_mel;
+    const float* pf = dev_in ? pitch_frames : ab.d_pf;
+    const float* ef = dev_in ? energy_frames : ab.d_ef;
+    region_begin(h, "total");
+    // text side: the token-rate path of ev_synthesize up to embed_projection1 (same kernels, same layout: the same x_proj bits)
+    RowCtx trc{Rt, h->d_tok_valid, h->d_tok_seq, h->d_tok_off, h->d_tok_len, B, max_tok, (double)NT};
+    WPTR(tok_emb, float, "tok_emb"); WPTR(spk_emb, float, "spk_emb");
+    float enc_alpha;
+    if (get_scalar(h, "enc.alpha", &enc_alpha)) return -1;
+    { KScope ks(h, "embed_pe", 0, (double)NT * C * 12.0);
+      launch_embed_pe(ab.d_ling, h->d_cu, h->d_tok_seq, h->d_tok_pos, tok_emb, c.n_vocab, h->pe_dev, enc_alpha, (float*)ab.x.p, nullptr, Rt, C, h->stream); }
+    if (run_stack(h, "enc", c.enc_layers, DT_F32, trc, ab.x, ab.hb, ab.qkv, ab.ctx, ab.ffn, ab.y, nullptr, nullptr)) return -1;
+    WPTR(wcond, float, "proj.wcond"); WPTR(bproj, float, "proj.b"); WPTR(wproj, char, "proj.w32");
+    { KScope ks(h, "cond_vector", 2.0 * B * C * (C + 2.0 * c.bert_dim), 0);
+      launch_cond_vector(ab.d_spk, ab.d_style, ab.d_content, spk_emb, c.n_speaker, wcond, bproj, ab.d_u, B, C, c.bert_dim, h->stream); }
+    {
+        ConvGemmParams p = gemm_defaults();
+        p.dtype = DT_F32; p.A = ab.y.p; p.lda = C; p.W = wproj; p.M = Rt; p.N = C; p.K = C; p.row_valid = h->d_tok_valid;
+        p.row_seq = h->d_tok_seq; p.seq_bias = ab.d_u; p.ld_seq_bias = C; p.out32 = (float*)ab.xp.p; p.ldo = C;
+        if (tok_weights(h, "proj.w", p)) return -1;
+        if (gemm(h, "variance_f32_gemm", p, NT)) return -1;
+    }
+    // the aligner's convs (split-precision GEMMs whatever the frame-rate precision): text on the token rows, mel on the frame rows
+    auto aln_conv = [&](const char* w, const void* A, int lda, int K, int taps, int act, const Buf& o, const RowCtx& rc) -> int {
+        WPTR(bias, float, std::string("aln.") + w + ".b");
+        ConvGemmParams p = gemm_defaults();
+        p.dtype = DT_F32; p.A = A; p.lda = lda; p.M = rc.R; p.N = C; p.K = K; p.taps = taps; p.center = (taps - 1) / 2; p.bias = bias;
+        p.row_valid = rc.valid; p.act = act; p.out32 = (float*)o.p; p.ldo = C;
+        if (tok_weights(h, std::string("aln.") + w + ".w", p)) return -1;
+        return gemm(h, "align_f32_gemm", p, rc.n_valid);
+    };
+    RowCtx frc{Rf, h->d_frm_valid, h->d_frm_seq, h->d_frm_off, h->d_mel_len, B, max_frames, (double)total_frames};
+    if (aln_conv("t1", ab.xp.p, C, C, 3, ACT_RELU, ab.t1, trc) || aln_conv("t2", ab.t1.p, C, C, 1, ACT_NONE, ab.t2, trc)) return -1;
+    { KScope ks(h, "mel_to_rows", 0, (double)total_frames * c.n_mels * (mel_es + 4));
+      launch_mel_to_rows(melsrc, mel_is_f16, ab.d_eoff, h->d_frm_seq, h->d_frm_pos, h->d_mel_len, ab.melrows.p, 1, Rf, c.n_mels, MEL_PAD, h->stream); }
+    if (aln_conv("f1", ab.melrows.p, MEL_PAD, MEL_PAD, 3, ACT_RELU, ab.f1, frc) || aln_conv("f2", ab.f1.p, C, C, 3, ACT_RELU, ab.f2, frc) ||
+        aln_conv("f3", ab.f2.p, C, C, 1, ACT_NONE, ab.f3, frc)) return -1;
+    { KScope ks(h, "align_score", 3.0 * (double)lp_elems * C, (double)lp_elems * 8.0 + (double)(NT + total_frames) * C * 4.0);
+      launch_align_score((const float*)ab.t2.p, (const float*)ab.f3.p, C, ab.d_seqs, B, max_frames, ab.d_lp, h->stream); }
+    { KScope ks(h, "align_mas", 2.0 * (double)lp_elems, (double)lp_elems * 4.0 + (double)total_frames * 64 * 4 * 2);
+      launch_align_mas(ab.d_lp, ab.d_seqs, B, max_tok, ab.d_bits, pf, ef, ab.d_dur, ab.d_pitch, ab.d_energy, ab.d_score, h->stream); }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    h->aln_lp = ab.d_lp; h->aln_lp_elems = lp_elems;
+    if (keep) {
+        add_tap(h, "x_proj", ab.xp.p, DT_F32, C, C, 0, 0);
+        add_tap(h, "aln_text", ab.t2.p, DT_F32, C, C, 0, 0);
+        add_tap(h, "aln_feats", ab.f3.p, DT_F32, C, C, 1, 0);
+    }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total_tokens = NT; out->total_frames = total_frames;
+    out->durations = ab.d_dur; out->pitch = ab.d_pitch; out->energy = ab.d_energy; out->score = ab.d_score;
+    out->mel_lens = h->aln_mel_lens.data(); out->mel_offsets = h->aln_mel_offs.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
 void ev_default_bert_config(ev_bert_config* c) {
     memset(c, 0, sizeof *c);
@@ -1718,6 +1897,14 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
         if (!host_dst) return (int64_t)need;
         if (cap < need || !h->last_dur_eff) return fail(h, "ev_get_stage(dur_eff): buffer too small or no synthesis yet");
         HIPCHK(h, hipMemcpy(host_dst, h->last_dur_eff, need, hipMemcpyDeviceToHost));
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "log_p_attn")) {     // ev_align: the (T_b, N_b) blocks of the utterances, concatenated
+        const size_t need = (size_t)h->aln_lp_elems * 4;
+        if (!h->aln_lp) return fail(h, "ev_get_stage(log_p_attn): the last call was not ev_align");
+        if (!host_dst) return (int64_t)need;
+        if (cap < need) return fail(h, "ev_get_stage(log_p_attn): need %zu bytes, cap %zu", need, cap);
+        HIPCHK(h, hipMemcpy(host_dst, h->aln_lp, need, hipMemcpyDeviceToHost));
         return (int64_t)need;
     }
     if (!strcmp(name, "mel_len")) {

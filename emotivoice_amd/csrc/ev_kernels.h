@@ -221,4 +221,21 @@ void launch_wav_to_i16(const float* wav, int16_t* out, int64_t n, hipStream_t s)
 void launch_row_maps(const int32_t* off, const int32_t* len, int B, int32_t* seq, int32_t* pos, uint8_t* valid, int rows, hipStream_t s);
 void launch_fill_zero(void* p, size_t bytes, hipStream_t s);
 
+// ev_align (ev_align.hip).  Per utterance: its rows in the token / frame layouts, its sizes and its offsets into the packed outputs.
+#define EV_ALIGN_MAX_TOKENS 2048
+#define EV_ALIGN_MAX_FRAMES 16384
+struct AlignSeq {
+    int32_t tok_row, tokens, frm_row, frames;   // first row in the token / frame layout, N, T
+    int64_t lp_off;                             // element offset of the (T, N) log_p block
+    int64_t tok_packed, frm_packed;             // packed token / frame offsets (cu_seqlens[b], mel_offsets[b])
+    int64_t bits_off;                           // word offset of the (T, 64) decision words
+};
+// log_p[t, n] = log_softmax_n(-||feats[t] - text[n]||_2) + log betabinom.pmf(n; N, t + 1, T - t): text / feats are the aligner's fp32 row
+// layouts ([rows][C]); one block per (64 frames, utterance)
+void launch_align_score(const float* text, const float* feats, int C, const AlignSeq* seqs, int B, int max_frames, float* log_p, hipStream_t s);
+// monotonic alignment search + durations, per-token means of the optional frame tracks and the mean log_p along the path; one wave per
+// utterance.  bits: sum_b frames_b * 64 words of scratch
+void launch_align_mas(const float* log_p, const AlignSeq* seqs, int B, int max_tokens, uint32_t* bits, const float* pitch_frames,
+                      const float* energy_frames, int64_t* dur, float* pitch_tok, float* energy_tok, float* score, hipStream_t s);
+
 }  // namespace ev

@@ -187,6 +187,71 @@ class EVEngine:
         self.last = res
         return res
 
+    def align_raw(self, B: int, ling_ptr: int, cu_seqlens: np.ndarray, speaker_ptr: int, style_ptr: int, content_ptr: int, mel_ptr: int,
+                  mel_is_f16: bool, mel_lens: np.ndarray, pitch_ptr: Optional[int] = None, energy_ptr: Optional[int] = None,
+                  flags: int = 0) -> _ffi.ev_align_result:
+        """ev_align (include/evhip.h).  The returned struct's device arrays stay valid until the next align on this engine."""
+        cu = np.ascontiguousarray(cu_seqlens, np.int32)
+        ml = np.ascontiguousarray(mel_lens, np.int32)
+        res = _ffi.ev_align_result()
+        res.struct_size = C.sizeof(_ffi.ev_align_result)
+        self._check(self._lib.ev_align(self._h, B, C.c_void_p(ling_ptr), cu.ctypes.data_as(C.c_void_p), C.c_void_p(speaker_ptr),
+                                       C.c_void_p(style_ptr), C.c_void_p(content_ptr), C.c_void_p(mel_ptr), 1 if mel_is_f16 else 0,
+                                       ml.ctypes.data_as(C.c_void_p), C.c_void_p(pitch_ptr) if pitch_ptr else None,
+                                       C.c_void_p(energy_ptr) if energy_ptr else None, flags, C.byref(res)))
+        self.last_align = res
+        return res
+
+    def align_to_numpy(self, res: _ffi.ev_align_result) -> Dict[str, object]:
+        B, NT = res.batch, res.total_tokens
+        mel_lens = np.array([res.mel_lens[b] for b in range(B)], np.int32)
+        out: Dict[str, object] = dict(mel_lens=mel_lens, mel_offsets=np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64),
+                                      durations=self.d2h(res.durations, (NT,), np.int64), score=self.d2h(res.score, (B,), np.float32))
+        out["pitch"] = self.d2h(res.pitch, (NT,), np.float32) if res.pitch else None
+        out["energy"] = self.d2h(res.energy, (NT,), np.float32) if res.energy else None
+        return out
+
+    def align(self, utts: Sequence[dict], mels: Sequence[np.ndarray], pitch: Optional[Sequence[np.ndarray]] = None,
+              energy: Optional[Sequence[np.ndarray]] = None) -> Dict[str, object]:
+        """Forced alignment of recordings of known text (ev_align).  utts: as synthesize(); mels: one (n_mels, T_b) array per utterance, fp32
+        or fp16 (the vocoder() convention); pitch / energy: optional per-frame tracks, one (T_b,) array per utterance, in the checkpoint's
+        normalised units.  Returns durations (packed (total_tokens,) int64) and durations_list, pitch / energy (per-token means, packed, or
+        None), score (B,) = mean log_p_attn along the path, mel_lens, cu_seqlens."""
+        B = len(utts)
+        if len(mels) != B:
+            raise ValueError("%d mels for %d utterances" % (len(mels), B))
+        ling = np.ascontiguousarray(np.concatenate([np.asarray(u["ling"], np.int64) for u in utts]))
+        cu = np.zeros(B + 1, np.int32)
+        cu[1:] = np.cumsum([len(u["ling"]) for u in utts])
+        spk = np.ascontiguousarray([int(u["speaker"]) for u in utts], np.int64)
+        style = np.ascontiguousarray(np.stack([np.asarray(u["style"], np.float32) for u in utts]))
+        content = np.ascontiguousarray(np.stack([np.asarray(u["content"], np.float32) for u in utts]))
+        is16 = np.asarray(mels[0]).dtype == np.float16
+        mdt = np.float16 if is16 else np.float32
+        for b, m in enumerate(mels):
+            if np.asarray(m).ndim != 2 or np.asarray(m).shape[0] != self.shapes.n_mels:
+                raise ValueError("mels[%d]: expected (%d, T), got %s" % (b, self.shapes.n_mels, np.asarray(m).shape))
+        flat = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(m, mdt).ravel() for m in mels]))
+        lens = np.array([np.asarray(m).shape[1] for m in mels], np.int32)
+
+        def track(xs, name):
+            if xs is None:
+                return None
+            if len(xs) != B:
+                raise ValueError("%d %s tracks for %d utterances" % (len(xs), name, B))
+            for b, x in enumerate(xs):
+                if np.asarray(x).reshape(-1).size != lens[b]:
+                    raise ValueError("%s[%d]: expected %d frames, got %d" % (name, b, lens[b], np.asarray(x).size))
+            return np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in xs]))
+
+        pf, ef = track(pitch, "pitch"), track(energy, "energy")
+        res = self.align_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, flat.ctypes.data, is16, lens,
+                             pf.ctypes.data if pf is not None else None, ef.ctypes.data if ef is not None else None)
+        out = self.align_to_numpy(res)
+        out["cu_seqlens"] = cu
+        out["durations_list"] = [out["durations"][cu[b]:cu[b + 1]] for b in range(B)]
+        return out
+
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)
         self._check(self._lib.ev_set_forced_durations(self._h, d.ctypes.data_as(C.c_void_p), d.size))
@@ -287,7 +352,7 @@ class EVEngine:
         need = self._lib.ev_get_stage(self._h, name.encode(), None, 0)
         if need < 0:
             raise EVError(self._lib.ev_last_error(self._h).decode())
-        if name in ("dur", "dur_eff", "mel_len"):
+        if name in ("dur", "dur_eff", "mel_len"):      # "log_p_attn" (after align): the (T_b, N_b) fp32 blocks, concatenated
             out = np.empty(need // 8, np.int64)
         else:
             out = np.empty(need // 4, np.float32)

@@ -305,8 +305,25 @@ def pack_state_dict(sd: Dict[str, object], shapes=None, pe_len: int = 4096) -> T
     wpost = _fold_weight_norm(sd, f"{g}.conv_post")     # [1, C, 7]
     b.add("voc.post.w", np.ascontiguousarray(wpost[0].T), DT_F32)   # [7][C]
     b.add("voc.post.b", f32(f"{g}.conv_post.bias").reshape(1), DT_F32)
+    if any(k.startswith("am.alignment_module.") for k in sd):
+        _pack_aligner(b, sd)
     blob, manifest = b.finish()
     return blob, json.dumps(manifest)
+
+
+ALIGNER_CONVS = (("t1", "t_conv1"), ("t2", "t_conv2"), ("f1", "f_conv1"), ("f2", "f_conv2"), ("f3", "f_conv3"))
+
+
+def _pack_aligner(b: "_Blob", sd) -> None:
+    """The teacher-forced branch's AlignmentModule (reference modules/alignment.py:13-25) for ev_align: every conv as a token- / frame-rate
+    fp32 GEMM weight [N][taps][K] ("aln.<c>.w32") plus its split hi / lo pair ("aln.<c>.w32h" / "w32l"), f_conv1's K (n_mels) zero-padded to
+    MEL_PAD like voc.pre.  Appended after every other entry: the entries before them are those of a blob packed without the aligner."""
+    for short, name in ALIGNER_CONVS:
+        w = _np(sd[f"am.alignment_module.{name}.weight"]).astype(np.float32)
+        g = _conv_to_gemm(w, MEL_PAD if short == "f1" else None)
+        b.add(f"aln.{short}.w32", g, DT_F32)
+        b.split(f"aln.{short}.w", g)
+        b.add(f"aln.{short}.b", _np(sd[f"am.alignment_module.{name}.bias"]).astype(np.float32), DT_F32)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@
  *                           fed through the embeddings and the length regulator exactly where the teacher-forced branch
  *                           feeds ps / es / ds (model_open_source.py:113-139); an extension, not part of the reference call
  *   ev_vocoder           <- HiFiGANGenerator.forward on pre-computed mels     (models/hifigan/models.py:115-131)
+ *   ev_align             <- the teacher-forced branch's alignment: AlignmentModule + viterbi_decode + average_by_duration
+ *                           (model_open_source.py:113-119, modules/alignment.py:27-162), batched on the device
  *   ev_get_stage         <- register_forward_hook taps used by the parity tests
  *   ev_last_error        <- Python exceptions (no exceptions cross the ABI)
  *
@@ -205,6 +207,8 @@ int ev_synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_se
  * Ordering of device per-token arrays: like ling, they are read in the order of the handle's stream (ev_set_stream), which the internal
  * stream gives no ordering against any other stream, the null stream included.  The caller makes sure they are written before the call:
  * produce them on the stream set with ev_set_stream, or synchronise the producing stream first (emotivoice_amd.prosody.pack_prosody does).
+ * The device arrays of an ev_align_result qualify as they are: ev_align has completed them before it returns, and they stay valid across
+ * this call (they live in ev_align's own workspace until the next ev_align), so a re-voicing passes them straight back here.
  * The per-utterance arrays are always HOST memory and are validated: alpha[b] > 0 and finite, scales / shifts finite.  The per-token arrays
  * follow EV_FLAG_DEVICE_INPUTS like ling.  Host per-token values are validated too: pitch / energy must not be +-inf, durations must lie
  * in [-1, EV_PROSODY_MAX_DURATION].  Device per-token values cannot be checked without a sync; the kernels treat a non-finite pitch /
@@ -231,6 +235,53 @@ typedef struct ev_prosody {
 int ev_synthesize_prosody(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_seqlens, const int64_t* speaker,
                           const float* style, const float* content, float alpha, const ev_prosody* prosody,
                           uint32_t flags, ev_result* out);
+
+/* Forced alignment (ev_align): the teacher-forced branch's AlignmentModule + monotonic alignment search + per-token averages
+ * (reference model_open_source.py:113-119, modules/alignment.py:27-162), batched on the device.  For utterance b with N tokens and
+ * T = mel_lens[b] frames, with the reference's B = 1 semantics (zero conv halo at the utterance's own edges):
+ *   1. text:  x = embed_projection1 output (the "x_proj" tap of ev_synthesize, same inputs, same bits);  t = t_conv2(relu(t_conv1(x)))
+ *   2. mel:   f = f_conv3(relu(f_conv2(relu(f_conv1(mel)))))           (kernels 3 / 3 / 1, and 3 / 1 on the text side)
+ *   3. score: log_p[t, n] = log_softmax_n(-||f_t - x_n||_2) + (float)log betabinom.pmf(n; N, t + 1, T - t)     ("log_p_attn")
+ *   4. MAS:   Q in fp64: Q[0, j] = sum_{j' <= j} log_p[j', 0] summed SEQUENTIALLY in fp64 -- the one deliberate deviation: the reference
+ *             sums that row in float32 (numpy's pairwise order unjitted, numba's when jitted); Q[i, j] = max(Q[i-1, j-1], Q[i, j-1]) + log_p[j, i];
+ *             backtrack from A[T-1] = N-1, taking i-1 on a tie (>=);  durations = bincount(A)   (>= 1 each, summing to T)
+ *   5. pitch[n] / energy[n] = mean of pitch_frames / energy_frames over token n's frames (fp64 sum, one rounding to fp32)
+ *   6. score[b] = mean_t log_p[t, A[t]]  (= -bin_loss of the utterance; fp64 sum)
+ * The distance is evaluated in direct form on fp32 (never as |f|^2 + |x|^2 - 2 f.x), the convs are split-precision (fp32-class) GEMMs
+ * whatever decoder_precision / vocoder_precision say: the results are the same bits on every precision mode and for an utterance
+ * alone or in any batch.
+ * Inputs: ling / cu_seqlens / speaker / style / content exactly as ev_synthesize; mel packed as ev_vocoder takes it (per utterance
+ * (n_mels, mel_lens[b]) row-major, fp32 or fp16); mel_lens HOST; pitch_frames / energy_frames (total_frames,) packed like mel's frames, in
+ * the checkpoint's normalised units, or NULL (then the result's pitch / energy are NULL).  EV_FLAG_DEVICE_INPUTS covers every input pointer
+ * except cu_seqlens and mel_lens.
+ * Rejected before anything is launched (message naming the utterance or field): struct_size != sizeof(ev_align_result), mel_lens[b] <
+ * N_b (no monotonic path gives every token a frame), N_b > EV_ALIGN_MAX_TOKENS or mel_lens[b] > EV_ALIGN_MAX_FRAMES, bad ids (as
+ * ev_synthesize), a weight blob without the aligner ("aln.*": packed only from state dicts that carry am.alignment_module.*).
+ * Lifetime: the result and its device arrays live in a workspace of their own.  They stay valid across ev_synthesize[_prosody] and
+ * ev_vocoder calls on the same handle, until the next ev_align or ev_destroy -- so durations / pitch / energy can be passed straight
+ * back as ev_prosody.durations / .pitch / .energy with EV_FLAG_DEVICE_INPUTS (they are complete when ev_align returns: it synchronises).
+ * ev_align itself may invalidate an earlier ev_result, like any call.  After ev_align, ev_get_stage serves "log_p_attn" (the (T_b, N_b)
+ * fp32 blocks of the utterances, concatenated) and, with keep_stages, "aln_text" (t_conv2 out, token rows) and "aln_feats" (f_conv3
+ * out, frame rows); "dur" / "dur_eff" have no data until the next synthesis. */
+#define EV_ALIGN_MAX_TOKENS 2048      /* tokens per utterance */
+#define EV_ALIGN_MAX_FRAMES 16384     /* mel frames per utterance (~262 s at 16 kHz / 256) */
+typedef struct ev_align_result {
+    uint32_t struct_size;          /* sizeof(ev_align_result), set by the caller; any other value is rejected (room to grow, as ev_prosody) */
+    int32_t  batch;
+    int32_t  total_tokens;
+    int32_t  reserved0;
+    int64_t  total_frames;
+    const int64_t* durations;      /* (total_tokens,) DEVICE, packed like ling: frames per token; >= 1 each, sum over utterance b = mel_lens[b] */
+    const float*   pitch;          /* (total_tokens,) DEVICE: per-token mean of pitch_frames over the token's frames, or NULL */
+    const float*   energy;         /* same for energy_frames, or NULL */
+    const float*   score;          /* (batch,) DEVICE: mean over the utterance's frames of log_p_attn along the path (= -bin_loss of that utterance) */
+    const int32_t* mel_lens;       /* (batch,) HOST */
+    const int64_t* mel_offsets;    /* (batch+1,) HOST */
+} ev_align_result;
+
+int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_seqlens, const int64_t* speaker,
+             const float* style, const float* content, const void* mel, int mel_is_f16, const int32_t* mel_lens,
+             const float* pitch_frames, const float* energy_frames, uint32_t flags, ev_align_result* out);
 
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
