@@ -141,6 +141,24 @@ SIGNATURES = {
     "ev_op_layernorm": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P, C.c_float, _P, _P]),
     "ev_op_layernorm_planes": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, C.c_uint, _P]),
     "ev_op_attention": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "ev_op_embed_pe": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_float, _P, _P, C.c_int, C.c_int, _P]),
+    "ev_op_bert_embed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "ev_op_bert_pooler": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "ev_op_cond_vector": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ev_op_var_embed_add": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ev_op_prosody_tracks": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
+    "ev_op_durations": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "ev_op_durations_prosody": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "ev_op_gauss_upsample": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, C.c_int, C.c_int, _P]),
+    "ev_op_mel_to_rows": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ev_op_conv_post": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_float, C.c_int, C.c_float, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "ev_op_row_maps": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "ev_op_pack_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int64, _P, _P]),
+    "ev_op_wav_to_i16": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "ev_op_pe_extend": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    # the per-utterance arrays of the two aligner ops are HOST arrays (the wrapper builds the device table)
+    "ev_op_align_score": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "ev_op_align_mas": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

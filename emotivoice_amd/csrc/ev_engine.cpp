@@ -1981,6 +1981,7 @@ int ev_op_resblock_pair_c64(const ev_res_pair_desc* d, void* stream) {
 }
 int ev_op_layernorm(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, const uint8_t* row_valid,
                     void* out16, float* out32, const float* dot_w, float dot_b, float* dot_out, void* stream) {
+    if (rows <= 0 || C < 128 || C > 1024 || C % 128 || (dot_w && !dot_out)) return -2;      // one wave per row, NV float2 chunks of 128 channels per lane
     LayerNormParams p{};
     p.x = x; p.ldx = C; p.rows = rows; p.C = C; p.gamma = gamma; p.beta = beta; p.eps = eps; p.row_valid = row_valid; p.out16 = out16;
     p.out32 = out32; p.ldo = C; p.dot_w = dot_w; p.dot_b = dot_b; p.dot_out = dot_out;
@@ -1989,7 +1990,7 @@ int ev_op_layernorm(const float* x, int rows, int C, const float* gamma, const f
 }
 int ev_op_layernorm_planes(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, const uint8_t* row_valid,
                            void* h, void* q4h, void* q4l, void* qsh, void* qsl, unsigned qs_stride, void* stream) {
-    if (C > 512 || C % 128 || !h || !q4h || !q4l || !qsh || !qsl) return -2;
+    if (rows <= 0 || C < 128 || C > 512 || C % 128 || !h || !q4h || !q4l || !qsh || !qsl) return -2;
     LayerNormParams p{};
     p.x = x; p.ldx = C; p.rows = rows; p.C = C; p.gamma = gamma; p.beta = beta; p.eps = eps; p.row_valid = row_valid; p.ldo = C;
     p.mxo_h = h; p.mxo_q4[0] = q4h; p.mxo_q4[1] = q4l; p.mxo_qs[0] = qsh; p.mxo_qs[1] = qsl; p.mxo_qs_stride = qs_stride;
@@ -1998,12 +1999,160 @@ int ev_op_layernorm_planes(const float* x, int rows, int C, const float* gamma, 
 }
 int ev_op_attention(const void* qkv, int is_f16, int C, int heads, const int32_t* seq_off, const int32_t* seq_len, int B, int max_len,
                     void* out, void* stream) {
+    const int dk = heads > 0 && C % heads == 0 ? C / heads : 0;
+    if (is_f16 < 0 || is_f16 > 2 || B <= 0 || max_len <= 0) return -2;
+    if (is_f16 == 0 ? (dk != 48 && dk != 64) : dk != 48) return -2;          // the MFMA kernels are built for d_k = 48 (fp32: also 64)
     AttnParams p{};
     // is_f16 == 2: fp32 rows, split-precision products
     p.qkv = qkv; p.dtype = is_f16 == 1 ? DT_F16 : (is_f16 == 2 ? DT_F32S : DT_F32); p.ld = 3 * C; p.C = C; p.heads = heads; p.seq_off = seq_off; p.seq_len = seq_len;
     p.B = B; p.max_len = max_len; p.out = out; p.ldo = C;
     launch_attention(p, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The non-GEMM launchers (ev_misc.hip, ev_align.hip).  Each wrapper refuses (-2) what its kernel silently assumes; include/evhip_ops.h states the limits.
+int ev_op_embed_pe(const int64_t* ling, const int32_t* cu_seqlens, const int32_t* row_seq, const int32_t* row_pos, const float* emb, int n_vocab,
+                   const float* pe, float alpha, float* out, float* tap_out, int rows, int C, void* stream) {
+    if (rows <= 0 || C <= 0 || C % 2 || n_vocab < 1 || !out) return -2;
+    launch_embed_pe(ling, cu_seqlens, row_seq, row_pos, emb, n_vocab, pe, alpha, out, tap_out, rows, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_bert_embed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, const int32_t* row_seq, const int32_t* row_pos,
+                     const float* word, const float* pos_emb, const float* type_emb, int vocab, int max_pos, int n_types, float* out, int rows,
+                     int C, void* stream) {
+    if (rows <= 0 || C <= 0 || C % 2 || vocab < 1 || max_pos < 1 || n_types < 1 || !out) return -2;
+    launch_bert_embed(ids, type_ids, cu_seqlens, row_seq, row_pos, word, pos_emb, type_emb, vocab, max_pos, n_types, out, rows, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_bert_pooler(const float* x, int ldx, const int32_t* seq_off, const float* W, const float* bias, float* out, int B, int C, void* stream) {
+    if (B <= 0 || B > 65535 || C <= 0 || ldx < C) return -2;
+    launch_bert_pooler(x, ldx, seq_off, W, bias, out, B, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_cond_vector(const int64_t* speaker, const float* style, const float* content, const float* spk_emb, int n_speaker, const float* Wcond,
+                      const float* bias, float* u, int B, int C, int bert, void* stream) {
+    if (B <= 0 || B > 65535 || C <= 0 || bert < 0 || n_speaker < 1) return -2;
+    launch_cond_vector(speaker, style, content, spk_emb, n_speaker, Wcond, bias, u, B, C, bert, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_var_embed_add(const float* x, const float* pitch, const float* energy, const float* wp, const float* bp, const float* we, const float* be,
+                        const uint8_t* row_valid, float* out, int rows, int C, int k, void* stream) {
+    if (rows <= 0 || C <= 0 || C % 2 || k < 1 || k % 2 == 0 || !row_valid) return -2;
+    launch_var_embed_add(x, pitch, energy, wp, bp, we, be, row_valid, out, rows, C, k, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_prosody_tracks(const float* pitch, const float* energy, const int32_t* row_seq, const int32_t* row_pos, const int32_t* cu_seqlens,
+                         const float* pitch_ovr, const float* energy_ovr, const float* ctrl, int B, float* pitch_out, float* energy_out, int rows,
+                         void* stream) {
+    if (rows <= 0 || B <= 0 || !ctrl) return -2;
+    launch_prosody_tracks(pitch, energy, row_seq, row_pos, cu_seqlens, pitch_ovr, energy_ovr, ctrl, B, pitch_out, energy_out, rows, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_durations(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const int64_t* forced,
+                    const int32_t* cu_seqlens, int64_t* dur_packed, float* logd_packed, float* centre_rows, int32_t* mel_len, void* stream) {
+    if (B <= 0 || !(alpha > 0.f)) return -2;
+    launch_durations(log_d, tok_off, tok_len, B, alpha, forced, cu_seqlens, dur_packed, logd_packed, centre_rows, mel_len, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_durations_prosody(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const float* alpha_b,
+                            const int64_t* partial, int64_t dur_cap, const int32_t* cu_seqlens, int64_t* dur_packed, int64_t* dur_eff,
+                            float* logd_packed, float* centre_rows, int32_t* mel_len, void* stream) {
+    if (B <= 0 || !(alpha > 0.f) || dur_cap < 0 || dur_cap > (int64_t)1 << 20 || !dur_eff) return -2;
+    launch_durations_prosody(log_d, tok_off, tok_len, B, alpha, alpha_b, partial, dur_cap, cu_seqlens, dur_packed, dur_eff, logd_packed, centre_rows,
+                             mel_len, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_gauss_upsample(const float* xvar, const float* centre_rows, const int32_t* tok_off, const int32_t* tok_len, const int32_t* frm_row_seq,
+                         const int32_t* frm_row_pos, const float* pe, float pe_alpha, float delta, float* out, float* tap_out, int rows, int C,
+                         void* stream) {
+    if (rows <= 0 || C <= 0 || C > 512 || C % 2 || !(delta > 0.f)) return -2;      // acc[4]: four float2 chunks of 128 channels per lane
+    launch_gauss_upsample(xvar, centre_rows, tok_off, tok_len, frm_row_seq, frm_row_pos, pe, pe_alpha, delta, out, tap_out, rows, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_mel_to_rows(const void* mel, int is_f16, const int64_t* mel_elem_off, const int32_t* frm_row_seq, const int32_t* frm_row_pos,
+                      const int32_t* mel_len, void* out, int out_f32, int rows, int n_mels, int ldo, void* stream) {
+    if (rows <= 0 || n_mels <= 0 || ldo < n_mels) return -2;
+    launch_mel_to_rows(mel, is_f16, mel_elem_off, frm_row_seq, frm_row_pos, mel_len, out, out_f32, rows, n_mels, ldo, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_conv_post(const void* x, int is_f32, int ldx, const float* w, float bias, int k, float pre_slope, const uint8_t* row_valid, int valid_shift,
+                    float* wav_rows, int rows, int C, void* stream) {
+    if (rows <= 0 || C != 32 || k < 1 || k > 15 || k % 2 == 0 || ldx < C || ldx % (is_f32 ? 4 : 8)) return -2;      // 16 taps of weights and 256 + 16 rows fit the LDS
+    if (!row_valid || valid_shift < 0 || valid_shift > 30 || !(pre_slope >= 0.f && pre_slope <= 1.f)) return -2;  // max(v, s v) form of leaky-relu
+    launch_conv_post(x, is_f32, ldx, w, bias, k, pre_slope, row_valid, valid_shift, wav_rows, rows, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_row_maps(const int32_t* off, const int32_t* len, int B, int32_t* seq, int32_t* pos, uint8_t* valid, int rows, void* stream) {
+    if (rows <= 0 || B <= 0) return -2;
+    launch_row_maps(off, len, B, seq, pos, valid, rows, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_pack_rows(const void* src, int is_f16, int ld, int C, const int64_t* seq_row_off, const int64_t* seq_out_off, const int32_t* seq_rows, int B,
+                    int64_t max_rows, float* dst, void* stream) {
+    if (B <= 0 || B > 65535 || C <= 0 || ld < C || max_rows < 0) return -2;
+    launch_pack_rows(src, is_f16 ? DT_F16 : DT_F32, ld, C, seq_row_off, seq_out_off, seq_rows, B, max_rows, dst, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_wav_to_i16(const float* wav, int16_t* out, int64_t n, void* stream) {
+    if (n <= 0) return -2;
+    launch_wav_to_i16(wav, out, n, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int ev_op_pe_extend(float* pe, const float* div, int row0, int row1, int C, void* stream) {
+    if (row0 < 0 || row1 <= row0 || C <= 0 || C % 2) return -2;
+    launch_pe_extend(pe, div, row0, row1, C, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// The AlignSeq table of the two aligner kernels is built here from per-utterance HOST arrays (no struct crosses the boundary); both calls
+// copy it to the device, launch, and wait for the stream before releasing it.
+static int op_align_table(int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row, const int32_t* frames, const int64_t* lp_off,
+                          const int64_t* tok_packed, const int64_t* frm_packed, const int64_t* bits_off, bool mas, AlignSeq** d_out, int* max_tok,
+                          int* max_frm) {
+    if (B <= 0 || B > 65535 || !tokens || !frames || !lp_off) return -2;
+    std::vector<AlignSeq> tab((size_t)B);
+    *max_tok = 0; *max_frm = 0;
+    for (int b = 0; b < B; ++b) {
+        if (tokens[b] < 1 || tokens[b] > EV_ALIGN_MAX_TOKENS || frames[b] < 1 || frames[b] > EV_ALIGN_MAX_FRAMES || lp_off[b] < 0) return -2;
+        if (mas && frames[b] < tokens[b]) return -2;          // a monotonic path gives every token at least one frame
+        AlignSeq q{};
+        q.tok_row = tok_row ? tok_row[b] : 0; q.tokens = tokens[b]; q.frm_row = frm_row ? frm_row[b] : 0; q.frames = frames[b];
+        q.lp_off = lp_off[b]; q.tok_packed = tok_packed ? tok_packed[b] : 0; q.frm_packed = frm_packed ? frm_packed[b] : 0;
+        q.bits_off = bits_off ? bits_off[b] : 0;
+        if (q.tok_row < 0 || q.frm_row < 0 || q.tok_packed < 0 || q.frm_packed < 0 || q.bits_off < 0) return -2;
+        tab[(size_t)b] = q;
+        *max_tok = std::max(*max_tok, tokens[b]); *max_frm = std::max(*max_frm, frames[b]);
+    }
+    AlignSeq* d = nullptr;
+    if (hipMalloc((void**)&d, tab.size() * sizeof(AlignSeq)) != hipSuccess) return -1;
+    if (hipMemcpy(d, tab.data(), tab.size() * sizeof(AlignSeq), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return -1; }
+    *d_out = d;
+    return 0;
+}
+int ev_op_align_score(const float* text, const float* feats, int C, int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row,
+                      const int32_t* frames, const int64_t* lp_off, float* log_p, void* stream) {
+    if (C <= 0 || C % 32 || !tok_row || !frm_row || !log_p) return -2;      // channels are staged 32 at a time
+    AlignSeq* d = nullptr; int max_tok = 0, max_frm = 0;
+    int rc = op_align_table(B, tok_row, tokens, frm_row, frames, lp_off, nullptr, nullptr, nullptr, false, &d, &max_tok, &max_frm);
+    if (rc) return rc;
+    launch_align_score(text, feats, C, d, B, max_frm, log_p, (hipStream_t)stream);
+    rc = hipGetLastError() == hipSuccess ? 0 : -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    (void)hipFree(d);
+    return rc;
+}
+int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int32_t* frames, const int64_t* lp_off, const int64_t* tok_packed,
+                    const int64_t* frm_packed, const int64_t* bits_off, uint32_t* bits, const float* pitch_frames, const float* energy_frames,
+                    int64_t* dur, float* pitch_tok, float* energy_tok, float* score, void* stream) {
+    if (!log_p || !tok_packed || !frm_packed || !bits_off || !bits || !dur || !score) return -2;
+    if ((pitch_frames && !pitch_tok) || (energy_frames && !energy_tok)) return -2;
+    AlignSeq* d = nullptr; int max_tok = 0, max_frm = 0;
+    int rc = op_align_table(B, nullptr, tokens, nullptr, frames, lp_off, tok_packed, frm_packed, bits_off, true, &d, &max_tok, &max_frm);
+    if (rc) return rc;
+    launch_align_mas(log_p, d, B, max_tok, bits, pitch_frames, energy_frames, dur, pitch_tok, energy_tok, score, (hipStream_t)stream);
+    rc = hipGetLastError() == hipSuccess ? 0 : -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    (void)hipFree(d);
+    return rc;
 }
 
 }  // extern "C"

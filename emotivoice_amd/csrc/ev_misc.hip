@@ -1092,17 +1092,17 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* log_d, cons
         }
         if (tid == 0) mel_len[b] = all_zero ? n : total_s;
     } else {
-        // general alpha (an extension: the reference's inference branch never scales, model_open_source.py:142): sequential fp32
-        // cumsum for the centres; the length follows alignment.py:194 torch.sum(ds * alpha).int() evaluated in double, so that it
-        // does not depend on the order of a float reduction (the CPU oracle does the same)
+        // general alpha (an extension: the reference's inference branch never scales, model_open_source.py:142): the fp32 products
+        // ds * alpha are summed in double and the centre is rounded once (a sequential fp32 running sum was 6e-7 off at 255 tokens,
+        // six times the reference's own cumsum: tests/test_gpu_misc_ops.py); the length follows alignment.py:194
+        // torch.sum(ds * alpha).int() evaluated in double, so that it does not depend on the order of a float reduction (the CPU
+        // oracle does the same)
         if (tid == 0) {
-            float cs = 0.f;
             double tot = 0.0;
             for (int j = 0; j < n; ++j) {
                 const float d = all_zero ? 1.0f : (float)dur_scan[c0 + j] * alpha;
-                cs += d;
                 tot += (double)d;
-                centre_rows[off + j] = cs - d / 2.0f;
+                centre_rows[off + j] = (float)(tot - (double)d * 0.5);
             }
             mel_len[b] = (int)tot;
         }

@@ -96,7 +96,7 @@ int ev_op_resblock_pair_c64_mx(const ev_res_pair_desc* d, void* hip_stream);
 int ev_op_resblock_pair_c64(const ev_res_pair_desc* d, void* hip_stream);
 
 /* LayerNorm(eps) over channels, optional fused Linear(C,1) head (reference modules/encoder.py:112-127,
- * modules/variance.py:29-33,46). */
+ * modules/variance.py:29-33,46).  One wave per row: C % 128 == 0, 128 <= C <= 1024 (-2 otherwise); rows > 0; out16 / out32 / dot_out optional. */
 int ev_op_layernorm(const float* x, int rows, int C, const float* gamma, const float* beta, float eps,
                     const uint8_t* row_valid, void* out16, float* out32, const float* dot_w, float dot_b,
                     float* dot_out, void* hip_stream);
@@ -110,9 +110,87 @@ int ev_op_layernorm_planes(const float* x, int rows, int C, const float* gamma, 
 
 /* Multi-head self-attention restricted to each utterance's rows (reference modules/encoder.py:72-109).
  * is_f16: 1 = fp16 rows (fp16 MFMA flash kernel), 0 = fp32 rows, exact fp32 MFMA products, 2 = fp32 rows, split-precision products
- * (three fp16 MFMAs each: the mel decoder in the strict / mx modes). */
+ * (three fp16 MFMAs each: the mel decoder in the strict / mx modes).  d_k = C / heads must be 48 (is_f16 == 0: 48 or 64), max_len >= every
+ * seq_len (it sizes the grid and, for is_f16 == 2, picks the 4 / 8 / 16-wave kernel at 64 / 128); only rows [seq_off, seq_off + seq_len) are read. */
 int ev_op_attention(const void* qkv, int is_f16, int C, int heads, const int32_t* seq_off, const int32_t* seq_len,
                     int B, int max_len, void* out, void* hip_stream);
+
+/* ---- the non-GEMM kernels (emotivoice_amd/csrc/ev_misc.hip, ev_align.hip; tests/test_gpu_misc_ops.py).  Each entry point launches exactly the launcher the
+ * engine uses, on caller-provided device pointers, and returns -2 without launching for a shape its kernel would silently mishandle.  "rows" follow the
+ * gap layout: row_seq[r] = utterance of row r or -1 (gap), row_pos[r] = position inside it, cu_seqlens[b] = packed offset of utterance b. */
+
+/* out[r] = emb[clamp(ling[cu[b] + pos], 0, n_vocab - 1)] + alpha * pe[pos]; tap_out[r] (optional) = the embedding row; gap rows = 0
+ * (reference model_open_source.py:107, modules/encoder.py:257-261).  C even; pe needs max(pos) + 1 rows. */
+int ev_op_embed_pe(const int64_t* ling, const int32_t* cu_seqlens, const int32_t* row_seq, const int32_t* row_pos, const float* emb, int n_vocab,
+                   const float* pe, float alpha, float* out, float* tap_out, int rows, int C, void* hip_stream);
+/* out[r] = (word[clamp(id)] + type[clamp(type_id)]) + pos_emb[min(pos, max_pos - 1)] (transformers BertEmbeddings.forward; reference
+ * models/prompt_tts_modified/simbert.py:37); type_ids NULL = type 0; gap rows = 0.  C even. */
+int ev_op_bert_embed(const int64_t* ids, const int64_t* type_ids, const int32_t* cu_seqlens, const int32_t* row_seq, const int32_t* row_pos,
+                     const float* word, const float* pos_emb, const float* type_emb, int vocab, int max_pos, int n_types, float* out, int rows,
+                     int C, void* hip_stream);
+/* out[b] = tanh(W x[seq_off[b]] + bias) (transformers BertPooler; simbert.py:49-55).  W [C][C]; B <= 65535; ldx >= C. */
+int ev_op_bert_pooler(const float* x, int ldx, const int32_t* seq_off, const float* W, const float* bias, float* out, int B, int C, void* hip_stream);
+/* u[b] = bias + Wcond[:, :C] spk_emb[clamp(speaker[b])] + Wcond[:, C:C+bert] style[b] + Wcond[:, C+bert:] content[b]
+ * (reference model_open_source.py:109-111).  Wcond [C][C + 2 bert]; B <= 65535. */
+int ev_op_cond_vector(const int64_t* speaker, const float* style, const float* content, const float* spk_emb, int n_speaker, const float* Wcond,
+                      const float* bias, float* u, int B, int C, int bert, void* hip_stream);
+/* out[r] = x[r] + (bp + sum_t wp[t] pitch[r + t - (k-1)/2]) + (be + sum_t we[t] energy[r + t - (k-1)/2]) on valid rows, 0 elsewhere
+ * (Conv1d(1 -> C, k, pad (k-1)/2), reference model_open_source.py:131-134).  wp / we [k][C]; k odd, C even; row_valid required.  Halo: pitch / energy are
+ * read at [r - (k-1)/2, r + (k-1)/2] for every valid row r, so (k-1)/2 readable (zero) scalars on both sides of each utterance. */
+int ev_op_var_embed_add(const float* x, const float* pitch, const float* energy, const float* wp, const float* bp, const float* we, const float* be,
+                        const uint8_t* row_valid, float* out, int rows, int C, int k, void* hip_stream);
+/* ev_synthesize_prosody's effective tracks: src = override[cu[b] + pos] if given and finite else the prediction; out = scale * src + shift per utterance
+ * (one fma), an identity transform copies src bit for bit; ctrl SoA [5][B] = alpha, pitch_scale, pitch_shift, energy_scale, energy_shift; gap rows = +0. */
+int ev_op_prosody_tracks(const float* pitch, const float* energy, const int32_t* row_seq, const int32_t* row_pos, const int32_t* cu_seqlens,
+                         const float* pitch_ovr, const float* energy_ovr, const float* ctrl, int B, float* pitch_out, float* energy_out, int rows,
+                         void* hip_stream);
+/* d = max(rint(exp(log_d) - 1), 0) or forced[]; all-zero guard (every d := 1); centre = cumsum(d alpha) - d alpha / 2; mel_len = int(sum d alpha)
+ * (reference modules/variance.py:47-51, modules/alignment.py:183-202).  One block per utterance; alpha == 1: exact integer scan, else a sequential fp32
+ * running sum.  alpha > 0.  log_d / centre_rows are token rows (tok_off), dur_packed / logd_packed / forced packed (cu_seqlens). */
+int ev_op_durations(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const int64_t* forced,
+                    const int32_t* cu_seqlens, int64_t* dur_packed, float* logd_packed, float* centre_rows, int32_t* mel_len, void* hip_stream);
+/* the same with per-utterance scales alpha_b (NULL = alpha) and per-token overrides partial (packed; >= 0 forced and clamped to dur_cap, negative =
+ * predicted; NULL = none): dur_packed keeps the predictions, dur_eff (required) receives what is scanned.  0 <= dur_cap <= 2^20. */
+int ev_op_durations_prosody(const float* log_d, const int32_t* tok_off, const int32_t* tok_len, int B, float alpha, const float* alpha_b,
+                            const int64_t* partial, int64_t dur_cap, const int32_t* cu_seqlens, int64_t* dur_packed, int64_t* dur_eff,
+                            float* logd_packed, float* centre_rows, int32_t* mel_len, void* hip_stream);
+/* tap[t] = sum_j softmax_j(-delta (t - c_j)^2) x[j]; out[t] = tap[t] + pe_alpha * pe[t]; gap rows = 0 (reference modules/alignment.py:204-210,
+ * modules/encoder.py:257-261).  C even, C <= 512 (four float2 accumulators per lane); delta > 0; tap_out optional. */
+int ev_op_gauss_upsample(const float* xvar, const float* centre_rows, const int32_t* tok_off, const int32_t* tok_len, const int32_t* frm_row_seq,
+                         const int32_t* frm_row_pos, const float* pe, float pe_alpha, float delta, float* out, float* tap_out, int rows, int C,
+                         void* hip_stream);
+/* mel of utterance b = (n_mels, mel_len[b]) at element mel_elem_off[b] (fp32, or fp16 if is_f16) -> channels-last rows [rows][ldo] (fp16, or fp32 if
+ * out_f32) with zero gap rows and zero pad channels n_mels..ldo-1.  ldo >= n_mels. */
+int ev_op_mel_to_rows(const void* mel, int is_f16, const int64_t* mel_elem_off, const int32_t* frm_row_seq, const int32_t* frm_row_pos,
+                      const int32_t* mel_len, void* out, int out_f32, int rows, int n_mels, int ldo, void* hip_stream);
+/* wav[r] = tanh(bias + sum_{t, c} w[t][c] a[r + t - (k-1)/2][c]) on rows with row_valid[r >> valid_shift] != 0, else 0 (reference
+ * models/hifigan/models.py:127-129).  fp16 x: a = x; fp32 x: a = max(x, pre_slope x), pre_slope in [0, 1].  C == 32, k odd <= 15, ldx >= 32 and a multiple
+ * of 16 bytes, row_valid required.  Halo: every 256-row block stages rows [256 i - (k-1)/2, 256 i + 256 + (k-1)/2), so rows
+ * [-(k-1)/2, 256 ceil(rows / 256) + (k-1)/2) of x must be readable, and zero outside the utterances. */
+int ev_op_conv_post(const void* x, int is_f32, int ldx, const float* w, float bias, int k, float pre_slope, const uint8_t* row_valid, int valid_shift,
+                    float* wav_rows, int rows, int C, void* hip_stream);
+/* seq[r] = the utterance b with off[b] <= r < off[b] + len[b] or -1, pos[r] = r - off[b] or 0, valid[r] = 1 or 0.  off ascending. */
+int ev_op_row_maps(const int32_t* off, const int32_t* len, int B, int32_t* seq, int32_t* pos, uint8_t* valid, int rows, void* hip_stream);
+/* dst[(seq_out_off[b] + r) * C + c] = (float)src[(seq_row_off[b] + r) * ld + c], r < seq_rows[b] (src fp16 if is_f16, else fp32).  max_rows = max_b
+ * seq_rows[b] sizes the grid (grid-stride above 4096 blocks); B <= 65535; ld >= C. */
+int ev_op_pack_rows(const void* src, int is_f16, int ld, int C, const int64_t* seq_row_off, const int64_t* seq_out_off, const int32_t* seq_rows, int B,
+                    int64_t max_rows, float* dst, void* hip_stream);
+/* out[i] = (int16)(int32)(wav[i] * 32768.0f): truncation toward zero, wrap-around (reference inference_am_vocoder_joint.py:130-131). */
+int ev_op_wav_to_i16(const float* wav, int16_t* out, int64_t n, void* hip_stream);
+/* rows [row0, row1) of the sinusoid table: pe[t][2i] = sin((float)t * div[i]), pe[t][2i+1] = cos(.) (reference modules/encoder.py:216-237).  C even. */
+int ev_op_pe_extend(float* pe, const float* div, int row0, int row1, int C, void* hip_stream);
+/* log_p[lp_off[b] + t N + n] = log_softmax_n(-||feats[frm_row[b] + t] - text[tok_row[b] + n]||_2) + log betabinom.pmf(n; N, t + 1, T - t)
+ * (reference modules/alignment.py:27-55).  The per-utterance arrays are HOST arrays of B entries; the call waits for the stream.  C % 32 == 0,
+ * 1 <= tokens <= 2048, 1 <= frames <= 16384 (-2 otherwise). */
+int ev_op_align_score(const float* text, const float* feats, int C, int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row,
+                      const int32_t* frames, const int64_t* lp_off, float* log_p, void* hip_stream);
+/* Monotonic alignment search on log_p (T, N) per utterance with Q in fp64 (reference modules/alignment.py:93-122, 145-162): dur[tok_packed[b] + n],
+ * the per-token fp64 means of the optional frame tracks (pitch_frames / energy_frames at frm_packed[b] + t; both NULL-able), score[b] = the mean
+ * log_p along the path.  bits: scratch, 64 words per frame at bits_off[b].  HOST per-utterance arrays; the call waits for the stream.  One wave per
+ * utterance, RM = 1, 2, .. 32 tokens per lane chosen by the batch's longest utterance.  1 <= tokens <= 2048, tokens <= frames <= 16384 (-2 otherwise). */
+int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int32_t* frames, const int64_t* lp_off, const int64_t* tok_packed,
+                    const int64_t* frm_packed, const int64_t* bits_off, uint32_t* bits, const float* pitch_frames, const float* energy_frames,
+                    int64_t* dur, float* pitch_tok, float* energy_tok, float* score, void* hip_stream);
 
 #ifdef __cplusplus
 }

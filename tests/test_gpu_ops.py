@@ -1733,3 +1733,159 @@ def test_layernorm_writes_its_consumers_plane_set(lib):
         assert np.array_equal(sl_(qs[i]).cpu().numpy(), sb), i
     assert not hpl[PAD:PAD + rows].cpu().numpy()[~valid.bool().cpu().numpy()].any()
     assert float(hpl[:PAD].float().min()) == 3.0 and float(hpl[PAD + rows:].float().max()) == 3.0            # slack rows untouched
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Attention and LayerNorm at their dispatch / tile edges, against float64 references (tests/misc_ops_ref.py).  Measure: the worst ROW's relative L2.
+# Bound: 4 x what the plain fp32 torch op on the CPU measures against the same reference on the same inputs (misc_ops_ref.BASELINES; for the
+# fp16-operand and split-precision paths the CPU evaluation rounds the operands where the kernels' comments say they do), floor 4 fp32 ulp.
+import misc_ops_ref as MR      # noqa: E402
+
+_EDGE_REPORTS = {}          # what the edge tests measured, written next to parity_report.json
+
+
+def _attn_launch(lib, mode, C_, H, blocks, max_len, nan_gaps=True):
+    """blocks: list of (n, 3 C) arrays; gap rows and 64 rows on both ends hold NaN (a kernel that USED one would give a non-finite output)"""
+    lens = [b.shape[0] for b in blocks]
+    offs, rows = [], 64
+    for n in lens:
+        offs.append(rows)
+        rows += n + 4
+    rows += 60
+    dt = np.float16 if mode == 1 else np.float32
+    qkv = np.full((rows, 3 * C_), np.nan if nan_gaps else 0.0, dt)
+    for o, b in zip(offs, blocks):
+        qkv[o:o + len(b)] = b
+    dq = torch.from_numpy(qkv).cuda()
+    out = torch.full((rows, C_), 777.0, device="cuda", dtype=dq.dtype)
+    so, sl = torch.tensor(offs, dtype=torch.int32, device="cuda"), torch.tensor(lens, dtype=torch.int32, device="cuda")
+    assert lib.ev_op_attention(dq.data_ptr(), mode, C_, H, so.data_ptr(), sl.data_ptr(), len(lens), max_len, out.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    keep = np.ones(rows, bool)
+    res = []
+    for of, n in zip(offs, lens):
+        keep[of:of + n] = False
+        res.append(o[of:of + n])
+    assert (o[keep] == dt(777.0)).all(), "rows outside the utterances were written"
+    return res
+
+
+_ATT_KERNELS = {"f32_dk48": "attention_mfma_f32_kernel<48>", "f32_dk64": "attention_mfma_f32_kernel<64>", "f16_dk48": "attention_mfma_kernel",
+                "x3_dk48": "attention_mfma_x3_lds_kernel<48,4|8|16>"}
+
+
+@pytest.mark.parametrize("family", MR.ATT_FAMILIES)
+@pytest.mark.parametrize("mode_name", list(MR.ATT_MODES), ids=[_ATT_KERNELS[m] for m in MR.ATT_MODES])
+def test_attention_edges(lib, mode_name, family):
+    """Lengths 1 .. 1000 around every tile and dispatch edge, as one batch (max_len = 1000) and each alone with max_len = its own length.
+    launch_attention picks by (dtype, d_k, max_len): fp32 rows -> attention_mfma_f32_kernel<48> / <64> (SimBERT, 12 x 64); fp16 rows ->
+    attention_mfma_kernel; split precision -> attention_mfma_x3_lds_kernel<48, 4> for max_len <= 64, <48, 8> for <= 128, <48, 16> above: the solo
+    launches of lengths <= 64 / 65 .. 128 / > 128 are what reach NW = 4 / 8 / 16, and their bits must equal the batch's (NW = 16) -- the engine's
+    batch-invariance promise.  Families: see misc_ops_ref.attention_inputs (peaked: the other keys underflow; ascending: every tile rescales;
+    constant: the mean of v; bigv: |v| ~ 1e4 under tiny probabilities)."""
+    mode, C_, H = MR.ATT_MODES[mode_name]
+    cases = list(MR.attention_cases(mode_name, families=(family,)))
+    key = cases[0][0]
+    bnd = MR.bound(MR.BASELINES[key])
+    batch = _attn_launch(lib, mode, C_, H, [c[2] for c in cases], max(MR.ATT_LENS))
+    worst = {}
+    for (_, cid, qkv, ref, _), got_b in zip(cases, batch):
+        n = qkv.shape[0]
+        got_s = _attn_launch(lib, mode, C_, H, [qkv], n)[0]
+        assert np.isfinite(got_b.astype(np.float32)).all() and np.isfinite(got_s.astype(np.float32)).all(), cid
+        worst[cid] = max(MR.worst_row_rel(got_b, ref), MR.worst_row_rel(got_s, ref))
+        if mode == 2:
+            nw = 4 if n <= 64 else (8 if n <= 128 else 16)
+            assert np.array_equal(got_s.view(np.uint32), got_b.view(np.uint32)), "solo (NW = %d) and in-batch (NW = 16) differ at n = %d" % (nw, n)
+    from test_gpu_parity import _report as write_report
+    write_report(key, {"bound": bnd, "measured": worst}, "attention_edges_report.json", _EDGE_REPORTS.setdefault("attention", {}))
+    print(key, "worst", max(worst.values()), "bound", bnd)
+    assert max(worst.values()) <= bnd, (key, bnd, {k: v for k, v in worst.items() if v > bnd})
+
+
+def test_attention_rejects_unsupported_head_sizes(lib):
+    t = torch.zeros(8, device="cuda")
+    for mode, C_, H in ((0, 384, 12), (1, 768, 12), (2, 768, 12), (3, 384, 8)):
+        assert lib.ev_op_attention(t.data_ptr(), mode, C_, H, t.data_ptr(), t.data_ptr(), 1, 8, t.data_ptr(), None) == -2
+
+
+@pytest.mark.parametrize("family", MR.LN_FAMILIES)
+def test_layernorm_edges(lib, family):
+    """layernorm_kernel<4, false> (C <= 512) and <8, false> (C = 640, 768, 1024); rows 1, 2, 3, 5 (the rows % 4 tail of the 4-rows-per-block grid)
+    and 300; with and without row_valid, the fused dot head and the fp16 output.  nearconst: eps = 1e-12 makes the 1e-6 spread the reference's own
+    amplification of the fp32 inputs' rounding, which the fp32 CPU baseline shares."""
+    worst = {}
+    for key, cid, (x, g, b, w), ref, _ in MR.layernorm_cases():
+        if not key.endswith(family):
+            continue
+        rows, Cc = x.shape
+        dx, dg, db, dw = (torch.from_numpy(a).cuda() for a in (x, g, b, w))
+        for masked in (False, True):
+            valid = np.ones(rows, np.uint8)
+            if masked:
+                valid[rows // 2] = 0
+            dv = torch.from_numpy(valid).cuda()
+            o32 = torch.full((rows + 8, Cc), 9.0, device="cuda")
+            o16 = torch.full((rows + 8, Cc), 9.0, device="cuda", dtype=torch.float16)
+            dot = torch.full((rows + 8,), 9.0, device="cuda")
+            assert lib.ev_op_layernorm(dx.data_ptr(), rows, Cc, dg.data_ptr(), db.data_ptr(), 1e-12, dv.data_ptr() if masked else None, o16[4:].data_ptr(),
+                                       o32[4:].data_ptr(), dw.data_ptr(), 0.25, dot[4:].data_ptr(), None) == 0
+            only32 = torch.full((rows + 8, Cc), 9.0, device="cuda")
+            assert lib.ev_op_layernorm(dx.data_ptr(), rows, Cc, dg.data_ptr(), db.data_ptr(), 1e-12, dv.data_ptr() if masked else None, None,
+                                       only32[4:].data_ptr(), None, 0.0, None, None) == 0
+            torch.cuda.synchronize()
+            for t in (o32, o16, dot, only32):
+                tn = t.float().cpu().numpy()
+                assert (tn[:4] == 9.0).all() and (tn[4 + rows:] == 9.0).all(), "guard rows overwritten"
+            g32, g16, gd = o32[4:4 + rows].cpu().numpy(), o16[4:4 + rows].cpu().numpy(), dot[4:4 + rows].cpu().numpy()
+            assert np.array_equal(only32[4:4 + rows].cpu().numpy(), g32)           # the optional outputs do not change the fp32 rows
+            r = ref.copy()
+            on = valid != 0
+            assert not g32[~on].any() and not g16[~on].any() and not gd[~on].any()
+            r[~on] = 0
+            dot_e = MR.dot_err(gd[on] - 0.25, r[on], w) if on.any() else 0.0
+            for sub, v in (("", MR.worst_row_rel(g32, r)), ("/f16", MR.worst_row_rel(g16, r)), ("/dot", dot_e)):
+                worst[key + sub] = max(worst.get(key + sub, 0.0), v)
+                assert v <= MR.bound(MR.BASELINES[key + sub]), (cid, sub, masked, v, MR.bound(MR.BASELINES[key + sub]))
+    from test_gpu_parity import _report as write_report
+    for k, v in worst.items():
+        write_report(k, [v, MR.bound(MR.BASELINES[k])], "layernorm_edges_report.json", _EDGE_REPORTS.setdefault("layernorm", {}))
+    print(worst)
+
+
+def test_layernorm_rejects_widths_the_kernel_mishandles(lib):
+    t = torch.zeros(2048, device="cuda")
+    for Cc in (64, 192, 1152, 2048):
+        assert lib.ev_op_layernorm(t.data_ptr(), 1, Cc, t.data_ptr(), t.data_ptr(), 1e-12, None, None, t.data_ptr(), None, 0.0, None, None) == -2
+    assert lib.ev_op_layernorm_planes(t.data_ptr(), 1, 640, t.data_ptr(), t.data_ptr(), 1e-12, None, t.data_ptr(), t.data_ptr(), t.data_ptr(), t.data_ptr(),
+                                      t.data_ptr(), 4, None) == -2
+
+
+@pytest.mark.parametrize("Cc", [128, 256, 384, 512])
+def test_layernorm_planes_every_width(lib, Cc):
+    """layernorm_kernel<4, true> at every width it serves, rows = 7 (rows % 4 tail): bit for bit the host planes (mxfp4.py) of the kernel's own fp32 output"""
+    torch.manual_seed(Cc)
+    rows = 7
+    x = (torch.randn(rows, Cc, device="cuda") * torch.exp(0.5 * torch.randn(rows, 1, device="cuda")) + 0.3)
+    g, b = torch.randn(Cc, device="cuda") * 0.5 + 1.0, torch.randn(Cc, device="cuda") * 0.2
+    valid = torch.ones(rows, dtype=torch.uint8, device="cuda")
+    valid[2] = 0
+    y = torch.full((rows, Cc), 9.0, device="cuda")
+    assert lib.ev_op_layernorm(x.data_ptr(), rows, Cc, g.data_ptr(), b.data_ptr(), 1e-12, valid.data_ptr(), None, y.data_ptr(), None, 0.0, None, None) == 0
+    Rr = rows + 2 * PAD
+    hpl = torch.full((Rr, Cc), 3.0, device="cuda", dtype=torch.float16)
+    q4 = [torch.full((Rr, Cc // 2), 0x77, device="cuda", dtype=torch.uint8) for _ in range(2)]
+    qs = [torch.full((Cc // 128, Rr, 4), 130, device="cuda", dtype=torch.uint8) for _ in range(2)]
+    assert lib.ev_op_layernorm_planes(x.data_ptr(), rows, Cc, g.data_ptr(), b.data_ptr(), 1e-12, valid.data_ptr(), hpl[PAD:].data_ptr(),
+                                      q4[0][PAD:].data_ptr(), q4[1][PAD:].data_ptr(), qs[0][0, PAD:].data_ptr(), qs[1][0, PAD:].data_ptr(), Rr * 4, None) == 0
+    torch.cuda.synchronize()
+    _, _, _, (h16, ch, cl, sh, sl) = _mx_act_parts(y.cpu())
+    assert np.array_equal(hpl[PAD:PAD + rows].cpu().numpy().view(np.uint16), h16.view(np.uint16))
+    sl_ = lambda q: q[:, PAD:PAD + rows].permute(1, 0, 2).reshape(rows, Cc // 32)      # noqa: E731
+    for i, (codes, sb) in enumerate(((ch, sh), (cl, sl))):
+        assert np.array_equal(q4[i][PAD:PAD + rows].cpu().numpy(), codes), i
+        assert np.array_equal(sl_(qs[i]).cpu().numpy(), sb), i
+    assert float(hpl[:PAD].float().min()) == 3.0 and float(hpl[PAD + rows:].float().max()) == 3.0            # slack rows untouched
+    for q in q4:
+        assert int(q[:PAD].min()) == 0x77 and int(q[PAD + rows:].max()) == 0x77

@@ -42,12 +42,14 @@ NEAR_EPS = 2e-5         # |frac(exp(log_d) - 1) - 0.5| below which a duration ma
 REPORT = {}
 
 
-def _report(key, val):
-    REPORT[key] = val
+def _report(key, val, name="parity_report.json", report=None):
+    """records val under key and rewrites the report file; the other GPU test files keep reports of their own (name, report) next to this one"""
+    report = REPORT if report is None else report
+    report[key] = val
     out = os.path.join(ROOT, "gpurun_out")
     os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, "parity_report.json"), "w") as f:
-        json.dump(REPORT, f, indent=1, sort_keys=True)
+    with open(os.path.join(out, name), "w") as f:
+        json.dump(report, f, indent=1, sort_keys=True)
 
 
 def rel_l2_ac(a, b):
