@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("EVHIP_LIB", os.path.join(_HERE, "csrc", "libevhip.so"
 EV_ABI_VERSION = 7
 EV_PREC_F16, EV_PREC_F32, EV_PREC_X3, EV_PREC_MX = 0, 1, 2, 3
 EV_FLAG_DEVICE_INPUTS, EV_FLAG_NO_VOCODER, EV_FLAG_WANT_INT16, EV_FLAG_FORCED_DURATIONS = 1, 2, 4, 8
+EV_FLAG_DEVICE_MEL = 16      # ev_align: mel / pitch_frames / energy_frames are device pointers (an ev_features_result), the rest host
 
 
 class ev_config(C.Structure):
@@ -59,6 +60,23 @@ class ev_align_result(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_tokens", C.c_int32), ("reserved0", C.c_int32), ("total_frames", C.c_int64),
         ("durations", C.c_void_p), ("pitch", C.c_void_p), ("energy", C.c_void_p), ("score", C.c_void_p),
+        ("mel_lens", C.POINTER(C.c_int32)), ("mel_offsets", C.POINTER(C.c_int64)),
+    ]
+
+
+EV_FEATURES_MAX_NFFT, EV_FEATURES_MAX_MELS, EV_FEATURES_MAX_RUN = 2048, 128, 24576
+
+
+class ev_features_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("mel_clip", C.c_float),
+        ("energy_floor", C.c_float), ("mel_basis", C.c_void_p), ("window", C.c_void_p),
+    ]
+
+
+class ev_features_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_frames", C.c_int64), ("mel", C.c_void_p), ("energy", C.c_void_p),
         ("mel_lens", C.POINTER(C.c_int32)), ("mel_offsets", C.POINTER(C.c_int64)),
     ]
 
@@ -119,6 +137,9 @@ SIGNATURES = {
     "ev_synthesize": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_uint32, C.POINTER(ev_result)]),
     "ev_synthesize_prosody": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.POINTER(ev_prosody), C.c_uint32, C.POINTER(ev_result)]),
     "ev_align": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_uint32, C.POINTER(ev_align_result)]),
+    "ev_default_features_config": (None, [C.POINTER(ev_features_config)]),
+    "ev_features_setup": (C.c_int, [_P, C.POINTER(ev_features_config)]),
+    "ev_features": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(ev_features_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -159,6 +180,8 @@ SIGNATURES = {
     # the per-utterance arrays of the two aligner ops are HOST arrays (the wrapper builds the device table)
     "ev_op_align_score": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "ev_op_align_mas": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # wav_lens, mel_basis and window are HOST arrays (the wrapper packs the basis planes)
+    "ev_op_stft_mel": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
 }
 
 _lib = None

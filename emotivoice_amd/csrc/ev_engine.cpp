@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[4] = {nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[4] = {0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align)
+    char* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[5] = {0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features (likewise)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -91,6 +91,10 @@ struct ev_handle {
     // ev_align: host halves of its result (kept apart from the synthesis' mel_lens / mel_offs) and the "log_p_attn" stage of the last call
     std::vector<int32_t> aln_mel_lens; std::vector<int64_t> aln_mel_offs; std::vector<AlignSeq> aln_seqs;
     const float* aln_lp = nullptr; int64_t aln_lp_elems = 0;
+    // ev_features: its setup (basis planes on the device), the host halves of its result and the "feat_mag" stage of the last call
+    ev_features_config fcfg{}; bool feat_ready = false; char* feat_basis = nullptr; float* feat_melT = nullptr;
+    std::vector<int32_t> feat_mel_lens; std::vector<int64_t> feat_mel_offs;
+    const float* feat_mag = nullptr; int64_t feat_mag_elems = 0;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1103,7 +1107,9 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 4; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 5; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    if (h->feat_basis) (void)hipFree(h->feat_basis);
+    if (h->feat_melT) (void)hipFree(h->feat_melT);
     if (h->sblob) (void)hipFree(h->sblob);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->pe_dev) (void)hipFree(h->pe_dev);
@@ -1600,6 +1606,7 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const 
     const int C = c.hidden;
     const bool keep = c.keep_stages != 0;
     const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    const bool dev_mel = dev_in || (flags & EV_FLAG_DEVICE_MEL) != 0;     // mel / pitch_frames / energy_frames already on the device
     const int NT = cu[B];
     int max_tok = 0, max_frames = 0;
     int64_t rows = GAP, lp_elems = 0, total_frames = 0;
@@ -1651,9 +1658,9 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const 
         build_frame_layout(h, ap, pass == 0, B);
         ab.d_ling = ap.arr<int64_t>(NT); ab.d_spk = ap.arr<int64_t>(B); ab.d_style = ap.arr<float>((size_t)B * c.bert_dim);
         ab.d_content = ap.arr<float>((size_t)B * c.bert_dim); ab.d_u = ap.arr<float>((size_t)B * C); ab.d_eoff = ap.arr<int64_t>(B);
-        ab.d_mel = dev_in ? nullptr : ap.take((size_t)total_frames * c.n_mels * mel_es);
-        ab.d_pf = (pitch_frames && !dev_in) ? ap.arr<float>(total_frames) : nullptr;
-        ab.d_ef = (energy_frames && !dev_in) ? ap.arr<float>(total_frames) : nullptr;
+        ab.d_mel = dev_mel ? nullptr : ap.take((size_t)total_frames * c.n_mels * mel_es);
+        ab.d_pf = (pitch_frames && !dev_mel) ? ap.arr<float>(total_frames) : nullptr;
+        ab.d_ef = (energy_frames && !dev_mel) ? ap.arr<float>(total_frames) : nullptr;
         ab.d_seqs = ap.arr<AlignSeq>(B); ab.d_bits = ap.arr<uint32_t>((size_t)total_frames * 64);
         ab.d_dur = ap.arr<int64_t>(NT); ab.d_pitch = pitch_frames ? ap.arr<float>(NT) : nullptr; ab.d_energy = energy_frames ? ap.arr<float>(NT) : nullptr;
         ab.d_score = ap.arr<float>(B); ab.d_lp = ap.arr<float>((size_t)lp_elems);
@@ -1694,15 +1701,15 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const 
         HIPCHK(h, hipMemcpyAsync(h->d_mel_len, mel_lens, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(ab.d_eoff, elem_off.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(ab.d_seqs, h->aln_seqs.data(), (size_t)B * sizeof(AlignSeq), hipMemcpyHostToDevice, h->stream));
-        if (!dev_in) {
+        if (!dev_mel) {
             HIPCHK(h, hipMemcpyAsync(ab.d_mel, mel, (size_t)total_frames * c.n_mels * mel_es, hipMemcpyHostToDevice, h->stream));
             if (pitch_frames) HIPCHK(h, hipMemcpyAsync(ab.d_pf, pitch_frames, (size_t)total_frames * 4, hipMemcpyHostToDevice, h->stream));
             if (energy_frames) HIPCHK(h, hipMemcpyAsync(ab.d_ef, energy_frames, (size_t)total_frames * 4, hipMemcpyHostToDevice, h->stream));
         }
     }
-    const void* melsrc = dev_in ? mel : ab.d_mel;
-    const float* pf = dev_in ? pitch_frames : ab.d_pf;
-    const float* ef = dev_in ? energy_frames : ab.d_ef;
+    const void* melsrc = dev_mel ? mel : ab.d_mel;
+    const float* pf = dev_mel ? pitch_frames : ab.d_pf;
+    const float* ef = dev_mel ? energy_frames : ab.d_ef;
     region_begin(h, "total");
     // text side: the token-rate path of ev_synthesize up to embed_projection1 (same kernels, same layout: the same x_proj bits)
     RowCtx trc{Rt, h->d_tok_valid, h->d_tok_seq, h->d_tok_off, h->d_tok_len, B, max_tok, (double)NT};
@@ -1756,6 +1763,142 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const 
     out->struct_size = sz; out->batch = B; out->total_tokens = NT; out->total_frames = total_frames;
     out->durations = ab.d_dur; out->pitch = ab.d_pitch; out->energy = ab.d_energy; out->score = ab.d_score;
     out->mel_lens = h->aln_mel_lens.data(); out->mel_offsets = h->aln_mel_offs.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- acoustic features (include/evhip.h: ev_features)
+static_assert(EV_FEATURES_MAX_NFFT == STFT_MAX_NFFT && EV_FEATURES_MAX_MELS == STFT_MAX_MELS && EV_FEATURES_MAX_RUN == STFT_MAX_RUN,
+              "include/evhip.h states the limits of ev_features.hip");
+void ev_default_features_config(ev_features_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_features_config);
+    c->n_fft = 1024; c->hop = 256; c->n_mels = 80; c->mel_clip = 1e-5f; c->energy_floor = 1e-10f;
+}
+
+static int features_check_config(ev_handle* h, const char* who, int n_fft, int hop, int n_mels) {
+    if (n_fft < 128 || n_fft % 128 || n_fft > STFT_MAX_NFFT) return fail(h, "%s: n_fft %d must be a multiple of 128 in [128, %d]", who, n_fft, STFT_MAX_NFFT);
+    if (n_mels < 1 || n_mels > STFT_MAX_MELS) return fail(h, "%s: n_mels %d outside [1, %d]", who, n_mels, STFT_MAX_MELS);
+    if (hop < 8 || hop % 8 || hop > n_fft) return fail(h, "%s: hop %d must be a multiple of 8 in [8, n_fft]", who, hop);
+    if (!stft_shape_ok(n_fft, hop, n_mels)) return fail(h, "%s: hop %d: the 63 hop + n_fft samples of a 64-frame tile exceed %d", who, hop, STFT_MAX_RUN);
+    return 0;
+}
+
+// packs the basis planes on the host and uploads them; *basis / *melT are hipMalloc'ed
+static int features_upload_tables(ev_handle* h, int n_fft, int n_mels, const float* mel_basis, const float* window, char** basis, float** melT) {
+    std::vector<uint16_t> hb(stft_basis_halfs(n_fft));
+    std::vector<float> hm(stft_melT_floats(n_fft));
+    stft_pack_basis(n_fft, window, hb.data());
+    stft_pack_mel(n_fft, n_mels, mel_basis, hm.data());
+    *basis = nullptr; *melT = nullptr;
+    hipError_t e = hipMalloc((void**)basis, hb.size() * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)melT, hm.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(*basis, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(*melT, hm.data(), hm.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {       // nothing half-built is left behind
+        if (*basis) (void)hipFree(*basis);
+        if (*melT) (void)hipFree(*melT);
+        *basis = nullptr; *melT = nullptr;
+        return fail(h, "ev_features: uploading the basis planes failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+int ev_features_setup(ev_handle* h, const ev_features_config* cfg) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_features_setup: null config");
+    if (cfg->struct_size != sizeof(ev_features_config))
+        return fail(h, "ev_features_setup: struct_size %u != sizeof(ev_features_config) %zu", cfg->struct_size, sizeof(ev_features_config));
+    if (features_check_config(h, "ev_features_setup", cfg->n_fft, cfg->hop, cfg->n_mels)) return -1;
+    if (!cfg->mel_basis) return fail(h, "ev_features_setup: mel_basis is required");
+    if (!(cfg->mel_clip > 0.f) || !std::isfinite(cfg->mel_clip)) return fail(h, "ev_features_setup: mel_clip must be positive and finite");
+    if (!(cfg->energy_floor >= 0.f) || !std::isfinite(cfg->energy_floor)) return fail(h, "ev_features_setup: energy_floor must be >= 0 and finite");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->feat_ready = false;
+    if (h->feat_basis) { HIPCHK(h, hipFree(h->feat_basis)); h->feat_basis = nullptr; }
+    if (h->feat_melT) { HIPCHK(h, hipFree(h->feat_melT)); h->feat_melT = nullptr; }
+    if (features_upload_tables(h, cfg->n_fft, cfg->n_mels, cfg->mel_basis, cfg->window, &h->feat_basis, &h->feat_melT)) return -1;
+    h->fcfg = *cfg; h->fcfg.mel_basis = nullptr; h->fcfg.window = nullptr;
+    h->feat_ready = true;
+    return 0;
+}
+
+// frame counts, offsets and the tile table of a batch; 0 or the index + 1 of the first utterance that is too short (-(index + 1): too long)
+static int features_layout(int B, const int64_t* wav_lens, int n_fft, int hop, std::vector<StftSeq>& seqs, std::vector<StftTile>& tiles,
+                           std::vector<int32_t>& lens, std::vector<int64_t>& offs) {
+    seqs.resize(B); lens.resize(B); offs.resize((size_t)B + 1); tiles.clear();
+    int64_t wo = 0, fo = 0;
+    for (int b = 0; b < B; ++b) {
+        if (wav_lens[b] < n_fft / 2 + 1) return b + 1;
+        const int64_t T = wav_lens[b] / hop + 1;
+        if (T > EV_ALIGN_MAX_FRAMES) return -(b + 1);
+        seqs[b] = StftSeq{wo, wav_lens[b], fo, (int32_t)T, 0};
+        lens[b] = (int32_t)T; offs[b] = fo;
+        for (int t0 = 0; t0 < T; t0 += 64) tiles.push_back(StftTile{b, t0});
+        wo += wav_lens[b]; fo += T;
+    }
+    offs[B] = fo;
+    return 0;
+}
+
+int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, float energy_mean, float energy_std, uint32_t flags,
+                ev_features_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out || B <= 0) return fail(h, "ev_features: bad argument");
+    if (out->struct_size != sizeof(ev_features_result))
+        return fail(h, "ev_features: out->struct_size %u != sizeof(ev_features_result) %zu", out->struct_size, sizeof(ev_features_result));
+    if (!h->feat_ready) return fail(h, "ev_features: ev_features_setup has not been called");
+    if ((size_t)B > PIN_MAX_B) return fail(h, "ev_features: at most %zu utterances per call", PIN_MAX_B);
+    if (!std::isfinite(energy_std) || !(energy_std > 0.f)) return fail(h, "ev_features: energy_std must be positive and finite");
+    if (!std::isfinite(energy_mean)) return fail(h, "ev_features: energy_mean must be finite");
+    const ev_features_config& fc = h->fcfg;
+    const int n_bins = fc.n_fft / 2 + 1;
+    std::vector<StftSeq> seqs; std::vector<StftTile> tiles; std::vector<int32_t> lens; std::vector<int64_t> offs;
+    const int bad = features_layout(B, wav_lens, fc.n_fft, fc.hop, seqs, tiles, lens, offs);
+    if (bad > 0) return fail(h, "ev_features: wav_lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", bad - 1, (long long)wav_lens[bad - 1], fc.n_fft / 2 + 1);
+    if (bad < 0) return fail(h, "ev_features: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / fc.hop + 1), EV_ALIGN_MAX_FRAMES);
+    const int64_t total_frames = offs[B], total_samples = seqs[B - 1].wav_off + seqs[B - 1].len;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    h->feat_mag = nullptr;
+    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_mel = nullptr, *d_energy = nullptr, *d_mag = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 4, pass == 0};
+        if (pass == 1 && arena_reserve(h, 4, need)) return -1;
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(tiles.size());
+        d_mel = ap.arr<float>((size_t)total_frames * fc.n_mels); d_energy = ap.arr<float>((size_t)total_frames);
+        d_mag = keep ? ap.arr<float>((size_t)total_frames * n_bins) : nullptr;
+        need = ap.off;
+    }
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_seqs, seqs.data(), (size_t)B * sizeof(StftSeq), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(StftTile), hipMemcpyHostToDevice, h->stream));
+    region_begin(h, "total");
+    {
+        StftParams p{};
+        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)tiles.size();
+        p.basis = h->feat_basis; p.melT = h->feat_melT; p.n_fft = fc.n_fft; p.hop = fc.hop; p.n_mels = fc.n_mels; p.nmi = stft_mels_per_group(fc.n_mels);
+        p.n_bins = n_bins; p.n_btiles = stft_bin_tiles(fc.n_fft); p.mel_clip = fc.mel_clip; p.energy_floor = fc.energy_floor;
+        p.energy_mean = energy_mean; p.energy_std = energy_std; p.mel = d_mel; p.energy = d_energy; p.mag = d_mag;
+        const double tile_frames = 64.0 * (double)tiles.size();
+        KScope ks(h, "stft_mel", 2.0 * 3.0 * tile_frames * fc.n_fft * 2.0 * n_bins + 2.0 * tile_frames * n_bins * fc.n_mels,
+                  (double)total_samples * es + (double)total_frames * (fc.n_mels + 1) * 4.0);
+        if (launch_stft_mel(p, h->stream)) return fail(h, "ev_features: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    h->feat_mel_lens = lens; h->feat_mel_offs = offs;
+    h->feat_mag = d_mag; h->feat_mag_elems = keep ? total_frames * n_bins : 0;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total_frames = total_frames; out->mel = d_mel; out->energy = d_energy;
+    out->mel_lens = h->feat_mel_lens.data(); out->mel_offsets = h->feat_mel_offs.data();
     return 0;
 }
 
@@ -1897,6 +2040,14 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
         if (!host_dst) return (int64_t)need;
         if (cap < need || !h->last_dur_eff) return fail(h, "ev_get_stage(dur_eff): buffer too small or no synthesis yet");
         HIPCHK(h, hipMemcpy(host_dst, h->last_dur_eff, need, hipMemcpyDeviceToHost));
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "feat_mag")) {       // ev_features (keep_stages): the (total_frames, n_fft / 2 + 1) magnitudes of the last ev_features
+        const size_t need = (size_t)h->feat_mag_elems * 4;
+        if (!h->feat_mag) return fail(h, "ev_get_stage(feat_mag): no ev_features call with keep_stages yet");
+        if (!host_dst) return (int64_t)need;
+        if (cap < need) return fail(h, "ev_get_stage(feat_mag): need %zu bytes, cap %zu", need, cap);
+        if (hipMemcpy(host_dst, h->feat_mag, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(feat_mag): D2H failed");
         return (int64_t)need;
     }
     if (!strcmp(name, "log_p_attn")) {     // ev_align: the (T_b, N_b) blocks of the utterances, concatenated
@@ -2103,6 +2254,33 @@ int ev_op_pe_extend(float* pe, const float* div, int row0, int row1, int C, void
     launch_pe_extend(pe, div, row0, row1, C, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* mel_basis, const float* window, int n_fft, int hop,
+                   int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
+                   void* stream) {
+    if (!wav || !wav_lens || !mel_basis || !mel || !energy || B < 1 || B > 65535 || !stft_shape_ok(n_fft, hop, n_mels)) return -2;
+    std::vector<StftSeq> seqs; std::vector<StftTile> tiles; std::vector<int32_t> lens; std::vector<int64_t> offs;
+    if (features_layout(B, wav_lens, n_fft, hop, seqs, tiles, lens, offs)) return -2;
+    char* basis = nullptr; float* melT = nullptr; char* tab = nullptr;
+    int rc = features_upload_tables(nullptr, n_fft, n_mels, mel_basis, window, &basis, &melT) ? -1 : 0;
+    const size_t sb = (size_t)B * sizeof(StftSeq), tb = tiles.size() * sizeof(StftTile);
+    if (rc == 0 && hipMalloc((void**)&tab, sb + tb) != hipSuccess) rc = -1;
+    if (rc == 0 && (hipMemcpy(tab, seqs.data(), sb, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(tab + sb, tiles.data(), tb, hipMemcpyHostToDevice) != hipSuccess)) rc = -1;
+    if (rc == 0) {
+        StftParams p{};
+        p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = (const StftSeq*)tab; p.tiles = (const StftTile*)(tab + sb); p.n_tiles = (int)tiles.size();
+        p.basis = basis; p.melT = melT; p.n_fft = n_fft; p.hop = hop; p.n_mels = n_mels; p.nmi = stft_mels_per_group(n_mels); p.n_bins = n_fft / 2 + 1;
+        p.n_btiles = stft_bin_tiles(n_fft); p.mel_clip = mel_clip; p.energy_floor = energy_floor; p.energy_mean = energy_mean; p.energy_std = energy_std;
+        p.mel = mel; p.energy = energy; p.mag = mag;
+        if (launch_stft_mel(p, (hipStream_t)stream)) rc = -2;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    if (basis) (void)hipFree(basis);
+    if (melT) (void)hipFree(melT);
+    if (tab) (void)hipFree(tab);
+    return rc;
+}
+
 // The AlignSeq table of the two aligner kernels is built here from per-utterance HOST arrays (no struct crosses the boundary); both calls
 // copy it to the device, launch, and wait for the stream before releasing it.
 static int op_align_table(int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row, const int32_t* frames, const int64_t* lp_off,

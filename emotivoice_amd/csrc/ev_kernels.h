@@ -238,4 +238,28 @@ void launch_align_score(const float* text, const float* feats, int C, const Alig
 void launch_align_mas(const float* log_p, const AlignSeq* seqs, int B, int max_tokens, uint32_t* bits, const float* pitch_frames,
                       const float* energy_frames, int64_t* dur, float* pitch_tok, float* energy_tok, float* score, hipStream_t s);
 
+// ev_features (ev_features.hip): wav -> log-mel and frame energy.  Limits of the kernel: n_fft a multiple of 128 up to STFT_MAX_NFFT, hop a multiple
+// of 8 up to n_fft, n_mels <= STFT_MAX_MELS, and the 63 hop + n_fft samples of a 64-frame tile within STFT_MAX_RUN (they stay in LDS).
+constexpr int STFT_MAX_NFFT = 2048, STFT_MAX_MELS = 128, STFT_MAX_RUN = 24576;
+struct StftSeq { int64_t wav_off, len, frm_off; int32_t frames, reserved; };   // sample offset / length of the utterance, its packed frame offset, T
+struct StftTile { int32_t seq, t0; };                                           // one block: utterance and first frame
+struct StftParams {
+    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
+    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
+    const void* basis; const float* melT;             // stft_pack_basis / stft_pack_mel, on the device
+    int n_fft, hop, n_mels, nmi, n_bins, n_btiles;    // nmi = stft_mels_per_group, n_bins = n_fft / 2 + 1, n_btiles = stft_bin_tiles
+    float mel_clip, energy_floor, energy_mean, energy_std;
+    float* mel;                                       // per utterance (n_mels, T) row-major at frm_off * n_mels: log(max(mel_basis @ mag, mel_clip))
+    float* energy;                                    // (total_frames,): (sqrt(max(sum_k mag^2, energy_floor)) - energy_mean) / energy_std
+    float* mag;                                       // (total_frames, n_bins) or null
+};
+int stft_shape_ok(int n_fft, int hop, int n_mels);
+int stft_bin_tiles(int n_fft);
+int stft_mels_per_group(int n_mels);
+size_t stft_basis_halfs(int n_fft);
+size_t stft_melT_floats(int n_fft);
+void stft_pack_basis(int n_fft, const float* window /* host (n_fft,) or null = periodic hann */, uint16_t* out /* host, stft_basis_halfs */);
+void stft_pack_mel(int n_fft, int n_mels, const float* mel_basis /* host (n_mels, n_bins) */, float* out /* host, stft_melT_floats */);
+int launch_stft_mel(const StftParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
+
 }  // namespace ev

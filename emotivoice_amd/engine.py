@@ -91,6 +91,8 @@ class EVEngine:
         self.device_id = device_id
         self._blob_keepalive = None
         self.last: Optional[_ffi.ev_result] = None
+        self.feature_config = None                  # set by features_setup()
+        self.last_features: Optional[_ffi.ev_features_result] = None
 
     # -- lifecycle
     def close(self):
@@ -190,7 +192,8 @@ class EVEngine:
     def align_raw(self, B: int, ling_ptr: int, cu_seqlens: np.ndarray, speaker_ptr: int, style_ptr: int, content_ptr: int, mel_ptr: int,
                   mel_is_f16: bool, mel_lens: np.ndarray, pitch_ptr: Optional[int] = None, energy_ptr: Optional[int] = None,
                   flags: int = 0) -> _ffi.ev_align_result:
-        """ev_align (include/evhip.h).  The returned struct's device arrays stay valid until the next align on this engine."""
+        """ev_align (include/evhip.h).  The returned struct's device arrays stay valid until the next align on this engine.  flags:
+        EV_FLAG_DEVICE_INPUTS (every pointer on the device) or EV_FLAG_DEVICE_MEL (mel / pitch / energy frames only: a features_raw result)."""
         cu = np.ascontiguousarray(cu_seqlens, np.int32)
         ml = np.ascontiguousarray(mel_lens, np.int32)
         res = _ffi.ev_align_result()
@@ -251,6 +254,55 @@ class EVEngine:
         out["cu_seqlens"] = cu
         out["durations_list"] = [out["durations"][cu[b]:cu[b + 1]] for b in range(B)]
         return out
+
+    # -- acoustic features (ev_features): wav -> mel, energy on the device
+    def features_setup(self, config=None):
+        """ev_features_setup.  config: an emotivoice_amd.features.FeatureConfig (default: the reference's values).  Needs no weights."""
+        from .features import FeatureConfig
+        fc = (config or FeatureConfig()).validate()
+        mb, win = fc.tables()
+        c = _ffi.ev_features_config()
+        self._lib.ev_default_features_config(C.byref(c))
+        c.n_fft, c.hop, c.n_mels, c.mel_clip, c.energy_floor = fc.n_fft, fc.hop, fc.n_mels, fc.mel_clip, fc.energy_floor
+        c.mel_basis = mb.ctypes.data
+        c.window = win.ctypes.data if win is not None else None
+        self._check(self._lib.ev_features_setup(self._h, C.byref(c)))
+        self.feature_config = fc
+
+    def features_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, wav_lens: np.ndarray, energy_mean: float = 0.0, energy_std: float = 1.0,
+                     flags: int = 0) -> _ffi.ev_features_result:
+        """ev_features (include/evhip.h).  The returned struct's device arrays stay valid until the next features call on this engine."""
+        wl = np.ascontiguousarray(wav_lens, np.int64)
+        res = _ffi.ev_features_result()
+        res.struct_size = C.sizeof(_ffi.ev_features_result)
+        self._check(self._lib.ev_features(self._h, B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, wl.ctypes.data_as(C.c_void_p),
+                                          C.c_float(energy_mean), C.c_float(energy_std), flags, C.byref(res)))
+        self.last_features = res
+        return res
+
+    def features_to_numpy(self, res: _ffi.ev_features_result) -> Dict[str, object]:
+        B, n_mels = res.batch, self.feature_config.n_mels
+        mel_lens = np.array([res.mel_lens[b] for b in range(B)], np.int32)
+        offs = np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64)
+        mel = self.d2h(res.mel, (res.total_frames * n_mels,), np.float32)
+        energy = self.d2h(res.energy, (res.total_frames,), np.float32)
+        return dict(mel_lens=mel_lens, mel_offsets=offs, energy=energy,
+                    mel_list=[mel[offs[b] * n_mels:offs[b + 1] * n_mels].reshape(n_mels, mel_lens[b]) for b in range(B)],
+                    energy_list=[energy[offs[b]:offs[b + 1]] for b in range(B)])
+
+    def features(self, wavs: Sequence[np.ndarray], energy_stats=(0.0, 1.0)) -> Dict[str, object]:
+        """Mel spectrogram and frame energy of recordings (ev_features).  wavs: one 1-D array per utterance, all int16 or all floating in
+        [-1, 1]; energy_stats: (mean, std) the energy is standardised with (the corpus statistics of the checkpoint; (0, 1) = raw).
+        Returns mel_list ((n_mels, T_b) each: what align() / vocoder() take), energy_list ((T_b,) each) and mel_lens."""
+        if self.feature_config is None:
+            self.features_setup()
+        from .features import pack_wavs
+        fc = self.feature_config
+        flat, is16, lens = pack_wavs(wavs, fc.n_fft, fc.hop)
+        mean, std = float(energy_stats[0]), float(energy_stats[1])
+        if not (np.isfinite(mean) and np.isfinite(std) and std > 0):
+            raise ValueError("energy_stats: mean must be finite and std positive and finite")
+        return self.features_to_numpy(self.features_raw(len(wavs), flat.ctypes.data, is16, lens, mean, std))
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)

@@ -134,7 +134,9 @@ enum {
     EV_FLAG_DEVICE_INPUTS = 1,  /* all input pointers are device pointers (zero-copy from a torch-ROCm tensor) */
     EV_FLAG_NO_VOCODER = 2,     /* acoustic model only (mel out) */
     EV_FLAG_WANT_INT16 = 4,     /* also produce the caller epilogue wav*32768 -> int16 (inference_am_vocoder_joint.py:130-131) */
-    EV_FLAG_FORCED_DURATIONS = 8 /* teacher-forced durations (test mode): use result-independent durations passed via ev_set_forced_durations */
+    EV_FLAG_FORCED_DURATIONS = 8, /* teacher-forced durations (test mode): use result-independent durations passed via ev_set_forced_durations */
+    EV_FLAG_DEVICE_MEL = 16      /* ev_align only: mel, pitch_frames and energy_frames are device pointers, the other inputs stay host pointers
+                                    (an ev_features_result goes straight into ev_align) */
 };
 
 /* Result of one call.  All pointers are DEVICE pointers owned by the handle.
@@ -253,7 +255,8 @@ int ev_synthesize_prosody(ev_handle* h, int B, const int64_t* ling, const int32_
  * Inputs: ling / cu_seqlens / speaker / style / content exactly as ev_synthesize; mel packed as ev_vocoder takes it (per utterance
  * (n_mels, mel_lens[b]) row-major, fp32 or fp16); mel_lens HOST; pitch_frames / energy_frames (total_frames,) packed like mel's frames, in
  * the checkpoint's normalised units, or NULL (then the result's pitch / energy are NULL).  EV_FLAG_DEVICE_INPUTS covers every input pointer
- * except cu_seqlens and mel_lens.
+ * except cu_seqlens and mel_lens; EV_FLAG_DEVICE_MEL covers mel, pitch_frames and energy_frames only (the arrays of an ev_features_result: they
+ * are complete when ev_features returns and live in its own workspace).
  * Rejected before anything is launched (message naming the utterance or field): struct_size != sizeof(ev_align_result), mel_lens[b] <
  * N_b (no monotonic path gives every token a frame), N_b > EV_ALIGN_MAX_TOKENS or mel_lens[b] > EV_ALIGN_MAX_FRAMES, bad ids (as
  * ev_synthesize), a weight blob without the aligner ("aln.*": packed only from state dicts that carry am.alignment_module.*).
@@ -282,6 +285,52 @@ typedef struct ev_align_result {
 int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_seqlens, const int64_t* speaker,
              const float* style, const float* content, const void* mel, int mel_is_f16, const int32_t* mel_lens,
              const float* pitch_frames, const float* energy_frames, uint32_t flags, ev_align_result* out);
+
+/* Acoustic features (ev_features): wav -> the log-mel spectrogram ev_align / ev_vocoder take and the per-frame energy, on the device.  The reference
+ * computes them in its training stack (prompt_dataset.get_mel -> TacotronSTFT.mel_spectrogram, models/prompt_tts_modified/tacotron_stft.py:71-80,
+ * stft.py:48-76, with config/joint/config.py's filter length = window length 1024, hop 256, 80 mels, 16 kHz, 0-8000 Hz).  For an utterance of L
+ * samples in [-1, 1] (int16 input: x / 32768):
+ *   1. reflect-pad n_fft / 2 samples on each side (L >= n_fft / 2 + 1);  2. frames t = 0 .. L / hop, T = L / hop + 1, frame t = padded[hop t, hop t + n_fft);
+ *   3. re / im[k, t] = frame . basis, k = 0 .. n_fft / 2, basis = float32(cos / -sin(2 pi k n / n_fft)) * float32(window[n]), a float32 product;
+ *   4. mag = sqrt(re^2 + im^2);  5. mel = log(max(mel_basis @ mag, mel_clip));  6. energy[t] = sqrt(max(sum_k mag[k, t]^2, energy_floor)),
+ *      returned standardised as (e - energy_mean) / energy_std.
+ * Arithmetic: step 3 runs on the matrix cores in the split-precision (fp32-class) arithmetic of EV_PREC_X3 -- samples and basis as fp16 hi + lo parts,
+ * three fp16 MFMAs per product, fp32 accumulation -- whatever decoder_precision / vocoder_precision say; step 5's matrix product is fp32, its log and
+ * step 6's sum fp64 rounded once.  No atomics and no split of a frame's sums over blocks: an utterance gives the same bits alone, anywhere in a
+ * batch, as int16 or as the equal floats, and on every precision mode.  Pitch extraction is not part of this (ev_align accepts a missing track). */
+#define EV_FEATURES_MAX_NFFT 2048      /* n_fft: a multiple of 128 up to this */
+#define EV_FEATURES_MAX_MELS 128       /* n_mels */
+#define EV_FEATURES_MAX_RUN  24576     /* 63 hop + n_fft: the samples of a 64-frame tile, which stay in LDS */
+typedef struct ev_features_config {
+    uint32_t struct_size;          /* sizeof(ev_features_config); any other value is rejected */
+    int32_t  n_fft;                /* 1024: filter length = window length; a multiple of 128, at most 2048 */
+    int32_t  hop;                  /* 256: a multiple of 8, at most n_fft, 63 hop + n_fft <= 24576 */
+    int32_t  n_mels;               /* 80: at most 128 */
+    float    mel_clip;             /* 1e-5 */
+    float    energy_floor;         /* 1e-10 */
+    const float* mel_basis;        /* HOST (n_mels, n_fft / 2 + 1) row-major, required (emotivoice_amd/features.py: mel_filterbank) */
+    const float* window;           /* HOST (n_fft,) or NULL = periodic hann */
+} ev_features_config;
+void ev_default_features_config(ev_features_config* cfg);      /* the reference's values; mel_basis is left NULL */
+/* Builds the basis planes and keeps them on the device (copies mel_basis / window; may be called again).  Independent of ev_load_weights. */
+int ev_features_setup(ev_handle* h, const ev_features_config* cfg);
+
+typedef struct ev_features_result {
+    uint32_t struct_size;          /* sizeof(ev_features_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total_frames;
+    const float*   mel;            /* DEVICE, packed per utterance as (n_mels, T_b) row-major: exactly what ev_align / ev_vocoder take */
+    const float*   energy;         /* DEVICE (total_frames,): (e - energy_mean) / energy_std */
+    const int32_t* mel_lens;       /* (batch,) HOST */
+    const int64_t* mel_offsets;    /* (batch+1,) HOST */
+} ev_features_result;
+/* wav: the B utterances back to back, fp32 or int16 (wav_is_i16), a device pointer with EV_FLAG_DEVICE_INPUTS; wav_lens HOST.  Rejected before
+ * anything is launched (message naming the field or utterance): a wrong struct_size, no ev_features_setup, wav_lens[b] < n_fft / 2 + 1,
+ * T_b > EV_ALIGN_MAX_FRAMES, a non-finite or non-positive energy_std (or a non-finite energy_mean).  The result lives in a workspace of its own and is
+ * complete when the call returns; it stays valid across ev_align / ev_synthesize[_prosody] / ev_vocoder until the next ev_features or ev_destroy.
+ * On a handle created with keep_stages, ev_get_stage("feat_mag") returns the (total_frames, n_fft / 2 + 1) magnitudes of the last ev_features. */
+int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, float energy_mean, float energy_std,
+                uint32_t flags, ev_features_result* out);
 
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);

@@ -192,6 +192,15 @@ int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int3
                     const int64_t* frm_packed, const int64_t* bits_off, uint32_t* bits, const float* pitch_frames, const float* energy_frames,
                     int64_t* dur, float* pitch_tok, float* energy_tok, float* score, void* hip_stream);
 
+/* ev_features' kernel on caller-provided DEVICE buffers: wav (B utterances back to back, fp32 or int16) -> mel (per utterance (n_mels, T_b) row-major,
+ * T_b = wav_lens[b] / hop + 1, packed in utterance order), energy (sum_b T_b,) and, unless NULL, mag (sum_b T_b, n_fft / 2 + 1); semantics as ev_features
+ * (include/evhip.h).  wav_lens, mel_basis (n_mels, n_fft / 2 + 1) and window (n_fft,) or NULL are HOST arrays: the call packs the basis planes, waits for
+ * the stream and frees them.  -2 for what the kernel would mishandle: n_fft not a multiple of 128 or above 2048, hop not a multiple of 8 or above n_fft,
+ * 63 hop + n_fft > 24576, n_mels outside [1, 128], wav_lens[b] < n_fft / 2 + 1, T_b > 16384, B outside [1, 65535]. */
+int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* mel_basis, const float* window, int n_fft, int hop,
+                   int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
+                   void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
