@@ -81,6 +81,23 @@ class ev_features_result(C.Structure):
     ]
 
 
+EV_PITCH_TILE_FRAMES, EV_PITCH_MAX_WIN, EV_PITCH_MAX_LDS = 8, 2048, 65536
+
+
+class ev_pitch_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32), ("f_min", C.c_float),
+        ("f_max", C.c_float), ("threshold", C.c_float), ("silence_rms", C.c_float),
+    ]
+
+
+class ev_pitch_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_frames", C.c_int64), ("pitch", C.c_void_p), ("f0_hz", C.c_void_p),
+        ("aperiodicity", C.c_void_p), ("mel_lens", C.POINTER(C.c_int32)), ("mel_offsets", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -140,6 +157,8 @@ SIGNATURES = {
     "ev_default_features_config": (None, [C.POINTER(ev_features_config)]),
     "ev_features_setup": (C.c_int, [_P, C.POINTER(ev_features_config)]),
     "ev_features": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(ev_features_result)]),
+    "ev_default_pitch_config": (None, [C.POINTER(ev_pitch_config)]),
+    "ev_pitch": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_pitch_config), C.c_float, C.c_float, C.c_uint32, C.POINTER(ev_pitch_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -182,6 +201,9 @@ SIGNATURES = {
     "ev_op_align_mas": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # wav_lens, mel_basis and window are HOST arrays (the wrapper packs the basis planes)
     "ev_op_stft_mel": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    # wav_lens / frames are HOST arrays
+    "ev_op_pitch_yin": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "ev_op_pitch_fill": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_float, _P, _P]),
 }
 
 _lib = None

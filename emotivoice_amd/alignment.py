@@ -4,7 +4,8 @@
 ``ev_synthesize_prosody`` (the values the reference's teacher-forced branch feeds as ds / ps / es, model_open_source.py:113-139), and
 ``transfer`` re-voices recordings: align them with their own conditioning, then synthesise the same phonemes with another speaker /
 prompt and the recording's timing (and, optionally, its intonation and energy).  ``align_recordings`` / ``transfer_from_recordings`` start from
-the waveforms: the mel and the energy track are computed on the device (ev_features) and never leave it on the way into ev_align.
+the waveforms: the mel and the energy track (ev_features) and, with ``pitch_stats``, the pitch track (ev_pitch) are computed on the device and
+never leave it on the way into ev_align.
 """
 from __future__ import annotations
 
@@ -76,11 +77,15 @@ def transfer(engine, src_utts: Sequence[dict], mels: Sequence[np.ndarray], dst_u
     return out
 
 
-def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], energy_stats=None) -> Dict[str, object]:
+def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], energy_stats=None, pitch_stats=None,
+                     pitch_config=None) -> Dict[str, object]:
     """Forced alignment of recordings given as waveforms (16 kHz, one 1-D int16 or floating array per utterance): ev_features, then
     ev_align with EV_FLAG_DEVICE_MEL -- the mel (and the energy track) go from one call into the other on the device.  energy_stats:
-    (mean, std) of the checkpoint's energy normalisation; with it the result carries the per-token energy means, without it none.  There
-    is no pitch track (pitch extraction is not part of the engine).  Returns what ``EVEngine.align`` returns."""
+    (mean, std) of the checkpoint's energy normalisation; with it the result carries the per-token energy means, without it none.
+    pitch_stats: (mean, std) in Hz of the checkpoint's pitch normalisation; with it ev_pitch runs on the same packed waveforms and its device
+    track goes into ev_align, so the result carries the per-token pitch means (``pitch_config``: an emotivoice_amd.pitch.PitchConfig on the
+    feature setup's hop, default its defaults); without it there is no pitch.  The track is YIN's, not the dio + stonemask track the
+    checkpoint was trained on.  Returns what ``EVEngine.align`` returns."""
     from . import _ffi
     from .features import pack_wavs
     B = len(utts)
@@ -93,6 +98,14 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
         raise ValueError("the feature setup has %d mels, the model %d" % (fc.n_mels, engine.shapes.n_mels))
     flat, is16, lens = pack_wavs(wavs, fc.n_fft, fc.hop)
     mean, std = (0.0, 1.0) if energy_stats is None else (float(energy_stats[0]), float(energy_stats[1]))
+    pitch_ptr = None
+    if pitch_stats is not None:
+        from .pitch import PitchConfig, check_stats
+        pc = (pitch_config or PitchConfig(hop=fc.hop)).validate()
+        if pc.hop != fc.hop:
+            raise ValueError("the pitch config has hop %d, the feature setup %d: the two tracks must share the frame grid" % (pc.hop, fc.hop))
+        pm, ps = check_stats(pitch_stats)
+        pitch_ptr = engine.pitch_raw(B, flat.ctypes.data, is16, lens, pm, ps, pc).pitch
     feats = engine.features_raw(B, flat.ctypes.data, is16, lens, mean, std)
     mel_lens = np.array([feats.mel_lens[b] for b in range(B)], np.int32)
     ling = np.ascontiguousarray(np.concatenate([np.asarray(u["ling"], np.int64) for u in utts]))
@@ -102,7 +115,7 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
     style = np.ascontiguousarray(np.stack([np.asarray(u["style"], np.float32) for u in utts]))
     content = np.ascontiguousarray(np.stack([np.asarray(u["content"], np.float32) for u in utts]))
     res = engine.align_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, feats.mel, False, mel_lens,
-                           None, feats.energy if energy_stats is not None else None, flags=_ffi.EV_FLAG_DEVICE_MEL)
+                           pitch_ptr, feats.energy if energy_stats is not None else None, flags=_ffi.EV_FLAG_DEVICE_MEL)
     out = engine.align_to_numpy(res)
     out["cu_seqlens"] = cu
     out["durations_list"] = [out["durations"][cu[b]:cu[b + 1]] for b in range(B)]
@@ -110,16 +123,17 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
 
 
 def transfer_from_recordings(engine, src_utts: Sequence[dict], wavs: Sequence[np.ndarray], dst_utts: Sequence[dict], energy_stats=None,
-                             energy: bool = True, vocoder: bool = True) -> Dict[str, object]:
+                             energy: bool = True, vocoder: bool = True, pitch_stats=None, pitch: bool = True) -> Dict[str, object]:
     """The wav-in counterpart of ``transfer``: align the recordings (``align_recordings``), then synthesise ``dst_utts`` with their durations
-    and, where ``energy_stats`` is given and ``energy`` asks for it, their per-token energy.  Pitch is always the prediction."""
+    and, where ``energy_stats`` / ``pitch_stats`` are given and ``energy`` / ``pitch`` ask for it, their per-token energy / pitch (the pitch
+    from ev_pitch's track).  Without ``pitch_stats``, or with ``pitch=False``, the pitch is the predictor's."""
     if len(src_utts) != len(dst_utts):
         raise ValueError("%d source and %d target utterances" % (len(src_utts), len(dst_utts)))
     for b, (s, d) in enumerate(zip(src_utts, dst_utts)):
         if not np.array_equal(np.asarray(s["ling"], np.int64), np.asarray(d["ling"], np.int64)):
             raise ValueError("utterance %d: source and target phonemes (ling) differ" % b)
-    aligned = align_recordings(engine, src_utts, wavs, energy_stats=energy_stats)
-    pros = prosody_from_alignment(aligned, pitch=False, energy=energy and energy_stats is not None)
+    aligned = align_recordings(engine, src_utts, wavs, energy_stats=energy_stats, pitch_stats=pitch_stats if pitch else None)
+    pros = prosody_from_alignment(aligned, pitch=pitch and pitch_stats is not None, energy=energy and energy_stats is not None)
     out = engine.synthesize(dst_utts, prosody=pros, vocoder=vocoder)
     out["alignment"] = aligned
     return out

@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[5] = {0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features (likewise)
+    char* arena[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[6] = {0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch (likewise)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -95,6 +95,8 @@ struct ev_handle {
     ev_features_config fcfg{}; bool feat_ready = false; char* feat_basis = nullptr; float* feat_melT = nullptr;
     std::vector<int32_t> feat_mel_lens; std::vector<int64_t> feat_mel_offs;
     const float* feat_mag = nullptr; int64_t feat_mag_elems = 0;
+    // ev_pitch: the host halves of its result
+    std::vector<int32_t> pit_mel_lens; std::vector<int64_t> pit_mel_offs;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1107,7 +1109,7 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 5; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 6; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
     if (h->feat_melT) (void)hipFree(h->feat_melT);
     if (h->sblob) (void)hipFree(h->sblob);
@@ -1902,6 +1904,124 @@ int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     return 0;
 }
 
+// ------------------------------------------------------------------- pitch extraction (include/evhip.h: ev_pitch)
+static_assert(EV_PITCH_TILE_FRAMES == PITCH_TF && EV_PITCH_MAX_WIN == PITCH_MAX_WIN && EV_PITCH_MAX_LDS == PITCH_MAX_LDS,
+              "include/evhip.h states the limits of ev_pitch.hip");
+void ev_default_pitch_config(ev_pitch_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_pitch_config);
+    c->sample_rate = 16000; c->hop = 256; c->win = 1024; c->f_min = 80.f; c->f_max = 400.f; c->threshold = 0.15f; c->silence_rms = 1e-3f;
+}
+
+// every rejection of a config, in the order include/evhip.h lists them; sets the lag range
+static int pitch_check_config(ev_handle* h, const char* who, const ev_pitch_config& c, int* tau_min, int* tau_max) {
+    if (c.sample_rate < 1) return fail(h, "%s: sample_rate %d must be positive", who, c.sample_rate);
+    if (c.win < 1 || c.win > PITCH_MAX_WIN) return fail(h, "%s: win %d outside [1, EV_PITCH_MAX_WIN %d]", who, c.win, PITCH_MAX_WIN);
+    if (c.hop < 1 || c.hop > c.win) return fail(h, "%s: hop %d outside [1, win %d]", who, c.hop, c.win);
+    if (!std::isfinite(c.f_min) || !std::isfinite(c.f_max) || !(c.f_min > 0.f) || !(c.f_min < c.f_max) || !((double)c.f_max <= (double)c.sample_rate / 4.0))
+        return fail(h, "%s: f_min %g / f_max %g must be finite with 0 < f_min < f_max <= sample_rate / 4 = %g", who, (double)c.f_min, (double)c.f_max, (double)c.sample_rate / 4.0);
+    const double tmax = std::ceil((double)c.sample_rate / (double)c.f_min);
+    const int tmin = (int)std::floor((double)c.sample_rate / (double)c.f_max);
+    if (tmax + 1.0 > (double)c.win) return fail(h, "%s: tau_max + 1 = %.0f > win %d (f_min %g is too low for the window)", who, tmax + 1.0, c.win, (double)c.f_min);
+    if (!(c.threshold > 0.f) || !(c.threshold <= 1.f)) return fail(h, "%s: threshold %g outside (0, 1]", who, (double)c.threshold);
+    if (!std::isfinite(c.silence_rms) || c.silence_rms < 0.f) return fail(h, "%s: silence_rms must be >= 0 and finite", who);
+    if (!pitch_shape_ok(c.hop, c.win, tmin, (int)tmax))
+        return fail(h, "%s: win %d, hop %d, tau %d .. %d: the kernel needs win >= 8, tau_min < tau_max and a tile of %zu bytes within EV_PITCH_MAX_LDS %d", who,
+                    c.win, c.hop, tmin, (int)tmax, pitch_lds_bytes(c.hop, c.win, (int)tmax), PITCH_MAX_LDS);
+    *tau_min = tmin; *tau_max = (int)tmax;
+    return 0;
+}
+
+// frame counts, offsets and the tile table of a batch; 0 or the index + 1 of the first empty utterance (-(index + 1): too long)
+static int pitch_layout(int B, const int64_t* wav_lens, int hop, std::vector<StftSeq>& seqs, std::vector<StftTile>& tiles, std::vector<int32_t>& lens,
+                        std::vector<int64_t>& offs) {
+    seqs.resize(B); lens.resize(B); offs.resize((size_t)B + 1); tiles.clear();
+    int64_t wo = 0, fo = 0;
+    for (int b = 0; b < B; ++b) {
+        if (wav_lens[b] < 1) return b + 1;
+        const int64_t T = wav_lens[b] / hop + 1;
+        if (T > EV_ALIGN_MAX_FRAMES) return -(b + 1);
+        seqs[b] = StftSeq{wo, wav_lens[b], fo, (int32_t)T, 0};
+        lens[b] = (int32_t)T; offs[b] = fo;
+        for (int t0 = 0; t0 < T; t0 += PITCH_TF) tiles.push_back(StftTile{b, t0});
+        wo += wav_lens[b]; fo += T;
+    }
+    offs[B] = fo;
+    return 0;
+}
+
+static PitchParams pitch_params(const ev_pitch_config& c, int tau_min, int tau_max) {
+    PitchParams p{};
+    p.sample_rate = c.sample_rate; p.hop = c.hop; p.win = c.win; p.tau_min = tau_min; p.tau_max = tau_max; p.threshold = c.threshold;
+    p.e0_floor = (double)c.win * (double)c.silence_rms * (double)c.silence_rms;
+    return p;
+}
+
+int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, const ev_pitch_config* cfg, float pitch_mean,
+             float pitch_std, uint32_t flags, ev_pitch_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out || B <= 0) return fail(h, "ev_pitch: bad argument");
+    if (out->struct_size != sizeof(ev_pitch_result))
+        return fail(h, "ev_pitch: out->struct_size %u != sizeof(ev_pitch_result) %zu", out->struct_size, sizeof(ev_pitch_result));
+    ev_pitch_config pc;
+    ev_default_pitch_config(&pc);
+    if (cfg) {
+        if (cfg->struct_size != sizeof(ev_pitch_config))
+            return fail(h, "ev_pitch: cfg->struct_size %u != sizeof(ev_pitch_config) %zu", cfg->struct_size, sizeof(ev_pitch_config));
+        pc = *cfg;
+    }
+    int tau_min = 0, tau_max = 0;
+    if (pitch_check_config(h, "ev_pitch", pc, &tau_min, &tau_max)) return -1;
+    if ((size_t)B > PIN_MAX_B) return fail(h, "ev_pitch: at most %zu utterances per call", PIN_MAX_B);
+    if (!std::isfinite(pitch_std) || !(pitch_std > 0.f)) return fail(h, "ev_pitch: pitch_std must be positive and finite");
+    if (!std::isfinite(pitch_mean)) return fail(h, "ev_pitch: pitch_mean must be finite");
+    std::vector<StftSeq> seqs; std::vector<StftTile> tiles; std::vector<int32_t> lens; std::vector<int64_t> offs;
+    const int bad = pitch_layout(B, wav_lens, pc.hop, seqs, tiles, lens, offs);
+    if (bad > 0) return fail(h, "ev_pitch: wav_lens[%d] = %lld < 1", bad - 1, (long long)wav_lens[bad - 1]);
+    if (bad < 0) return fail(h, "ev_pitch: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / pc.hop + 1), EV_ALIGN_MAX_FRAMES);
+    const int64_t total_frames = offs[B], total_samples = seqs[B - 1].wav_off + seqs[B - 1].len;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_pitch = nullptr, *d_f0 = nullptr, *d_ap = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 5, pass == 0};
+        if (pass == 1 && arena_reserve(h, 5, need)) return -1;
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(tiles.size());
+        d_pitch = ap.arr<float>((size_t)total_frames); d_f0 = ap.arr<float>((size_t)total_frames); d_ap = ap.arr<float>((size_t)total_frames);
+        need = ap.off;
+    }
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_seqs, seqs.data(), (size_t)B * sizeof(StftSeq), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(StftTile), hipMemcpyHostToDevice, h->stream));
+    region_begin(h, "total");
+    {
+        PitchParams p = pitch_params(pc, tau_min, tau_max);
+        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)tiles.size();
+        p.f0 = d_f0; p.ap = d_ap; p.tau = nullptr;
+        KScope ks(h, "pitch_yin", 3.0 * (double)total_frames * (tau_max + 2.0) * pc.win, (double)total_samples * es + (double)total_frames * 8.0);
+        if (launch_pitch_yin(p, h->stream)) return fail(h, "ev_pitch: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "pitch_fill", 8.0 * (double)total_frames, (double)total_frames * 8.0);
+        launch_pitch_fill(d_f0, d_seqs, B, pitch_mean, pitch_std, d_pitch, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    h->pit_mel_lens = lens; h->pit_mel_offs = offs;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total_frames = total_frames; out->pitch = d_pitch; out->f0_hz = d_f0; out->aperiodicity = d_ap;
+    out->mel_lens = h->pit_mel_lens.data(); out->mel_offsets = h->pit_mel_offs.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
 void ev_default_bert_config(ev_bert_config* c) {
     memset(c, 0, sizeof *c);
@@ -2278,6 +2398,54 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
     if (basis) (void)hipFree(basis);
     if (melT) (void)hipFree(melT);
     if (tab) (void)hipFree(tab);
+    return rc;
+}
+
+int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sample_rate, int hop, int win, float f_min, float f_max,
+                    float threshold, float silence_rms, float* f0_hz, float* aperiodicity, int32_t* tau, void* stream) {
+    if (!wav || !wav_lens || !f0_hz || !aperiodicity || B < 1 || B > 65535) return -2;
+    ev_pitch_config c;
+    ev_default_pitch_config(&c);
+    c.sample_rate = sample_rate; c.hop = hop; c.win = win; c.f_min = f_min; c.f_max = f_max; c.threshold = threshold; c.silence_rms = silence_rms;
+    int tau_min = 0, tau_max = 0;
+    if (pitch_check_config(nullptr, "ev_op_pitch_yin", c, &tau_min, &tau_max)) return -2;
+    std::vector<StftSeq> seqs; std::vector<StftTile> tiles; std::vector<int32_t> lens; std::vector<int64_t> offs;
+    if (pitch_layout(B, wav_lens, hop, seqs, tiles, lens, offs)) return -2;
+    char* tab = nullptr;
+    const size_t sb = (size_t)B * sizeof(StftSeq), tb = tiles.size() * sizeof(StftTile);
+    if (hipMalloc((void**)&tab, sb + tb) != hipSuccess) return -1;
+    int rc = 0;
+    if (hipMemcpy(tab, seqs.data(), sb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(tab + sb, tiles.data(), tb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (rc == 0) {
+        PitchParams p = pitch_params(c, tau_min, tau_max);
+        p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = (const StftSeq*)tab; p.tiles = (const StftTile*)(tab + sb); p.n_tiles = (int)tiles.size();
+        p.f0 = f0_hz; p.ap = aperiodicity; p.tau = tau;
+        if (launch_pitch_yin(p, (hipStream_t)stream)) rc = -2;
+        else if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    (void)hipFree(tab);
+    return rc;
+}
+int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pitch_mean, float pitch_std, float* pitch, void* stream) {
+    if (!f0_hz || !frames || !pitch || pitch == f0_hz || B < 1 || B > 65535) return -2;
+    if (!std::isfinite(pitch_mean) || !std::isfinite(pitch_std) || !(pitch_std > 0.f)) return -2;
+    std::vector<StftSeq> seqs((size_t)B);
+    int64_t fo = 0;
+    for (int b = 0; b < B; ++b) {
+        if (frames[b] < 1 || frames[b] > EV_ALIGN_MAX_FRAMES) return -2;
+        seqs[(size_t)b] = StftSeq{0, 0, fo, frames[b], 0};
+        fo += frames[b];
+    }
+    StftSeq* d = nullptr;
+    if (hipMalloc((void**)&d, seqs.size() * sizeof(StftSeq)) != hipSuccess) return -1;
+    int rc = hipMemcpy(d, seqs.data(), seqs.size() * sizeof(StftSeq), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    if (rc == 0) {
+        launch_pitch_fill(f0_hz, d, B, pitch_mean, pitch_std, pitch, (hipStream_t)stream);
+        if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    (void)hipFree(d);
     return rc;
 }
 

@@ -262,4 +262,24 @@ void stft_pack_basis(int n_fft, const float* window /* host (n_fft,) or null = p
 void stft_pack_mel(int n_fft, int n_mels, const float* mel_basis /* host (n_mels, n_bins) */, float* out /* host, stft_melT_floats */);
 int launch_stft_mel(const StftParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
 
+// ev_pitch (ev_pitch.hip): wav -> per-frame F0 (YIN), then the continuous fill and the standardisation.  The utterance and tile tables are the
+// StftSeq / StftTile of ev_features, with tiles of PITCH_TF frames.  Limits of the kernel: win <= PITCH_MAX_WIN, 1 <= hop <= win, 4 <= tau_min <
+// tau_max, tau_max + 1 <= win, and the tile's LDS (pitch_lds_bytes: its run of samples and three numbers per (frame, lag)) within PITCH_MAX_LDS.
+constexpr int PITCH_TF = 8, PITCH_MAX_WIN = 2048, PITCH_MAX_LDS = 65536;
+struct PitchParams {
+    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
+    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
+    int sample_rate, hop, win, tau_min, tau_max;
+    float threshold; double e0_floor;                 // win * silence_rms^2
+    float* f0;                                        // (total_frames,): Hz, 0 = unvoiced
+    float* ap;                                        // (total_frames,): d' at the chosen lag, 1 = unvoiced
+    int32_t* tau;                                     // (total_frames,) or null: the chosen lag, -1 = unvoiced
+};
+int pitch_run_samples(int hop, int win, int tau_max);
+size_t pitch_lds_bytes(int hop, int win, int tau_max);
+int pitch_shape_ok(int hop, int win, int tau_min, int tau_max);
+int launch_pitch_yin(const PitchParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
+// out[t] = (cont[t] - mean) / stdv, cont = f0 with unvoiced frames held at the edges and interpolated between voiced neighbours; out != f0
+void launch_pitch_fill(const float* f0, const StftSeq* seqs, int B, float mean, float stdv, float* out, hipStream_t s);
+
 }  // namespace ev

@@ -93,6 +93,7 @@ class EVEngine:
         self.last: Optional[_ffi.ev_result] = None
         self.feature_config = None                  # set by features_setup()
         self.last_features: Optional[_ffi.ev_features_result] = None
+        self.last_pitch: Optional[_ffi.ev_pitch_result] = None
 
     # -- lifecycle
     def close(self):
@@ -303,6 +304,44 @@ class EVEngine:
         if not (np.isfinite(mean) and np.isfinite(std) and std > 0):
             raise ValueError("energy_stats: mean must be finite and std positive and finite")
         return self.features_to_numpy(self.features_raw(len(wavs), flat.ctypes.data, is16, lens, mean, std))
+
+    # -- pitch extraction (ev_pitch): wav -> F0 track on the device
+    def pitch_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, wav_lens: np.ndarray, pitch_mean: float = 0.0, pitch_std: float = 1.0,
+                  config=None, flags: int = 0) -> _ffi.ev_pitch_result:
+        """ev_pitch (include/evhip.h).  config: an emotivoice_amd.pitch.PitchConfig or None (= ev_default_pitch_config).  The returned struct's
+        device arrays stay valid until the next pitch call on this engine."""
+        wl = np.ascontiguousarray(wav_lens, np.int64)
+        c = None
+        if config is not None:
+            c = _ffi.ev_pitch_config()
+            self._lib.ev_default_pitch_config(C.byref(c))
+            c.sample_rate, c.hop, c.win = int(config.sample_rate), int(config.hop), int(config.win)
+            c.f_min, c.f_max, c.threshold, c.silence_rms = config.f_min, config.f_max, config.threshold, config.silence_rms
+        res = _ffi.ev_pitch_result()
+        res.struct_size = C.sizeof(_ffi.ev_pitch_result)
+        self._check(self._lib.ev_pitch(self._h, B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, wl.ctypes.data_as(C.c_void_p),
+                                       C.byref(c) if c is not None else None, C.c_float(pitch_mean), C.c_float(pitch_std), flags, C.byref(res)))
+        self.last_pitch = res
+        return res
+
+    def pitch_to_numpy(self, res: _ffi.ev_pitch_result) -> Dict[str, object]:
+        B, n = res.batch, res.total_frames
+        mel_lens = np.array([res.mel_lens[b] for b in range(B)], np.int32)
+        offs = np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64)
+        pitch, f0, ap = (self.d2h(ptr, (n,), np.float32) for ptr in (res.pitch, res.f0_hz, res.aperiodicity))
+        cut = lambda x: [x[offs[b]:offs[b + 1]] for b in range(B)]      # noqa: E731
+        return dict(mel_lens=mel_lens, mel_offsets=offs, pitch=pitch, pitch_list=cut(pitch), f0_list=cut(f0), aperiodicity_list=cut(ap))
+
+    def pitch(self, wavs: Sequence[np.ndarray], pitch_stats=(0.0, 1.0), config=None) -> Dict[str, object]:
+        """F0 track of recordings (ev_pitch: YIN on ev_features' frame grid -- not the reference's dio + stonemask).  wavs: one 1-D array per
+        utterance, all int16 or all floating in [-1, 1]; pitch_stats: (mean, std) in Hz the continuous track is standardised with (the
+        checkpoint's corpus statistics; (0, 1) = Hz).  Returns pitch_list ((T_b,) each: what align() takes as pitch), f0_list (Hz, 0 =
+        unvoiced), aperiodicity_list and mel_lens."""
+        from .pitch import PitchConfig, check_stats, pack_wavs
+        pc = (config or PitchConfig()).validate()
+        mean, std = check_stats(pitch_stats)
+        flat, is16, lens = pack_wavs(wavs, pc.hop)
+        return self.pitch_to_numpy(self.pitch_raw(len(wavs), flat.ctypes.data, is16, lens, mean, std, pc))
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)

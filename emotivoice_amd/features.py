@@ -104,9 +104,10 @@ class FeatureConfig:
         return np.ascontiguousarray(mb, np.float32), win
 
 
-def pack_wavs(wavs, n_fft: int = 1024, hop: int = 256):
+def pack_wavs(wavs, n_fft: int = 1024, hop: int = 256, min_samples: Optional[int] = None):
     """Utterances back to back for ev_features: (flat array, is_int16, lens int64).  All int16 or all floating (converted to float32);
-    too short (< n_fft // 2 + 1 samples) or too long (> MAX_FRAMES frames) utterances are errors that name the utterance."""
+    too short (< n_fft // 2 + 1 samples) or too long (> MAX_FRAMES frames) utterances are errors that name the utterance.  ``min_samples``: another
+    minimum length, for a call without reflect padding (ev_pitch: 1)."""
     if len(wavs) == 0:
         raise ValueError("no utterances")
     arrs = [np.asarray(w).reshape(-1) for w in wavs]
@@ -116,7 +117,9 @@ def pack_wavs(wavs, n_fft: int = 1024, hop: int = 256):
             raise ValueError("wavs[%d]: int16 and floating utterances cannot be mixed in one call" % b)
         if not is16 and not np.issubdtype(a.dtype, np.floating):
             raise ValueError("wavs[%d]: expected int16 or floating samples, got %s" % (b, a.dtype))
-        if a.size < n_fft // 2 + 1:
+        if min_samples is not None and a.size < min_samples:
+            raise ValueError("wavs[%d]: %d samples < %d" % (b, a.size, min_samples))
+        if min_samples is None and a.size < n_fft // 2 + 1:
             raise ValueError("wavs[%d]: %d samples < n_fft / 2 + 1 = %d (reflect padding needs that many)" % (b, a.size, n_fft // 2 + 1))
         if frames_for(a.size, hop) > MAX_FRAMES:
             raise ValueError("wavs[%d]: %d frames > EV_ALIGN_MAX_FRAMES %d" % (b, frames_for(a.size, hop), MAX_FRAMES))

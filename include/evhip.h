@@ -297,7 +297,7 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu_seqlens
  * Arithmetic: step 3 runs on the matrix cores in the split-precision (fp32-class) arithmetic of EV_PREC_X3 -- samples and basis as fp16 hi + lo parts,
  * three fp16 MFMAs per product, fp32 accumulation -- whatever decoder_precision / vocoder_precision say; step 5's matrix product is fp32, its log and
  * step 6's sum fp64 rounded once.  No atomics and no split of a frame's sums over blocks: an utterance gives the same bits alone, anywhere in a
- * batch, as int16 or as the equal floats, and on every precision mode.  Pitch extraction is not part of this (ev_align accepts a missing track). */
+ * batch, as int16 or as the equal floats, and on every precision mode.  The pitch track is a call of its own: ev_pitch, below. */
 #define EV_FEATURES_MAX_NFFT 2048      /* n_fft: a multiple of 128 up to this */
 #define EV_FEATURES_MAX_MELS 128       /* n_mels */
 #define EV_FEATURES_MAX_RUN  24576     /* 63 hop + n_fft: the samples of a 64-frame tile, which stay in LDS */
@@ -331,6 +331,61 @@ typedef struct ev_features_result {
  * On a handle created with keep_stages, ev_get_stage("feat_mag") returns the (total_frames, n_fft / 2 + 1) magnitudes of the last ev_features. */
 int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, float energy_mean, float energy_std,
                 uint32_t flags, ev_features_result* out);
+
+/* Pitch extraction (ev_pitch): wav -> per-frame F0 on ev_features' frame grid, in the units ev_align takes as pitch_frames.  The reference gets
+ * its training pitch from pyworld (feats.Pitch: dio + stonemask at a frame period of 1000 hop / sr ms, a "continuous pitch" fill of the unvoiced
+ * frames, then (f0 - pitch_stats[0]) / pitch_stats[1]).  This is not DIO + StoneMask: the estimator here is YIN (a cumulative-mean-normalised
+ * difference function), specified below; only the frame grid, the fill (step 6) and the standardisation (step 7) restate the reference.  Agreement
+ * with pyworld's track has not been measured.  Lags: tau_min = floor(sample_rate / f_max), tau_max = ceil(sample_rate / f_min), both evaluated in
+ * fp64 on the float fields.  For an utterance of L >= 1 samples in [-1, 1] (int16 input: x / 32768), W = win:
+ *   1. frames t = 0 .. L / hop, T = L / hop + 1 (ev_features' grid and count, dio's time axis).  Frame t reads the S = W + tau_max + 1 samples
+ *      s[0 .. S) that start at t hop - S / 2 (integer division); samples outside [0, L) are zero (no reflection).  a = s[0 .. W).
+ *   2. d[tau] = sum_{j < W} (a[j] - s[j + tau])^2, tau = 0 .. tau_max + 1: the direct form in fp32 (never E0 + E_tau - 2 r), summed in an order fixed
+ *      by (W, tau) alone -- four interleaved partial sums over j mod 4, j ascending, combined as (s0 + s1) + (s2 + s3).
+ *   3. cs[tau] = sum_{k = 1 .. tau} d[k], a running fp64 sum;  d'[0] = 1, d'[tau] = (float)(d[tau] * tau / cs[tau]) where cs[tau] > 0, else 1.
+ *   4. the frame is unvoiced if E0 = sum_j a[j]^2 < W silence_rms^2.  Otherwise tau = the first lag in [tau_min, tau_max] with d'[tau] < threshold,
+ *      walked on while tau + 1 <= tau_max and d'[tau + 1] < d'[tau]; no such lag: unvoiced.
+ *   5. y0, y1, y2 = d'[tau - 1], d'[tau], d'[tau + 1];  off = 0.5 (y0 - y2) / (y0 - 2 y1 + y2) clamped to [-0.5, 0.5], 0 unless the denominator is
+ *      > 0 (fp64);  f0 = sample_rate / (tau + off), aperiodicity = y1.  Unvoiced frames: f0 = 0, aperiodicity = 1.
+ *   6. continuous track (the reference's Pitch._convert_to_continuous_pitch): no voiced frame: all zero.  Otherwise frames before the first voiced
+ *      frame take its value, frames after the last voiced one take its value, and an unvoiced frame t between voiced neighbours a < t < b gets
+ *      f0[a] + ((f0[b] - f0[a]) / (b - a)) (t - a), evaluated in fp64 and rounded once.
+ *   7. pitch[t] = (cont[t] - pitch_mean) / pitch_std; an all-unvoiced utterance gives (0 - pitch_mean) / pitch_std, as the reference would.
+ * No atomics and no split of a frame's sums over blocks: an utterance gives the same bits alone, anywhere in a batch, as int16 or as the equal
+ * floats, from host or device memory, and on every precision mode.  Needs neither weights nor ev_features_setup. */
+#define EV_PITCH_TILE_FRAMES 8         /* frames per block of the kernel */
+#define EV_PITCH_MAX_WIN 2048          /* win */
+#define EV_PITCH_MAX_LDS 65536         /* bytes of a tile: 4 (7 hop + win + tau_max + 1) + 96 (tau_max + 2 rounded up to even) + 32 */
+typedef struct ev_pitch_config {
+    uint32_t struct_size;          /* sizeof(ev_pitch_config); any other value is rejected */
+    int32_t  sample_rate;          /* 16000 */
+    int32_t  hop;                  /* 256: 1 .. win */
+    int32_t  win;                  /* 1024: the integration window W; tau_max + 1 <= win <= EV_PITCH_MAX_WIN and the tile within EV_PITCH_MAX_LDS */
+    float    f_min;                /* 80 */
+    float    f_max;                /* 400: 0 < f_min < f_max <= sample_rate / 4 */
+    float    threshold;            /* 0.15: in (0, 1] */
+    float    silence_rms;          /* 1e-3: >= 0 */
+} ev_pitch_config;
+void ev_default_pitch_config(ev_pitch_config* cfg);
+
+typedef struct ev_pitch_result {
+    uint32_t struct_size;          /* sizeof(ev_pitch_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total_frames;
+    const float*   pitch;          /* DEVICE (total_frames,): step 7, what ev_align takes as pitch_frames */
+    const float*   f0_hz;          /* DEVICE (total_frames,): step 5, 0 = unvoiced */
+    const float*   aperiodicity;   /* DEVICE (total_frames,) */
+    const int32_t* mel_lens;       /* (batch,) HOST */
+    const int64_t* mel_offsets;    /* (batch+1,) HOST */
+} ev_pitch_result;
+/* wav / wav_is_i16 / wav_lens / EV_FLAG_DEVICE_INPUTS as ev_features; cfg NULL = ev_default_pitch_config.  Rejected before anything is launched
+ * (message naming the field or utterance): a wrong struct_size (config or result), wav_lens[b] < 1, T_b > EV_ALIGN_MAX_FRAMES, hop < 1 or hop > win,
+ * win above EV_PITCH_MAX_WIN or a tile above EV_PITCH_MAX_LDS, f_min / f_max not finite or not 0 < f_min < f_max <= sample_rate / 4, tau_max + 1 > win,
+ * threshold outside (0, 1], a negative or non-finite silence_rms, a non-finite pitch_mean, a non-finite or non-positive pitch_std.  The result lives
+ * in a workspace of its own and is complete when the call returns; it stays valid across ev_features / ev_align / ev_synthesize[_prosody] /
+ * ev_vocoder until the next ev_pitch or ev_destroy, so `pitch` goes into ev_align beside an ev_features_result under EV_FLAG_DEVICE_MEL. */
+int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, const ev_pitch_config* cfg,
+             float pitch_mean, float pitch_std, uint32_t flags, ev_pitch_result* out);
 
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);

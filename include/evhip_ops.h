@@ -201,6 +201,14 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
                    int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
                    void* hip_stream);
 
+/* ev_pitch's two kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_pitch).  ev_op_pitch_yin: steps 1-5, wav (B utterances back
+ * to back, fp32 or int16) -> f0_hz and aperiodicity (sum_b T_b,), T_b = wav_lens[b] / hop + 1, and, unless NULL, the chosen lag tau (-1 = unvoiced).
+ * ev_op_pitch_fill: steps 6-7, f0_hz (sum_b frames[b],) -> pitch of the same shape; pitch must not be f0_hz.  wav_lens / frames are HOST arrays; the
+ * calls wait for the stream.  -2 for what ev_pitch rejects, B outside [1, 65535], or frames[b] outside [1, 16384]. */
+int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sample_rate, int hop, int win, float f_min, float f_max,
+                    float threshold, float silence_rms, float* f0_hz, float* aperiodicity, int32_t* tau, void* hip_stream);
+int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pitch_mean, float pitch_std, float* pitch, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
