@@ -98,6 +98,23 @@ class ev_pitch_result(C.Structure):
     ]
 
 
+EV_RESAMPLE_MAX_RATIO, EV_RESAMPLE_MAX_TAPS, EV_RESAMPLE_TILE = 1024, 32769, 256
+
+
+class ev_resample_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("sr_in", C.c_int32), ("sr_out", C.c_int32), ("half_len", C.c_int32), ("taps", C.c_void_p),
+        ("trim_frac", C.c_float), ("trim_pad", C.c_int32),
+    ]
+
+
+class ev_resample_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_samples", C.c_int64), ("wav", C.c_void_p), ("wav_lens", C.POINTER(C.c_int64)),
+        ("wav_offsets", C.POINTER(C.c_int64)), ("trim_start", C.POINTER(C.c_int64)), ("trim_end", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -159,6 +176,10 @@ SIGNATURES = {
     "ev_features": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(ev_features_result)]),
     "ev_default_pitch_config": (None, [C.POINTER(ev_pitch_config)]),
     "ev_pitch": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_pitch_config), C.c_float, C.c_float, C.c_uint32, C.POINTER(ev_pitch_result)]),
+    "ev_default_resample_config": (None, [C.POINTER(ev_resample_config)]),
+    "ev_resample_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int]),
+    "ev_resample_setup": (C.c_int, [_P, C.POINTER(ev_resample_config)]),
+    "ev_resample": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_resample_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -204,6 +225,9 @@ SIGNATURES = {
     # wav_lens / frames are HOST arrays
     "ev_op_pitch_yin": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
     "ev_op_pitch_fill": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_float, _P, _P]),
+    # wav_lens / lens / out_lens / trim_start / trim_end and the taps are HOST arrays
+    "ev_op_resample": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "ev_op_trim": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

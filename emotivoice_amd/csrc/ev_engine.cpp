@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[6] = {0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch (likewise)
+    char* arena[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[7] = {0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample (likewise)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -97,6 +97,10 @@ struct ev_handle {
     const float* feat_mag = nullptr; int64_t feat_mag_elems = 0;
     // ev_pitch: the host halves of its result
     std::vector<int32_t> pit_mel_lens; std::vector<int64_t> pit_mel_offs;
+    // ev_resample: its setup (the phase-major table on the device), the host halves of its result and the "resample_raw" stage of the last call
+    ev_resample_config rcfg{}; bool rs_ready = false; int rs_up = 1, rs_down = 1, rs_half = 0; float* rs_tab = nullptr; size_t rs_tab_floats = 0;
+    std::vector<int64_t> rs_lens, rs_offs, rs_start, rs_end;
+    const float* rs_raw = nullptr; int64_t rs_raw_elems = 0;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1109,7 +1113,8 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 6; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 7; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    if (h->rs_tab) (void)hipFree(h->rs_tab);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
     if (h->feat_melT) (void)hipFree(h->feat_melT);
     if (h->sblob) (void)hipFree(h->sblob);
@@ -2022,6 +2027,227 @@ int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t
     return 0;
 }
 
+// ------------------------------------------------------------------- sample-rate conversion and trimming (include/evhip.h: ev_resample)
+static_assert(EV_RESAMPLE_TILE == RS_TM, "include/evhip.h states the tile of ev_resample.hip");
+static const int64_t RS_MAX_OUT = (int64_t)EV_ALIGN_MAX_FRAMES * 256;
+void ev_default_resample_config(ev_resample_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_resample_config);
+    c->sr_in = 16000; c->sr_out = 16000;
+}
+
+static double bessel_i0(double x) {      // the power series: every term positive, so it converges to the last bit for any x >= 0
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+static int resample_ratio(int sr_in, int sr_out, int* up, int* down) {      // 0, or -1 for a rate < 1
+    if (sr_in < 1 || sr_out < 1) return -1;
+    int a = sr_in, b = sr_out;
+    while (b) { const int t = a % b; a = b; b = t; }
+    *up = sr_out / a; *down = sr_in / a;
+    return 0;
+}
+
+int ev_resample_design(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int cap) {
+    int up = 0, down = 0;
+    if (resample_ratio(sr_in, sr_out, &up, &down) || up > EV_RESAMPLE_MAX_RATIO || down > EV_RESAMPLE_MAX_RATIO) return 0;
+    if (zeros < 1 || zeros > 4096 || !(rolloff > 0.0) || !(rolloff <= 1.0) || !std::isfinite(beta) || beta < 0.0) return 0;
+    const int q = std::max(up, down), half = zeros * q, n = 2 * half + 1;
+    if (cap < n || !taps) return -n;
+    std::vector<double> g((size_t)n);
+    const double i0b = bessel_i0(beta);
+    double sum = 0.0;
+    for (int i = -half; i <= half; ++i) {
+        const double x = rolloff * (double)i / (double)q, r = (double)i / (double)half;
+        const double px = M_PI * x;
+        const double sinc = i == 0 ? 1.0 : sin(px) / px;
+        g[(size_t)(i + half)] = sinc * bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    }
+    for (int i = 0; i < n; ++i) sum += g[(size_t)i];
+    for (int i = 0; i < n; ++i) taps[i] = (float)((double)up * g[(size_t)i] / sum);
+    return half;
+}
+
+// every rejection of a config, in the order include/evhip.h lists them; gives the ratio and the taps (the caller's or the default design)
+static int resample_check_config(ev_handle* h, const char* who, const ev_resample_config& c, int* up, int* down, int* half, std::vector<float>& taps) {
+    if (c.sr_in < 1 || c.sr_out < 1) return fail(h, "%s: sr_in %d / sr_out %d must be positive", who, c.sr_in, c.sr_out);
+    (void)resample_ratio(c.sr_in, c.sr_out, up, down);
+    if (*up > EV_RESAMPLE_MAX_RATIO || *down > EV_RESAMPLE_MAX_RATIO)
+        return fail(h, "%s: sr_in %d -> sr_out %d is up %d / down %d; both must be <= EV_RESAMPLE_MAX_RATIO %d", who, c.sr_in, c.sr_out, *up, *down, EV_RESAMPLE_MAX_RATIO);
+    if (c.taps) {
+        if (c.half_len < 1) return fail(h, "%s: half_len %d must be >= 1 with taps", who, c.half_len);
+        if (2 * (int64_t)c.half_len + 1 > EV_RESAMPLE_MAX_TAPS) return fail(h, "%s: half_len %d gives more than EV_RESAMPLE_MAX_TAPS %d taps", who, c.half_len, EV_RESAMPLE_MAX_TAPS);
+        taps.assign(c.taps, c.taps + 2 * (size_t)c.half_len + 1);
+        for (size_t i = 0; i < taps.size(); ++i)
+            if (!std::isfinite(taps[i])) return fail(h, "%s: taps[%zu] is not finite", who, i);
+        *half = c.half_len;
+    } else {
+        const int n = -ev_resample_design(c.sr_in, c.sr_out, 16, 0.945, 9.0, nullptr, 0);
+        if (n < 3 || n > EV_RESAMPLE_MAX_TAPS) return fail(h, "%s: the default design has %d taps > EV_RESAMPLE_MAX_TAPS %d", who, n, EV_RESAMPLE_MAX_TAPS);
+        taps.resize((size_t)n);
+        *half = ev_resample_design(c.sr_in, c.sr_out, 16, 0.945, 9.0, taps.data(), n);
+    }
+    if (!std::isfinite(c.trim_frac) || c.trim_frac < 0.f || !(c.trim_frac < 1.f)) return fail(h, "%s: trim_frac %g outside [0, 1)", who, (double)c.trim_frac);
+    if (c.trim_pad < 0) return fail(h, "%s: trim_pad %d must be >= 0", who, c.trim_pad);
+    return 0;
+}
+
+// the table on the device (hipMalloc'ed); nothing half-built is left behind
+static int resample_upload_table(int up, int half, const std::vector<float>& taps, float** tab, size_t* floats) {
+    std::vector<float> ht(resample_table_floats(up, half));
+    resample_pack_table(up, half, taps.data(), ht.data());
+    *tab = nullptr;
+    if (hipMalloc((void**)tab, ht.size() * 4) != hipSuccess) return -1;
+    if (hipMemcpy(*tab, ht.data(), ht.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(*tab); *tab = nullptr; return -1; }
+    *floats = ht.size();
+    return 0;
+}
+
+int ev_resample_setup(ev_handle* h, const ev_resample_config* cfg) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_resample_setup: null config");
+    if (cfg->struct_size != sizeof(ev_resample_config))
+        return fail(h, "ev_resample_setup: struct_size %u != sizeof(ev_resample_config) %zu", cfg->struct_size, sizeof(ev_resample_config));
+    int up = 0, down = 0, half = 0;
+    std::vector<float> taps;
+    if (resample_check_config(h, "ev_resample_setup", *cfg, &up, &down, &half, taps)) return -1;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float* tab = nullptr; size_t floats = 0;
+    if (resample_upload_table(up, half, taps, &tab, &floats)) return fail(h, "ev_resample_setup: uploading the tap table failed");
+    if (h->rs_tab) (void)hipFree(h->rs_tab);
+    h->rs_tab = tab; h->rs_tab_floats = floats; h->rs_up = up; h->rs_down = down; h->rs_half = half;
+    h->rcfg = *cfg; h->rcfg.taps = nullptr;
+    h->rs_ready = true;
+    return 0;
+}
+
+// output lengths, offsets and the tile table of a batch; 0 or the index + 1 of the first empty utterance (-(index + 1): too long with `extra` added)
+static int resample_layout(int B, const int64_t* wav_lens, int up, int down, int64_t extra, std::vector<ResampleSeq>& seqs, std::vector<ResampleTile>& tiles) {
+    seqs.resize(B); tiles.clear();
+    int64_t io = 0, oo = 0;
+    for (int b = 0; b < B; ++b) {
+        if (wav_lens[b] < 1) return b + 1;
+        if (wav_lens[b] > RS_MAX_OUT * EV_RESAMPLE_MAX_RATIO) return -(b + 1);      // keeps L up inside int64
+        const int64_t n = (wav_lens[b] * up + down - 1) / down;
+        if (n + extra > RS_MAX_OUT) return -(b + 1);
+        seqs[b] = ResampleSeq{io, wav_lens[b], oo, n};
+        for (int64_t m0 = 0; m0 < n; m0 += RS_TM) tiles.push_back(ResampleTile{b, (int32_t)m0});
+        io += wav_lens[b]; oo += n;
+    }
+    return 0;
+}
+
+static int resample_launch(const void* wav, int wav_is_i16, int up, int down, int half, const float* tab, const ResampleSeq* d_seqs, const ResampleTile* d_tiles,
+                           int n_tiles, int64_t total_in, float* y, hipStream_t s) {
+    if (up == 1 && down == 1) { launch_resample_copy(wav, wav_is_i16, total_in, y, s); return 0; }
+    ResampleParams p{};
+    p.wav = wav; p.wav_is_i16 = wav_is_i16; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = n_tiles;
+    p.up = up; p.down = down; p.half = half; p.row = resample_row_len(up, half); p.tab = tab; p.out = y;
+    return launch_resample_poly(p, s);
+}
+
+// cuts (first, last per utterance, from trim_scan) -> the result's lens / offsets / start / end and the gather table; returns the longest output
+static int64_t trim_plan(int B, const std::vector<ResampleSeq>& seqs, const int64_t* cuts, int pad, std::vector<TrimSeq>& ts, int64_t* lens, int64_t* offs,
+                         int64_t* start, int64_t* end) {
+    ts.resize(B);
+    int64_t o = 0, longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t s = cuts[2 * b], e = cuts[2 * b + 1], n = e - s + 2 * (int64_t)pad;
+        ts[b] = TrimSeq{seqs[b].out_off + s, o, e - s};
+        lens[b] = n; start[b] = s; end[b] = e;
+        if (offs) offs[b] = o;
+        o += n; longest = std::max(longest, n);
+    }
+    if (offs) offs[B] = o;
+    return longest;
+}
+
+int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, uint32_t flags, ev_resample_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out) return fail(h, "ev_resample: bad argument");
+    if (out->struct_size != sizeof(ev_resample_result))
+        return fail(h, "ev_resample: out->struct_size %u != sizeof(ev_resample_result) %zu", out->struct_size, sizeof(ev_resample_result));
+    if (!h->rs_ready) return fail(h, "ev_resample: ev_resample_setup has not been called");
+    if (B < 1 || B > 65535) return fail(h, "ev_resample: B %d outside [1, 65535]", B);
+    const ev_resample_config& rc = h->rcfg;
+    const int up = h->rs_up, down = h->rs_down, half = h->rs_half, pad = rc.trim_pad;
+    const bool trim = rc.trim_frac > 0.f;
+    std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;
+    const int bad = resample_layout(B, wav_lens, up, down, trim ? 2 * (int64_t)pad : 0, seqs, tiles);
+    if (bad > 0) return fail(h, "ev_resample: wav_lens[%d] = %lld < 1", bad - 1, (long long)wav_lens[bad - 1]);
+    if (bad < 0) return fail(h, "ev_resample: utterance %d (%lld samples) gives more than EV_ALIGN_MAX_FRAMES * 256 = %lld output samples", -bad - 1,
+                             (long long)wav_lens[-bad - 1], (long long)RS_MAX_OUT);
+    const int64_t total_in = seqs[B - 1].in_off + seqs[B - 1].len, total_n = seqs[B - 1].out_off + seqs[B - 1].n;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    h->rs_raw = nullptr;
+    void* d_wav = nullptr; ResampleSeq* d_seqs = nullptr; ResampleTile* d_tiles = nullptr; TrimSeq* d_ts = nullptr; int64_t* d_cuts = nullptr;
+    float *d_y = nullptr, *d_out = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 6, pass == 0};
+        if (pass == 1 && arena_reserve(h, 6, need)) return -1;
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        d_seqs = ap.arr<ResampleSeq>(B); d_tiles = ap.arr<ResampleTile>(tiles.size());
+        d_y = ap.arr<float>((size_t)total_n);
+        if (trim) { d_ts = ap.arr<TrimSeq>(B); d_cuts = ap.arr<int64_t>(2 * (size_t)B); d_out = ap.arr<float>((size_t)total_n + 2 * (size_t)pad * B); }
+        need = ap.off;
+    }
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_seqs, seqs.data(), (size_t)B * sizeof(ResampleSeq), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(ResampleTile), hipMemcpyHostToDevice, h->stream));
+    std::vector<int64_t> lens((size_t)B), offs((size_t)B + 1), start((size_t)B), end((size_t)B);
+    region_begin(h, "total");
+    {
+        const bool copy = up == 1 && down == 1;
+        KScope ks(h, copy ? "resample_copy" : "resample_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)total_in * es + (double)total_n * 4.0);
+        if (resample_launch(dev_in ? wav : d_wav, wav_is_i16 != 0, up, down, half, h->rs_tab, d_seqs, d_tiles, (int)tiles.size(), total_in, d_y, h->stream))
+            return fail(h, "ev_resample: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (trim) {
+        {
+            KScope ks(h, "trim_scan", 2.0 * (double)total_n, 2.0 * (double)total_n * 4.0);
+            launch_trim_scan(d_y, d_seqs, B, rc.trim_frac, d_cuts, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        std::vector<int64_t> cuts(2 * (size_t)B);
+        HIPCHK(h, hipMemcpyAsync(cuts.data(), d_cuts, cuts.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<TrimSeq> ts;
+        const int64_t longest = trim_plan(B, seqs, cuts.data(), pad, ts, lens.data(), offs.data(), start.data(), end.data());
+        HIPCHK(h, hipMemcpyAsync(d_ts, ts.data(), (size_t)B * sizeof(TrimSeq), hipMemcpyHostToDevice, h->stream));
+        {
+            KScope ks(h, "trim_gather", 0.0, 2.0 * (double)offs[B] * 4.0);
+            launch_trim_gather(d_y, d_ts, B, longest, pad, d_out, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+    } else {
+        for (int b = 0; b < B; ++b) { lens[b] = seqs[b].n; offs[b] = seqs[b].out_off; start[b] = 0; end[b] = seqs[b].n; }
+        offs[B] = total_n;
+    }
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    h->rs_lens = lens; h->rs_offs = offs; h->rs_start = start; h->rs_end = end;
+    h->rs_raw = keep ? d_y : nullptr; h->rs_raw_elems = keep ? total_n : 0;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total_samples = offs[B]; out->wav = trim ? d_out : d_y;
+    out->wav_lens = h->rs_lens.data(); out->wav_offsets = h->rs_offs.data(); out->trim_start = h->rs_start.data(); out->trim_end = h->rs_end.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
 void ev_default_bert_config(ev_bert_config* c) {
     memset(c, 0, sizeof *c);
@@ -2168,6 +2394,22 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
         if (!host_dst) return (int64_t)need;
         if (cap < need) return fail(h, "ev_get_stage(feat_mag): need %zu bytes, cap %zu", need, cap);
         if (hipMemcpy(host_dst, h->feat_mag, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(feat_mag): D2H failed");
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "resample_taps")) {  // ev_resample_setup: the (up, row) phase-major table in use
+        const size_t need = h->rs_tab_floats * 4;
+        if (!h->rs_ready) return fail(h, "ev_get_stage(resample_taps): ev_resample_setup has not been called");
+        if (!host_dst) return (int64_t)need;
+        if (cap < need) return fail(h, "ev_get_stage(resample_taps): need %zu bytes, cap %zu", need, cap);
+        if (hipMemcpy(host_dst, h->rs_tab, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(resample_taps): D2H failed");
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "resample_raw")) {   // ev_resample (keep_stages): the untrimmed y of the last ev_resample, packed
+        const size_t need = (size_t)h->rs_raw_elems * 4;
+        if (!h->rs_raw) return fail(h, "ev_get_stage(resample_raw): no ev_resample call with keep_stages yet");
+        if (!host_dst) return (int64_t)need;
+        if (cap < need) return fail(h, "ev_get_stage(resample_raw): need %zu bytes, cap %zu", need, cap);
+        if (hipMemcpy(host_dst, h->rs_raw, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(resample_raw): D2H failed");
         return (int64_t)need;
     }
     if (!strcmp(name, "log_p_attn")) {     // ev_align: the (T_b, N_b) blocks of the utterances, concatenated
@@ -2446,6 +2688,70 @@ int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pit
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
     }
     (void)hipFree(d);
+    return rc;
+}
+
+int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sr_in, int sr_out, const float* taps, int half_len, float* y,
+                   void* stream) {
+    if (!wav || !wav_lens || !y || B < 1 || B > 65535) return -2;
+    ev_resample_config c;
+    ev_default_resample_config(&c);
+    c.sr_in = sr_in; c.sr_out = sr_out; c.taps = taps; c.half_len = half_len;
+    int up = 0, down = 0, half = 0;
+    std::vector<float> ht;
+    if (resample_check_config(nullptr, "ev_op_resample", c, &up, &down, &half, ht)) return -2;
+    std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;
+    if (resample_layout(B, wav_lens, up, down, 0, seqs, tiles)) return -2;
+    float* tab = nullptr; size_t floats = 0;
+    if (resample_upload_table(up, half, ht, &tab, &floats)) return -1;
+    char* lay = nullptr;
+    const size_t sb = (size_t)B * sizeof(ResampleSeq), tb = tiles.size() * sizeof(ResampleTile);
+    int rc = hipMalloc((void**)&lay, sb + tb) == hipSuccess ? 0 : -1;
+    if (rc == 0 && (hipMemcpy(lay, seqs.data(), sb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(lay + sb, tiles.data(), tb, hipMemcpyHostToDevice) != hipSuccess)) rc = -1;
+    if (rc == 0) {
+        if (resample_launch(wav, wav_is_i16 != 0, up, down, half, tab, (const ResampleSeq*)lay, (const ResampleTile*)(lay + sb), (int)tiles.size(),
+                            seqs[B - 1].in_off + seqs[B - 1].len, y, (hipStream_t)stream)) rc = -2;
+        else if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    if (lay) (void)hipFree(lay);
+    (void)hipFree(tab);
+    return rc;
+}
+int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int trim_pad, float* out, int64_t* out_lens, int64_t* trim_start,
+               int64_t* trim_end, void* stream) {
+    if (!y || !lens || !out || !out_lens || !trim_start || !trim_end || out == y || B < 1 || B > 65535) return -2;
+    if (!std::isfinite(trim_frac) || !(trim_frac > 0.f) || !(trim_frac < 1.f) || trim_pad < 0) return -2;
+    std::vector<ResampleSeq> seqs((size_t)B);
+    int64_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] + 2 * (int64_t)trim_pad > RS_MAX_OUT) return -2;
+        seqs[(size_t)b] = ResampleSeq{o, lens[b], o, lens[b]};
+        o += lens[b];
+    }
+    char* lay = nullptr;
+    const size_t sb = (size_t)B * sizeof(ResampleSeq), cb = 2 * (size_t)B * sizeof(int64_t), tb = (size_t)B * sizeof(TrimSeq);
+    if (hipMalloc((void**)&lay, sb + cb + tb) != hipSuccess) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* d_cuts = (int64_t*)(lay + sb);
+    std::vector<int64_t> cuts(2 * (size_t)B);
+    std::vector<TrimSeq> ts;
+    int rc = hipMemcpy(lay, seqs.data(), sb, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    if (rc == 0) {
+        launch_trim_scan(y, (const ResampleSeq*)lay, B, trim_frac, d_cuts, s);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    }
+    if (rc == 0 && hipMemcpy(cuts.data(), d_cuts, cb, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+    if (rc == 0) {
+        const int64_t longest = trim_plan(B, seqs, cuts.data(), trim_pad, ts, out_lens, nullptr, trim_start, trim_end);
+        if (hipMemcpy(lay + sb + cb, ts.data(), tb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+        if (rc == 0) {
+            launch_trim_gather(y, (const TrimSeq*)(lay + sb + cb), B, longest, trim_pad, out, s);
+            if (hipGetLastError() != hipSuccess) rc = -1;
+            if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+        }
+    }
+    (void)hipFree(lay);
     return rc;
 }
 

@@ -282,4 +282,28 @@ int launch_pitch_yin(const PitchParams& p, hipStream_t s);      // 0, or -1 for 
 // out[t] = (cont[t] - mean) / stdv, cont = f0 with unvoiced frames held at the edges and interpolated between voiced neighbours; out != f0
 void launch_pitch_fill(const float* f0, const StftSeq* seqs, int B, float mean, float stdv, float* out, hipStream_t s);
 
+// ev_resample (ev_resample.hip): polyphase sample-rate conversion, then the silence trim.  A tile is RS_TM consecutive outputs of one utterance.  The
+// taps go in as a phase-major table (resample_pack_table): row p = (m down) mod up holds h[i], i = p (mod up), from the largest i <= half downwards,
+// zero-filled to resample_row_len (odd).  A tile's run of inputs stays in LDS up to RS_MAX_RUN_BYTES, the table beside it up to RS_MAX_LDS in all.
+constexpr int RS_TM = 256, RS_MAX_RUN_BYTES = 49152, RS_MAX_LDS = 65536;
+struct ResampleSeq { int64_t in_off, len, out_off, n; };      // input offset / length, output offset / length n = ceil(len up / down)
+struct ResampleTile { int32_t seq, m0; };                     // one block: utterance and first output
+struct TrimSeq { int64_t src_off, dst_off, cut; };            // the cut y[src_off .. src_off + cut) goes to out[dst_off + pad ..)
+struct ResampleParams {
+    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
+    const ResampleSeq* seqs; const ResampleTile* tiles; int n_tiles;
+    int up, down, half, row;                          // row = resample_row_len(up, half)
+    const float* tab;                                 // (up, row) on the device
+    float* out;                                       // packed at out_off
+    int run_cap;                                      // set by the launcher: floats of LDS for the run, 0 = read through L1
+};
+int resample_row_len(int up, int half);
+size_t resample_table_floats(int up, int half);
+void resample_pack_table(int up, int half, const float* taps /* host (2 half + 1,) */, float* out /* host, resample_table_floats */);
+int64_t resample_run_max(int up, int down, int half);           // an upper bound of a tile's run of input samples
+int launch_resample_poly(const ResampleParams& p, hipStream_t s);      // 0, or -1 for bad parameters
+void launch_resample_copy(const void* wav, int wav_is_i16, int64_t total, float* out, hipStream_t s);      // sr_in == sr_out
+void launch_trim_scan(const float* y, const ResampleSeq* seqs, int B, float frac, int64_t* cuts /* (2 B,): first, last */, hipStream_t s);
+void launch_trim_gather(const float* y, const TrimSeq* seqs, int B, int64_t max_len, int pad, float* out, hipStream_t s);
+
 }  // namespace ev

@@ -94,6 +94,8 @@ class EVEngine:
         self.feature_config = None                  # set by features_setup()
         self.last_features: Optional[_ffi.ev_features_result] = None
         self.last_pitch: Optional[_ffi.ev_pitch_result] = None
+        self.resample_config = None                 # set by resample_setup()
+        self.last_resample: Optional[_ffi.ev_resample_result] = None
 
     # -- lifecycle
     def close(self):
@@ -342,6 +344,53 @@ class EVEngine:
         mean, std = check_stats(pitch_stats)
         flat, is16, lens = pack_wavs(wavs, pc.hop)
         return self.pitch_to_numpy(self.pitch_raw(len(wavs), flat.ctypes.data, is16, lens, mean, std, pc))
+
+    # -- sample-rate conversion and trimming (ev_resample): wav at any common rate -> wav at the model's rate on the device
+    def resample_setup(self, config):
+        """ev_resample_setup.  config: an emotivoice_amd.resample.ResampleConfig.  The default design is built by the library; other design
+        parameters, or the caller's own taps, go in as taps.  Needs no weights."""
+        rc = config.validate()
+        c = _ffi.ev_resample_config()
+        self._lib.ev_default_resample_config(C.byref(c))
+        c.sr_in, c.sr_out = int(rc.sr_in), int(rc.sr_out)
+        taps = None
+        if not rc.is_default_design():
+            taps = np.ascontiguousarray(rc.design(), np.float32)
+            c.taps, c.half_len = taps.ctypes.data, (taps.size - 1) // 2
+        if rc.trim:
+            c.trim_frac, c.trim_pad = rc.trim_frac, rc.pad()
+        self._check(self._lib.ev_resample_setup(self._h, C.byref(c)))
+        self.resample_config = rc
+
+    def resample_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, wav_lens: np.ndarray, flags: int = 0) -> _ffi.ev_resample_result:
+        """ev_resample (include/evhip.h).  The returned struct's device waveform stays valid until the next resample call on this engine."""
+        wl = np.ascontiguousarray(wav_lens, np.int64)
+        res = _ffi.ev_resample_result()
+        res.struct_size = C.sizeof(_ffi.ev_resample_result)
+        self._check(self._lib.ev_resample(self._h, B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, wl.ctypes.data_as(C.c_void_p), flags, C.byref(res)))
+        self.last_resample = res
+        return res
+
+    def resample_to_numpy(self, res: _ffi.ev_resample_result) -> Dict[str, object]:
+        B = res.batch
+        lens = np.array([res.wav_lens[b] for b in range(B)], np.int64)
+        offs = np.array([res.wav_offsets[b] for b in range(B + 1)], np.int64)
+        wav = self.d2h(res.wav, (res.total_samples,), np.float32)
+        return dict(wav=wav, wav_list=[wav[offs[b]:offs[b + 1]] for b in range(B)], wav_lens=lens, wav_offsets=offs,
+                    trim_start=np.array([res.trim_start[b] for b in range(B)], np.int64),
+                    trim_end=np.array([res.trim_end[b] for b in range(B)], np.int64))
+
+    def resample(self, wavs: Sequence[np.ndarray], sr_in: int, **config) -> Dict[str, object]:
+        """Recordings at ``sr_in`` -> waveforms at ``sr_out`` (default 16 kHz), optionally trimmed and padded as the reference's get_mel does
+        (``trim=True``).  wavs: one 1-D array per utterance, all int16 or all floating; further keywords: the fields of
+        emotivoice_amd.resample.ResampleConfig.  The filter is this project's polyphase windowed sinc, not librosa's soxr.  Returns wav_list
+        (float32), wav_lens, trim_start and trim_end (indices into the untrimmed resampled utterance)."""
+        from .resample import ResampleConfig, pack_wavs
+        rc = ResampleConfig(sr_in=sr_in, **config).validate()
+        if self.resample_config is None or self.resample_config.key() != rc.key():
+            self.resample_setup(rc)
+        flat, is16, lens = pack_wavs(wavs, rc)
+        return self.resample_to_numpy(self.resample_raw(len(wavs), flat.ctypes.data, is16, lens))
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)

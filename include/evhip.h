@@ -387,6 +387,67 @@ typedef struct ev_pitch_result {
 int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, const ev_pitch_config* cfg,
              float pitch_mean, float pitch_std, uint32_t flags, ev_pitch_result* out);
 
+/* Sample-rate conversion and trimming (ev_resample): a recording at sr_in -> the waveform at sr_out (the model's 16 kHz), optionally trimmed and
+ * padded, on the device -- the step the reference runs before it computes a mel: librosa.resample(y, orig_sr, 16000) when it prepares a corpus,
+ * then prompt_dataset.get_mel's trim (cut what lies below 0.5 % of the peak, pad 50 ms of zeros on each side).  The resampler is NOT librosa's
+ * (soxr): it is the polyphase windowed-sinc filter specified here, and agreement with soxr has not been measured.  The trim restates the reference.
+ * Deliberate difference: the reference writes a PCM-16 file between the two steps; here nothing is re-quantised between them.
+ *   Rates and lengths: g = gcd(sr_in, sr_out), up = sr_out / g, down = sr_in / g, q = max(up, down).  An utterance of L >= 1 samples gives
+ *     n = ceil(L up / down) outputs (int64 arithmetic).
+ *   Prototype filter (designed in fp64, rounded once to fp32): half = zeros q, i = -half .. half,
+ *     g[i] = sinc(rolloff i / q) I0(beta sqrt(1 - (i / half)^2)) / I0(beta),  h[i] = (float)(up g[i] / sum g),  sinc(x) = sin(pi x) / (pi x);
+ *     the default design has zeros = 16, rolloff = 0.945, beta = 9.0.  A caller's own taps h[-half_len .. half_len] replace it.
+ *   Output sample: y[m] = sum_k x[k] h[m down - k up], k from k_lo = ceil((m down - half) / up) to k_hi = floor((m down + half) / up), ascending,
+ *     x[k] = +0.0 outside [0, L) (zero padding, no reflection); m down in int64.  fp32 fmaf into four interleaved partial sums over (k - k_lo) mod 4,
+ *     combined as (s0 + s1) + (s2 + s3) -- the order rule of ev_pitch step 2, so the bits of y[m] depend on (utterance, m) alone.
+ *     int16 input is x / 32768.  sr_in == sr_out is a copy (int16 -> float) with no filter.
+ *   Trim (only with trim_frac > 0, on the fp32 y): peak = max |y|, thr = (float)peak * (float)trim_frac (one fp32 product); start = the first index
+ *     with |y| > thr, end = the LAST such index; the output is trim_pad zeros, y[start .. end), trim_pad zeros -- the slice excludes `end`, so the
+ *     last sample above the threshold is dropped, as the reference does.  No sample above the threshold (an all-zero utterance): start = end = 0 and
+ *     the output is 2 trim_pad zeros (the reference raises there; the caller sees it in trim_start / trim_end).  The reference's values are
+ *     trim_frac = 0.005 and trim_pad = sr_out / 20.
+ * No atomics and no floating sum split over threads: an utterance gives the same bits alone or anywhere in a batch, as int16 or as the equal floats,
+ * from host or device memory, and on every precision mode; the max and first / last index reductions are exact in any order.  Needs no weights. */
+#define EV_RESAMPLE_MAX_RATIO 1024    /* up and down after the gcd */
+#define EV_RESAMPLE_MAX_TAPS  32769   /* 2 half + 1 */
+#define EV_RESAMPLE_TILE      256     /* outputs per block of the kernel */
+typedef struct ev_resample_config {
+    uint32_t struct_size;          /* sizeof(ev_resample_config); any other value is rejected */
+    int32_t  sr_in, sr_out;        /* >= 1; up and down <= EV_RESAMPLE_MAX_RATIO */
+    int32_t  half_len;             /* with taps: (len - 1) / 2 >= 1; ignored without */
+    const float* taps;             /* HOST (2 half_len + 1) or NULL = the default design; copied */
+    float    trim_frac;            /* 0 = no trim; in [0, 1) */
+    int32_t  trim_pad;             /* zeros on each side after the trim; >= 0 */
+} ev_resample_config;
+void ev_default_resample_config(ev_resample_config* cfg);      /* 16000 -> 16000, taps NULL, trim off */
+/* Host only, no device touched: writes the design's 2 half + 1 taps (half = zeros max(up, down)) and returns half, or, with cap < 2 half + 1 (taps may
+ * then be NULL), the negative needed capacity -(2 half + 1).  0 for arguments outside the design's domain: a rate < 1, up or down above
+ * EV_RESAMPLE_MAX_RATIO, zeros outside [1, 4096], rolloff not in (0, 1], beta negative or non-finite. */
+int ev_resample_design(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int cap);
+/* Copies the taps (or designs the default ones) and builds the device table.  Rejected (message naming the field): a wrong struct_size, sr_in or
+ * sr_out < 1, up or down > EV_RESAMPLE_MAX_RATIO, taps with half_len < 1, more than EV_RESAMPLE_MAX_TAPS taps, a non-finite tap, trim_frac outside
+ * [0, 1) or non-finite, trim_pad < 0.  A rejected setup leaves the previous one in place. */
+int ev_resample_setup(ev_handle* h, const ev_resample_config* cfg);
+
+typedef struct ev_resample_result {
+    uint32_t struct_size;          /* sizeof(ev_resample_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total_samples;
+    const float*   wav;            /* DEVICE, utterances back to back: what ev_features / ev_pitch take with EV_FLAG_DEVICE_INPUTS */
+    const int64_t* wav_lens;       /* (batch,)   HOST */
+    const int64_t* wav_offsets;    /* (batch+1,) HOST */
+    const int64_t* trim_start;     /* (batch,) HOST, indices into the untrimmed resampled utterance; 0 / n_b without trim */
+    const int64_t* trim_end;       /* (batch,) HOST */
+} ev_resample_result;
+/* wav / wav_is_i16 / wav_lens / EV_FLAG_DEVICE_INPUTS as ev_features.  Rejected before anything is launched (message naming the field or utterance):
+ * a wrong struct_size, no ev_resample_setup, B outside [1, 65535], wav_lens[b] < 1, an utterance whose output (with its padding) exceeds
+ * EV_ALIGN_MAX_FRAMES * 256 samples.  The result lives in a workspace of its own and is complete when the call returns; it stays valid across
+ * ev_features / ev_pitch / ev_align / ev_synthesize[_prosody] / ev_vocoder until the next ev_resample or ev_destroy -- the contract of
+ * ev_features_result.  ev_get_stage("resample_taps") returns the phase-major table in use: (up, R) floats, R = (2 half / up + 1) | 1, row
+ * p = (m down) mod up holding h[i], i = p (mod up), from the largest i <= half downwards, zero-filled; with keep_stages, "resample_raw" returns the
+ * untrimmed y of the last call, packed at ceil(L_b up / down) each. */
+int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, uint32_t flags, ev_resample_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 

@@ -209,6 +209,17 @@ int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_l
                     float threshold, float silence_rms, float* f0_hz, float* aperiodicity, int32_t* tau, void* hip_stream);
 int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pitch_mean, float pitch_std, float* pitch, void* hip_stream);
 
+/* ev_resample's kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_resample).  ev_op_resample: wav (B utterances back to back,
+ * fp32 or int16) -> y (sum_b n_b,), n_b = ceil(wav_lens[b] up / down), packed in utterance order; taps HOST (2 half_len + 1) or NULL = the default
+ * design (half_len ignored); sr_in == sr_out copies.  ev_op_trim: y (B utterances of lens[b] samples back to back) -> out, the padded cuts back to
+ * back (at most sum_b lens[b] + 2 B trim_pad floats), and the HOST arrays out_lens, trim_start, trim_end (B each); out must not overlap y.  wav_lens /
+ * lens are HOST arrays; the calls wait for the stream.  -2 for what ev_resample_setup / ev_resample reject, B outside [1, 65535], and for
+ * ev_op_trim a trim_frac outside (0, 1). */
+int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sr_in, int sr_out, const float* taps, int half_len, float* y,
+                   void* hip_stream);
+int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int trim_pad, float* out, int64_t* out_lens, int64_t* trim_start,
+               int64_t* trim_end, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
