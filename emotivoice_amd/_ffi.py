@@ -115,6 +115,24 @@ class ev_resample_result(C.Structure):
     ]
 
 
+EV_STITCH_MAX_FADE, EV_STITCH_MAX_PAUSE, EV_STITCH_MAX_DOC = 4096, 1 << 24, 1 << 30
+
+
+class ev_stitch_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("trim_frac", C.c_float), ("trim_abs", C.c_float), ("keep", C.c_int32), ("fade", C.c_int32),
+        ("lead", C.c_int32), ("tail", C.c_int32), ("want_i16", C.c_int32),
+    ]
+
+
+class ev_stitch_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch_docs", C.c_int32), ("batch_segs", C.c_int32), ("reserved", C.c_int32), ("total_samples", C.c_int64),
+        ("wav", C.c_void_p), ("wav_i16", C.c_void_p), ("doc_lens", C.POINTER(C.c_int64)), ("doc_offsets", C.POINTER(C.c_int64)),
+        ("seg_pos", C.POINTER(C.c_int64)), ("seg_start", C.POINTER(C.c_int64)), ("seg_end", C.POINTER(C.c_int64)), ("seg_peak", C.POINTER(C.c_float)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -180,6 +198,11 @@ SIGNATURES = {
     "ev_resample_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int]),
     "ev_resample_setup": (C.c_int, [_P, C.POINTER(ev_resample_config)]),
     "ev_resample": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_resample_result)]),
+    "ev_default_stitch_config": (None, [C.POINTER(ev_stitch_config)]),
+    "ev_stitch_ramp": (C.c_int, [C.c_int, _P]),
+    # n, seg_doc, pause_after in; pos, fl, fr, doc_lens out: HOST arrays
+    "ev_stitch_plan": (C.c_int, [C.c_int, _P, _P, _P, C.POINTER(ev_stitch_config), _P, _P, _P, _P]),
+    "ev_stitch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(ev_stitch_config), C.c_uint32, C.POINTER(ev_stitch_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -228,6 +251,9 @@ SIGNATURES = {
     # wav_lens / lens / out_lens / trim_start / trim_end and the taps are HOST arrays
     "ev_op_resample": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "ev_op_trim": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
+    # everything but wav / out / out_i16 is a HOST array
+    "ev_op_stitch_scan": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "ev_op_stitch_mix": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

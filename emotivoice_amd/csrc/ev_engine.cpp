@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[7] = {0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample (likewise)
+    char* arena[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -101,6 +101,9 @@ struct ev_handle {
     ev_resample_config rcfg{}; bool rs_ready = false; int rs_up = 1, rs_down = 1, rs_half = 0; float* rs_tab = nullptr; size_t rs_tab_floats = 0;
     std::vector<int64_t> rs_lens, rs_offs, rs_start, rs_end;
     const float* rs_raw = nullptr; int64_t rs_raw_elems = 0;
+    // ev_stitch: the ramp table of the last call (device, EV_STITCH_MAX_FADE floats once allocated; its host copy feeds the upload) and the host halves of its result
+    float* st_tab = nullptr; int st_F = -1; std::vector<float> st_tab_host;
+    std::vector<int64_t> st_doc_lens, st_doc_offs, st_pos, st_start, st_end; std::vector<float> st_peak;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1113,8 +1116,9 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 7; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 8; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->rs_tab) (void)hipFree(h->rs_tab);
+    if (h->st_tab) (void)hipFree(h->st_tab);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
     if (h->feat_melT) (void)hipFree(h->feat_melT);
     if (h->sblob) (void)hipFree(h->sblob);
@@ -2248,6 +2252,205 @@ int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     return 0;
 }
 
+// ------------------------------------------------------------------- long-form stitching (include/evhip.h: ev_stitch)
+static_assert(EV_STITCH_MAX_FADE == ST_MAX_FADE, "include/evhip.h states the ramp table's limit of ev_stitch.hip");
+void ev_default_stitch_config(ev_stitch_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_stitch_config);
+}
+
+int ev_stitch_ramp(int F, float* tab) {
+    if (F < 0 || F > EV_STITCH_MAX_FADE || (F > 0 && !tab)) return -1;
+    for (int i = 0; i < F; ++i) tab[i] = (float)(0.5 - 0.5 * cos(M_PI * ((double)i + 0.5) / (double)F));
+    return F;
+}
+
+static int stitch_check_trim(ev_handle* h, const char* who, float trim_frac, float trim_abs) {
+    if (!std::isfinite(trim_frac) || trim_frac < 0.f || !(trim_frac < 1.f)) return fail(h, "%s: trim_frac %g outside [0, 1)", who, (double)trim_frac);
+    if (!std::isfinite(trim_abs) || trim_abs < 0.f) return fail(h, "%s: trim_abs %g must be finite and >= 0", who, (double)trim_abs);
+    return 0;
+}
+
+// the config and the per-segment arrays that do not depend on the waveform: the number of documents, or -1 with the message
+static int stitch_check(ev_handle* h, const char* who, int S, const int32_t* seg_doc, const int32_t* pause_after, const ev_stitch_config* c) {
+    if (!c || !seg_doc || !pause_after) return fail(h, "%s: bad argument", who);
+    if (c->struct_size != sizeof(ev_stitch_config))
+        return fail(h, "%s: cfg->struct_size %u != sizeof(ev_stitch_config) %zu", who, c->struct_size, sizeof(ev_stitch_config));
+    if (S < 1 || S > 65535) return fail(h, "%s: S %d outside [1, 65535]", who, S);
+    if (stitch_check_trim(h, who, c->trim_frac, c->trim_abs)) return -1;
+    if (c->keep < 0) return fail(h, "%s: keep %d must be >= 0", who, c->keep);
+    if (c->fade < 0 || c->fade > EV_STITCH_MAX_FADE) return fail(h, "%s: fade %d outside [0, EV_STITCH_MAX_FADE = %d]", who, c->fade, EV_STITCH_MAX_FADE);
+    if (c->lead < 0) return fail(h, "%s: lead %d must be >= 0", who, c->lead);
+    if (c->tail < 0) return fail(h, "%s: tail %d must be >= 0", who, c->tail);
+    if (seg_doc[0] != 0) return fail(h, "%s: seg_doc[0] = %d, the documents count from 0", who, seg_doc[0]);
+    for (int s = 1; s < S; ++s)
+        if (seg_doc[s] != seg_doc[s - 1] && seg_doc[s] != seg_doc[s - 1] + 1)
+            return fail(h, "%s: seg_doc[%d] = %d after %d: neither the same document nor the next", who, s, seg_doc[s], seg_doc[s - 1]);
+    for (int s = 0; s + 1 < S; ++s)
+        if (seg_doc[s + 1] == seg_doc[s] && (pause_after[s] < -EV_STITCH_MAX_FADE || pause_after[s] > EV_STITCH_MAX_PAUSE))
+            return fail(h, "%s: pause_after[%d] = %d outside [-EV_STITCH_MAX_FADE, EV_STITCH_MAX_PAUSE]", who, s, pause_after[s]);
+    return seg_doc[S - 1] + 1;
+}
+
+int ev_stitch_plan(int S, const int64_t* n, const int32_t* seg_doc, const int32_t* pause_after, const ev_stitch_config* cfg, int64_t* pos, int32_t* fl,
+                   int32_t* fr, int64_t* doc_lens) {
+    const int D = stitch_check(nullptr, "ev_stitch_plan", S, seg_doc, pause_after, cfg);
+    if (D < 0) return -1;
+    if (!n || !pos || !fl || !fr || !doc_lens) return fail(nullptr, "ev_stitch_plan: bad argument");
+    for (int s = 0; s < S; ++s)
+        if (n[s] < 0 || n[s] > EV_STITCH_MAX_DOC) return fail(nullptr, "ev_stitch_plan: n[%d] = %lld outside [0, EV_STITCH_MAX_DOC]", s, (long long)n[s]);
+    const int64_t F = cfg->fade;
+    for (int s = 0; s < S; ++s) {
+        if (s == 0 || seg_doc[s] != seg_doc[s - 1]) { pos[s] = cfg->lead; fl[s] = (int32_t)std::min(F, n[s] / 2); }
+        if (s == S - 1 || seg_doc[s + 1] != seg_doc[s]) {
+            fr[s] = (int32_t)std::min(F, n[s] / 2);
+            const int64_t len = pos[s] + n[s] + cfg->tail;
+            if (len > EV_STITCH_MAX_DOC)
+                return fail(nullptr, "ev_stitch_plan: document %d has %lld samples, more than EV_STITCH_MAX_DOC = %d", seg_doc[s], (long long)len, EV_STITCH_MAX_DOC);
+            doc_lens[seg_doc[s]] = len;
+            continue;
+        }
+        int64_t ov = 0;
+        if (pause_after[s] < 0 && n[s] > 0 && n[s + 1] > 0) ov = std::min(std::min(-(int64_t)pause_after[s], F), std::min(n[s] / 2, n[s + 1] / 2));
+        const int64_t gap = ov > 0 ? 0 : std::max((int64_t)pause_after[s], (int64_t)0);
+        pos[s + 1] = pos[s] + n[s] + gap - ov;
+        fr[s] = (int32_t)(ov > 0 ? ov : std::min(F, n[s] / 2));
+        fl[s + 1] = (int32_t)(ov > 0 ? ov : std::min(F, n[s + 1] / 2));
+    }
+    return D;
+}
+
+// the planned segments -> the mix kernel's tables and the documents' offsets (D + 1); returns the packed length
+static int64_t stitch_tables(int S, int D, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl, const int32_t* fr,
+                             const int64_t* doc_lens, std::vector<StitchMixSeg>& ms, std::vector<StitchDoc>& docs, std::vector<StitchTile>& tiles, int64_t* offs) {
+    ms.resize((size_t)S); docs.assign((size_t)D, StitchDoc{0, 0, 0, 0}); tiles.clear();
+    for (int s = 0; s < S; ++s) {
+        ms[(size_t)s] = StitchMixSeg{src[s], pos[s], (int32_t)n[s], fl[s], fr[s], 0};
+        StitchDoc& d = docs[(size_t)seg_doc[s]];
+        if (d.nseg == 0) d.seg0 = s;
+        d.nseg++;
+    }
+    int64_t o = 0;
+    for (int d = 0; d < D; ++d) {
+        docs[(size_t)d].out_off = o; docs[(size_t)d].len = doc_lens[d];
+        offs[d] = o;
+        for (int64_t t = 0; t * ST_TILE < doc_lens[d]; ++t) tiles.push_back(StitchTile{d, (int32_t)t});
+        o += doc_lens[d];
+    }
+    offs[D] = o;
+    return o;
+}
+
+int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets, const int64_t* seg_lens, const int32_t* seg_doc, const int32_t* pause_after,
+              const ev_stitch_config* cfg, uint32_t flags, ev_stitch_result* out) {
+    if (!h) return -1;
+    if (!wav || !seg_offsets || !seg_lens || !seg_doc || !pause_after || !out) return fail(h, "ev_stitch: bad argument");
+    if (out->struct_size != sizeof(ev_stitch_result))
+        return fail(h, "ev_stitch: out->struct_size %u != sizeof(ev_stitch_result) %zu", out->struct_size, sizeof(ev_stitch_result));
+    ev_stitch_config dflt;
+    if (!cfg) { ev_default_stitch_config(&dflt); cfg = &dflt; }
+    const int D = stitch_check(h, "ev_stitch", S, seg_doc, pause_after, cfg);
+    if (D < 0) return -1;
+    const ev_stitch_config c = *cfg;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, trim = c.trim_frac > 0.f || c.trim_abs > 0.f, i16 = c.want_i16 != 0;
+    // the layout of the input, and each document's length before any cut: what the workspace is sized for and what EV_STITCH_MAX_DOC is judged on
+    std::vector<StitchSeg> segs((size_t)S);
+    std::vector<int64_t> bound((size_t)D, (int64_t)c.lead + c.tail);
+    int64_t lo_off = INT64_MAX, hi_end = 0, n_part = 0, max_len = 0;
+    for (int s = 0; s < S; ++s) {
+        if (seg_offsets[s] < 0) return fail(h, "ev_stitch: seg_offsets[%d] = %lld < 0", s, (long long)seg_offsets[s]);
+        if (seg_lens[s] < 1) return fail(h, "ev_stitch: seg_lens[%d] = %lld < 1", s, (long long)seg_lens[s]);
+        int64_t& bd = bound[(size_t)seg_doc[s]];
+        bd += std::min(seg_lens[s], (int64_t)EV_STITCH_MAX_DOC + 1);
+        if (s + 1 < S && seg_doc[s + 1] == seg_doc[s]) bd += std::max(pause_after[s], 0);
+        if (bd > EV_STITCH_MAX_DOC)
+            return fail(h, "ev_stitch: document %d exceeds EV_STITCH_MAX_DOC = %d samples at segment %d (lead + tail + segments + pauses, before the cut)",
+                        seg_doc[s], EV_STITCH_MAX_DOC, s);
+        segs[(size_t)s] = StitchSeg{seg_offsets[s], seg_lens[s], n_part};
+        n_part += (seg_lens[s] + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
+        lo_off = std::min(lo_off, seg_offsets[s]); hi_end = std::max(hi_end, seg_offsets[s] + seg_lens[s]); max_len = std::max(max_len, seg_lens[s]);
+    }
+    if (!dev_in) for (auto& sg : segs) sg.off -= lo_off;      // the host's samples lo_off .. hi_end are copied
+    int64_t cap_out = 0, cap_tiles = 0;
+    for (int d = 0; d < D; ++d) { cap_out += bound[(size_t)d]; cap_tiles += (bound[(size_t)d] + ST_TILE - 1) / ST_TILE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    float* d_wav = nullptr; StitchSeg* d_segs = nullptr; float *d_part = nullptr, *d_peak = nullptr; int64_t* d_cuts = nullptr;
+    StitchMixSeg* d_ms = nullptr; StitchDoc* d_docs = nullptr; StitchTile* d_tiles = nullptr; float* d_out = nullptr; int16_t* d_i16 = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 7, pass == 0};
+        if (pass == 1 && arena_reserve(h, 7, need)) return -1;
+        d_wav = dev_in ? nullptr : ap.arr<float>((size_t)(hi_end - lo_off));
+        if (trim) { d_segs = ap.arr<StitchSeg>(S); d_part = ap.arr<float>((size_t)n_part); d_peak = ap.arr<float>(S); d_cuts = ap.arr<int64_t>(2 * (size_t)S); }
+        d_ms = ap.arr<StitchMixSeg>(S); d_docs = ap.arr<StitchDoc>(D); d_tiles = ap.arr<StitchTile>((size_t)cap_tiles);
+        d_out = ap.arr<float>((size_t)cap_out);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)cap_out);
+        need = ap.off;
+    }
+    if (!h->st_tab) HIPCHK(h, hipMalloc((void**)&h->st_tab, (size_t)EV_STITCH_MAX_FADE * sizeof(float)));
+    h->st_tab_host.resize((size_t)c.fade);
+    (void)ev_stitch_ramp(c.fade, h->st_tab_host.data());
+    h->st_F = c.fade;
+    if (c.fade > 0) HIPCHK(h, hipMemcpyAsync(h->st_tab, h->st_tab_host.data(), (size_t)c.fade * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav + lo_off, (size_t)(hi_end - lo_off) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const float* x = dev_in ? wav : d_wav;
+    std::vector<int64_t> a((size_t)S, 0), b((size_t)S), n((size_t)S), src((size_t)S);
+    std::vector<float> peak((size_t)S, 0.f);
+    for (int s = 0; s < S; ++s) b[(size_t)s] = seg_lens[s];
+    region_begin(h, "total");
+    if (trim) {
+        HIPCHK(h, hipMemcpyAsync(d_segs, segs.data(), (size_t)S * sizeof(StitchSeg), hipMemcpyHostToDevice, h->stream));
+        {
+            KScope ks(h, "stitch_peak", 0.0, (double)(hi_end - lo_off) * 4.0);
+            launch_stitch_peak(x, d_segs, S, max_len, d_part, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        {
+            KScope ks(h, "stitch_edges", 0.0, (double)n_part * 4.0);
+            launch_stitch_edges(x, d_segs, S, d_part, c.trim_frac, c.trim_abs, d_peak, d_cuts, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        std::vector<int64_t> cuts(2 * (size_t)S);
+        HIPCHK(h, hipMemcpyAsync(cuts.data(), d_cuts, cuts.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(peak.data(), d_peak, (size_t)S * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int s = 0; s < S; ++s) {
+            const int64_t first = cuts[2 * (size_t)s], last = cuts[2 * (size_t)s + 1];
+            a[(size_t)s] = first < 0 ? 0 : std::max((int64_t)0, first - c.keep);
+            b[(size_t)s] = first < 0 ? 0 : std::min(seg_lens[s], last + 1 + c.keep);
+        }
+    }
+    for (int s = 0; s < S; ++s) { n[(size_t)s] = b[(size_t)s] - a[(size_t)s]; src[(size_t)s] = segs[(size_t)s].off + a[(size_t)s]; }
+    std::vector<int64_t> pos((size_t)S), doc_lens((size_t)D), offs((size_t)D + 1);
+    std::vector<int32_t> fl((size_t)S), fr((size_t)S);
+    if (ev_stitch_plan(S, n.data(), seg_doc, pause_after, &c, pos.data(), fl.data(), fr.data(), doc_lens.data()) != D)
+        return fail(h, "ev_stitch: %s", ev_last_error(nullptr));
+    std::vector<StitchMixSeg> ms; std::vector<StitchDoc> docs; std::vector<StitchTile> tiles;
+    const int64_t total = stitch_tables(S, D, src.data(), n.data(), seg_doc, pos.data(), fl.data(), fr.data(), doc_lens.data(), ms, docs, tiles, offs.data());
+    if (total > cap_out || (int64_t)tiles.size() > cap_tiles) return fail(h, "ev_stitch: the plan outgrew its workspace");      // the cut only shortens
+    HIPCHK(h, hipMemcpyAsync(d_ms, ms.data(), (size_t)S * sizeof(StitchMixSeg), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_docs, docs.data(), (size_t)D * sizeof(StitchDoc), hipMemcpyHostToDevice, h->stream));
+    if (!tiles.empty()) HIPCHK(h, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(StitchTile), hipMemcpyHostToDevice, h->stream));
+    {
+        KScope ks(h, "stitch_mix", 0.0, (double)total * (i16 ? 10.0 : 8.0));
+        if (launch_stitch_mix(x, d_ms, d_docs, d_tiles, (int64_t)tiles.size(), h->st_tab, c.fade, d_out, i16 ? d_i16 : nullptr, h->stream))
+            return fail(h, "ev_stitch: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    h->st_doc_lens = doc_lens; h->st_doc_offs = offs; h->st_pos = pos; h->st_start = a; h->st_end = b; h->st_peak = peak;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch_docs = D; out->batch_segs = S; out->total_samples = total; out->wav = d_out; out->wav_i16 = i16 ? d_i16 : nullptr;
+    out->doc_lens = h->st_doc_lens.data(); out->doc_offsets = h->st_doc_offs.data(); out->seg_pos = h->st_pos.data();
+    out->seg_start = h->st_start.data(); out->seg_end = h->st_end.data(); out->seg_peak = h->st_peak.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
 void ev_default_bert_config(ev_bert_config* c) {
     memset(c, 0, sizeof *c);
@@ -2402,6 +2605,14 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
         if (!host_dst) return (int64_t)need;
         if (cap < need) return fail(h, "ev_get_stage(resample_taps): need %zu bytes, cap %zu", need, cap);
         if (hipMemcpy(host_dst, h->rs_tab, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(resample_taps): D2H failed");
+        return (int64_t)need;
+    }
+    if (!strcmp(name, "stitch_ramp")) {    // ev_stitch: the F floats of the ramp table of the last call
+        if (h->st_F < 0) return fail(h, "ev_get_stage(stitch_ramp): no ev_stitch call yet");
+        const size_t need = (size_t)h->st_F * 4;
+        if (!host_dst) return (int64_t)need;
+        if (cap < need) return fail(h, "ev_get_stage(stitch_ramp): need %zu bytes, cap %zu", need, cap);
+        if (need && hipMemcpy(host_dst, h->st_tab, need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage(stitch_ramp): D2H failed");
         return (int64_t)need;
     }
     if (!strcmp(name, "resample_raw")) {   // ev_resample (keep_stages): the untrimmed y of the last ev_resample, packed
@@ -2750,6 +2961,70 @@ int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int 
             if (hipGetLastError() != hipSuccess) rc = -1;
             if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
         }
+    }
+    (void)hipFree(lay);
+    return rc;
+}
+
+int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const int64_t* seg_lens, float trim_frac, float trim_abs, float* peak,
+                      int64_t* first, int64_t* last, void* stream) {
+    if (!wav || !seg_offsets || !seg_lens || !peak || !first || !last || S < 1 || S > 65535) return -2;
+    if (stitch_check_trim(nullptr, "ev_op_stitch_scan", trim_frac, trim_abs)) return -2;
+    std::vector<StitchSeg> segs((size_t)S);
+    int64_t n_part = 0, max_len = 0;
+    for (int s = 0; s < S; ++s) {
+        if (seg_offsets[s] < 0 || seg_lens[s] < 1) return -2;
+        segs[(size_t)s] = StitchSeg{seg_offsets[s], seg_lens[s], n_part};
+        n_part += (seg_lens[s] + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
+        max_len = std::max(max_len, seg_lens[s]);
+    }
+    const size_t sb = (size_t)S * sizeof(StitchSeg), cb = 2 * (size_t)S * sizeof(int64_t), pb = align_up((size_t)S * sizeof(float), 8), qb = (size_t)n_part * sizeof(float);
+    char* lay = nullptr;
+    if (hipMalloc((void**)&lay, sb + cb + pb + qb) != hipSuccess) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* d_cuts = (int64_t*)(lay + sb); float* d_peak = (float*)(lay + sb + cb); float* d_part = (float*)(lay + sb + cb + pb);
+    std::vector<int64_t> cuts(2 * (size_t)S);
+    int rc = hipMemcpy(lay, segs.data(), sb, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    if (rc == 0) {
+        launch_stitch_peak(wav, (const StitchSeg*)lay, S, max_len, d_part, s);
+        launch_stitch_edges(wav, (const StitchSeg*)lay, S, d_part, trim_frac, trim_abs, d_peak, d_cuts, s);
+        if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    }
+    if (rc == 0 && (hipMemcpy(cuts.data(), d_cuts, cb, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(peak, d_peak, (size_t)S * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
+    if (rc == 0) for (int i = 0; i < S; ++i) { first[i] = cuts[2 * (size_t)i]; last[i] = cuts[2 * (size_t)i + 1]; }
+    (void)hipFree(lay);
+    return rc;
+}
+int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl,
+                     const int32_t* fr, const float* tab, int F, int D, const int64_t* doc_lens, float* out, int16_t* out_i16, void* stream) {
+    if (!wav || !src || !n || !seg_doc || !pos || !fl || !fr || !doc_lens || !out || S < 1 || S > 65535) return -2;
+    if (F < 0 || F > EV_STITCH_MAX_FADE || (F > 0 && !tab) || seg_doc[0] != 0) return -2;
+    for (int s = 0; s < S; ++s) {
+        const bool head = s == 0 || seg_doc[s] != seg_doc[s - 1];
+        if (s > 0 && seg_doc[s] != seg_doc[s - 1] && seg_doc[s] != seg_doc[s - 1] + 1) return -2;
+        if (seg_doc[s] >= D || src[s] < 0 || n[s] < 0 || n[s] > EV_STITCH_MAX_DOC || pos[s] < 0) return -2;
+        if (doc_lens[seg_doc[s]] < 0 || doc_lens[seg_doc[s]] > EV_STITCH_MAX_DOC || pos[s] + n[s] > doc_lens[seg_doc[s]]) return -2;
+        if (fl[s] < 0 || fr[s] < 0 || fl[s] > std::min((int64_t)F, n[s]) || fr[s] > std::min((int64_t)F, n[s])) return -2;
+        if (!head && (pos[s] < pos[s - 1] || pos[s] + n[s] < pos[s - 1] + n[s - 1])) return -2;
+        if (!head && s >= 2 && seg_doc[s - 2] == seg_doc[s] && pos[s] < pos[s - 2] + n[s - 2]) return -2;
+    }
+    if (seg_doc[S - 1] + 1 != D) return -2;
+    std::vector<StitchMixSeg> ms; std::vector<StitchDoc> docs; std::vector<StitchTile> tiles; std::vector<int64_t> offs((size_t)D + 1);
+    stitch_tables(S, D, src, n, seg_doc, pos, fl, fr, doc_lens, ms, docs, tiles, offs.data());
+    const size_t mb = (size_t)S * sizeof(StitchMixSeg), db = (size_t)D * sizeof(StitchDoc), tb = tiles.size() * sizeof(StitchTile), fb = (size_t)F * sizeof(float);
+    char* lay = nullptr;
+    if (hipMalloc((void**)&lay, mb + db + tb + fb + 16) != hipSuccess) return -1;
+    int rc = 0;
+    if (hipMemcpy(lay, ms.data(), mb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(lay + mb, docs.data(), db, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (rc == 0 && tb && hipMemcpy(lay + mb + db, tiles.data(), tb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (rc == 0 && fb && hipMemcpy(lay + mb + db + tb, tab, fb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+    if (rc == 0) {
+        if (launch_stitch_mix(wav, (const StitchMixSeg*)lay, (const StitchDoc*)(lay + mb), (const StitchTile*)(lay + mb + db), (int64_t)tiles.size(),
+                              (const float*)(lay + mb + db + tb), F, out, out_i16, (hipStream_t)stream)) rc = -2;
+        else if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
     }
     (void)hipFree(lay);
     return rc;

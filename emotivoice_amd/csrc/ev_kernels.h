@@ -306,4 +306,18 @@ void launch_resample_copy(const void* wav, int wav_is_i16, int64_t total, float*
 void launch_trim_scan(const float* y, const ResampleSeq* seqs, int B, float frac, int64_t* cuts /* (2 B,): first, last */, hipStream_t s);
 void launch_trim_gather(const float* y, const TrimSeq* seqs, int B, int64_t max_len, int pad, float* out, hipStream_t s);
 
+// ev_stitch (ev_stitch.hip): segments -> documents.  The scan spreads a segment's peak over blocks of ST_PEAK_CHUNK samples and finds its edges in
+// chunks of ST_EDGE_CHUNK; the mix writes one tile of ST_TILE output samples per block with the ramp table (F <= ST_MAX_FADE floats) in LDS.
+constexpr int ST_PEAK_CHUNK = 4096, ST_EDGE_CHUNK = 1024, ST_TILE = 1024, ST_MAX_FADE = 4096;
+struct StitchSeg { int64_t off, len, part_off; };                  // first sample, length, index of the first of its ceil(len / ST_PEAK_CHUNK) partial peaks
+struct StitchMixSeg { int64_t src, pos; int32_t n, fl, fr, pad; }; // the cut wav[src .. src + n) starts at sample pos of its document; fade lengths left / right
+struct StitchDoc { int64_t out_off, len; int32_t seg0, nseg; };    // output offset / length, its run of segments
+struct StitchTile { int32_t doc, tile; };                          // one block: document and tile
+void launch_stitch_peak(const float* wav, const StitchSeg* segs, int S, int64_t max_len, float* part, hipStream_t s);
+void launch_stitch_edges(const float* wav, const StitchSeg* segs, int S, const float* part, float frac, float abs_thr, float* peak /* (S,) */,
+                         int64_t* cuts /* (2 S,): first, last, or -1, -1 */, hipStream_t s);
+// In one document pos and pos + n are non-decreasing, pos[s + 2] >= pos[s] + n[s], fl, fr <= min(F, n) and pos + n <= len (ev_stitch_plan gives that).
+int launch_stitch_mix(const float* wav, const StitchMixSeg* segs, const StitchDoc* docs, const StitchTile* tiles, int64_t n_tiles, const float* tab, int F,
+                      float* out, int16_t* out_i16 /* or NULL */, hipStream_t s);      // 0, or -1 for bad parameters
+
 }  // namespace ev

@@ -96,6 +96,7 @@ class EVEngine:
         self.last_pitch: Optional[_ffi.ev_pitch_result] = None
         self.resample_config = None                 # set by resample_setup()
         self.last_resample: Optional[_ffi.ev_resample_result] = None
+        self.last_stitch: Optional[_ffi.ev_stitch_result] = None
 
     # -- lifecycle
     def close(self):
@@ -392,6 +393,86 @@ class EVEngine:
         flat, is16, lens = pack_wavs(wavs, rc)
         return self.resample_to_numpy(self.resample_raw(len(wavs), flat.ctypes.data, is16, lens))
 
+    # -- long-form stitching (ev_stitch): the sentences of one batch -> finished documents on the device
+    def stitch_raw(self, S: int, wav_ptr: int, seg_offsets: np.ndarray, seg_lens: np.ndarray, seg_doc: np.ndarray, pause_after: np.ndarray,
+                   config=None, flags: int = 0) -> _ffi.ev_stitch_result:
+        """ev_stitch (include/evhip.h).  config: an emotivoice_amd.longform.StitchConfig, an _ffi.ev_stitch_config or None (the library's default:
+        plain concatenation).  wav_ptr is a device pointer with EV_FLAG_DEVICE_INPUTS; the four arrays are host arrays.  The returned struct's
+        device documents stay valid until the next stitch call on this engine."""
+        so, sl = np.ascontiguousarray(seg_offsets, np.int64), np.ascontiguousarray(seg_lens, np.int64)
+        sd, pa = np.ascontiguousarray(seg_doc, np.int32), np.ascontiguousarray(pause_after, np.int32)
+        if not (so.size == sl.size == sd.size == pa.size == S):
+            raise ValueError("seg_offsets / seg_lens / seg_doc / pause_after must have S = %d entries each" % S)
+        c = config.to_struct() if hasattr(config, "to_struct") else config
+        res = _ffi.ev_stitch_result()
+        res.struct_size = C.sizeof(_ffi.ev_stitch_result)
+        self._check(self._lib.ev_stitch(self._h, S, C.c_void_p(wav_ptr), so.ctypes.data_as(C.c_void_p), sl.ctypes.data_as(C.c_void_p),
+                                        sd.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p), C.byref(c) if c is not None else None, flags,
+                                        C.byref(res)))
+        self.last_stitch = res
+        return res
+
+    def stitch_to_numpy(self, res: _ffi.ev_stitch_result, int16_only: bool = False) -> Dict[str, object]:
+        """One D2H copy of the fp32 documents (or, with ``int16_only`` and a result that has them, of the int16 ones only; without it both) and
+        the host arrays of the result."""
+        D, S = res.batch_docs, res.batch_segs
+        lens = np.array([res.doc_lens[d] for d in range(D)], np.int64)
+        offs = np.array([res.doc_offsets[d] for d in range(D + 1)], np.int64)
+        out: Dict[str, object] = dict(doc_lens=lens, doc_offsets=offs,
+                                      seg_pos=np.array([res.seg_pos[s] for s in range(S)], np.int64),
+                                      seg_start=np.array([res.seg_start[s] for s in range(S)], np.int64),
+                                      seg_end=np.array([res.seg_end[s] for s in range(S)], np.int64),
+                                      seg_peak=np.array([res.seg_peak[s] for s in range(S)], np.float32))
+        if not (int16_only and res.wav_i16):
+            out["wav"] = self.d2h(res.wav, (res.total_samples,), np.float32)
+            out["docs"] = [out["wav"][offs[d]:offs[d + 1]] for d in range(D)]
+        if res.wav_i16:
+            out["wav_i16"] = self.d2h(res.wav_i16, (res.total_samples,), np.int16)
+            out["docs_i16"] = [out["wav_i16"][offs[d]:offs[d + 1]] for d in range(D)]
+        return out
+
+    def stitch(self, wavs: Sequence[np.ndarray], docs: Sequence[int], pauses: Sequence, **config) -> Dict[str, object]:
+        """Host waveforms -> documents.  wavs: one 1-D float array per segment; docs: the document of every segment (non-decreasing from 0);
+        pauses: one entry per segment, the pause after it as a class of emotivoice_amd.longform.pauses_ms, milliseconds (negative: a
+        cross-fade) or None; further keywords: the fields of emotivoice_amd.longform.StitchConfig.  Needs no weights."""
+        from .longform import StitchConfig, plan_document
+        sc = StitchConfig(**config).validate()
+        seg_doc, pause_after = plan_document(docs, pauses, sc.sample_rate)
+        lens = np.array([np.asarray(w).size for w in wavs], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in wavs]))
+        return self.stitch_to_numpy(self.stitch_raw(len(wavs), flat.ctypes.data, offs, lens, seg_doc, pause_after, sc))
+
+    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None) -> Dict[str, object]:
+        """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
+        dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
+        None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
+        documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
+        checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
+        config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's."""
+        from .longform import StitchConfig, flatten_documents, plan_document
+        sc = (config or StitchConfig()).validate()
+        if int(sc.sample_rate) != int(self.shapes.sr):
+            raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
+        utts, seg_doc, pauses = flatten_documents(documents)
+        S = len(utts)
+        if S > 65535:
+            raise ValueError("%d sentences exceed the 65535 segments of one ev_stitch call; split the documents over several calls" % S)
+        seg_doc, pause_after = plan_document(seg_doc, pauses, sc.sample_rate)
+        res, _ = self._synthesize_call(utts, alpha, 0, None, prosody)
+        up = self.shapes.upsample_factor
+        mel_offs = np.array([res.mel_offsets[b] for b in range(S + 1)], np.int64)
+        st = self.stitch_raw(S, res.wav, mel_offs[:-1] * up, np.diff(mel_offs) * up, seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16)
+        sr = float(sc.sample_rate)
+        start = out["seg_pos"] / sr
+        end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr
+        out["documents"] = out["docs_i16"] if sc.want_int16 else out["docs"]
+        out["seg_doc"] = seg_doc
+        out["sentence_times"] = [[(float(start[s]), float(end[s])) for s in np.nonzero(seg_doc == d)[0]] for d in range(st.batch_docs)]
+        out["sample_rate"] = int(sc.sample_rate)
+        return out
+
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)
         self._check(self._lib.ev_set_forced_durations(self._h, d.ctypes.data_as(C.c_void_p), d.size))
@@ -425,12 +506,8 @@ class EVEngine:
         return out
 
     # -- numpy convenience API
-    def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None) -> Dict[str, object]:
-        """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
-        reference builds per input line (inference_am_vocoder_joint.py:113-119).
-        prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
-        for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way."""
+    def _synthesize_call(self, utts: Sequence[dict], alpha: float, flags: int, forced_durations, prosody):
+        """The packing and the one ev_synthesize[_prosody] call of ``synthesize``: (ev_result, cu_seqlens)."""
         B = len(utts)
         packed = None
         if prosody is not None:
@@ -442,11 +519,6 @@ class EVEngine:
         spk = np.ascontiguousarray([int(u["speaker"]) for u in utts], np.int64)
         style = np.ascontiguousarray(np.stack([np.asarray(u["style"], np.float32) for u in utts]))
         content = np.ascontiguousarray(np.stack([np.asarray(u["content"], np.float32) for u in utts]))
-        flags = 0
-        if want_int16:
-            flags |= _ffi.EV_FLAG_WANT_INT16
-        if not vocoder:
-            flags |= _ffi.EV_FLAG_NO_VOCODER
         if forced_durations is not None:
             self.set_forced_durations(forced_durations)
             flags |= _ffi.EV_FLAG_FORCED_DURATIONS
@@ -455,6 +527,20 @@ class EVEngine:
         else:
             res = self.synthesize_prosody_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, alpha,
                                               packed, flags)
+        return res, cu
+
+    def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
+                   forced_durations: Optional[np.ndarray] = None, prosody=None) -> Dict[str, object]:
+        """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
+        reference builds per input line (inference_am_vocoder_joint.py:113-119).
+        prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
+        for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way."""
+        flags = 0
+        if want_int16:
+            flags |= _ffi.EV_FLAG_WANT_INT16
+        if not vocoder:
+            flags |= _ffi.EV_FLAG_NO_VOCODER
+        res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
         out = self.result_to_numpy(res, want_int16)
         out["cu_seqlens"] = cu
         return out

@@ -448,6 +448,79 @@ typedef struct ev_resample_result {
  * untrimmed y of the last call, packed at ceil(L_b up / down) each. */
 int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, uint32_t flags, ev_resample_result* out);
 
+/* Long-form stitching (ev_stitch): the waveforms of one synthesis batch -> finished documents on the device: every segment (sentence) cut at its
+ * edge silence, laid out with a pause or a cross-fade to its neighbour, ramped at its free ends, and written as fp32 and, when asked, as int16.
+ * The reference has no such stage ("Support longer text" is the open item of its roadmap); the arithmetic is the one specified here.
+ *   Inputs: S segments wav + seg_offsets[s] of seg_lens[s] >= 1 fp32 samples; seg_doc[s] non-decreasing from 0 in steps of at most 1 (the segments
+ *     of one document are consecutive); pause_after[s] in samples, ignored for the last segment of a document.
+ *   Cut: peak_s = max |x|, thr_s = max((float)peak_s * trim_frac as one fp32 product, trim_abs); first / last = the first and the LAST index with
+ *     |x| > thr_s; a_s = max(0, first - keep), b_s = min(L_s, last + 1 + keep), n_s = b_s - a_s.  The last sample above the threshold is KEPT: this
+ *     differs from ev_resample's trim, which restates the reference's slice y[start .. end) and drops it.  No sample above the threshold:
+ *     a_s = b_s = 0, an empty segment.  trim_frac == 0 && trim_abs == 0: no scan is launched, a_s = 0, b_s = L_s and seg_peak is 0.
+ *   Plan (host, int64; ev_stitch_plan).  For consecutive segments s, s + 1 of one document: ov_s = 0 if pause_after[s] >= 0 or either segment is
+ *     empty, else ov_s = min(-pause_after[s], F, n_s / 2, n_{s+1} / 2) (integer division); gap_s = max(pause_after[s], 0) when ov_s = 0, else 0.
+ *     pos_first = lead, pos_{s+1} = pos_s + n_s + gap_s - ov_s, doc_len = pos_last + n_last + tail.  Fade lengths per side: at a joint with
+ *     ov_s > 0, FR_s = FL_{s+1} = ov_s; elsewhere (the document's ends included) FL_s = FR_s = min(F, n_s / 2).  At most two segments cover any
+ *     output sample: pos_{s+2} = pos_s + n_s + (gap_s + gap_{s+1}) + (n_{s+1} - ov_s - ov_{s+1}) >= pos_s + n_s, since ov_s and ov_{s+1} are each
+ *     at most n_{s+1} / 2 rounded down.
+ *   Ramp table (ev_stitch_ramp): tab[i] = (float)(0.5 - 0.5 cos(pi (i + 0.5) / F)), i < F, in fp64, rounded once.  r(i, L) = tab[((2 i + 1) F) / (2 L)]
+ *     for i < L (int64 index), 1.0f for i >= L or L = 0.  With L = F the index is i, and tab[i] + tab[F - 1 - i] = 1 in exact arithmetic.
+ *   Output sample p of a document: every covering segment contributes c = x[a_s + i] * (r(i, FL_s) * r(n_s - 1 - i, FR_s)), i = p - pos_s, two
+ *     rounded fp32 products; out = c where one segment covers p, c_earlier + c_later (one rounded fp32 sum, no fma) where two do, +0.0 where none
+ *     does.  Where both ramps are 1 the source bits pass through.
+ *   int16 (want_i16): (int)(out * 32768.0f) truncated toward zero, then clamped to [-32768, 32767] -- a deliberate difference from
+ *     EV_FLAG_WANT_INT16's wrapping cast, because a cross-fade can exceed 1.
+ * No atomics and no floating sum split over threads: a document's bits are the same alone or anywhere in a batch and from host or device memory;
+ * the max and first / last index reductions are exact in any order.  Needs no weights. */
+#define EV_STITCH_MAX_FADE  4096            /* samples */
+#define EV_STITCH_MAX_PAUSE (1 << 24)       /* samples */
+#define EV_STITCH_MAX_DOC   (1 << 30)       /* samples per document */
+typedef struct ev_stitch_config {
+    uint32_t struct_size;          /* sizeof(ev_stitch_config); any other value is rejected */
+    float    trim_frac;            /* in [0, 1) */
+    float    trim_abs;             /* >= 0, finite; both zero = no cut */
+    int32_t  keep;                 /* samples kept on each side of the cut; >= 0 */
+    int32_t  fade;                 /* F, in [0, EV_STITCH_MAX_FADE] */
+    int32_t  lead, tail;           /* zeros before the first / after the last segment of every document; >= 0 */
+    int32_t  want_i16;             /* != 0: also the int16 documents */
+} ev_stitch_config;
+void ev_default_stitch_config(ev_stitch_config* cfg);      /* no trim, keep 0, fade 0, lead = tail = 0, fp32 only: plain concatenation */
+/* Host only, no device touched.  ev_stitch_ramp writes tab[0 .. F) and returns F, or -1 for F outside [0, EV_STITCH_MAX_FADE].  ev_stitch_plan
+ * takes the cut lengths n[s] >= 0 and writes pos, fl, fr (S each) and doc_lens (one per document); it returns the number of documents, or -1 with
+ * a message naming the field or segment (ev_last_error(NULL)) for what ev_stitch rejects in cfg, seg_doc, pause_after, S, a negative n[s] or a
+ * document longer than EV_STITCH_MAX_DOC.  ev_stitch plans with this function. */
+int ev_stitch_ramp(int F, float* tab);
+int ev_stitch_plan(int S, const int64_t* n, const int32_t* seg_doc, const int32_t* pause_after, const ev_stitch_config* cfg, int64_t* pos, int32_t* fl,
+                   int32_t* fr, int64_t* doc_lens);
+
+typedef struct ev_stitch_result {
+    uint32_t struct_size;          /* sizeof(ev_stitch_result), set by the caller; any other value is rejected */
+    int32_t  batch_docs;
+    int32_t  batch_segs;
+    int32_t  reserved;
+    int64_t  total_samples;
+    const float*   wav;            /* DEVICE, the documents back to back */
+    const int16_t* wav_i16;        /* DEVICE, the same layout, or NULL without want_i16 */
+    const int64_t* doc_lens;       /* (batch_docs,)     HOST */
+    const int64_t* doc_offsets;    /* (batch_docs + 1,) HOST */
+    const int64_t* seg_pos;        /* (batch_segs,) HOST: the cut segment's first sample inside its document */
+    const int64_t* seg_start;      /* (batch_segs,) HOST: a_s, an index into the segment */
+    const int64_t* seg_end;        /* (batch_segs,) HOST: b_s */
+    const float*   seg_peak;       /* (batch_segs,) HOST: max |x| of the whole segment; 0 when no scan was launched */
+} ev_stitch_result;
+/* wav: a device pointer with EV_FLAG_DEVICE_INPUTS (the other flags are ignored); seg_offsets, seg_lens, seg_doc and pause_after are always HOST
+ * arrays, so an ev_result.wav with seg_offsets = mel_offsets * 256 goes straight in.  cfg NULL = ev_default_stitch_config.  Rejected before anything
+ * is launched (message naming the field or segment; the previous result stays valid): a wrong struct_size of cfg or out, S outside [1, 65535],
+ * seg_offsets[s] < 0, seg_lens[s] < 1, a seg_doc that does not start at 0, decreases or skips, fade outside [0, EV_STITCH_MAX_FADE], a negative
+ * keep / lead / tail, pause_after[s] outside [-EV_STITCH_MAX_FADE, EV_STITCH_MAX_PAUSE], a non-finite or negative trim_frac / trim_abs, trim_frac
+ * >= 1, and a document longer than EV_STITCH_MAX_DOC samples -- judged before the cut, as lead + tail + its segments + its positive pauses.  The
+ * cuts come back to the host between the scan and the mix (one synchronisation, as ev_resample's trim).  The result lives in a workspace of its
+ * own and is complete when the call returns; it stays valid across ev_synthesize[_prosody] / ev_vocoder / ev_align / ev_features / ev_pitch /
+ * ev_resample until the next ev_stitch or ev_destroy -- the contract of ev_features_result.  ev_get_stage("stitch_ramp") returns the F floats of
+ * the ramp table of the last ev_stitch. */
+int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets, const int64_t* seg_lens, const int32_t* seg_doc,
+              const int32_t* pause_after, const ev_stitch_config* cfg, uint32_t flags, ev_stitch_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 

@@ -220,6 +220,19 @@ int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
 int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int trim_pad, float* out, int64_t* out_lens, int64_t* trim_start,
                int64_t* trim_end, void* hip_stream);
 
+/* ev_stitch's kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_stitch).  ev_op_stitch_scan: the two scan kernels on the S
+ * segments wav + seg_offsets[s] of seg_lens[s] samples -> the HOST arrays peak, first, last (S each): max |x|, and the first / last index with
+ * |x| > max(peak * trim_frac, trim_abs), or -1, -1 where no sample is.  ev_op_stitch_mix: the mix kernel on segments that are already cut and
+ * planned: segment s is wav[src[s] .. src[s] + n[s]) at sample pos[s] of document seg_doc[s] with fade lengths fl[s] / fr[s]; tab = the F ramp
+ * values; the D documents of doc_lens samples go to out (and out_i16 unless NULL) back to back.  Every array but wav / out / out_i16 is a HOST
+ * array; the calls wait for the stream.  -2 for what ev_stitch rejects and, for ev_op_stitch_mix, a layout the kernel would mishandle: n[s]
+ * outside [0, 2^30], fl / fr outside [0, min(F, n[s])], pos or pos + n decreasing inside a document, pos[s + 2] < pos[s] + n[s], a segment that
+ * leaves its document, D not seg_doc's count of documents. */
+int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const int64_t* seg_lens, float trim_frac, float trim_abs, float* peak,
+                      int64_t* first, int64_t* last, void* hip_stream);
+int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl,
+                     const int32_t* fr, const float* tab, int F, int D, const int64_t* doc_lens, float* out, int16_t* out_i16, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
