@@ -72,7 +72,9 @@ size_t ev_op_mx_scratch_bytes(int M, int K);
 /* Fused HiFi-GAN ResBlock1 pair for C = 32: xt = lrelu(c1(lrelu(x)) + b1); out = epi(c2(xt) + b2 + x)
  * (reference models/hifigan/models.py:50-57).  `epi` uses the ev_conv_gemm_desc fields bias (= b2), res (= x), res_dtype,
  * ldres, row_valid, valid_shift, out_scale, acc32, ldacc, add16_a, add16_b, ldadd (acc32 and add16 are mutually exclusive here),
- * post_lrelu, post_slope (in [0, 1]), out16, out32, ldo, out32_before_post. */
+ * post_lrelu, post_slope (in [0, 1]), out16, out32, ldo, out32_before_post.
+ * Kernel variant: a k = 3 call with ntiles = ceil(M / 254) >= 4 x the device's CU count takes the two-blocks-per-CU kernel (grid 2 x CUs), every other call the
+ * one-block kernel (grid min(ntiles, CUs)); epi.reserved0 bit 2 (4) selects the one-block kernel for every call.  Both give the same bits. */
 typedef struct ev_res_pair_desc {
     const void* x; int ldx;
     const void* w1; const float* b1;
@@ -85,7 +87,10 @@ typedef struct ev_res_pair_desc {
 int ev_op_resblock_pair_c32(const ev_res_pair_desc* d, void* hip_stream);
 /* The same pair in the MX arithmetic (one fp16 MFMA + two block-scaled fp4 MFMAs per product): x and out32 fp32 [rows][32], w1 / w2 the
  * fp16 hi parts of the weights, w1_mx / w2_mx their fp4 planes; epi: bias, res (= x, fp32), row_valid, out_scale, acc32 (optional, may
- * alias out32), out32, ldo. */
+ * alias out32), out32, ldo.
+ * Kernel variant, by epi.reserved0: 0 = the rule on the layer's shape (the E5M2-operand kernel at k = 3, the fp4 kernel at k = 7 / 11); bit 5 (32) = the E5M2 kernel
+ * at every k; bit 4 (16) = the fp4 kernel at every k (it wins over bit 5); bit 2 (4), fp4 only = the lock-step kernel (256-row tiles) instead of the two-group one
+ * (128-row tiles, taken from two tiles on) -- the two fp4 kernels give the same bits, the E5M2 kernel different ones. */
 int ev_op_resblock_pair_c32_mx(const ev_res_pair_desc* d, void* hip_stream);
 /* The pair at C = 64, k = 3 in the MX arithmetic with plane sets in and out: x = the fp16 hi plane [rows][64] of the plane set of leaky_relu(x, 1 / res_inv_slope),
  * epi.mx_x4 / mx_xs / mx_xs_stride its code / scale planes; w1 / w2 fp16 hi parts [64][3][64], w1_mx / w2_mx = mxfp4.pack_c64_weight_planes; epi: bias (= b2),
