@@ -217,6 +217,7 @@ SIGNATURES = {
     "ev_style_load_weights": (C.c_int, [_P, C.POINTER(ev_bert_config), _P, C.c_size_t]),
     "ev_style_embed": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint32, _P]),
     "ev_op_conv_gemm": (C.c_int, [C.POINTER(ev_conv_gemm_desc), _P]),
+    "ev_op_conv_gemm_group3": (C.c_int, [C.POINTER(ev_conv_gemm_desc), C.c_int, _P]),
     "ev_op_mx_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ev_op_resblock_pair_c32": (C.c_int, [C.POINTER(ev_res_pair_desc), _P]),
     "ev_op_resblock_pair_c64": (C.c_int, [C.POINTER(ev_res_pair_desc), _P]),

@@ -2657,18 +2657,33 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
 }
 
 // ------------------------------------------------------------------- per-kernel test entry points (include/evhip_ops.h)
+// what ev_op_conv_gemm and ev_op_conv_gemm_group3 refuse (-2) before any launcher sees the descriptor
+static bool op_conv_gemm_desc_ok(const ConvGemmParams& p) {
+    const int es = p.dtype == DT_F16 ? 2 : 4;
+    if (p.M % ROW_ALIGN || p.N % 32 || (p.K * es) % 64 || (p.taps - 1) * p.dil > 64) return false;
+    if (p.dtype == DT_F32S && (p.K % 32 || !p.W_lo)) return false;
+    if (p.dtype == DT_MX && (p.K % 32 || !p.W)) return false;
+    if (mx_check(p) || splitk_check(p)) return false;
+    if (!p.out16 && !p.out32 && !p.mxo_h) return false;
+    if (p.pro_lrelu && !(p.pro_slope >= 0.f && p.pro_slope <= 1.f)) return false;
+    return true;
+}
 int ev_op_conv_gemm(const ev_conv_gemm_desc* d, void* stream) {
     static_assert(sizeof(ev_conv_gemm_desc) == sizeof(ConvGemmParams), "descriptor layout must match ConvGemmParams");
     ConvGemmParams p;
     memcpy(&p, d, sizeof p);
-    const int es = p.dtype == DT_F16 ? 2 : 4;
-    if (p.M % ROW_ALIGN || p.N % 32 || (p.K * es) % 64 || (p.taps - 1) * p.dil > 64) return -2;
-    if (p.dtype == DT_F32S && (p.K % 32 || !p.W_lo)) return -2;
-    if (p.dtype == DT_MX && (p.K % 32 || !p.W)) return -2;
-    if (mx_check(p) || splitk_check(p)) return -2;
-    if (!p.out16 && !p.out32 && !p.mxo_h) return -2;
-    if (p.pro_lrelu && !(p.pro_slope >= 0.f && p.pro_slope <= 1.f)) return -2;
+    if (!op_conv_gemm_desc_ok(p)) return -2;
     launch_conv_gemm(p, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// three descriptors as ONE grouped grid (launch_conv_gemm_group3): 0 = launched (check_only: would be), -1 = not a triple the grouped kernel takes (nothing launched)
+int ev_op_conv_gemm_group3(const ev_conv_gemm_desc* d3, int check_only, void* stream) {
+    ConvGemmParams ps[3];
+    memcpy(ps, d3, sizeof ps);
+    for (int i = 0; i < 3; ++i)
+        if (!op_conv_gemm_desc_ok(ps[i])) return -2;
+    if (launch_conv_gemm_group3(ps, (hipStream_t)stream, check_only != 0)) return -1;
+    if (check_only) return 0;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 size_t ev_op_mx_scratch_bytes(int M, int K) { return mx_scratch_bytes(M, K); }

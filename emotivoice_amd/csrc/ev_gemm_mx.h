@@ -603,6 +603,7 @@ int launch_conv_gemm_group3(const ConvGemmParams* ps, hipStream_t s, bool check_
     if (e != mx_epi_variant(ps[1]) || e != mx_epi_variant(ps[2])) return -1;
     if (e != EPI_MXP && e != (EPI_RESPL | EPI_LEAN | EPI_MXP)) return -1;
     if (check_only) return 0;
+    (void)device_cus();          // per-device large-LDS opt-in for the per-kernel entry point that runs without a handle (as launch_conv_gemm)
     ConvGemmGroup3 g;
     for (int i = 0; i < 3; ++i) g.p[i] = ps[order[i]];
     const int tiles = (ps[0].M / PH_BM) * (ps[0].N / 128), padded = (tiles + 7) & ~7;

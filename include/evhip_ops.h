@@ -1,6 +1,6 @@
 /*
- * evhip_ops.h -- per-kernel entry points of libevhip.so used by the parity tests (tests/test_gpu_ops.py).
- * They launch one gfx950 kernel on caller-provided DEVICE pointers and are not needed by an integrator;
+ * evhip_ops.h -- per-kernel entry points of libevhip.so used by the parity tests (tests/test_gpu_ops.py, test_gpu_pair_long.py,
+ * test_gpu_group3.py).  They launch one gfx950 kernel on caller-provided DEVICE pointers and are not needed by an integrator;
  * the drop-in boundary is include/evhip.h.  Each op cites the reference op it is checked against.
  */
 #ifndef EVHIP_OPS_H_
@@ -66,6 +66,13 @@ typedef struct ev_conv_gemm_desc {
 } ev_conv_gemm_desc;
 
 int ev_op_conv_gemm(const ev_conv_gemm_desc* d, void* hip_stream);
+/* Three independent dtype-3 convs as ONE grid (conv_gemm_mx_group3_kernel, emotivoice_amd/csrc/ev_gemm_mx.h): what the engine issues for the same-level convs of
+ * a stage's three ResBlocks.  d3 = three descriptors with taps {3, 7, 11} in any order, plane sets in, the same M / N / K (M % 256 == 0, N % 128 == 0,
+ * K % 128 == 0) and the same epilogue form, one of two: planes only (conv1 of a pair), or residual from a plane set + planes only (conv2 inside a ResBlock);
+ * no acc32, no out32, reserved0 == 0.  Returns -2 if a member fails the descriptor checks of the single launch, -1 if the three are not such a triple (nothing is
+ * launched: the caller issues them one by one) or the launch failed, 0 otherwise; check_only != 0 answers without launching.  Checked against the three single
+ * launches of the same descriptors, bit for bit (tests/test_gpu_group3.py). */
+int ev_op_conv_gemm_group3(const ev_conv_gemm_desc* d3, int check_only, void* hip_stream);
 /* scratch bytes a dtype-3 call with an [M][K] activation needs (fp16 hi plane, two fp4 code planes, two E8M0 scale planes) */
 size_t ev_op_mx_scratch_bytes(int M, int K);
 
