@@ -133,6 +133,19 @@ class ev_stitch_result(C.Structure):
     ]
 
 
+EV_COMPARE_CHUNK, EV_COMPARE_FLOOR = 4096, 1e-60
+
+
+class ev_compare_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64),
+        ("sum_d", C.POINTER(C.c_double)), ("sum_d2", C.POINTER(C.c_double)), ("sum_y", C.POINTER(C.c_double)), ("sum_y2", C.POINTER(C.c_double)),
+        ("rel_l2", C.POINTER(C.c_double)), ("rel_l2_ac", C.POINTER(C.c_double)), ("max_abs_d", C.POINTER(C.c_float)),
+        ("argmax_d", C.POINTER(C.c_int64)), ("peak_y", C.POINTER(C.c_float)), ("nonfinite", C.POINTER(C.c_int64)),
+        ("chunk_d2", C.POINTER(C.c_double)), ("chunk_y2", C.POINTER(C.c_double)), ("chunk_offsets", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -203,6 +216,8 @@ SIGNATURES = {
     # n, seg_doc, pause_after in; pos, fl, fr, doc_lens out: HOST arrays
     "ev_stitch_plan": (C.c_int, [C.c_int, _P, _P, _P, C.POINTER(ev_stitch_config), _P, _P, _P, _P]),
     "ev_stitch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(ev_stitch_config), C.c_uint32, C.POINTER(ev_stitch_result)]),
+    # lens is a HOST array; a and b are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
+    "ev_compare": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint32, C.POINTER(ev_compare_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

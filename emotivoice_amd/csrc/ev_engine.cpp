@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise)
+    char* arena[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise), [8] ev_compare (scratch only: its result is host memory)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -104,6 +104,9 @@ struct ev_handle {
     // ev_stitch: the ramp table of the last call (device, EV_STITCH_MAX_FADE floats once allocated; its host copy feeds the upload) and the host halves of its result
     float* st_tab = nullptr; int st_F = -1; std::vector<float> st_tab_host;
     std::vector<int64_t> st_doc_lens, st_doc_offs, st_pos, st_start, st_end; std::vector<float> st_peak;
+    // ev_compare: its result, all of it host memory
+    std::vector<double> cmp_d, cmp_d2, cmp_y, cmp_y2, cmp_rel, cmp_rel_ac, cmp_chunk_d2, cmp_chunk_y2;
+    std::vector<float> cmp_max_d, cmp_peak_y; std::vector<int64_t> cmp_arg, cmp_nonf, cmp_chunk_offs;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1116,7 +1119,7 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 8; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 9; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->rs_tab) (void)hipFree(h->rs_tab);
     if (h->st_tab) (void)hipFree(h->st_tab);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
@@ -2448,6 +2451,97 @@ int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets,
     out->struct_size = sz; out->batch_docs = D; out->batch_segs = S; out->total_samples = total; out->wav = d_out; out->wav_i16 = i16 ? d_i16 : nullptr;
     out->doc_lens = h->st_doc_lens.data(); out->doc_offsets = h->st_doc_offs.data(); out->seg_pos = h->st_pos.data();
     out->seg_start = h->st_start.data(); out->seg_end = h->st_end.data(); out->seg_peak = h->st_peak.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- signal comparison (include/evhip.h: ev_compare)
+static_assert(EV_COMPARE_CHUNK == CMP_CHUNK, "include/evhip.h states the chunk of ev_compare.hip");
+int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_t* lens, uint32_t flags, ev_compare_result* out) {
+    if (!h) return -1;
+    if (!a) return fail(h, "ev_compare: a is NULL");
+    if (!b) return fail(h, "ev_compare: b is NULL");
+    if (!lens) return fail(h, "ev_compare: lens is NULL");
+    if (!out) return fail(h, "ev_compare: out is NULL");
+    if (out->struct_size != sizeof(ev_compare_result))
+        return fail(h, "ev_compare: out->struct_size %u != sizeof(ev_compare_result) %zu", out->struct_size, sizeof(ev_compare_result));
+    if (B < 1 || B > 65535) return fail(h, "ev_compare: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    std::vector<int64_t> coffs((size_t)B + 1, 0);
+    int64_t total = 0;
+    for (int s = 0; s < B; ++s) {      // the chunk table's size is judged before it is built
+        if (lens[s] < 1) return fail(h, "ev_compare: lens[%d] = %lld < 1", s, (long long)lens[s]);
+        if (lens[s] > (int64_t)INT_MAX * CMP_CHUNK || coffs[(size_t)s] + (lens[s] + CMP_CHUNK - 1) / CMP_CHUNK > INT_MAX)
+            return fail(h, "ev_compare: lens[%d] = %lld: more than %d chunks of %d elements in one call", s, (long long)lens[s], INT_MAX, CMP_CHUNK);
+        coffs[(size_t)s + 1] = coffs[(size_t)s] + (lens[s] + CMP_CHUNK - 1) / CMP_CHUNK;
+        total += lens[s];
+    }
+    const int64_t NC = coffs[(size_t)B];
+    std::vector<CompareChunk> chunks;
+    chunks.reserve((size_t)NC);
+    for (int64_t s = 0, off = 0; s < B; off += lens[s], ++s)
+        for (int64_t i = 0; i < lens[s]; i += CMP_CHUNK) chunks.push_back(CompareChunk{off + i, (int32_t)std::min<int64_t>(CMP_CHUNK, lens[s] - i), 0});
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    float *d_a = nullptr, *d_b = nullptr; CompareChunk* d_chunks = nullptr; int64_t* d_coffs = nullptr; double *d_sums = nullptr, *d_maxd = nullptr;
+    int32_t *d_argd = nullptr, *d_nonf = nullptr; float* d_peak = nullptr; CompareSeg* d_seg = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 8, pass == 0};
+        if (pass == 1 && arena_reserve(h, 8, need)) return -1;
+        if (!dev_in) { d_a = ap.arr<float>((size_t)total); d_b = ap.arr<float>((size_t)total); }
+        d_chunks = ap.arr<CompareChunk>((size_t)NC); d_coffs = ap.arr<int64_t>((size_t)B + 1);
+        d_sums = ap.arr<double>(4 * (size_t)NC); d_maxd = ap.arr<double>((size_t)NC);
+        d_argd = ap.arr<int32_t>((size_t)NC); d_nonf = ap.arr<int32_t>((size_t)NC); d_peak = ap.arr<float>((size_t)NC);
+        d_seg = ap.arr<CompareSeg>((size_t)B);
+        need = ap.off;
+    }
+    if (!dev_in) {
+        HIPCHK(h, hipMemcpyAsync(d_a, a, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_b, b, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(d_chunks, chunks.data(), (size_t)NC * sizeof(CompareChunk), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_coffs, coffs.data(), ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    region_begin(h, "total");
+    {
+        KScope ks(h, "compare_chunks", 8.0 * (double)total, 8.0 * (double)total + 64.0 * (double)NC);
+        if (launch_compare_chunks(dev_in ? a : d_a, dev_in ? b : d_b, d_chunks, NC, d_sums, d_maxd, d_argd, d_peak, d_nonf, h->stream))
+            return fail(h, "ev_compare: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "compare_finish", 4.0 * (double)NC, 52.0 * (double)NC + (double)B * sizeof(CompareSeg));
+        launch_compare_finish(B, d_coffs, d_sums, NC, d_maxd, d_argd, d_peak, d_nonf, d_seg, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    std::vector<CompareSeg> seg((size_t)B);
+    std::vector<double> cd2((size_t)NC), cy2((size_t)NC);
+    HIPCHK(h, hipMemcpyAsync(seg.data(), d_seg, (size_t)B * sizeof(CompareSeg), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cd2.data(), d_sums + NC, (size_t)NC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cy2.data(), d_sums + 3 * NC, (size_t)NC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    // from here on nothing fails: the previous result is replaced
+    const size_t nb = (size_t)B;
+    h->cmp_d.resize(nb); h->cmp_d2.resize(nb); h->cmp_y.resize(nb); h->cmp_y2.resize(nb); h->cmp_rel.resize(nb); h->cmp_rel_ac.resize(nb);
+    h->cmp_max_d.resize(nb); h->cmp_peak_y.resize(nb); h->cmp_arg.resize(nb); h->cmp_nonf.resize(nb);
+    for (size_t s = 0; s < nb; ++s) {
+        const CompareSeg& g = seg[s];
+        const double n = (double)lens[s], num = sqrt(g.sum[1]);
+        const double var = g.sum[3] - (g.sum[2] * g.sum[2]) / n;      // the quotient sits between the product and the difference: nothing to fuse
+        h->cmp_d[s] = g.sum[0]; h->cmp_d2[s] = g.sum[1]; h->cmp_y[s] = g.sum[2]; h->cmp_y2[s] = g.sum[3];
+        h->cmp_rel[s] = num / sqrt(std::max(g.sum[3], EV_COMPARE_FLOOR));
+        h->cmp_rel_ac[s] = num / sqrt(std::max(var, EV_COMPARE_FLOOR));
+        h->cmp_max_d[s] = (float)g.max_d; h->cmp_peak_y[s] = g.peak_y; h->cmp_arg[s] = g.arg; h->cmp_nonf[s] = g.nonfinite;
+    }
+    h->cmp_chunk_d2.swap(cd2); h->cmp_chunk_y2.swap(cy2); h->cmp_chunk_offs.swap(coffs);
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total = total;
+    out->sum_d = h->cmp_d.data(); out->sum_d2 = h->cmp_d2.data(); out->sum_y = h->cmp_y.data(); out->sum_y2 = h->cmp_y2.data();
+    out->rel_l2 = h->cmp_rel.data(); out->rel_l2_ac = h->cmp_rel_ac.data(); out->max_abs_d = h->cmp_max_d.data(); out->argmax_d = h->cmp_arg.data();
+    out->peak_y = h->cmp_peak_y.data(); out->nonfinite = h->cmp_nonf.data();
+    out->chunk_d2 = h->cmp_chunk_d2.data(); out->chunk_y2 = h->cmp_chunk_y2.data(); out->chunk_offsets = h->cmp_chunk_offs.data();
     return 0;
 }
 

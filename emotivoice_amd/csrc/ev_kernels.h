@@ -320,4 +320,14 @@ void launch_stitch_edges(const float* wav, const StitchSeg* segs, int S, const f
 int launch_stitch_mix(const float* wav, const StitchMixSeg* segs, const StitchDoc* docs, const StitchTile* tiles, int64_t n_tiles, const float* tab, int F,
                       float* out, int16_t* out_i16 /* or NULL */, hipStream_t s);      // 0, or -1 for bad parameters
 
+// ev_compare (ev_compare.hip): two packed signals -> per-segment fp64 sums and maxima.  One block per chunk of CMP_CHUNK elements of one segment;
+// the chunk results land in per-chunk arrays (`sums`: four planes of n_chunks -- d, d^2, y, y^2) and a second kernel folds a segment's chunks in order.
+constexpr int CMP_CHUNK = 4096;
+struct CompareChunk { int64_t off; int32_t n, pad; };              // first element in the packed signals, its 1 .. CMP_CHUNK elements
+struct CompareSeg { double sum[4]; double max_d; int64_t arg, nonfinite; float peak_y; int32_t pad; };
+int launch_compare_chunks(const float* a, const float* b, const CompareChunk* chunks, int64_t n_chunks, double* sums, double* maxd, int32_t* argd,
+                          float* peak, int32_t* nonf, hipStream_t s);      // 0, or -1 for a grid that does not exist
+void launch_compare_finish(int B, const int64_t* chunk_offs /* (B + 1,) */, const double* sums, int64_t n_chunks, const double* maxd, const int32_t* argd,
+                           const float* peak, const int32_t* nonf, CompareSeg* out /* (B,) */, hipStream_t s);
+
 }  // namespace ev

@@ -97,6 +97,7 @@ class EVEngine:
         self.resample_config = None                 # set by resample_setup()
         self.last_resample: Optional[_ffi.ev_resample_result] = None
         self.last_stitch: Optional[_ffi.ev_stitch_result] = None
+        self.last_compare: Optional[_ffi.ev_compare_result] = None
 
     # -- lifecycle
     def close(self):
@@ -472,6 +473,48 @@ class EVEngine:
         out["sentence_times"] = [[(float(start[s]), float(end[s])) for s in np.nonzero(seg_doc == d)[0]] for d in range(st.batch_docs)]
         out["sample_rate"] = int(sc.sample_rate)
         return out
+
+    # -- signal comparison (ev_compare): how far a signal lies from a yardstick, per segment, on the device
+    def compare_raw(self, B: int, a_ptr: int, b_ptr: int, lens: np.ndarray, flags: int = 0) -> _ffi.ev_compare_result:
+        """ev_compare (include/evhip.h).  a_ptr (under test) and b_ptr (the yardstick) are host pointers, or device pointers with
+        EV_FLAG_DEVICE_INPUTS -- of this engine or of another one on the same device; lens is a host array.  The returned struct's arrays
+        are host memory and stay valid until the next compare call on this engine."""
+        ln = np.ascontiguousarray(lens, np.int64)
+        if ln.size != B:
+            raise ValueError("lens must have B = %d entries" % B)
+        res = _ffi.ev_compare_result()
+        res.struct_size = C.sizeof(_ffi.ev_compare_result)
+        self._check(self._lib.ev_compare(self._h, B, C.c_void_p(a_ptr), C.c_void_p(b_ptr), ln.ctypes.data_as(C.c_void_p), flags, C.byref(res)))
+        self.last_compare = res
+        return res
+
+    def compare_to_numpy(self, res: _ffi.ev_compare_result) -> Dict[str, object]:
+        """Copies of the result's host arrays (they outlive the next compare call)."""
+        B = res.batch
+        out: Dict[str, object] = dict(batch=B, total=int(res.total))
+        for k, dt in (("sum_d", np.float64), ("sum_d2", np.float64), ("sum_y", np.float64), ("sum_y2", np.float64), ("rel_l2", np.float64),
+                      ("rel_l2_ac", np.float64), ("max_abs_d", np.float32), ("argmax_d", np.int64), ("peak_y", np.float32), ("nonfinite", np.int64)):
+            out[k] = np.ctypeslib.as_array(getattr(res, k), (B,)).astype(dt, copy=True)
+        offs = np.ctypeslib.as_array(res.chunk_offsets, (B + 1,)).astype(np.int64, copy=True)
+        out["chunk_offsets"] = offs
+        out["chunk_d2"] = np.ctypeslib.as_array(res.chunk_d2, (int(offs[-1]),)).astype(np.float64, copy=True)
+        out["chunk_y2"] = np.ctypeslib.as_array(res.chunk_y2, (int(offs[-1]),)).astype(np.float64, copy=True)
+        return out
+
+    def compare(self, a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray]) -> Dict[str, object]:
+        """Host signals: a_list (under test) against b_list (the yardstick), one array per segment, equal sizes pairwise (any shape: a mel is
+        compared flattened).  Returns per-segment numpy arrays: sum_d, sum_d2, sum_y, sum_y2, rel_l2, rel_l2_ac (the mean of the yardstick
+        removed), max_abs_d, argmax_d, peak_y, nonfinite, and chunk_d2 / chunk_y2 / chunk_offsets (the sums of every 4096-element chunk).
+        Needs no weights."""
+        if len(a_list) != len(b_list) or not len(a_list):
+            raise ValueError("a_list and b_list must hold the same number (>= 1) of segments")
+        lens = np.array([np.asarray(x).size for x in a_list], np.int64)
+        for s, y in enumerate(b_list):
+            if np.asarray(y).size != lens[s]:
+                raise ValueError("segment %d: a has %d elements, b has %d" % (s, lens[s], np.asarray(y).size))
+        fa = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in a_list]))
+        fb = np.ascontiguousarray(np.concatenate([np.asarray(y, np.float32).reshape(-1) for y in b_list]))
+        return self.compare_to_numpy(self.compare_raw(len(a_list), fa.ctypes.data, fb.ctypes.data, lens))
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)

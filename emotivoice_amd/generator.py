@@ -49,11 +49,14 @@ class JETSGeneratorHIP:
         self.segment_size = self.shapes.segment_size
         self.upsample_factor = self.shapes.upsample_factor
         self._precision, self._dec_prec, self._voc_prec = precision, decoder_precision, vocoder_precision
+        self._requested = (precision, decoder_precision, vocoder_precision)      # a verified load may move the three above to another rung
         self._keep, self._pe_len = keep_stages, pe_len
         self._device_id: Optional[int] = None
         self._engine: Optional[EVEngine] = None
         self._blob = None
         self._stream_ptr = 0            # 0 = the engine's own stream
+        self._engine_kwargs: dict = {}  # EVEngine switches of the rung a verified load chose (load_state_dict(verify=...)); empty otherwise
+        self.precision_report = None    # the PrecisionReport of the last verified load
         self.training = False
 
     def close(self):
@@ -91,28 +94,70 @@ class JETSGeneratorHIP:
     def _ensure_engine(self):
         if self._engine is None:
             self._engine = EVEngine(self.shapes, self._device_id or 0, decoder_precision=self._dec_prec, keep_stages=self._keep,
-                                    vocoder_precision=self._voc_prec, precision=self._precision)
+                                    vocoder_precision=self._voc_prec, precision=self._precision, **self._engine_kwargs)
             self._stream_ptr = 0
             if self._blob is not None:
                 self._engine.load_blob(*self._blob)
         return self._engine
 
-    def load_state_dict(self, state_dict, strict: bool = True):
+    def load_state_dict(self, state_dict, strict: bool = True, verify=None):
         """Accepts ``ckpt['generator']`` (422 tensors, ``am.*`` / ``generator.*``; torch>=2.1 parametrization keys or the
-        legacy weight_g / weight_v keys).  strict=True mirrors torch: a missing tensor raises KeyError."""
+        legacy weight_g / weight_v keys).  strict=True mirrors torch: a missing tensor raises KeyError.
+        verify: None = load only.  True, or a dict of precision_guard.choose_precision keyword arguments (probe, bar, guard, ladder): after
+        packing, an object that runs "mx" measures its waveform against a strict engine on the device and moves to the cheapest rung of
+        the ladder that holds the bar (one warning when that is not the first); the report stays in ``precision_report``.  "fast" and
+        "strict" objects are explicit opt-ins and load as without it.  Needs the device at load time.  The rung and the report belong to
+        the weights they were measured on: a later load without ``verify`` (or ``load_packed``) returns the object to the precision it was
+        constructed with and clears ``precision_report``."""
         if strict:
             known = ("am.", "generator.", "module.am.", "module.generator.")
             bad = [k for k in state_dict if not k.startswith(known)]
             if bad:
                 raise RuntimeError("Unexpected key(s) in state_dict: " + ", ".join(bad[:5]))
         self._blob = pack_state_dict(state_dict, self.shapes, self._pe_len)
-        if self._engine is not None:
+        if verify is None or verify is False:
+            moved = self._move_to(self._requested, {})
+            self.precision_report = None
+        else:
+            moved = self._verify_precision({} if verify is True else dict(verify))
+        if self._engine is not None and not moved:      # an engine rebuilt on another rung has loaded the blob already
             self._engine.load_blob(*self._blob)
         return self
 
+    def _move_to(self, precisions, engine_kwargs) -> bool:
+        """Puts the object on (precision, decoder_precision, vocoder_precision) + EVEngine switches; True when that replaced a live engine
+        (the new one has loaded the blob).  Its stream is the engine's own again until the next forward with device tensors attaches torch's."""
+        from .engine import resolve_precision
+        if resolve_precision(*precisions) == resolve_precision(self._precision, self._dec_prec, self._voc_prec) and engine_kwargs == self._engine_kwargs:
+            return False
+        had_engine = self._engine is not None
+        self.close()
+        (self._precision, self._dec_prec, self._voc_prec), self._engine_kwargs = precisions, dict(engine_kwargs)
+        if had_engine:
+            self._ensure_engine()
+        return had_engine
+
+    def _verify_precision(self, kwargs) -> bool:
+        """Runs the precision guard on the packed blob and moves the object to the chosen rung; True when that replaced a live engine."""
+        from .engine import resolve_precision
+        from .precision_guard import choose_precision
+        self.precision_report = None
+        if resolve_precision(*self._requested) != ("mx", "mx"):
+            return self._move_to(self._requested, {})
+        kwargs.setdefault("device", self._device_id or 0)
+        rep = choose_precision(self.shapes, self._blob, **kwargs)
+        self.precision_report = rep
+        if rep.escalated:
+            import warnings
+            warnings.warn("this checkpoint misses the precision bar in the default mode; running %s %s instead.  %s"
+                          % (rep.chosen, rep.chosen_kwargs or "", rep.line()), RuntimeWarning, stacklevel=3)
+        return self._move_to((rep.chosen, None, None), rep.chosen_kwargs)
+
     def load_packed(self, blob: bytes, manifest_json: Optional[str] = None):
         self._blob = (blob, manifest_json)
-        if self._engine is not None:
+        moved = self._move_to(self._requested, {})
+        self.precision_report = None
+        if self._engine is not None and not moved:
             self._engine.load_blob(blob, manifest_json)
         return self
 

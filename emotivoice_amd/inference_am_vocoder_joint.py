@@ -81,7 +81,10 @@ def synthesize_checkpoint(config, conf, checkpoint_path, out_dir, args, state_di
     if state_dict is None:
         import torch
         state_dict = torch.load(checkpoint_path, map_location="cpu")["generator"]      # :72-73
-    gen.to(args.device).load_state_dict(state_dict)
+    verify = True if getattr(args, "verify_precision", False) else None
+    gen.to(args.device).load_state_dict(state_dict, verify=verify)
+    if gen.precision_report is not None:
+        print(gen.precision_report.line())
     gen.eval()
     if os.path.exists(out_dir):                               # :86-89
         for j in glob.glob(os.path.join(out_dir, "*")):
@@ -127,6 +130,8 @@ def main(argv=None):
                    help="mx: the contract mode (waveform within 1e-3 of the reference, fp4 cross terms); fast: fp16; strict: split precision")
     p.add_argument("--synthetic-weights", action="store_true",
                    help="no checkpoint directory: synthesise with the seeded synthetic checkpoint (named 'synthetic')")
+    p.add_argument("--verify-precision", action="store_true",
+                   help="with --precision mx: measure the checkpoint against a strict engine at load time and run the cheapest mode within 1e-3 of it")
     args = p.parse_args(argv)
 
     config = _load_config(args.config_folder)

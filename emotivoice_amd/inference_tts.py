@@ -172,7 +172,10 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
         else:
             import torch
             state_dict = torch.load(os.path.join(root_path, "ckpt", args.checkpoint), map_location="cpu")["generator"]     # :73-75
-    gen.to("cuda:%d" % gpu_id).load_state_dict(state_dict)
+    verify = True if getattr(args, "verify_precision", False) else None
+    gen.to("cuda:%d" % gpu_id).load_state_dict(state_dict, verify=verify)
+    if gen.precision_report is not None:
+        print(gen.precision_report.line())
     gen.eval()
     token2id = read_table(config.token_list_path)                                 # :78-79
     with open(config.speaker2id_path, encoding="utf-8") as f:                       # :81-82
@@ -210,6 +213,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--frontend_workers", type=int, default=1, help="fork-pool workers for the G2P of a process")
     p.add_argument("--phoneme-input", action="store_true", help="the lines already are space-separated phoneme tokens")
     p.add_argument("--synthetic-weights", action="store_true", help="seeded synthetic checkpoint instead of <logdir>/ckpt/<checkpoint>")
+    p.add_argument("--verify-precision", action="store_true",
+                   help="with --precision mx: measure the checkpoint against a strict engine at load time and run the cheapest mode within 1e-3 of it")
     return p
 
 

@@ -521,6 +521,58 @@ typedef struct ev_stitch_result {
 int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets, const int64_t* seg_lens, const int32_t* seg_doc,
               const int32_t* pause_after, const ev_stitch_config* cfg, uint32_t flags, ev_stitch_result* out);
 
+/* Signal comparison (ev_compare): how far a signal a (under test) lies from a signal b (the yardstick), per segment, on the device -- the
+ * measurement behind "waveform within 1e-3 of the reference" (the tests' rel_l2 / rel_l2_ac), without a device -> host copy of either signal.
+ * Nothing is waveform-specific: a mel is compared with lens = mel_lens * n_mels.  The reference has no such stage; the arithmetic is the one
+ * specified here, in fp64 with a fixed order, so that a float64 restatement reproduces every output bit.
+ *   Inputs: a and b, B segments each, packed back to back with the same lens[b] >= 1 fp32 elements; segment b starts at element
+ *     off_b = lens[0] + .. + lens[b - 1] of both.  n_b = lens[b].
+ *   Per element i of a segment: x = (double)a[i], y = (double)b[i].  Where a[i] or b[i] is not finite (NaN, +-inf) the element counts once in
+ *     nonfinite[b] and enters everything else as d = 0, y = 0.  Otherwise d = x - y (one fp64 rounding).  The element's terms are d, d * d, y and
+ *     y * y, each product one fp64 rounding; no product is fused with a sum.
+ *   Sums (sum_d, sum_d2, sum_y, sum_y2; each on its own, the same rule): the segment is cut into chunks of EV_COMPARE_CHUNK elements, chunk c =
+ *     elements [c * EV_COMPARE_CHUNK, min((c + 1) * EV_COMPARE_CHUNK, n_b)).  Inside a chunk, t = 0 .. 255: s[t] = +0.0, then the terms of the
+ *     chunk's elements t, t + 256, t + 512, ... (those that exist) are added to s[t] in ascending order.  Then the halving tree: for o = 128, 64,
+ *     .., 1: s[t] = s[t] + s[t + o] for every t < o.  s[0] is the chunk's sum (chunk_d2 / chunk_y2 hold it for d * d and y * y).  The segment's
+ *     sum starts at +0.0 and adds its chunks' sums in ascending chunk order.  Every addition is one fp64 rounding.
+ *   Maxima: max_abs_d[b] = (float)max_i |d| (the fp64 maximum, rounded once to fp32, so +inf where it exceeds FLT_MAX); argmax_d[b] = the
+ *     smallest i with |d| equal to that maximum (0 where every d is 0); peak_y[b] = max_i |b[i]| over the elements that count (exact in fp32).
+ *   Ratios (host, C double, from the sums; sqrt, max, *, / and - one correctly rounded operation each, in the order written):
+ *     rel_l2[b]    = sqrt(sum_d2) / sqrt(max(sum_y2, EV_COMPARE_FLOOR))
+ *     rel_l2_ac[b] = sqrt(sum_d2) / sqrt(max(sum_y2 - (sum_y * sum_y) / (double)n_b, EV_COMPARE_FLOOR))
+ *     rel_l2_ac removes the yardstick's mean in one pass: sum (y - mean)^2 = sum_y2 - sum_y^2 / n.  The subtraction cancels where the mean
+ *     dominates: with |mean| = k * rms_ac the relative error of the denominator's square is about (1 + k^2) * 2^-52 times a small factor, so the
+ *     ratio is good to 1e-9 for k up to a few hundred (the synthetic-weight fixtures have k = 3).  n_b includes the elements counted in nonfinite.
+ * No atomics; the order of every sum is fixed by (segment, index) alone and the maxima are exact in any order, so a segment gives the same bits
+ * alone or anywhere in a batch, and from host or device memory.  Needs no weights. */
+#define EV_COMPARE_CHUNK 4096
+#define EV_COMPARE_FLOOR 1e-60      /* the square of the 1e-30 the tests' rel_l2 clamps a norm with */
+typedef struct ev_compare_result {
+    uint32_t struct_size;          /* sizeof(ev_compare_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* elements per signal */
+    const double*  sum_d;          /* every array: HOST, (batch,) unless stated */
+    const double*  sum_d2;
+    const double*  sum_y;
+    const double*  sum_y2;
+    const double*  rel_l2;
+    const double*  rel_l2_ac;
+    const float*   max_abs_d;
+    const int64_t* argmax_d;       /* index inside the segment */
+    const float*   peak_y;
+    const int64_t* nonfinite;
+    const double*  chunk_d2;       /* (chunk_offsets[batch],): the chunks' sums of d * d, segment after segment: where in a segment the error sits */
+    const double*  chunk_y2;       /* (chunk_offsets[batch],): the same for y * y */
+    const int64_t* chunk_offsets;  /* (batch + 1,): segment b owns chunks chunk_offsets[b] .. chunk_offsets[b + 1], ceil(n_b / EV_COMPARE_CHUNK) of them */
+} ev_compare_result;
+/* a, b: host pointers, or with EV_FLAG_DEVICE_INPUTS (the other flags are ignored) device pointers on the handle's device -- both of one kind.
+ * Device signals may belong to other handles: the ev_result.wav of a strict engine and of an mx engine go straight in (a result is complete when
+ * its call returns, so no ordering between the handles' streams is needed).  lens is always a HOST array.  Rejected before anything is
+ * launched (message naming the field or segment; the previous result stays valid): a NULL h, a, b, lens or out, a wrong struct_size, B outside
+ * [1, 65535], lens[b] < 1.  The call synchronises (as ev_resample's trim): every array of the result is HOST memory in a workspace of its own,
+ * complete when the call returns, and stays valid across every other entry point until the next ev_compare or ev_destroy. */
+int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_t* lens, uint32_t flags, ev_compare_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 
