@@ -146,6 +146,23 @@ class ev_compare_result(C.Structure):
     ]
 
 
+EV_FLAC_WRAP, EV_FLAC_CLAMP, EV_FLAC_MAX_SAMPLES = 0, 1, 1 << 30
+
+
+class ev_flac_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("block_size", C.c_int32), ("max_fixed_order", C.c_int32),
+                ("max_partition_order", C.c_int32), ("convert", C.c_int32)]
+
+
+class ev_flac_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_bytes", C.c_int64), ("total_frames", C.c_int64),
+        ("bytes", C.c_void_p),
+        ("stream_offsets", C.POINTER(C.c_int64)), ("stream_frames", C.POINTER(C.c_int64)), ("frame_offsets", C.POINTER(C.c_int64)),
+        ("frame_kind", C.POINTER(C.c_uint8)), ("frame_porder", C.POINTER(C.c_uint8)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -218,6 +235,10 @@ SIGNATURES = {
     "ev_stitch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.POINTER(ev_stitch_config), C.c_uint32, C.POINTER(ev_stitch_result)]),
     # lens is a HOST array; a and b are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
     "ev_compare": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_uint32, C.POINTER(ev_compare_result)]),
+    "ev_default_flac_config": (None, [C.POINTER(ev_flac_config)]),
+    "ev_flac_bound": (C.c_int64, [C.c_int64, C.c_int]),      # host only
+    # lens is a HOST array; pcm is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_flac": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_flac_config), C.c_uint32, C.POINTER(ev_flac_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -269,6 +290,7 @@ SIGNATURES = {
     "ev_op_trim": (C.c_int, [_P, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
     # everything but wav / out / out_i16 is a HOST array
     "ev_op_stitch_scan": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "ev_op_flac_encode": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(ev_flac_config), _P, _P, _P, _P, _P]),
     "ev_op_stitch_mix": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 

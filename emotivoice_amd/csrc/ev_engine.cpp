@@ -73,8 +73,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise), [8] ev_compare (scratch only: its result is host memory)
+    char* arena[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise), [8] ev_compare (scratch only: its result is host memory), [9] ev_flac (likewise [3])
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -107,6 +107,8 @@ struct ev_handle {
     // ev_compare: its result, all of it host memory
     std::vector<double> cmp_d, cmp_d2, cmp_y, cmp_y2, cmp_rel, cmp_rel_ac, cmp_chunk_d2, cmp_chunk_y2;
     std::vector<float> cmp_max_d, cmp_peak_y; std::vector<int64_t> cmp_arg, cmp_nonf, cmp_chunk_offs;
+    // ev_flac: the host halves of its result
+    std::vector<int64_t> fl_stream_offs, fl_stream_frames, fl_frame_offs; std::vector<uint8_t> fl_kind, fl_porder;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1119,7 +1121,7 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 9; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 10; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->rs_tab) (void)hipFree(h->rs_tab);
     if (h->st_tab) (void)hipFree(h->st_tab);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
@@ -2545,6 +2547,138 @@ int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_
     return 0;
 }
 
+// ------------------------------------------------------------------- FLAC encoding (include/evhip.h: ev_flac)
+void ev_default_flac_config(ev_flac_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c; c->sample_rate = 16000; c->block_size = 4096; c->max_fixed_order = 4; c->max_partition_order = 5; c->convert = EV_FLAC_WRAP;
+}
+
+static int flac_block_code(int block_size) {      // the frame header's code of N, or -1
+    for (int i = 0; i < 5; ++i) if (block_size == 256 << i) return 8 + i;
+    return -1;
+}
+static int flac_rate_code(int sample_rate) {
+    static const int rates[7] = {8000, 16000, 22050, 24000, 32000, 44100, 48000};
+    for (int i = 0; i < 7; ++i) if (sample_rate == rates[i]) return 4 + i;
+    return -1;
+}
+
+int64_t ev_flac_bound(int64_t n, int block_size) {
+    if (n < 1 || n > EV_FLAC_MAX_SAMPLES || flac_block_code(block_size) < 0) return -1;
+    const int64_t full = n / block_size, rest = n % block_size;
+    return FLAC_STREAM_HEADER + full * (2 * (int64_t)block_size + 15) + (rest ? 2 * rest + 15 : 0);
+}
+
+int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out) {
+    if (!h) return -1;
+    if (!pcm) return fail(h, "ev_flac: pcm is NULL");
+    if (!lens) return fail(h, "ev_flac: lens is NULL");
+    if (!out) return fail(h, "ev_flac: out is NULL");
+    if (out->struct_size != sizeof(ev_flac_result))
+        return fail(h, "ev_flac: out->struct_size %u != sizeof(ev_flac_result) %zu", out->struct_size, sizeof(ev_flac_result));
+    ev_flac_config dflt;
+    if (!cfg) { ev_default_flac_config(&dflt); cfg = &dflt; }
+    if (cfg->struct_size != sizeof(ev_flac_config))
+        return fail(h, "ev_flac: cfg->struct_size %u != sizeof(ev_flac_config) %zu", cfg->struct_size, sizeof(ev_flac_config));
+    const ev_flac_config c = *cfg;
+    const int sr_code = flac_rate_code(c.sample_rate), bs_code = flac_block_code(c.block_size);
+    if (sr_code < 0) return fail(h, "ev_flac: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
+    if (bs_code < 0) return fail(h, "ev_flac: block_size = %d is not one of 256, 512, 1024, 2048, 4096", c.block_size);
+    if (c.max_fixed_order < 0 || c.max_fixed_order > 4) return fail(h, "ev_flac: max_fixed_order = %d outside [0, 4]", c.max_fixed_order);
+    if (c.max_partition_order < 0 || c.max_partition_order > 6) return fail(h, "ev_flac: max_partition_order = %d outside [0, 6]", c.max_partition_order);
+    if (c.convert != EV_FLAC_WRAP && c.convert != EV_FLAC_CLAMP) return fail(h, "ev_flac: convert = %d is neither EV_FLAC_WRAP nor EV_FLAC_CLAMP", c.convert);
+    if (B < 1 || B > 65535) return fail(h, "ev_flac: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, i16 = pcm_is_i16 != 0;
+    const int N = c.block_size, stride = 2 * N + 24;
+    int64_t total = 0, NF = 0, cap = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1) return fail(h, "ev_flac: lens[%d] = %lld < 1", b, (long long)lens[b]);
+        if (lens[b] > EV_FLAC_MAX_SAMPLES) return fail(h, "ev_flac: lens[%d] = %lld > EV_FLAC_MAX_SAMPLES = %d", b, (long long)lens[b], EV_FLAC_MAX_SAMPLES);
+        total += lens[b]; NF += (lens[b] + N - 1) / N; cap += ev_flac_bound(lens[b], N);
+        if (NF > INT_MAX) return fail(h, "ev_flac: lens[%d] = %lld: more than %d frames in one call", b, (long long)lens[b], INT_MAX);
+    }
+    std::vector<FlacFrame> frames;
+    frames.reserve((size_t)NF);
+    std::vector<int64_t> sframes((size_t)B);
+    for (int64_t b = 0, off = 0; b < B; off += lens[b], ++b) {
+        sframes[(size_t)b] = (lens[b] + N - 1) / N;
+        for (int64_t i = 0; i < lens[b]; i += N) frames.push_back(FlacFrame{off + i, (int32_t)std::min<int64_t>(N, lens[b] - i), (int32_t)(i / N), (int32_t)b, 0});
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    const size_t es = i16 ? sizeof(int16_t) : sizeof(float);
+    char* d_pcm = nullptr; FlacFrame* d_frames = nullptr; int32_t* d_sizes = nullptr; uint32_t* d_desc = nullptr; uint8_t *d_scratch = nullptr, *d_hdr = nullptr, *d_bytes = nullptr;
+    int64_t* d_foffs = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 9, pass == 0};
+        if (pass == 1 && arena_reserve(h, 9, need)) return -1;
+        if (!dev_in) d_pcm = ap.arr<char>((size_t)total * es);
+        d_frames = ap.arr<FlacFrame>((size_t)NF); d_sizes = ap.arr<int32_t>((size_t)NF); d_desc = ap.arr<uint32_t>((size_t)NF);
+        d_foffs = ap.arr<int64_t>((size_t)NF); d_hdr = ap.arr<uint8_t>((size_t)B * FLAC_HEADER_STRIDE);
+        d_scratch = ap.arr<uint8_t>((size_t)NF * (size_t)stride + 16); d_bytes = ap.arr<uint8_t>((size_t)cap);
+        need = ap.off;
+    }
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_pcm, pcm, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_frames, frames.data(), (size_t)NF * sizeof(FlacFrame), hipMemcpyHostToDevice, h->stream));
+    FlacParams fp{};
+    fp.pcm = dev_in ? pcm : d_pcm; fp.pcm_is_i16 = i16; fp.convert = c.convert; fp.block_size = N; fp.bs_code = bs_code; fp.sr_code = sr_code;
+    fp.max_fixed_order = c.max_fixed_order; fp.max_partition_order = c.max_partition_order; fp.frames = d_frames; fp.scratch = d_scratch; fp.stride = stride;
+    fp.sizes = d_sizes; fp.desc = d_desc;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "flac_encode", 0.0, (double)total * (double)es + (double)NF * (double)stride);
+        if (launch_flac_encode(fp, NF, h->stream)) return fail(h, "ev_flac: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> sizes((size_t)NF); std::vector<uint32_t> desc((size_t)NF);
+    HIPCHK(h, hipMemcpyAsync(sizes.data(), d_sizes, (size_t)NF * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(desc.data(), d_desc, (size_t)NF * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the layout: per stream its header, then its frames; the header needs the stream's smallest and largest frame
+    std::vector<int64_t> soffs((size_t)B + 1, 0), foffs((size_t)NF + 1, 0);
+    std::vector<uint8_t> hdr((size_t)B * FLAC_HEADER_STRIDE, 0), kind((size_t)NF), porder((size_t)NF);
+    int64_t pos = 0, f = 0;
+    for (int b = 0; b < B; ++b) {
+        soffs[(size_t)b] = pos;
+        pos += FLAC_STREAM_HEADER;
+        int32_t lo = INT_MAX, hi = 0;
+        for (int64_t i = 0; i < sframes[(size_t)b]; ++i, ++f) {
+            const int32_t sz = sizes[(size_t)f];
+            if (sz < 1 || sz > 2 * N + 15) return fail(h, "ev_flac: frame %lld of segment %d reports %d bytes", (long long)i, b, sz);
+            foffs[(size_t)f] = pos; pos += sz; lo = std::min(lo, sz); hi = std::max(hi, sz);
+            kind[(size_t)f] = (uint8_t)(desc[(size_t)f] & 0xFFu); porder[(size_t)f] = (uint8_t)(desc[(size_t)f] >> 8 & 0xFFu);
+        }
+        uint8_t* p = hdr.data() + (size_t)b * FLAC_HEADER_STRIDE;
+        const uint64_t n = (uint64_t)lens[b], v = (uint64_t)c.sample_rate << 44 | (uint64_t)15 << 36 | n;      // 20 + 3 + 5 + 36 bits
+        memcpy(p, "fLaC", 4);
+        p[4] = 0x80; p[5] = 0; p[6] = 0; p[7] = 0x22;
+        p[8] = p[10] = (uint8_t)(N >> 8); p[9] = p[11] = (uint8_t)(N & 0xFF);
+        p[12] = (uint8_t)(lo >> 16); p[13] = (uint8_t)(lo >> 8); p[14] = (uint8_t)lo;
+        p[15] = (uint8_t)(hi >> 16); p[16] = (uint8_t)(hi >> 8); p[17] = (uint8_t)hi;
+        for (int i = 0; i < 8; ++i) p[18 + i] = (uint8_t)(v >> (56 - 8 * i));      // p[26 .. 42): the MD5, zero
+    }
+    soffs[(size_t)B] = pos; foffs[(size_t)NF] = pos;
+    if (pos > cap) return fail(h, "ev_flac: the streams outgrew their bound");
+    HIPCHK(h, hipMemcpyAsync(d_foffs, foffs.data(), (size_t)NF * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, h->stream));
+    {
+        KScope ks(h, "flac_gather", 0.0, 2.0 * (double)pos);
+        launch_flac_gather(d_scratch, stride, d_frames, NF, d_sizes, d_foffs, d_hdr, d_bytes, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // the uploads above read host vectors that end with this call
+    profiling_collect(h);
+    h->fl_stream_offs.swap(soffs); h->fl_stream_frames.swap(sframes); h->fl_frame_offs.swap(foffs); h->fl_kind.swap(kind); h->fl_porder.swap(porder);
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total_bytes = pos; out->total_frames = NF; out->bytes = d_bytes;
+    out->stream_offsets = h->fl_stream_offs.data(); out->stream_frames = h->fl_stream_frames.data(); out->frame_offsets = h->fl_frame_offs.data();
+    out->frame_kind = h->fl_kind.data(); out->frame_porder = h->fl_porder.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- SimBERT prompt / content encoder
 void ev_default_bert_config(ev_bert_config* c) {
     memset(c, 0, sizeof *c);
@@ -3103,6 +3237,40 @@ int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const
     if (rc == 0 && (hipMemcpy(cuts.data(), d_cuts, cb, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(peak, d_peak, (size_t)S * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     if (rc == 0) for (int i = 0; i < S; ++i) { first[i] = cuts[2 * (size_t)i]; last[i] = cuts[2 * (size_t)i + 1]; }
+    (void)hipFree(lay);
+    return rc;
+}
+int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, uint8_t* slots, int32_t* sizes,
+                      uint8_t* kind, uint8_t* porder, void* stream) {
+    ev_flac_config c;
+    if (cfg) c = *cfg; else ev_default_flac_config(&c);
+    if (!pcm || !lens || !slots || !sizes || !kind || !porder || B < 1 || B > 65535 || c.struct_size != sizeof(ev_flac_config)) return -2;
+    const int sr_code = flac_rate_code(c.sample_rate), bs_code = flac_block_code(c.block_size);
+    if (sr_code < 0 || bs_code < 0 || c.max_fixed_order < 0 || c.max_fixed_order > 4 || c.max_partition_order < 0 || c.max_partition_order > 6 ||
+        (c.convert != EV_FLAC_WRAP && c.convert != EV_FLAC_CLAMP) || (reinterpret_cast<uintptr_t>(slots) & 3)) return -2;
+    const int N = c.block_size;
+    std::vector<FlacFrame> frames;
+    int64_t off = 0;
+    for (int b = 0; b < B; off += lens[b], ++b) {
+        if (lens[b] < 1 || lens[b] > EV_FLAC_MAX_SAMPLES || (int64_t)frames.size() + (lens[b] + N - 1) / N > INT_MAX) return -2;
+        for (int64_t i = 0; i < lens[b]; i += N) frames.push_back(FlacFrame{off + i, (int32_t)std::min<int64_t>(N, lens[b] - i), (int32_t)(i / N), (int32_t)b, 0});
+    }
+    const size_t NF = frames.size(), fb = NF * sizeof(FlacFrame), sb = NF * sizeof(int32_t);
+    char* lay = nullptr;
+    if (hipMalloc((void**)&lay, fb + 2 * sb) != hipSuccess) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    FlacParams fp{};
+    fp.pcm = pcm; fp.pcm_is_i16 = pcm_is_i16 != 0; fp.convert = c.convert; fp.block_size = N; fp.bs_code = bs_code; fp.sr_code = sr_code;
+    fp.max_fixed_order = c.max_fixed_order; fp.max_partition_order = c.max_partition_order; fp.frames = (const FlacFrame*)lay; fp.scratch = slots;
+    fp.stride = 2 * N + 24; fp.sizes = (int32_t*)(lay + fb); fp.desc = (uint32_t*)(lay + fb + sb);
+    std::vector<uint32_t> desc(NF);
+    int rc = hipMemcpy(lay, frames.data(), fb, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    if (rc == 0) {
+        if (launch_flac_encode(fp, (int64_t)NF, s) || hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    }
+    if (rc == 0 && (hipMemcpy(sizes, fp.sizes, sb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(desc.data(), fp.desc, sb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
+    if (rc == 0) for (size_t f = 0; f < NF; ++f) { kind[f] = (uint8_t)(desc[f] & 0xFFu); porder[f] = (uint8_t)(desc[f] >> 8 & 0xFFu); }
     (void)hipFree(lay);
     return rc;
 }

@@ -330,4 +330,22 @@ int launch_compare_chunks(const float* a, const float* b, const CompareChunk* ch
 void launch_compare_finish(int B, const int64_t* chunk_offs /* (B + 1,) */, const double* sums, int64_t n_chunks, const double* maxd, const int32_t* argd,
                            const float* peak, const int32_t* nonf, CompareSeg* out /* (B,) */, hipStream_t s);
 
+// ev_flac (ev_flac.hip): packed PCM -> FLAC streams.  One block per frame encodes it into a slot of `stride` bytes (a multiple of 4, at least
+// 2 block_size + 24) of a scratch buffer and reports its size and decision; the host lays the frames out; the gather copies every frame to its byte
+// offset and, with a stream's first frame, the stream's FLAC_STREAM_HEADER bytes from a table with FLAC_HEADER_STRIDE bytes per segment.
+constexpr int FLAC_MAX_BLOCK = 4096, FLAC_STREAM_HEADER = 42, FLAC_HEADER_STRIDE = 48;
+struct FlacFrame { int64_t src; int32_t n, index, seg, pad; };     // first sample in the packed input, 1 .. block_size samples, frame number in its segment, the segment
+struct FlacParams {
+    const void* pcm; int pcm_is_i16, convert;         // int16, or fp32 converted with wrap (0) or clamp (1)
+    int block_size, bs_code, sr_code;                 // N and the frame header's codes for N and the sample rate
+    int max_fixed_order, max_partition_order;
+    const FlacFrame* frames;
+    uint8_t* scratch; int stride;
+    int32_t* sizes;                                   // (n_frames,): the frame's bytes
+    uint32_t* desc;                                   // (n_frames,): kind | partition order << 8
+};
+int launch_flac_encode(const FlacParams& p, int64_t n_frames, hipStream_t s);      // 0, or -1 for bad parameters
+void launch_flac_gather(const uint8_t* scratch, int stride, const FlacFrame* frames, int64_t n_frames, const int32_t* sizes, const int64_t* frame_offs,
+                        const uint8_t* headers, uint8_t* out, hipStream_t s);
+
 }  // namespace ev

@@ -98,6 +98,7 @@ class EVEngine:
         self.last_resample: Optional[_ffi.ev_resample_result] = None
         self.last_stitch: Optional[_ffi.ev_stitch_result] = None
         self.last_compare: Optional[_ffi.ev_compare_result] = None
+        self.last_flac: Optional[_ffi.ev_flac_result] = None
 
     # -- lifecycle
     def close(self):
@@ -444,15 +445,20 @@ class EVEngine:
         flat = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in wavs]))
         return self.stitch_to_numpy(self.stitch_raw(len(wavs), flat.ctypes.data, offs, lens, seg_doc, pause_after, sc))
 
-    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None) -> Dict[str, object]:
+    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
         documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
-        config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's."""
+        config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
+        flac=True adds flac_list, one FLAC stream (``bytes``) per document, encoded on the device from ev_stitch's int16 documents (it turns
+        config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to)."""
+        import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
+        if flac and not sc.want_int16:
+            sc = dataclasses.replace(sc, want_int16=True).validate()
         if int(sc.sample_rate) != int(self.shapes.sr):
             raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
         utts, seg_doc, pauses = flatten_documents(documents)
@@ -465,6 +471,13 @@ class EVEngine:
         mel_offs = np.array([res.mel_offsets[b] for b in range(S + 1)], np.int64)
         st = self.stitch_raw(S, res.wav, mel_offs[:-1] * up, np.diff(mel_offs) * up, seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
         out = self.stitch_to_numpy(st, int16_only=sc.want_int16)
+        if flac:
+            from .flac import FlacConfig
+            empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
+            if empty:
+                raise ValueError("flac: document %d is empty after the cut" % empty[0])
+            fr = self.flac_raw(st.batch_docs, st.wav_i16, True, out["doc_lens"], FlacConfig(sample_rate=int(sc.sample_rate)), _ffi.EV_FLAG_DEVICE_INPUTS)
+            out["flac_list"] = self.flac_to_numpy(fr)["streams"]
         sr = float(sc.sample_rate)
         start = out["seg_pos"] / sr
         end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr
@@ -515,6 +528,79 @@ class EVEngine:
         fa = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in a_list]))
         fb = np.ascontiguousarray(np.concatenate([np.asarray(y, np.float32).reshape(-1) for y in b_list]))
         return self.compare_to_numpy(self.compare_raw(len(a_list), fa.ctypes.data, fb.ctypes.data, lens))
+
+    # -- FLAC encoding (ev_flac): packed PCM -> one FLAC stream per segment, on the device
+    def flac_raw(self, B: int, pcm_ptr: int, pcm_is_i16: bool, lens: np.ndarray, config=None, flags: int = 0) -> _ffi.ev_flac_result:
+        """ev_flac (include/evhip.h).  pcm_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens is a host array.  config:
+        an emotivoice_amd.flac.FlacConfig, an _ffi.ev_flac_config or None (the library's default).  The returned struct's device bytes and host
+        arrays stay valid until the next flac call on this engine."""
+        ln = np.ascontiguousarray(lens, np.int64)
+        if ln.size != B:
+            raise ValueError("lens must have B = %d entries" % B)
+        c = config.validate().to_struct() if hasattr(config, "to_struct") else config
+        res = _ffi.ev_flac_result()
+        res.struct_size = C.sizeof(_ffi.ev_flac_result)
+        self._check(self._lib.ev_flac(self._h, B, C.c_void_p(pcm_ptr), 1 if pcm_is_i16 else 0, ln.ctypes.data_as(C.c_void_p),
+                                      C.byref(c) if c is not None else None, flags, C.byref(res)))
+        self.last_flac = res
+        return res
+
+    def flac_to_numpy(self, res: _ffi.ev_flac_result) -> Dict[str, object]:
+        """One D2H copy of total_bytes and copies of the result's host arrays.  streams: one ``bytes`` per segment; frame_kind / frame_porder:
+        one uint8 array per segment (0 constant, 1 verbatim, 8 + o fixed; the partition order)."""
+        B, NF = res.batch, int(res.total_frames)
+        raw = self.d2h(res.bytes, (int(res.total_bytes),), np.uint8)
+        offs = np.ctypeslib.as_array(res.stream_offsets, (B + 1,)).astype(np.int64, copy=True)
+        nfr = np.ctypeslib.as_array(res.stream_frames, (B,)).astype(np.int64, copy=True)
+        kind = np.ctypeslib.as_array(res.frame_kind, (NF,)).astype(np.uint8, copy=True)
+        porder = np.ctypeslib.as_array(res.frame_porder, (NF,)).astype(np.uint8, copy=True)
+        f0 = np.concatenate([[0], np.cumsum(nfr)]).astype(np.int64)
+        return dict(streams=[raw[offs[b]:offs[b + 1]].tobytes() for b in range(B)], stream_offsets=offs, stream_frames=nfr,
+                    frame_offsets=np.ctypeslib.as_array(res.frame_offsets, (NF + 1,)).astype(np.int64, copy=True),
+                    frame_kind=[kind[f0[b]:f0[b + 1]] for b in range(B)], frame_porder=[porder[f0[b]:f0[b + 1]] for b in range(B)],
+                    total_bytes=int(res.total_bytes))
+
+    def flac(self, pcm_list: Sequence[np.ndarray], **config) -> Dict[str, object]:
+        """Host signals -> FLAC streams.  pcm_list: one 1-D array per segment, all int16 or all floating (converted on the device with
+        config's ``convert`` rule); further keywords: the fields of emotivoice_amd.flac.FlacConfig.  Needs no weights."""
+        from .flac import FlacConfig
+        fc = FlacConfig(**config).validate()
+        if not len(pcm_list):
+            raise ValueError("pcm_list must hold at least one segment")
+        arrs = [np.asarray(x) for x in pcm_list]
+        is16 = arrs[0].dtype == np.int16
+        for s, a in enumerate(arrs):
+            if a.ndim != 1 or (a.dtype == np.int16) != is16 or not (is16 or np.issubdtype(a.dtype, np.floating)):
+                raise ValueError("segment %d: 1-D arrays, all int16 or all floating" % s)
+        flat = np.ascontiguousarray(np.concatenate([a.astype(np.int16 if is16 else np.float32, copy=False) for a in arrs]))
+        lens = np.array([a.size for a in arrs], np.int64)
+        return self.flac_to_numpy(self.flac_raw(len(arrs), flat.ctypes.data, is16, lens, fc))
+
+    def _flac_of_result(self, res: _ffi.ev_result, mask) -> List[Optional[bytes]]:
+        """The utterances of an ev_result that ``mask`` selects, encoded from the fp32 device waveform with the wrapping conversion: one ev_flac
+        call per run of consecutive selected utterances (ev_flac takes its segments back to back)."""
+        from .flac import FlacConfig
+        B, up = res.batch, self.shapes.upsample_factor
+        sel = np.ones(B, bool) if mask is True else np.asarray(mask, bool)
+        if sel.shape != (B,):
+            raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (B, sel.shape))
+        if sel.any() and not res.wav:
+            raise ValueError("flac needs the vocoder's waveform")
+        fc = FlacConfig(sample_rate=int(self.shapes.sr), convert="wrap")
+        mel_offs = np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64)
+        out: List[Optional[bytes]] = [None] * B
+        b = 0
+        while b < B:
+            if not sel[b]:
+                b += 1
+                continue
+            e = b
+            while e < B and sel[e]:
+                e += 1
+            fr = self.flac_raw(e - b, res.wav + 4 * int(mel_offs[b]) * up, False, np.diff(mel_offs[b:e + 1]) * up, fc, _ffi.EV_FLAG_DEVICE_INPUTS)
+            out[b:e] = self.flac_to_numpy(fr)["streams"]
+            b = e
+        return out
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)
@@ -573,11 +659,16 @@ class EVEngine:
         return res, cu
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
-        for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way."""
+        for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
+        flac: None, True or one boolean per utterance: adds flac_list, the FLAC stream (``bytes``) of every selected utterance and None
+        for the others, encoded on the device from the fp32 waveform with the wrapping conversion -- a stream decodes to
+        wav_float_to_int16(wav_list[b])."""
+        if flac is not None and flac is not False and not vocoder:
+            raise ValueError("flac needs the vocoder's waveform")
         flags = 0
         if want_int16:
             flags |= _ffi.EV_FLAG_WANT_INT16
@@ -586,6 +677,8 @@ class EVEngine:
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
         out = self.result_to_numpy(res, want_int16)
         out["cu_seqlens"] = cu
+        if flac is not None and flac is not False:
+            out["flac_list"] = self._flac_of_result(res, flac)
         return out
 
     def vocoder(self, mels: Sequence[np.ndarray], want_int16: bool = False) -> Dict[str, object]:

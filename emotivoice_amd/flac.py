@@ -1,0 +1,59 @@
+"""FLAC responses (ev_flac): the configuration of the device encoder and a file writer.
+
+The encoder itself is HIP (csrc/ev_flac.hip) behind the C entry ev_flac; include/evhip.h states the stream it writes: 16-bit mono, a fixed block
+size, CONSTANT / VERBATIM / FIXED subframes, no LPC, no MD5.  Nothing here touches the device.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
+CONVERT = {"wrap": 0, "clamp": 1}
+KIND_CONSTANT, KIND_VERBATIM, KIND_FIXED = 0, 1, 8      # frame_kind: a FIXED subframe of order o is 8 + o
+
+
+@dataclass
+class FlacConfig:
+    sample_rate: int = 16000
+    block_size: int = 4096
+    max_fixed_order: int = 4
+    max_partition_order: int = 5
+    convert: str = "wrap"      # fp32 input only: "wrap" = the bits of wav_float_to_int16 (a pcm response), "clamp" = ev_stitch's int16 rule
+
+    def validate(self) -> "FlacConfig":
+        if int(self.sample_rate) not in SAMPLE_RATES:
+            raise ValueError("sample_rate %r is not one of %s" % (self.sample_rate, SAMPLE_RATES))
+        if int(self.block_size) not in BLOCK_SIZES:
+            raise ValueError("block_size %r is not one of %s" % (self.block_size, BLOCK_SIZES))
+        if not 0 <= int(self.max_fixed_order) <= 4:
+            raise ValueError("max_fixed_order %r outside [0, 4]" % (self.max_fixed_order,))
+        if not 0 <= int(self.max_partition_order) <= 6:
+            raise ValueError("max_partition_order %r outside [0, 6]" % (self.max_partition_order,))
+        if self.convert not in CONVERT:
+            raise ValueError("convert %r is neither 'wrap' nor 'clamp'" % (self.convert,))
+        return self
+
+    def to_struct(self):
+        from . import _ffi
+        c = _ffi.ev_flac_config()
+        c.struct_size = C.sizeof(_ffi.ev_flac_config)
+        c.sample_rate, c.block_size = int(self.sample_rate), int(self.block_size)
+        c.max_fixed_order, c.max_partition_order, c.convert = int(self.max_fixed_order), int(self.max_partition_order), CONVERT[self.convert]
+        return c
+
+
+def flac_bound(n: int, block_size: int = 4096) -> int:
+    """ev_flac_bound: the largest stream a segment of n samples can give (host only)."""
+    from . import _ffi
+    v = int(_ffi.lib().ev_flac_bound(int(n), int(block_size)))
+    if v < 0:
+        raise ValueError("flac_bound: n = %r or block_size = %r out of range" % (n, block_size))
+    return v
+
+
+def write_flac(path: str, data: bytes) -> None:
+    """Writes one stream as ev_flac made it.  Anything that is not a FLAC stream is refused: an array would need the device encoder."""
+    if not isinstance(data, (bytes, bytearray, memoryview)) or bytes(data[:4]) != b"fLaC":
+        raise ValueError("write_flac takes the bytes of a stream from EVEngine.flac / synthesize(..., flac=True), not samples")
+    with open(path, "wb") as f:
+        f.write(data)

@@ -46,6 +46,7 @@ class SynthesisRequest:
     future: Future = field(default_factory=Future)
     prosody: Optional[Prosody] = None     # per-utterance controls (mixed_prosody batchers only); its speed / alpha, if set, wins over ``alpha``
     t_submit: float = field(default_factory=time.perf_counter)
+    response_format: Optional[str] = None     # "flac": the Future resolves to the stream's bytes (flac_synth_fn batchers only); else to the waveform
 
 
 class DynamicBatcher:
@@ -55,12 +56,18 @@ class DynamicBatcher:
     (``embed_batch_fn(texts) -> (len(texts), 768)``: requests then carry the TEXTS and the worker embeds a whole batch at once,
     which also batches the BERT forward).
     ``mixed_prosody=True``: requests are no longer grouped by ``alpha``; ``synth_fn(utts, prosodies)`` then receives one Prosody per
-    utterance (speed folded in as its alpha) -- ``engine_prosody_synth_fn``."""
+    utterance (speed folded in as its alpha) -- ``engine_prosody_synth_fn``.
+    ``flac_synth_fn(utts, alpha_or_prosodies, mask) -> list`` (``engine_flac_synth_fn``): called instead of ``synth_fn`` for a batch in which
+    some request was submitted with ``response_format="flac"``; it returns, per utterance, the FLAC stream (``bytes``) where ``mask`` is True
+    and the float waveform elsewhere.  The encoding thus runs on the worker thread, on the same handle.  Batches without such a request call
+    ``synth_fn`` exactly as before."""
 
     def __init__(self, synth_fn: Callable[[List[dict], float], Sequence[np.ndarray]], max_batch: int = 32, max_wait_ms: float = 5.0,
                  max_tokens: int = 16384, embed_batch_fn: Optional[Callable[[List[str]], np.ndarray]] = None,
-                 n_vocab: Optional[int] = None, n_speaker: Optional[int] = None, max_len: int = 4096, mixed_prosody: bool = False):
+                 n_vocab: Optional[int] = None, n_speaker: Optional[int] = None, max_len: int = 4096, mixed_prosody: bool = False,
+                 flac_synth_fn: Optional[Callable[[List[dict], object, List[bool]], Sequence[object]]] = None):
         self.mixed_prosody = mixed_prosody
+        self.flac_synth_fn = flac_synth_fn
         self.synth_fn, self.max_batch, self.max_wait, self.max_tokens = synth_fn, max_batch, max_wait_ms * 1e-3, max_tokens
         self.embed_batch_fn, self.n_vocab, self.n_speaker, self.max_len = embed_batch_fn, n_vocab, n_speaker, max_len
         self._q: "queue.Queue[Optional[SynthesisRequest]]" = queue.Queue()
@@ -73,7 +80,8 @@ class DynamicBatcher:
         self._thread = threading.Thread(target=self._loop, name="ev-batcher", daemon=True)
         self._thread.start()
 
-    def submit(self, ling, speaker: int, style, content, alpha: float = 1.0, prosody: Optional[Prosody] = None) -> Future:
+    def submit(self, ling, speaker: int, style, content, alpha: float = 1.0, prosody: Optional[Prosody] = None,
+               response_format: Optional[str] = None) -> Future:
         """Validation happens HERE (ValueError -> the handler's 400), so that one malformed request cannot take the requests
         batched with it down: the reference serves every request on its own (openaiapi.py:159-184)."""
         ling = np.asarray(ling, np.int64).reshape(-1)
@@ -87,6 +95,8 @@ class DynamicBatcher:
             raise ValueError("speaker id out of range")
         if not (alpha > 0 and np.isfinite(alpha)):
             raise ValueError("alpha must be positive")
+        if response_format == "flac" and self.flac_synth_fn is None:
+            raise ValueError("response_format 'flac' needs a batcher with flac_synth_fn (engine_flac_synth_fn): FLAC is encoded on the device")
         if prosody is not None:
             if not self.mixed_prosody:
                 raise ValueError("prosody controls need a batcher with mixed_prosody=True")
@@ -102,7 +112,7 @@ class DynamicBatcher:
             if not np.isfinite(x).all():
                 raise ValueError("embedding is not finite")
             return x
-        req = SynthesisRequest(ling, int(speaker), emb(style), emb(content), float(alpha), prosody=prosody)
+        req = SynthesisRequest(ling, int(speaker), emb(style), emb(content), float(alpha), prosody=prosody, response_format=response_format)
         with self._lock:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -197,14 +207,23 @@ class DynamicBatcher:
                     r.style = table[r.style] if isinstance(r.style, str) else r.style
                     r.content = table[r.content] if isinstance(r.content, str) else r.content
         utts = [dict(ling=r.ling, speaker=r.speaker, style=r.style, content=r.content) for r in batch]
-        if self.mixed_prosody:
-            wavs = self.synth_fn(utts, [_request_prosody(r) for r in batch])
+        control = [_request_prosody(r) for r in batch] if self.mixed_prosody else batch[0].alpha
+        mask = [r.response_format == "flac" for r in batch]
+        if any(mask):
+            if self.flac_synth_fn is None:
+                raise RuntimeError("a flac request reached a batcher without flac_synth_fn")
+            wavs = self.flac_synth_fn(utts, control, mask)
         else:
-            wavs = self.synth_fn(utts, batch[0].alpha)
+            wavs = self.synth_fn(utts, control)
         if len(wavs) != len(batch):
             raise RuntimeError("synth_fn returned %d waveforms for %d requests" % (len(wavs), len(batch)))
-        for r, w in zip(batch, wavs):
-            _resolve(r.future, result=np.array(w, np.float32, copy=True))
+        for r, w, m in zip(batch, wavs, mask):
+            if m:
+                if not isinstance(w, (bytes, bytearray)):
+                    raise RuntimeError("flac_synth_fn returned %s where a FLAC stream was asked for" % type(w).__name__)
+                _resolve(r.future, result=bytes(w))
+            else:
+                _resolve(r.future, result=np.array(w, np.float32, copy=True))
 
     @staticmethod
     def _claim(r: "SynthesisRequest") -> bool:
@@ -288,6 +307,17 @@ def engine_prosody_synth_fn(engine) -> Callable[[List[dict], List[Prosody]], Seq
     return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies)["wav_list"]
 
 
+def engine_flac_synth_fn(engine) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+    """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
+    device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
+    second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody."""
+    def fn(utts, control, mask):
+        kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)
+        out = engine.synthesize(utts, flac=list(mask), **kw)
+        return [f if m else w for f, w, m in zip(out["flac_list"], out["wav_list"], mask)]
+    return fn
+
+
 def engine_embed_batch_fn(engine, tokenize: Callable[[str], Sequence[int]]) -> Callable[[List[str]], np.ndarray]:
     """``embed_batch_fn`` of a DynamicBatcher for the device SimBERT living on ``engine`` (ev_style_embed on the SAME handle as
     ev_synthesize -- which is why it has to run on the batcher's thread): ``tokenize(text) -> [CLS] ... [SEP]`` ids
@@ -295,7 +325,14 @@ def engine_embed_batch_fn(engine, tokenize: Callable[[str], Sequence[int]]) -> C
     return lambda texts: engine.style_embed([np.asarray(tokenize(t), np.int64) for t in texts])
 
 
-def encode_audio(wav_f32: np.ndarray, response_format: str, sample_rate: int) -> bytes:
+def encode_audio(wav_f32, response_format: str, sample_rate: int) -> bytes:
+    """``flac``: the stream was encoded on the device (a batcher with ``flac_synth_fn``) and arrives as ``bytes``, which pass through."""
+    if response_format == "flac":
+        if isinstance(wav_f32, (bytes, bytearray)):
+            return bytes(wav_f32)
+        raise ValueError("response_format 'flac' is encoded on the device: it needs a batcher with flac_synth_fn (engine_flac_synth_fn)")
+    if isinstance(wav_f32, (bytes, bytearray)):
+        raise ValueError("an encoded stream cannot be re-encoded as %r" % response_format)
     pcm = wav_float_to_int16(wav_f32)              # the reference's int16 epilogue (openaiapi.py:147-148)
     if response_format == "pcm":
         return pcm.tobytes()
@@ -305,7 +342,7 @@ def encode_audio(wav_f32: np.ndarray, response_format: str, sample_rate: int) ->
             w.setnchannels(1); w.setsampwidth(2); w.setframerate(sample_rate)
             w.writeframes(pcm.tobytes())
         return buf.getvalue()
-    raise ValueError("response_format %r is not available (wav, pcm); mp3 needs pydub / ffmpeg" % response_format)
+    raise ValueError("response_format %r is not available (wav, pcm, flac); mp3 needs pydub / ffmpeg" % response_format)
 
 
 class TTSService:
@@ -323,8 +360,9 @@ class TTSService:
             raise ValueError("TTSService needs embed= or a batcher with embed_batch_fn=")
 
     def submit(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, pitch_shift: float = 0.0, pitch_scale: float = 1.0,
-               energy_scale: float = 1.0) -> Future:
-        """``pitch_shift`` / ``pitch_scale`` / ``energy_scale`` (extension fields, in the predictor's normalised units; include/evhip.h
+               energy_scale: float = 1.0, response_format: Optional[str] = None) -> Future:
+        """``response_format="flac"`` travels with the request (a batcher with ``flac_synth_fn``); every other value is encoded by ``speech``.
+        ``pitch_shift`` / ``pitch_scale`` / ``energy_scale`` (extension fields, in the predictor's normalised units; include/evhip.h
         ev_prosody): anything but the identity needs a batcher with ``mixed_prosody=True``."""
         if not (0.25 <= speed <= 4.0):
             raise ValueError("speed must be within [0.25, 4]")
@@ -334,13 +372,14 @@ class TTSService:
         ling = np.array([self.token2id[ph] for ph in self.g2p(text).split()], np.int64)       # KeyError like openaiapi.py:128
         if ling.size == 0:
             raise ValueError("input has no phonemes")
+        extra = dict(response_format="flac") if response_format == "flac" else {}
         if self.embed is None:
-            return self.batcher.submit(ling, self.speaker2id[voice], prompt, text, alpha=1.0 / speed, prosody=prosody)
-        return self.batcher.submit(ling, self.speaker2id[voice], self.embed(prompt), self.embed(text), alpha=1.0 / speed, prosody=prosody)
+            return self.batcher.submit(ling, self.speaker2id[voice], prompt, text, alpha=1.0 / speed, prosody=prosody, **extra)
+        return self.batcher.submit(ling, self.speaker2id[voice], self.embed(prompt), self.embed(text), alpha=1.0 / speed, prosody=prosody, **extra)
 
     def speech(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, response_format: str = "wav", timeout: float = 120.0,
                pitch_shift: float = 0.0, pitch_scale: float = 1.0, energy_scale: float = 1.0) -> bytes:
-        fut = self.submit(text, voice, prompt, speed, pitch_shift, pitch_scale, energy_scale)
+        fut = self.submit(text, voice, prompt, speed, pitch_shift, pitch_scale, energy_scale, response_format=response_format)
         return encode_audio(fut.result(timeout=timeout), response_format, self.sample_rate)
 
 

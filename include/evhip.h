@@ -573,6 +573,79 @@ typedef struct ev_compare_result {
  * complete when the call returns, and stays valid across every other entry point until the next ev_compare or ev_destroy. */
 int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_t* lens, uint32_t flags, ev_compare_result* out);
 
+/* FLAC encoding (ev_flac): packed 16-bit PCM, or the fp32 that converts to it, -> one FLAC stream per segment, on the device: what a `flac`
+ * response carries.  The reference has no such stage (its compressed formats go through pydub / ffmpeg); FLAC is lossless, so a decoder returns
+ * every input sample.  Everything below is integer arithmetic with fixed tie rules: a restatement reproduces every output byte.
+ *   Input: B segments packed back to back, lens[b] >= 1 samples each, int16 (pcm_is_i16 != 0) or fp32.  An fp32 sample x converts as
+ *     t = x * 32768.0f (one fp32 product); NaN -> 0; otherwise t truncated toward zero and saturated to int32.  convert = EV_FLAC_WRAP keeps
+ *     the low 16 bits (two's complement): the bits of EV_FLAG_WANT_INT16, so a flac response decodes to what a pcm response carries.
+ *     convert = EV_FLAC_CLAMP clamps to [-32768, 32767]: ev_stitch's int16 rule.  convert is ignored for int16 input.
+ *   Stream of a segment of n samples: "fLaC"; the metadata block header 0x80 0x00 0x00 0x22 (last block, STREAMINFO, 34 bytes); STREAMINFO;
+ *     the frames; nothing else.  STREAMINFO, big-endian bit fields in order: min block size = max block size = N (16 bits each); min and
+ *     max frame size in bytes over this stream's frames (24 bits each); sample rate (20); channels - 1 = 0 (3); bits per sample - 1 = 15 (5);
+ *     n (36); MD5 = 16 zero bytes ("not known", which the format allows: an MD5 of the PCM is one serial chain per stream).
+ *   Blocks: N = block_size; ceil(n / N) frames; every frame holds N samples but the last, which holds the rest (1 .. N).
+ *   Frame header: 0xFF 0xF8 (sync, fixed block size); a byte of block-size code << 4 | sample-rate code; a byte 0x08 (channel code 0, sample-size
+ *     code 4 = 16 bits, a reserved 0 bit); the frame's index in its stream in the format's UTF-8-like coding (1 byte below 2^7, then 2 .. 6 bytes
+ *     carrying 11, 16, 21, 26, 31 bits); then, for a last frame shorter than N, its size - 1 in 8 bits (size <= 256, block-size code 6) or 16
+ *     bits (code 7); CRC-8 (polynomial 0x07, initial value 0, not reflected, no final xor) of the header bytes before it.  A frame of N samples
+ *     carries the table code 8 + log2(N / 256).  Sample-rate codes: 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10.
+ *   Subframe: a byte type << 1 (a 0 bit, the 6-bit type, a 0 bit: no wasted bits); types CONSTANT 0, VERBATIM 1, FIXED order o = 8 + o.  No LPC.
+ *   Choice, for a block of m samples:
+ *     1. All samples equal: CONSTANT, the sample in 16 bits (8 + 16 bits).
+ *     2. Otherwise for every order o = 0 .. min(max_fixed_order, m - 1): the residual r_i, i = o .. m - 1, is the o-th finite difference
+ *        (x_i; x_i - x_{i-1}; x_i - 2 x_{i-1} + x_{i-2}; x_i - 3 x_{i-1} + 3 x_{i-2} - x_{i-3}; x_i - 4 x_{i-1} + 6 x_{i-2} - 4 x_{i-3} + x_{i-4});
+ *        u_i = r_i >= 0 ? 2 r_i : -2 r_i - 1.  A partition order p is valid when p <= max_partition_order, m % 2^p == 0 and (m >> p) > o
+ *        (p = 0 always is); partition j = 0 .. 2^p - 1 holds the residuals of samples [j (m >> p), (j + 1)(m >> p)), without the o warm-up
+ *        samples in partition 0.  A partition of c residuals costs, with Rice parameter k = 0 .. 14, (k + 1) c + sum (u >> k) bits; it takes the
+ *        smallest cost, the smaller k on a tie.  Order p costs 4 + sum_j (4 + cost_j); the smallest wins, the smaller p on a tie.
+ *        bits_o = 8 + 16 o + 2 + that cost; the smallest wins, the smaller o on a tie.
+ *     3. If that minimum is >= 8 + 16 m: VERBATIM, the samples in 16 bits each.
+ *   FIXED subframe: the o warm-up samples in 16 bits each; 2 bits 00 (coding method 0: 4-bit parameters); p in 4 bits; per partition k in 4 bits
+ *     (the escape code 15 is never written), then per residual u >> k zero bits, a one bit, and the low k bits of u, most significant first.
+ *   Frame end: zero bits to the next byte boundary, then CRC-16 (polynomial 0x8005, initial value 0, not reflected, no final xor) of every byte
+ *     of the frame before it, high byte first.
+ * No atomics across blocks and nothing depends on the order of execution: a segment's bytes are the same alone or anywhere in a batch, from host or
+ * device memory, from int16 or from the fp32 that converts to it.  Needs no weights. */
+#define EV_FLAC_WRAP  0
+#define EV_FLAC_CLAMP 1
+#define EV_FLAC_MAX_SAMPLES (1 << 30)       /* per segment */
+typedef struct ev_flac_config {
+    uint32_t struct_size;          /* sizeof(ev_flac_config); any other value is rejected */
+    int32_t  sample_rate;          /* one of 8000, 16000, 22050, 24000, 32000, 44100, 48000 */
+    int32_t  block_size;           /* N: 256, 512, 1024, 2048 or 4096 */
+    int32_t  max_fixed_order;      /* in [0, 4] */
+    int32_t  max_partition_order;  /* in [0, 6] */
+    int32_t  convert;              /* EV_FLAC_WRAP or EV_FLAC_CLAMP; fp32 input only */
+} ev_flac_config;
+void ev_default_flac_config(ev_flac_config* cfg);      /* 16000, 4096, 4, 5, EV_FLAC_WRAP */
+/* Host only: an upper bound of the stream of a segment of n samples: 42 + (2 N + 15) per full frame + 2 r + 15 for a last frame of r < N samples
+ * (12 header bytes at most, one subframe byte, 16 bits a sample, two CRC bytes; VERBATIM is the largest subframe the choice can take).  -1 for n
+ * outside [1, EV_FLAC_MAX_SAMPLES] or a block_size outside the set. */
+int64_t ev_flac_bound(int64_t n, int block_size);
+
+typedef struct ev_flac_result {
+    uint32_t struct_size;          /* sizeof(ev_flac_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total_bytes;
+    int64_t  total_frames;
+    const uint8_t* bytes;          /* DEVICE, (total_bytes,): the streams back to back */
+    const int64_t* stream_offsets; /* (batch + 1,) HOST: stream b is bytes[stream_offsets[b] .. stream_offsets[b + 1]) */
+    const int64_t* stream_frames;  /* (batch,) HOST */
+    const int64_t* frame_offsets;  /* (total_frames + 1,) HOST: byte offsets of the frames in bytes, stream after stream; the last entry is total_bytes */
+    const uint8_t* frame_kind;     /* (total_frames,) HOST: 0 constant, 1 verbatim, 8 + o fixed */
+    const uint8_t* frame_porder;   /* (total_frames,) HOST: the partition order of a fixed subframe, else 0 */
+} ev_flac_result;
+/* pcm: a host pointer, or with EV_FLAG_DEVICE_INPUTS (the other flags are ignored) a device pointer on the handle's device; lens is always a HOST
+ * array, so an ev_result.wav with lens = mel_lens * 256, an ev_result.wav_i16 or an ev_stitch_result.wav_i16 goes straight in.  cfg NULL =
+ * ev_default_flac_config.  Rejected before anything is launched (message naming the field or segment; the previous result stays valid): a NULL
+ * h, pcm, lens or out, a wrong struct_size of cfg or out, B outside [1, 65535], lens[b] < 1 or > EV_FLAC_MAX_SAMPLES, a sample_rate outside the
+ * table, a block_size outside the set, max_fixed_order outside [0, 4], max_partition_order outside [0, 6], convert outside {0, 1}.  The frame
+ * sizes come back to the host between the encode and the gather (one synchronisation, as ev_stitch's cut).  The result lives in a workspace of
+ * its own and is complete when the call returns; it stays valid across every other entry point until the next ev_flac or ev_destroy -- the
+ * contract of ev_features_result. */
+int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 

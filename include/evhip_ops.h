@@ -245,6 +245,14 @@ int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const
 int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl,
                      const int32_t* fr, const float* tab, int F, int D, const int64_t* doc_lens, float* out, int16_t* out_i16, void* hip_stream);
 
+/* ev_flac's encode kernel on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_flac): the frames of B segments of pcm (int16 or
+ * fp32, packed back to back, lens[b] samples each) -> slots: frame f, counted segment after segment, starts at slots + f * (2 N + 24), N =
+ * cfg->block_size, and the kernel writes its sizes[f] bytes rounded up to a multiple of four there and nothing else.  sizes, kind and porder are
+ * HOST arrays of sum_b ceil(lens[b] / N) entries (kind: 0 constant, 1 verbatim, 8 + o fixed); lens is a HOST array; cfg NULL = the default.
+ * slots must be 4-byte aligned.  The call waits for the stream.  -2 for what ev_flac rejects. */
+int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, uint8_t* slots, int32_t* sizes,
+                      uint8_t* kind, uint8_t* porder, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
