@@ -163,6 +163,25 @@ class ev_flac_result(C.Structure):
     ]
 
 
+EV_LOUDNESS_MAX_SAMPLES, EV_LOUDNESS_TILE = 1 << 30, 4096
+EV_LOUDNESS_UNDEFINED, EV_LOUDNESS_BOOST_LIMITED, EV_LOUDNESS_PEAK_LIMITED = 1, 2, 4
+
+
+class ev_loudness_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("target_lufs", C.c_double), ("max_gain_db", C.c_double),
+                ("peak_ceiling", C.c_float), ("want_i16", C.c_int32)]
+
+
+class ev_loudness_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64),
+        ("wav", C.c_void_p), ("wav_i16", C.c_void_p),
+        ("loudness", C.POINTER(C.c_double)), ("rel_threshold", C.POINTER(C.c_double)), ("gain", C.POINTER(C.c_float)), ("peak", C.POINTER(C.c_float)),
+        ("flags", C.POINTER(C.c_uint8)), ("nonfinite", C.POINTER(C.c_int64)), ("block_offsets", C.POINTER(C.c_int64)),
+        ("block_ms", C.POINTER(C.c_double)), ("block_state", C.POINTER(C.c_uint8)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -239,6 +258,10 @@ SIGNATURES = {
     "ev_flac_bound": (C.c_int64, [C.c_int64, C.c_int]),      # host only
     # lens is a HOST array; pcm is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_flac": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_flac_config), C.c_uint32, C.POINTER(ev_flac_result)]),
+    "ev_default_loudness_config": (None, [C.POINTER(ev_loudness_config)]),
+    "ev_loudness_design": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),      # host only
+    # lens is a HOST array; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_loudness": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_loudness_config), C.c_uint32, C.POINTER(ev_loudness_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

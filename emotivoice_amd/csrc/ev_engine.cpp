@@ -18,6 +18,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -73,8 +75,8 @@ struct ev_handle {
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
     char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arena
-    char* arena[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
-                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise), [8] ev_compare (scratch only: its result is host memory), [9] ev_flac (likewise [3])
+    char* arena[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t arena_bytes[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [0] token-rate phase, [1] frame-rate phase + vocoder, [2] SimBERT,
+                                                                                                 // [3] ev_align (its results live here until the next ev_align), [4] ev_features, [5] ev_pitch, [6] ev_resample, [7] ev_stitch (likewise), [8] ev_compare (scratch only: its result is host memory), [9] ev_flac (likewise [3]), [10] ev_loudness (likewise)
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside arena 0
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -109,6 +111,9 @@ struct ev_handle {
     std::vector<float> cmp_max_d, cmp_peak_y; std::vector<int64_t> cmp_arg, cmp_nonf, cmp_chunk_offs;
     // ev_flac: the host halves of its result
     std::vector<int64_t> fl_stream_offs, fl_stream_frames, fl_frame_offs; std::vector<uint8_t> fl_kind, fl_porder;
+    // ev_loudness: the host halves of its result
+    std::vector<double> ld_loud, ld_rel, ld_ms; std::vector<float> ld_gain, ld_peak; std::vector<uint8_t> ld_flags, ld_state;
+    std::vector<int64_t> ld_nonf, ld_boffs;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;
@@ -1121,7 +1126,7 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 10; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
+    for (int i = 0; i < 11; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->rs_tab) (void)hipFree(h->rs_tab);
     if (h->st_tab) (void)hipFree(h->st_tab);
     if (h->feat_basis) (void)hipFree(h->feat_basis);
@@ -2676,6 +2681,208 @@ int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t*
     out->struct_size = sz; out->batch = B; out->total_bytes = pos; out->total_frames = NF; out->bytes = d_bytes;
     out->stream_offsets = h->fl_stream_offs.data(); out->stream_frames = h->fl_stream_frames.data(); out->frame_offsets = h->fl_frame_offs.data();
     out->frame_kind = h->fl_kind.data(); out->frame_porder = h->fl_porder.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- loudness normalisation (include/evhip.h: ev_loudness)
+static_assert(EV_LOUDNESS_TILE == LOUD_TILE, "include/evhip.h states the tile of ev_loudness.hip");
+void ev_default_loudness_config(ev_loudness_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c; c->sample_rate = 16000; c->target_lufs = NAN; c->max_gain_db = 20.0; c->peak_ceiling = (float)pow(10.0, -1.0 / 20.0); c->want_i16 = 0;
+}
+
+int ev_loudness_design(int sample_rate, double coef[10]) {
+    if (flac_rate_code(sample_rate) < 0 || !coef) return -1;
+    const double pi = 3.14159265358979323846, fs = (double)sample_rate;
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
+        coef[0] = (Vh + Vb * K / Q + K * K) / a0; coef[1] = 2.0 * (K * K - Vh) / a0; coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+        coef[3] = 2.0 * (K * K - 1.0) / a0; coef[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+        coef[5] = 1.0; coef[6] = -2.0; coef[7] = 1.0;
+        coef[8] = 2.0 * (K * K - 1.0) / a0; coef[9] = (1.0 - K / Q + K * K) / a0;
+    }
+    return 0;
+}
+
+// the kernels' constants: the coefficients and the powers A^(LOUD_RUN 2^d), d = 0 .. 8, of the cascade's transition matrix (transposed direct form II,
+// states: the shelf's two, then the high-pass's two), squared up in long double and rounded once
+static void loudness_coef(const double coef[10], LoudCoef* lc) {
+    for (int q = 0; q < 2; ++q) {
+        for (int i = 0; i < 3; ++i) lc->b[q][i] = coef[5 * q + i];
+        for (int i = 0; i < 2; ++i) lc->a[q][i] = coef[5 * q + 3 + i];
+    }
+    const long double a1 = coef[3], a2 = coef[4], c0 = coef[5], c1 = coef[6], c2 = coef[7], d1 = coef[8], d2 = coef[9];
+    long double M[16] = {-a1, 1, 0, 0, -a2, 0, 0, 0, c1 - d1 * c0, 0, -d1, 1, c2 - d2 * c0, 0, -d2, 0}, T[16];
+    auto square = [&]() {
+        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {
+            long double acc = 0;
+            for (int k = 0; k < 4; ++k) acc += M[i * 4 + k] * M[k * 4 + j];
+            T[i * 4 + j] = acc;
+        }
+        memcpy(M, T, sizeof M);
+    };
+    int run = 1;
+    while (run < LOUD_RUN) { square(); run *= 2; }
+    for (int d = 0; d < 9; ++d) {
+        for (int i = 0; i < 16; ++i) lc->P[d][i] = (double)M[i];
+        square();
+    }
+}
+
+static double loudness_lufs(double z) { return -0.691 + 10.0 * log10(z); }      // z = 0: -inf
+
+int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_loudness_config* cfg, uint32_t flags,
+                ev_loudness_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_loudness: wav is NULL");
+    if (!lens) return fail(h, "ev_loudness: lens is NULL");
+    if (!out) return fail(h, "ev_loudness: out is NULL");
+    if (out->struct_size != sizeof(ev_loudness_result))
+        return fail(h, "ev_loudness: out->struct_size %u != sizeof(ev_loudness_result) %zu", out->struct_size, sizeof(ev_loudness_result));
+    ev_loudness_config dflt;
+    if (!cfg) { ev_default_loudness_config(&dflt); cfg = &dflt; }
+    if (cfg->struct_size != sizeof(ev_loudness_config))
+        return fail(h, "ev_loudness: cfg->struct_size %u != sizeof(ev_loudness_config) %zu", cfg->struct_size, sizeof(ev_loudness_config));
+    const ev_loudness_config c = *cfg;
+    double coef[10];
+    if (ev_loudness_design(c.sample_rate, coef))
+        return fail(h, "ev_loudness: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
+    const bool measure_only = std::isnan(c.target_lufs);
+    if (!measure_only && !(c.target_lufs >= -70.0 && c.target_lufs <= 0.0))
+        return fail(h, "ev_loudness: target_lufs = %g is neither NaN (measure only) nor in [-70, 0]", c.target_lufs);
+    if (!(std::isfinite(c.max_gain_db) && c.max_gain_db >= 0.0)) return fail(h, "ev_loudness: max_gain_db = %g is not finite and >= 0", c.max_gain_db);
+    if (!(c.peak_ceiling > 0.f && c.peak_ceiling <= 1.f)) return fail(h, "ev_loudness: peak_ceiling = %g outside (0, 1]", (double)c.peak_ceiling);
+    if (B < 1 || B > 65535) return fail(h, "ev_loudness: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0 && !measure_only;
+    const int64_t step = c.sample_rate / 10, block = 4 * step;
+    int64_t total = 0, NT = 0, NB = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1) return fail(h, "ev_loudness: lens[%d] = %lld < 1", b, (long long)lens[b]);
+        if (lens[b] > EV_LOUDNESS_MAX_SAMPLES)
+            return fail(h, "ev_loudness: lens[%d] = %lld > EV_LOUDNESS_MAX_SAMPLES = %d", b, (long long)lens[b], EV_LOUDNESS_MAX_SAMPLES);
+        total += lens[b]; NT += (lens[b] + LOUD_TILE - 1) / LOUD_TILE; NB += lens[b] >= block ? (lens[b] - block) / step + 1 : 1;
+        if (NT > INT_MAX || (total + 1023) / 1024 > INT_MAX)
+            return fail(h, "ev_loudness: lens[%d] = %lld: more than %d tiles in one call", b, (long long)lens[b], INT_MAX);
+    }
+    std::vector<LoudTile> tiles;
+    tiles.reserve((size_t)NT);
+    std::vector<LoudSeg> segs((size_t)B);
+    std::vector<int64_t> offs((size_t)B + 1, 0);
+    for (int64_t b = 0, off = 0; b < B; off += lens[b], ++b) {
+        segs[(size_t)b] = LoudSeg{(int64_t)tiles.size(), (lens[b] + LOUD_TILE - 1) / LOUD_TILE};
+        offs[(size_t)b + 1] = off + lens[b];
+        for (int64_t i = 0; i < lens[b]; i += LOUD_TILE) tiles.push_back(LoudTile{off + i, i, (int32_t)std::min<int64_t>(LOUD_TILE, lens[b] - i), (int32_t)b});
+    }
+    LoudCoef lc;
+    loudness_coef(coef, &lc);
+    HIPCHK(h, hipSetDevice(h->device));
+    profiling_reset(h);
+    const size_t es = in16 ? sizeof(int16_t) : sizeof(float);
+    char* d_in = nullptr; LoudTile* d_tiles = nullptr; LoudSeg* d_segs = nullptr; LoudCoef* d_coef = nullptr; double *d_ends = nullptr, *d_init = nullptr;
+    LoudTileOut* d_outs = nullptr; int64_t* d_offs = nullptr; float *d_gain = nullptr, *d_wav = nullptr; int16_t* d_i16 = nullptr;
+    size_t need = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        ArenaPlan ap{h, 10, pass == 0};
+        if (pass == 1 && arena_reserve(h, 10, need)) return -1;
+        if (!dev_in) d_in = ap.arr<char>((size_t)total * es);
+        d_tiles = ap.arr<LoudTile>((size_t)NT); d_segs = ap.arr<LoudSeg>((size_t)B); d_coef = ap.arr<LoudCoef>(1);
+        d_ends = ap.arr<double>(4 * (size_t)NT); d_init = ap.arr<double>(4 * (size_t)NT); d_outs = ap.arr<LoudTileOut>((size_t)NT);
+        d_offs = ap.arr<int64_t>((size_t)B + 1); d_gain = ap.arr<float>((size_t)B);
+        if (!measure_only) d_wav = ap.arr<float>((size_t)total);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
+        need = ap.off;
+    }
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_in, wav, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_tiles, tiles.data(), (size_t)NT * sizeof(LoudTile), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_segs, segs.data(), (size_t)B * sizeof(LoudSeg), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_coef, &lc, sizeof lc, hipMemcpyHostToDevice, h->stream));
+    const void* x = dev_in ? wav : (const void*)d_in;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "loudness_measure", 60.0 * (double)total, 2.0 * (double)total * (double)es + (double)NT * (64.0 + sizeof(LoudTileOut)));
+        if (launch_loudness_measure(x, in16, d_tiles, NT, d_segs, B, d_coef, (int)step, d_ends, d_init, d_outs, h->stream))
+            return fail(h, "ev_loudness: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<LoudTileOut> touts((size_t)NT);
+    HIPCHK(h, hipMemcpyAsync(touts.data(), d_outs, (size_t)NT * sizeof(LoudTileOut), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the host half: step sums from the tiles' in ascending tile order, blocks, the two gates, the gain
+    std::vector<double> loud((size_t)B), rel((size_t)B), ms; std::vector<float> gain((size_t)B), peak((size_t)B); std::vector<uint8_t> fl((size_t)B), state;
+    std::vector<int64_t> nonf((size_t)B), boffs((size_t)B + 1, 0);
+    ms.reserve((size_t)NB); state.reserve((size_t)NB);
+    std::vector<double> S;
+    const double ninf = -std::numeric_limits<double>::infinity();
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lens[b], nbins = (n + step - 1) / step;
+        S.assign((size_t)nbins, 0.0);
+        float pk = 0.f; int64_t nf = 0;
+        for (int64_t t = 0; t < segs[(size_t)b].ntiles; ++t) {
+            const LoudTileOut& o = touts[(size_t)(segs[(size_t)b].tile0 + t)];
+            const int64_t pos = t * LOUD_TILE, tb0 = pos / step, nsl = (std::min<int64_t>(pos + LOUD_TILE, n) - 1) / step - tb0 + 1;
+            for (int64_t k = 0; k < nsl; ++k) S[(size_t)(tb0 + k)] += o.sum[k];
+            pk = std::max(pk, o.peak); nf += o.nonfinite;
+        }
+        const size_t j0 = ms.size();
+        if (n >= block) {
+            const int64_t nblk = (n - block) / step + 1;
+            for (int64_t j = 0; j < nblk; ++j) ms.push_back((((S[(size_t)j] + S[(size_t)j + 1]) + S[(size_t)j + 2]) + S[(size_t)j + 3]) / (double)block);
+        } else {
+            double acc = 0.0;
+            for (int64_t m = 0; m < nbins; ++m) acc += S[(size_t)m];
+            ms.push_back(acc / (double)n);
+        }
+        const size_t j1 = ms.size();
+        state.resize(j1, 0);
+        double acc = 0.0; int64_t cnt = 0;
+        for (size_t j = j0; j < j1; ++j) if (loudness_lufs(ms[j]) > -70.0) { state[j] = 1; acc += ms[j]; ++cnt; }
+        double L = ninf, gamma = ninf;
+        if (cnt > 0) {
+            gamma = loudness_lufs(acc / (double)cnt) - 10.0;
+            acc = 0.0; cnt = 0;
+            for (size_t j = j0; j < j1; ++j) if (state[j] == 1 && loudness_lufs(ms[j]) > gamma) { state[j] = 2; acc += ms[j]; ++cnt; }
+            if (cnt > 0) L = loudness_lufs(acc / (double)cnt);
+        }
+        uint8_t f = L == ninf ? EV_LOUDNESS_UNDEFINED : 0;
+        double g = 1.0;
+        if (!measure_only) {
+            if (L != ninf) g = pow(10.0, (c.target_lufs - L) / 20.0);
+            const double gmax = pow(10.0, c.max_gain_db / 20.0);
+            if (g > gmax) { g = gmax; f |= EV_LOUDNESS_BOOST_LIMITED; }
+            if (pk > 0.f) {
+                const double gpk = (double)c.peak_ceiling / (double)pk;
+                if (g > gpk) { g = gpk; f |= EV_LOUDNESS_PEAK_LIMITED; }
+            }
+        }
+        loud[(size_t)b] = L; rel[(size_t)b] = gamma; gain[(size_t)b] = (float)g; peak[(size_t)b] = pk; fl[(size_t)b] = f; nonf[(size_t)b] = nf;
+        boffs[(size_t)b + 1] = (int64_t)j1;
+    }
+    if (!measure_only) {
+        HIPCHK(h, hipMemcpyAsync(d_offs, offs.data(), ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_gain, gain.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        {
+            KScope ks(h, "loudness_gain", (double)total, (double)total * ((double)es + (i16 ? 6.0 : 4.0)));
+            if (launch_loudness_gain(x, in16, d_offs, B, d_gain, total, d_wav, i16 ? d_i16 : nullptr, h->stream))
+                return fail(h, "ev_loudness: the kernels do not build this shape");
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    region_end(h, "total");
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // the uploads above read host vectors that end with this call
+    profiling_collect(h);
+    h->ld_loud.swap(loud); h->ld_rel.swap(rel); h->ld_ms.swap(ms); h->ld_gain.swap(gain); h->ld_peak.swap(peak); h->ld_flags.swap(fl); h->ld_state.swap(state);
+    h->ld_nonf.swap(nonf); h->ld_boffs.swap(boffs);
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = sz; out->batch = B; out->total = total; out->wav = measure_only ? nullptr : d_wav; out->wav_i16 = i16 ? d_i16 : nullptr;
+    out->loudness = h->ld_loud.data(); out->rel_threshold = h->ld_rel.data(); out->gain = h->ld_gain.data(); out->peak = h->ld_peak.data();
+    out->flags = h->ld_flags.data(); out->nonfinite = h->ld_nonf.data(); out->block_offsets = h->ld_boffs.data(); out->block_ms = h->ld_ms.data();
+    out->block_state = h->ld_state.data();
     return 0;
 }
 

@@ -348,4 +348,21 @@ int launch_flac_encode(const FlacParams& p, int64_t n_frames, hipStream_t s);   
 void launch_flac_gather(const uint8_t* scratch, int stride, const FlacFrame* frames, int64_t n_frames, const int32_t* sizes, const int64_t* frame_offs,
                         const uint8_t* headers, uint8_t* out, hipStream_t s);
 
+// ev_loudness (ev_loudness.hip): packed segments -> per tile of LOUD_TILE samples (counted from its segment's start) the K-weighted sums of y^2 over
+// the 100 ms steps it reaches into, its sample peak and its count of non-finite samples; then, with one gain per segment, the scaled waveform.
+constexpr int LOUD_TILE = 4096, LOUD_RUN = 16, LOUD_SLOTS = 8;
+struct LoudTile { int64_t src, pos; int32_t n, seg; };      // first sample in the packed input, the same counted in its segment, 1 .. LOUD_TILE samples, the segment
+struct LoudSeg { int64_t tile0, ntiles; };                  // the segment's tiles are [tile0, tile0 + ntiles)
+struct LoudCoef {
+    double b[2][3], a[2][2];      // shelf, high-pass: b0 b1 b2, a1 a2
+    double P[9][16];              // P[d] = A^(LOUD_RUN 2^d), row-major, A the 4 x 4 transition matrix of the cascade; P[8] = A^LOUD_TILE
+};
+struct LoudTileOut { double sum[LOUD_SLOTS]; float peak; int32_t nonfinite; };      // sum[k]: step pos / step + k of the segment; unused slots are 0
+// ends and init are (n_tiles, 4) scratch; step is sample_rate / 10.  0, or -1 for a shape the kernels do not build.
+int launch_loudness_measure(const void* wav, int is16, const LoudTile* tiles, int64_t n_tiles, const LoudSeg* segs, int B, const LoudCoef* coef, int step,
+                            double* ends, double* init, LoudTileOut* outs, hipStream_t s);
+// offs: (B + 1,) device; out must be 16-byte aligned; out_i16 may be NULL
+int launch_loudness_gain(const void* wav, int is16, const int64_t* offs, int B, const float* gain, int64_t total, float* out, int16_t* out_i16,
+                         hipStream_t s);
+
 }  // namespace ev

@@ -99,6 +99,7 @@ class EVEngine:
         self.last_stitch: Optional[_ffi.ev_stitch_result] = None
         self.last_compare: Optional[_ffi.ev_compare_result] = None
         self.last_flac: Optional[_ffi.ev_flac_result] = None
+        self.last_loudness: Optional[_ffi.ev_loudness_result] = None
 
     # -- lifecycle
     def close(self):
@@ -414,9 +415,9 @@ class EVEngine:
         self.last_stitch = res
         return res
 
-    def stitch_to_numpy(self, res: _ffi.ev_stitch_result, int16_only: bool = False) -> Dict[str, object]:
+    def stitch_to_numpy(self, res: _ffi.ev_stitch_result, int16_only: bool = False, skip_wav: bool = False) -> Dict[str, object]:
         """One D2H copy of the fp32 documents (or, with ``int16_only`` and a result that has them, of the int16 ones only; without it both) and
-        the host arrays of the result."""
+        the host arrays of the result.  ``skip_wav``: the host arrays only."""
         D, S = res.batch_docs, res.batch_segs
         lens = np.array([res.doc_lens[d] for d in range(D)], np.int64)
         offs = np.array([res.doc_offsets[d] for d in range(D + 1)], np.int64)
@@ -425,6 +426,8 @@ class EVEngine:
                                       seg_start=np.array([res.seg_start[s] for s in range(S)], np.int64),
                                       seg_end=np.array([res.seg_end[s] for s in range(S)], np.int64),
                                       seg_peak=np.array([res.seg_peak[s] for s in range(S)], np.float32))
+        if skip_wav:
+            return out
         if not (int16_only and res.wav_i16):
             out["wav"] = self.d2h(res.wav, (res.total_samples,), np.float32)
             out["docs"] = [out["wav"][offs[d]:offs[d + 1]] for d in range(D)]
@@ -445,7 +448,7 @@ class EVEngine:
         flat = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in wavs]))
         return self.stitch_to_numpy(self.stitch_raw(len(wavs), flat.ctypes.data, offs, lens, seg_doc, pause_after, sc))
 
-    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None) -> Dict[str, object]:
+    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
@@ -453,7 +456,10 @@ class EVEngine:
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
         config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
         flac=True adds flac_list, one FLAC stream (``bytes``) per document, encoded on the device from ev_stitch's int16 documents (it turns
-        config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to)."""
+        config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to).
+        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every document is normalised on the device after ev_stitch
+        (ev_loudness: one gain per document, so the balance between its sentences stays) and before ev_flac; ``documents`` (int16 by the
+        clamping rule with config.want_int16) then hold the normalised audio and ``loudness`` the per-document figures."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
@@ -470,13 +476,27 @@ class EVEngine:
         up = self.shapes.upsample_factor
         mel_offs = np.array([res.mel_offsets[b] for b in range(S + 1)], np.int64)
         st = self.stitch_raw(S, res.wav, mel_offs[:-1] * up, np.diff(mel_offs) * up, seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
-        out = self.stitch_to_numpy(st, int16_only=sc.want_int16)
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=loudness is not None)
+        empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
+        pcm_i16 = st.wav_i16
+        if loudness is not None:
+            from .loudness import as_config
+            if empty:
+                raise ValueError("loudness: document %d is empty after the cut" % empty[0])
+            ld = self.loudness_raw(st.batch_docs, st.wav, False, out["doc_lens"], as_config(loudness, int(sc.sample_rate), sc.want_int16),
+                                   _ffi.EV_FLAG_DEVICE_INPUTS)
+            norm = self.loudness_to_numpy(ld, int16_only=sc.want_int16)
+            if "wav" in norm:
+                out["wav"], out["docs"] = norm.pop("wav"), norm.pop("wav_list")
+            if "wav_i16" in norm:
+                out["wav_i16"], out["docs_i16"] = norm.pop("wav_i16"), norm.pop("wav_i16_list")
+            out["loudness"] = norm
+            pcm_i16 = ld.wav_i16
         if flac:
             from .flac import FlacConfig
-            empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
             if empty:
                 raise ValueError("flac: document %d is empty after the cut" % empty[0])
-            fr = self.flac_raw(st.batch_docs, st.wav_i16, True, out["doc_lens"], FlacConfig(sample_rate=int(sc.sample_rate)), _ffi.EV_FLAG_DEVICE_INPUTS)
+            fr = self.flac_raw(st.batch_docs, pcm_i16, True, out["doc_lens"], FlacConfig(sample_rate=int(sc.sample_rate)), _ffi.EV_FLAG_DEVICE_INPUTS)
             out["flac_list"] = self.flac_to_numpy(fr)["streams"]
         sr = float(sc.sample_rate)
         start = out["seg_pos"] / sr
@@ -576,15 +596,16 @@ class EVEngine:
         lens = np.array([a.size for a in arrs], np.int64)
         return self.flac_to_numpy(self.flac_raw(len(arrs), flat.ctypes.data, is16, lens, fc))
 
-    def _flac_of_result(self, res: _ffi.ev_result, mask) -> List[Optional[bytes]]:
+    def _flac_of_result(self, res: _ffi.ev_result, mask, pcm_i16: Optional[int] = None) -> List[Optional[bytes]]:
         """The utterances of an ev_result that ``mask`` selects, encoded from the fp32 device waveform with the wrapping conversion: one ev_flac
-        call per run of consecutive selected utterances (ev_flac takes its segments back to back)."""
+        call per run of consecutive selected utterances (ev_flac takes its segments back to back).  ``pcm_i16``: a device int16 waveform in
+        the same packing (ev_loudness's) to encode instead."""
         from .flac import FlacConfig
         B, up = res.batch, self.shapes.upsample_factor
         sel = np.ones(B, bool) if mask is True else np.asarray(mask, bool)
         if sel.shape != (B,):
             raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (B, sel.shape))
-        if sel.any() and not res.wav:
+        if sel.any() and not (res.wav or pcm_i16):
             raise ValueError("flac needs the vocoder's waveform")
         fc = FlacConfig(sample_rate=int(self.shapes.sr), convert="wrap")
         mel_offs = np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64)
@@ -597,10 +618,70 @@ class EVEngine:
             e = b
             while e < B and sel[e]:
                 e += 1
-            fr = self.flac_raw(e - b, res.wav + 4 * int(mel_offs[b]) * up, False, np.diff(mel_offs[b:e + 1]) * up, fc, _ffi.EV_FLAG_DEVICE_INPUTS)
+            src = pcm_i16 + 2 * int(mel_offs[b]) * up if pcm_i16 else res.wav + 4 * int(mel_offs[b]) * up
+            fr = self.flac_raw(e - b, src, bool(pcm_i16), np.diff(mel_offs[b:e + 1]) * up, fc, _ffi.EV_FLAG_DEVICE_INPUTS)
             out[b:e] = self.flac_to_numpy(fr)["streams"]
             b = e
         return out
+
+    # -- loudness normalisation (ev_loudness): BS.1770 programme loudness, one gain per segment and the scaled waveform, on the device
+    def loudness_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, config=None, flags: int = 0) -> _ffi.ev_loudness_result:
+        """ev_loudness (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens is a host array.
+        config: an emotivoice_amd.loudness.LoudnessConfig, an _ffi.ev_loudness_config or None (the library's default: 16 kHz, measure only).
+        The returned struct's device waveforms and host arrays stay valid until the next loudness call on this engine."""
+        ln = np.ascontiguousarray(lens, np.int64)
+        if ln.size != B:
+            raise ValueError("lens must have B = %d entries" % B)
+        c = config.validate().to_struct() if hasattr(config, "to_struct") else config
+        res = _ffi.ev_loudness_result()
+        res.struct_size = C.sizeof(_ffi.ev_loudness_result)
+        self._check(self._lib.ev_loudness(self._h, B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, ln.ctypes.data_as(C.c_void_p),
+                                          C.byref(c) if c is not None else None, flags, C.byref(res)))
+        res._lens = ln.copy()      # the packing of res.wav / res.wav_i16, for loudness_to_numpy
+        self.last_loudness = res
+        return res
+
+    def loudness_to_numpy(self, res: _ffi.ev_loudness_result, int16_only: bool = False, lens=None) -> Dict[str, object]:
+        """Copies of the result's host arrays and, unless the call only measured, one D2H copy of the fp32 output (with ``int16_only`` and a
+        result that has it, of the int16 output only; without it both).  block_ms / block_state: one array per segment.  lens: the call's
+        lens, which cut the output into wav_list / wav_i16_list (None: the ones loudness_raw kept with the struct)."""
+        B = res.batch
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, (n,)).astype(dt, copy=True)      # noqa: E731
+        boffs = arr(res.block_offsets, B + 1, np.int64)
+        nb = int(boffs[-1])
+        ms, state = arr(res.block_ms, nb, np.float64), arr(res.block_state, nb, np.uint8)
+        out: Dict[str, object] = dict(loudness=arr(res.loudness, B, np.float64), rel_threshold=arr(res.rel_threshold, B, np.float64),
+                                      gain=arr(res.gain, B, np.float32), peak=arr(res.peak, B, np.float32), flags=arr(res.flags, B, np.uint8),
+                                      nonfinite=arr(res.nonfinite, B, np.int64), block_offsets=boffs,
+                                      block_ms=[ms[boffs[b]:boffs[b + 1]] for b in range(B)], block_state=[state[boffs[b]:boffs[b + 1]] for b in range(B)])
+        if not res.wav:
+            return out
+        lens = np.asarray(res._lens if lens is None else lens, np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        if not (int16_only and res.wav_i16):
+            out["wav"] = self.d2h(res.wav, (int(res.total),), np.float32)
+            out["wav_list"] = [out["wav"][offs[b]:offs[b + 1]] for b in range(B)]
+        if res.wav_i16:
+            out["wav_i16"] = self.d2h(res.wav_i16, (int(res.total),), np.int16)
+            out["wav_i16_list"] = [out["wav_i16"][offs[b]:offs[b + 1]] for b in range(B)]
+        return out
+
+    def loudness(self, wavs: Sequence[np.ndarray], **config) -> Dict[str, object]:
+        """Host signals -> their loudness and, with a target, the normalised signals.  wavs: one 1-D array per segment, all int16 or all
+        floating, at any rate of the table (recordings as well as synthesis); further keywords: the fields of
+        emotivoice_amd.loudness.LoudnessConfig (no target_lufs: measure only).  Needs no weights."""
+        from .loudness import LoudnessConfig
+        lc = LoudnessConfig(**config).validate()
+        if not len(wavs):
+            raise ValueError("wavs must hold at least one segment")
+        arrs = [np.asarray(x) for x in wavs]
+        is16 = arrs[0].dtype == np.int16
+        for s, a in enumerate(arrs):
+            if a.ndim != 1 or a.size < 1 or (a.dtype == np.int16) != is16 or not (is16 or np.issubdtype(a.dtype, np.floating)):
+                raise ValueError("segment %d: non-empty 1-D arrays, all int16 or all floating" % s)
+        flat = np.ascontiguousarray(np.concatenate([a.astype(np.int16 if is16 else np.float32, copy=False) for a in arrs]))
+        lens = np.array([a.size for a in arrs], np.int64)
+        return self.loudness_to_numpy(self.loudness_raw(len(arrs), flat.ctypes.data, is16, lens, lc))
 
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)
@@ -613,16 +694,16 @@ class EVEngine:
             self._check(self._lib.ev_memcpy_d2h(self._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(dev_ptr), out.nbytes))
         return out
 
-    def result_to_numpy(self, res: _ffi.ev_result, want_int16: bool = False) -> Dict[str, object]:
+    def result_to_numpy(self, res: _ffi.ev_result, want_int16: bool = False, skip_wav: bool = False) -> Dict[str, object]:
         B = res.batch
         mel_lens = np.array([res.mel_lens[b] for b in range(B)], np.int32)
         mel_offs = np.array([res.mel_offsets[b] for b in range(B + 1)], np.int64)
         up = self.shapes.upsample_factor
         out: Dict[str, object] = dict(mel_lens=mel_lens, mel_offsets=mel_offs)
-        if res.wav:
+        if res.wav and not skip_wav:
             out["wav"] = self.d2h(res.wav, (res.total_samples,), np.float32)
             out["wav_list"] = [out["wav"][mel_offs[b] * up:mel_offs[b + 1] * up] for b in range(B)]
-        if want_int16 and res.wav_i16:
+        if want_int16 and res.wav_i16 and not skip_wav:
             out["wav_i16"] = self.d2h(res.wav_i16, (res.total_samples,), np.int16)
         if res.mel:
             out["mel"] = self.d2h(res.mel, (res.total_frames, self.shapes.n_mels), np.float32)
@@ -659,16 +740,24 @@ class EVEngine:
         return res, cu
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
         for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
         flac: None, True or one boolean per utterance: adds flac_list, the FLAC stream (``bytes``) of every selected utterance and None
         for the others, encoded on the device from the fp32 waveform with the wrapping conversion -- a stream decodes to
-        wav_float_to_int16(wav_list[b])."""
+        wav_float_to_int16(wav_list[b]).
+        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every utterance is normalised on the device
+        (ev_loudness on the vocoder's waveform).  wav / wav_list then hold the normalised audio, want_int16 adds wav_i16 / wav_int16_list
+        by the clamping rule (not EV_FLAG_WANT_INT16's wrapping cast), ``loudness`` holds the per-utterance figures, and flac encodes the
+        normalised int16: a stream decodes to wav_int16_list[b]."""
         if flac is not None and flac is not False and not vocoder:
             raise ValueError("flac needs the vocoder's waveform")
+        if loudness is not None:
+            if not vocoder:
+                raise ValueError("loudness needs the vocoder's waveform")
+            return self._synthesize_normalised(utts, alpha, want_int16, forced_durations, prosody, flac, loudness)
         flags = 0
         if want_int16:
             flags |= _ffi.EV_FLAG_WANT_INT16
@@ -679,6 +768,26 @@ class EVEngine:
         out["cu_seqlens"] = cu
         if flac is not None and flac is not False:
             out["flac_list"] = self._flac_of_result(res, flac)
+        return out
+
+    def _synthesize_normalised(self, utts, alpha, want_int16, forced_durations, prosody, flac, loudness) -> Dict[str, object]:
+        """``synthesize`` with ``loudness=``: the synthesis call, ev_loudness on its device waveform, D2H copies of the normalised audio only."""
+        from .loudness import as_config
+        want_flac = flac is not None and flac is not False
+        lc = as_config(loudness, int(self.shapes.sr), want_int16 or want_flac)
+        res, cu = self._synthesize_call(utts, alpha, 0, forced_durations, prosody)
+        out = self.result_to_numpy(res, skip_wav=True)
+        out["cu_seqlens"] = cu
+        B, up = res.batch, self.shapes.upsample_factor
+        ld = self.loudness_raw(B, res.wav, False, np.diff(out["mel_offsets"]) * up, lc, _ffi.EV_FLAG_DEVICE_INPUTS)
+        norm = self.loudness_to_numpy(ld)
+        out["wav"], out["wav_list"] = norm.pop("wav"), norm.pop("wav_list")
+        i16, i16_list = norm.pop("wav_i16", None), norm.pop("wav_i16_list", None)
+        if want_int16 or want_flac:
+            out["wav_i16"], out["wav_int16_list"] = i16, i16_list
+        out["loudness"] = norm
+        if want_flac:
+            out["flac_list"] = self._flac_of_result(res, flac, pcm_i16=ld.wav_i16)
         return out
 
     def vocoder(self, mels: Sequence[np.ndarray], want_int16: bool = False) -> Dict[str, object]:

@@ -184,8 +184,12 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
     with open(args.text_file, "r", encoding="utf-8") as f:
         lines = f.readlines()
     eng = gen._ensure_engine()
+    synthesize = eng.synthesize
+    if getattr(args, "loudness", None) is not None:      # every utterance normalised on the device (ev_loudness) before it is written
+        import functools
+        synthesize = functools.partial(eng.synthesize, loudness=float(args.loudness))
     try:
-        stats = run_chunk(lines, start_idx, chunk_num, synthesize=eng.synthesize, embed=embed, g2p=g2p, token2id=token2id,
+        stats = run_chunk(lines, start_idx, chunk_num, synthesize=synthesize, embed=embed, g2p=g2p, token2id=token2id,
                           id2speaker=id2speaker, output_dir=output_dir, sampling_rate=int(getattr(config, "sampling_rate", gen.shapes.sr)),
                           batch=args.batch, g2p_map=pool.map if pool is not None else None, n_speaker=int(config.speaker_n_labels))
     finally:
@@ -215,6 +219,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--synthetic-weights", action="store_true", help="seeded synthetic checkpoint instead of <logdir>/ckpt/<checkpoint>")
     p.add_argument("--verify-precision", action="store_true",
                    help="with --precision mx: measure the checkpoint against a strict engine at load time and run the cheapest mode within 1e-3 of it")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="normalise every utterance on the device to this programme loudness (ITU-R BS.1770, e.g. -16), at most +20 dB and with the "
+                        "sample peak held at -1 dBFS; default: the vocoder's level, untouched")
     return p
 
 

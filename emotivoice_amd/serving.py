@@ -297,22 +297,36 @@ def _resolve(future: Future, result=None, exception: Optional[BaseException] = N
         pass
 
 
-def engine_synth_fn(engine) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
-    """``synth_fn`` of a DynamicBatcher for an EVEngine."""
-    return lambda utts, alpha: engine.synthesize(utts, alpha=alpha)["wav_list"]
+def _loudness_kw(loudness) -> dict:
+    """``loudness`` of the engine_*_synth_fn factories: a service-level setting (a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig),
+    not a request field, so that a batch stays homogeneous and the request schema stays the reference's.  None: synthesize is called exactly
+    as before."""
+    return {} if loudness is None else dict(loudness=loudness)
 
 
-def engine_prosody_synth_fn(engine) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
-    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch."""
-    return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies)["wav_list"]
+def engine_synth_fn(engine, loudness=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
+    """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness)."""
+    kw = _loudness_kw(loudness)
+    return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
 
 
-def engine_flac_synth_fn(engine) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_prosody_synth_fn(engine, loudness=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``: as
+    ``engine_synth_fn``."""
+    kw = _loudness_kw(loudness)
+    return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
+
+
+def engine_flac_synth_fn(engine, loudness=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
-    second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody."""
+    second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
+    streams then carry the normalised int16 (the clamping conversion)."""
+    lkw = _loudness_kw(loudness)
+
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)
+        kw.update(lkw)
         out = engine.synthesize(utts, flac=list(mask), **kw)
         return [f if m else w for f, w, m in zip(out["flac_list"], out["wav_list"], mask)]
     return fn

@@ -646,6 +646,82 @@ typedef struct ev_flac_result {
  * contract of ev_features_result. */
 int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out);
 
+/* Loudness normalisation (ev_loudness): packed segments -> their programme loudness after ITU-R BS.1770 / EBU R 128 (K-weighted, gated, in LUFS),
+ * their sample peak, one gain per segment that brings it to a target within two limits, and the scaled waveform, on the device: it sits between
+ * the vocoder (or ev_stitch) and ev_flac.  The reference has no such stage; the arithmetic is the one specified here.
+ *   Filter design (ev_loudness_design, fp64): two biquads from the analogue prototypes that reproduce the standard's 48 kHz table.  With
+ *     K = tan(pi f0 / fs) and a0 = 1 + K / Q + K^2:
+ *     shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G / 20), Vb = Vh^0.4996667741545416;
+ *       b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0, a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0];
+ *     high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1] (not normalised, as in the standard), a as above with this K, Q.
+ *     coef = shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2.  At 48000 Hz these are the standard's printed coefficients.
+ *   Measurement, all of it fp64.  An int16 sample is s / 32768, an fp32 sample is widened.  A non-finite sample (NaN, +-inf) counts once in
+ *     nonfinite[b] and enters the measurement as 0.  Each segment is filtered from a zero state, shelf then high-pass, giving y.
+ *     step = fs / 10, block = 4 step.  n >= block: nblk = (n - block) / step + 1 blocks, block j covers [j step, j step + block), z_j = the mean
+ *     of y^2 over it; samples after the last whole block are not measured.  n < block: one block of all n samples, so that a short word still
+ *     has a level.  l_j = -0.691 + 10 log10(z_j).  Absolute gate: keep l_j > -70.  Relative gate: Gamma = -0.691 + 10 log10(mean z over the
+ *     blocks the absolute gate kept) - 10; keep the blocks that also have l_j > Gamma.  loudness[b] = -0.691 + 10 log10(mean z over the blocks
+ *     both gates kept); no block past the absolute gate: loudness[b] = rel_threshold[b] = -inf.
+ *     peak[b] = max |x| over the finite samples: the SAMPLE peak, exact in fp32 (int16: |s| / 32768).  It is not the true (inter-sample) peak of
+ *     BS.1770 annex 2: a ceiling of -1 dBFS on it leaves the usual margin for that, it does not measure it.
+ *   Sums.  y^2 is summed per step [m step, (m + 1) step).  The device forms the sum of a step inside each tile of EV_LOUDNESS_TILE samples
+ *     (counted from the segment's start) that it reaches into, in an order fixed by the sample's index in its segment; the host adds a step's
+ *     tile sums in ascending tile order, a block's four steps in ascending order, then divides by the block's samples.  A float64 restatement
+ *     that filters sequentially therefore agrees to rounding (block_ms to about 1e-12 relative), not to the bit.
+ *   Gain (host, C double, operations in the order written).  target_lufs NaN = measure only: gain[b] = 1, no output.  Otherwise
+ *     1. g = 1 if loudness[b] is -inf (flag EV_LOUDNESS_UNDEFINED, which a measure-only call sets as well), 2. else g = 10^((target - L) / 20);
+ *     3. g = min(g, 10^(max_gain_db / 20)) (flag EV_LOUDNESS_BOOST_LIMITED when that lowers g); 4. if peak[b] > 0: g = min(g, (double)peak_ceiling /
+ *     (double)peak[b]) (flag EV_LOUDNESS_PEAK_LIMITED when that lowers g); 5. gain[b] = (float)g.
+ *   Output (skipped for measure only: wav and wav_i16 are NULL then): out = x * gain[b], one rounded fp32 product of the fp32 sample or of
+ *     (float)s / 32768.0f; where gain[b] == 1.0f the source bits pass through.  want_i16: ev_stitch's rule, (int)(out * 32768.0f) truncated toward
+ *     zero, then clamped to [-32768, 32767]; it never wraps; NaN -> 0.
+ * No atomics; every reduction's order is fixed by (segment, index) alone: a segment gives the same bits, doubles included, alone or anywhere in a
+ * batch, from host or device memory, as int16 or as the equal floats.  Needs no weights. */
+#define EV_LOUDNESS_MAX_SAMPLES (1 << 30)   /* per segment */
+#define EV_LOUDNESS_TILE 4096               /* samples */
+#define EV_LOUDNESS_UNDEFINED     1         /* flags[b]: no block passed the absolute gate; the gain is 1 before the peak limit */
+#define EV_LOUDNESS_BOOST_LIMITED 2         /* max_gain_db lowered the gain */
+#define EV_LOUDNESS_PEAK_LIMITED  4         /* peak_ceiling lowered the gain */
+typedef struct ev_loudness_config {
+    uint32_t struct_size;          /* sizeof(ev_loudness_config); any other value is rejected */
+    int32_t  sample_rate;          /* one of 8000, 16000, 22050, 24000, 32000, 44100, 48000 (ev_flac's table; all divisible by 10) */
+    double   target_lufs;          /* finite in [-70, 0], or NaN: measure only */
+    double   max_gain_db;          /* finite, >= 0: the largest boost */
+    float    peak_ceiling;         /* linear, in (0, 1]: the sample peak of the output stays at or below it (to fp32 rounding) */
+    int32_t  want_i16;             /* != 0: also the int16 output */
+} ev_loudness_config;
+void ev_default_loudness_config(ev_loudness_config* cfg);      /* 16000, NaN (measure only), 20.0, (float)10^(-1/20) = -1 dBFS, 0 */
+/* Host only: the ten coefficients above.  0, or -1 for a sample_rate outside the table. */
+int ev_loudness_design(int sample_rate, double coef[10]);
+
+typedef struct ev_loudness_result {
+    uint32_t struct_size;          /* sizeof(ev_loudness_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* samples: the sum of lens */
+    const float*   wav;            /* DEVICE, (total,), packed as the input; NULL for measure only */
+    const int16_t* wav_i16;        /* DEVICE, the same layout; NULL without want_i16 or for measure only */
+    const double*  loudness;       /* (batch,) HOST, LUFS; -inf when no block passed the absolute gate */
+    const double*  rel_threshold;  /* (batch,) HOST: Gamma, or -inf */
+    const float*   gain;           /* (batch,) HOST, linear */
+    const float*   peak;           /* (batch,) HOST: the sample peak of the input */
+    const uint8_t* flags;          /* (batch,) HOST: EV_LOUDNESS_* */
+    const int64_t* nonfinite;      /* (batch,) HOST */
+    const int64_t* block_offsets;  /* (batch + 1,) HOST: the blocks of segment b are [block_offsets[b], block_offsets[b + 1]) */
+    const double*  block_ms;       /* (block_offsets[batch],) HOST: z_j, segment after segment */
+    const uint8_t* block_state;    /* likewise: 0 dropped by the absolute gate, 1 dropped by the relative gate, 2 counted */
+} ev_loudness_result;
+/* wav: a host pointer, or with EV_FLAG_DEVICE_INPUTS (the other flags are ignored) a device pointer on the handle's device, which must not be the
+ * wav of the previous ev_loudness_result; lens is always a HOST array, so an ev_result.wav with lens = mel_lens * 256 or an ev_stitch_result.wav
+ * goes straight in, and the result's wav_i16 goes straight into ev_flac.  cfg NULL = ev_default_loudness_config.  Rejected before anything is
+ * launched (message naming the field or segment; the previous result stays valid): a NULL h, wav, lens or out, a wrong struct_size of cfg or out,
+ * B outside [1, 65535], lens[b] < 1 or > EV_LOUDNESS_MAX_SAMPLES, a sample_rate outside the table, a target_lufs that is neither NaN nor in
+ * [-70, 0], a negative or non-finite max_gain_db, a peak_ceiling outside (0, 1].  The tile sums and peaks come back to the host between the
+ * measurement and the gain pass: the call's one synchronisation in the middle of its work, as ev_stitch's cut; no waveform is copied to the host.
+ * The result lives in a workspace of its own and is complete when the call returns; it stays valid across every other entry point until the next
+ * ev_loudness or ev_destroy -- the contract of ev_features_result. */
+int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_loudness_config* cfg, uint32_t flags,
+                ev_loudness_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 
