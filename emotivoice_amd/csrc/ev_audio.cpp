@@ -1,0 +1,1252 @@
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness -- with
+// their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
+// Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
+// call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
+#include <math.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+#include "ev_host.h"
+
+using namespace ev;
+using namespace evh;
+
+namespace {
+
+// a host table to its place in the arena, on the handle's stream (the vector must live until the stream has been waited for)
+template <typename T> int upload(ev_handle* h, T* dst, const std::vector<T>& v) {
+    HIPCHK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// The device side of a per-kernel test entry point (the end of this file): ONE allocation that holds the host tables appended with add() and the
+// scratch reserved with room(), each at an aligned offset.  commit() allocates and uploads, at<T>() turns an offset into its pointer, and the end
+// of the scope frees -- after the wrapper has waited for the stream.
+struct DevTable {
+    struct Part { size_t off; const void* src; size_t bytes; };
+    std::vector<Part> parts; size_t size = 0; char* base = nullptr;
+    DevTable() = default;
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+    ~DevTable() { if (base) (void)hipFree(base); }
+    size_t room(size_t bytes) { const size_t off = align_up(size, 256); size = off + bytes; return off; }
+    size_t add(const void* src, size_t bytes) { const size_t off = room(bytes); parts.push_back(Part{off, src, bytes}); return off; }
+    template <typename T> size_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
+    int commit() {      // 0, or -1
+        if (hipMalloc((void**)&base, size + 16) != hipSuccess) { base = nullptr; return -1; }
+        for (const Part& p : parts)
+            if (p.bytes && hipMemcpy(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
+        return 0;
+    }
+    template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+};
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------- acoustic features (include/evhip.h: ev_features)
+static_assert(EV_FEATURES_MAX_NFFT == STFT_MAX_NFFT && EV_FEATURES_MAX_MELS == STFT_MAX_MELS && EV_FEATURES_MAX_RUN == STFT_MAX_RUN,
+              "include/evhip.h states the limits of ev_features.hip");
+void ev_default_features_config(ev_features_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_features_config);
+    c->n_fft = 1024; c->hop = 256; c->n_mels = 80; c->mel_clip = 1e-5f; c->energy_floor = 1e-10f;
+}
+
+static int features_check_config(ev_handle* h, const char* who, int n_fft, int hop, int n_mels) {
+    if (n_fft < 128 || n_fft % 128 || n_fft > STFT_MAX_NFFT) return fail(h, "%s: n_fft %d must be a multiple of 128 in [128, %d]", who, n_fft, STFT_MAX_NFFT);
+    if (n_mels < 1 || n_mels > STFT_MAX_MELS) return fail(h, "%s: n_mels %d outside [1, %d]", who, n_mels, STFT_MAX_MELS);
+    if (hop < 8 || hop % 8 || hop > n_fft) return fail(h, "%s: hop %d must be a multiple of 8 in [8, n_fft]", who, hop);
+    if (!stft_shape_ok(n_fft, hop, n_mels)) return fail(h, "%s: hop %d: the 63 hop + n_fft samples of a 64-frame tile exceed %d", who, hop, STFT_MAX_RUN);
+    return 0;
+}
+
+// packs the basis planes on the host and uploads them; *basis / *melT are hipMalloc'ed
+static int features_upload_tables(ev_handle* h, int n_fft, int n_mels, const float* mel_basis, const float* window, char** basis, float** melT) {
+    std::vector<uint16_t> hb(stft_basis_halfs(n_fft));
+    std::vector<float> hm(stft_melT_floats(n_fft));
+    stft_pack_basis(n_fft, window, hb.data());
+    stft_pack_mel(n_fft, n_mels, mel_basis, hm.data());
+    *basis = nullptr; *melT = nullptr;
+    hipError_t e = hipMalloc((void**)basis, hb.size() * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)melT, hm.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(*basis, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(*melT, hm.data(), hm.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {       // nothing half-built is left behind
+        if (*basis) (void)hipFree(*basis);
+        if (*melT) (void)hipFree(*melT);
+        *basis = nullptr; *melT = nullptr;
+        return fail(h, "ev_features: uploading the basis planes failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+int ev_features_setup(ev_handle* h, const ev_features_config* cfg) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_features_setup: null config");
+    if (check_struct_size(h, "ev_features_setup", "struct_size", cfg->struct_size, "ev_features_config", sizeof(ev_features_config))) return -1;
+    if (features_check_config(h, "ev_features_setup", cfg->n_fft, cfg->hop, cfg->n_mels)) return -1;
+    if (!cfg->mel_basis) return fail(h, "ev_features_setup: mel_basis is required");
+    if (!(cfg->mel_clip > 0.f) || !std::isfinite(cfg->mel_clip)) return fail(h, "ev_features_setup: mel_clip must be positive and finite");
+    if (!(cfg->energy_floor >= 0.f) || !std::isfinite(cfg->energy_floor)) return fail(h, "ev_features_setup: energy_floor must be >= 0 and finite");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->feat.ready = false;
+    if (h->feat.basis) { HIPCHK(h, hipFree(h->feat.basis)); h->feat.basis = nullptr; }
+    if (h->feat.melT) { HIPCHK(h, hipFree(h->feat.melT)); h->feat.melT = nullptr; }
+    if (features_upload_tables(h, cfg->n_fft, cfg->n_mels, cfg->mel_basis, cfg->window, &h->feat.basis, &h->feat.melT)) return -1;
+    h->feat.cfg = *cfg; h->feat.cfg.mel_basis = nullptr; h->feat.cfg.window = nullptr;
+    h->feat.ready = true;
+    return 0;
+}
+
+int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, float energy_mean, float energy_std, uint32_t flags,
+                ev_features_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out || B <= 0) return fail(h, "ev_features: bad argument");
+    if (check_struct_size(h, "ev_features", "out->struct_size", out->struct_size, "ev_features_result", sizeof(ev_features_result))) return -1;
+    if (!h->feat.ready) return fail(h, "ev_features: ev_features_setup has not been called");
+    if ((size_t)B > PIN_MAX_B) return fail(h, "ev_features: at most %zu utterances per call", PIN_MAX_B);
+    if (!std::isfinite(energy_std) || !(energy_std > 0.f)) return fail(h, "ev_features: energy_std must be positive and finite");
+    if (!std::isfinite(energy_mean)) return fail(h, "ev_features: energy_mean must be finite");
+    const ev_features_config& fc = h->feat.cfg;
+    const int n_bins = fc.n_fft / 2 + 1;
+    FrameGrid g;
+    const int bad = frame_grid_layout(B, wav_lens, fc.n_fft / 2 + 1, fc.hop, 64, g);
+    if (bad > 0) return fail(h, "ev_features: wav_lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", bad - 1, (long long)wav_lens[bad - 1], fc.n_fft / 2 + 1);
+    if (bad < 0) return fail(h, "ev_features: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / fc.hop + 1), EV_ALIGN_MAX_FRAMES);
+    const int64_t total_frames = g.offs[B], total_samples = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    if (call_begin(h)) return -1;
+    h->feat.mag = nullptr;
+    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_mel = nullptr, *d_energy = nullptr, *d_mag = nullptr;
+    if (arena_plan(h, ARENA_FEATURES, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size());
+        d_mel = ap.arr<float>((size_t)total_frames * fc.n_mels); d_energy = ap.arr<float>((size_t)total_frames);
+        d_mag = keep ? ap.arr<float>((size_t)total_frames * n_bins) : nullptr;
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
+    region_begin(h, "total");
+    {
+        StftParams p{};
+        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
+        p.basis = h->feat.basis; p.melT = h->feat.melT; p.n_fft = fc.n_fft; p.hop = fc.hop; p.n_mels = fc.n_mels; p.nmi = stft_mels_per_group(fc.n_mels);
+        p.n_bins = n_bins; p.n_btiles = stft_bin_tiles(fc.n_fft); p.mel_clip = fc.mel_clip; p.energy_floor = fc.energy_floor;
+        p.energy_mean = energy_mean; p.energy_std = energy_std; p.mel = d_mel; p.energy = d_energy; p.mag = d_mag;
+        const double tile_frames = 64.0 * (double)g.tiles.size();
+        KScope ks(h, "stft_mel", 2.0 * 3.0 * tile_frames * fc.n_fft * 2.0 * n_bins + 2.0 * tile_frames * n_bins * fc.n_mels,
+                  (double)total_samples * es + (double)total_frames * (fc.n_mels + 1) * 4.0);
+        if (launch_stft_mel(p, h->stream)) return fail(h, "ev_features: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    h->feat.mel_lens.swap(g.lens); h->feat.mel_offs.swap(g.offs);
+    h->feat.mag = d_mag; h->feat.mag_elems = keep ? total_frames * n_bins : 0;
+    reset_result(out);
+    out->batch = B; out->total_frames = total_frames; out->mel = d_mel; out->energy = d_energy;
+    out->mel_lens = h->feat.mel_lens.data(); out->mel_offsets = h->feat.mel_offs.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- pitch extraction (include/evhip.h: ev_pitch)
+static_assert(EV_PITCH_TILE_FRAMES == PITCH_TF && EV_PITCH_MAX_WIN == PITCH_MAX_WIN && EV_PITCH_MAX_LDS == PITCH_MAX_LDS,
+              "include/evhip.h states the limits of ev_pitch.hip");
+void ev_default_pitch_config(ev_pitch_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_pitch_config);
+    c->sample_rate = 16000; c->hop = 256; c->win = 1024; c->f_min = 80.f; c->f_max = 400.f; c->threshold = 0.15f; c->silence_rms = 1e-3f;
+}
+
+// every rejection of a config, in the order include/evhip.h lists them; sets the lag range
+static int pitch_check_config(ev_handle* h, const char* who, const ev_pitch_config& c, int* tau_min, int* tau_max) {
+    if (c.sample_rate < 1) return fail(h, "%s: sample_rate %d must be positive", who, c.sample_rate);
+    if (c.win < 1 || c.win > PITCH_MAX_WIN) return fail(h, "%s: win %d outside [1, EV_PITCH_MAX_WIN %d]", who, c.win, PITCH_MAX_WIN);
+    if (c.hop < 1 || c.hop > c.win) return fail(h, "%s: hop %d outside [1, win %d]", who, c.hop, c.win);
+    if (!std::isfinite(c.f_min) || !std::isfinite(c.f_max) || !(c.f_min > 0.f) || !(c.f_min < c.f_max) || !((double)c.f_max <= (double)c.sample_rate / 4.0))
+        return fail(h, "%s: f_min %g / f_max %g must be finite with 0 < f_min < f_max <= sample_rate / 4 = %g", who, (double)c.f_min, (double)c.f_max, (double)c.sample_rate / 4.0);
+    const double tmax = std::ceil((double)c.sample_rate / (double)c.f_min);
+    const int tmin = (int)std::floor((double)c.sample_rate / (double)c.f_max);
+    if (tmax + 1.0 > (double)c.win) return fail(h, "%s: tau_max + 1 = %.0f > win %d (f_min %g is too low for the window)", who, tmax + 1.0, c.win, (double)c.f_min);
+    if (!(c.threshold > 0.f) || !(c.threshold <= 1.f)) return fail(h, "%s: threshold %g outside (0, 1]", who, (double)c.threshold);
+    if (!std::isfinite(c.silence_rms) || c.silence_rms < 0.f) return fail(h, "%s: silence_rms must be >= 0 and finite", who);
+    if (!pitch_shape_ok(c.hop, c.win, tmin, (int)tmax))
+        return fail(h, "%s: win %d, hop %d, tau %d .. %d: the kernel needs win >= 8, tau_min < tau_max and a tile of %zu bytes within EV_PITCH_MAX_LDS %d", who,
+                    c.win, c.hop, tmin, (int)tmax, pitch_lds_bytes(c.hop, c.win, (int)tmax), PITCH_MAX_LDS);
+    *tau_min = tmin; *tau_max = (int)tmax;
+    return 0;
+}
+
+static PitchParams pitch_params(const ev_pitch_config& c, int tau_min, int tau_max) {
+    PitchParams p{};
+    p.sample_rate = c.sample_rate; p.hop = c.hop; p.win = c.win; p.tau_min = tau_min; p.tau_max = tau_max; p.threshold = c.threshold;
+    p.e0_floor = (double)c.win * (double)c.silence_rms * (double)c.silence_rms;
+    return p;
+}
+
+int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, const ev_pitch_config* cfg, float pitch_mean,
+             float pitch_std, uint32_t flags, ev_pitch_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out || B <= 0) return fail(h, "ev_pitch: bad argument");
+    if (check_struct_size(h, "ev_pitch", "out->struct_size", out->struct_size, "ev_pitch_result", sizeof(ev_pitch_result))) return -1;
+    ev_pitch_config pc;
+    ev_default_pitch_config(&pc);
+    if (cfg) {
+        if (check_struct_size(h, "ev_pitch", "cfg->struct_size", cfg->struct_size, "ev_pitch_config", sizeof(ev_pitch_config))) return -1;
+        pc = *cfg;
+    }
+    int tau_min = 0, tau_max = 0;
+    if (pitch_check_config(h, "ev_pitch", pc, &tau_min, &tau_max)) return -1;
+    if ((size_t)B > PIN_MAX_B) return fail(h, "ev_pitch: at most %zu utterances per call", PIN_MAX_B);
+    if (!std::isfinite(pitch_std) || !(pitch_std > 0.f)) return fail(h, "ev_pitch: pitch_std must be positive and finite");
+    if (!std::isfinite(pitch_mean)) return fail(h, "ev_pitch: pitch_mean must be finite");
+    FrameGrid g;
+    const int bad = frame_grid_layout(B, wav_lens, 1, pc.hop, PITCH_TF, g);
+    if (bad > 0) return fail(h, "ev_pitch: wav_lens[%d] = %lld < 1", bad - 1, (long long)wav_lens[bad - 1]);
+    if (bad < 0) return fail(h, "ev_pitch: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / pc.hop + 1), EV_ALIGN_MAX_FRAMES);
+    const int64_t total_frames = g.offs[B], total_samples = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    if (call_begin(h)) return -1;
+    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_pitch = nullptr, *d_f0 = nullptr, *d_ap = nullptr;
+    if (arena_plan(h, ARENA_PITCH, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size());
+        d_pitch = ap.arr<float>((size_t)total_frames); d_f0 = ap.arr<float>((size_t)total_frames); d_ap = ap.arr<float>((size_t)total_frames);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
+    region_begin(h, "total");
+    {
+        PitchParams p = pitch_params(pc, tau_min, tau_max);
+        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
+        p.f0 = d_f0; p.ap = d_ap; p.tau = nullptr;
+        KScope ks(h, "pitch_yin", 3.0 * (double)total_frames * (tau_max + 2.0) * pc.win, (double)total_samples * es + (double)total_frames * 8.0);
+        if (launch_pitch_yin(p, h->stream)) return fail(h, "ev_pitch: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "pitch_fill", 8.0 * (double)total_frames, (double)total_frames * 8.0);
+        launch_pitch_fill(d_f0, d_seqs, B, pitch_mean, pitch_std, d_pitch, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    h->pitch.mel_lens.swap(g.lens); h->pitch.mel_offs.swap(g.offs);
+    reset_result(out);
+    out->batch = B; out->total_frames = total_frames; out->pitch = d_pitch; out->f0_hz = d_f0; out->aperiodicity = d_ap;
+    out->mel_lens = h->pitch.mel_lens.data(); out->mel_offsets = h->pitch.mel_offs.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- sample-rate conversion and trimming (include/evhip.h: ev_resample)
+static_assert(EV_RESAMPLE_TILE == RS_TM, "include/evhip.h states the tile of ev_resample.hip");
+void ev_default_resample_config(ev_resample_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_resample_config);
+    c->sr_in = 16000; c->sr_out = 16000;
+}
+
+static double bessel_i0(double x) {      // the power series: every term positive, so it converges to the last bit for any x >= 0
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+static int resample_ratio(int sr_in, int sr_out, int* up, int* down) {      // 0, or -1 for a rate < 1
+    if (sr_in < 1 || sr_out < 1) return -1;
+    int a = sr_in, b = sr_out;
+    while (b) { const int t = a % b; a = b; b = t; }
+    *up = sr_out / a; *down = sr_in / a;
+    return 0;
+}
+
+int ev_resample_design(int sr_in, int sr_out, int zeros, double rolloff, double beta, float* taps, int cap) {
+    int up = 0, down = 0;
+    if (resample_ratio(sr_in, sr_out, &up, &down) || up > EV_RESAMPLE_MAX_RATIO || down > EV_RESAMPLE_MAX_RATIO) return 0;
+    if (zeros < 1 || zeros > 4096 || !(rolloff > 0.0) || !(rolloff <= 1.0) || !std::isfinite(beta) || beta < 0.0) return 0;
+    const int q = std::max(up, down), half = zeros * q, n = 2 * half + 1;
+    if (cap < n || !taps) return -n;
+    std::vector<double> g((size_t)n);
+    const double i0b = bessel_i0(beta);
+    double sum = 0.0;
+    for (int i = -half; i <= half; ++i) {
+        const double x = rolloff * (double)i / (double)q, r = (double)i / (double)half;
+        const double px = M_PI * x;
+        const double sinc = i == 0 ? 1.0 : sin(px) / px;
+        g[(size_t)(i + half)] = sinc * bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    }
+    for (int i = 0; i < n; ++i) sum += g[(size_t)i];
+    for (int i = 0; i < n; ++i) taps[i] = (float)((double)up * g[(size_t)i] / sum);
+    return half;
+}
+
+// every rejection of a config, in the order include/evhip.h lists them; gives the ratio and the taps (the caller's or the default design)
+static int resample_check_config(ev_handle* h, const char* who, const ev_resample_config& c, int* up, int* down, int* half, std::vector<float>& taps) {
+    if (c.sr_in < 1 || c.sr_out < 1) return fail(h, "%s: sr_in %d / sr_out %d must be positive", who, c.sr_in, c.sr_out);
+    (void)resample_ratio(c.sr_in, c.sr_out, up, down);
+    if (*up > EV_RESAMPLE_MAX_RATIO || *down > EV_RESAMPLE_MAX_RATIO)
+        return fail(h, "%s: sr_in %d -> sr_out %d is up %d / down %d; both must be <= EV_RESAMPLE_MAX_RATIO %d", who, c.sr_in, c.sr_out, *up, *down, EV_RESAMPLE_MAX_RATIO);
+    if (c.taps) {
+        if (c.half_len < 1) return fail(h, "%s: half_len %d must be >= 1 with taps", who, c.half_len);
+        if (2 * (int64_t)c.half_len + 1 > EV_RESAMPLE_MAX_TAPS) return fail(h, "%s: half_len %d gives more than EV_RESAMPLE_MAX_TAPS %d taps", who, c.half_len, EV_RESAMPLE_MAX_TAPS);
+        taps.assign(c.taps, c.taps + 2 * (size_t)c.half_len + 1);
+        for (size_t i = 0; i < taps.size(); ++i)
+            if (!std::isfinite(taps[i])) return fail(h, "%s: taps[%zu] is not finite", who, i);
+        *half = c.half_len;
+    } else {
+        const int n = -ev_resample_design(c.sr_in, c.sr_out, 16, 0.945, 9.0, nullptr, 0);
+        if (n < 3 || n > EV_RESAMPLE_MAX_TAPS) return fail(h, "%s: the default design has %d taps > EV_RESAMPLE_MAX_TAPS %d", who, n, EV_RESAMPLE_MAX_TAPS);
+        taps.resize((size_t)n);
+        *half = ev_resample_design(c.sr_in, c.sr_out, 16, 0.945, 9.0, taps.data(), n);
+    }
+    if (!std::isfinite(c.trim_frac) || c.trim_frac < 0.f || !(c.trim_frac < 1.f)) return fail(h, "%s: trim_frac %g outside [0, 1)", who, (double)c.trim_frac);
+    if (c.trim_pad < 0) return fail(h, "%s: trim_pad %d must be >= 0", who, c.trim_pad);
+    return 0;
+}
+
+// the table on the device (hipMalloc'ed); nothing half-built is left behind
+static int resample_upload_table(int up, int half, const std::vector<float>& taps, float** tab, size_t* floats) {
+    std::vector<float> ht(resample_table_floats(up, half));
+    resample_pack_table(up, half, taps.data(), ht.data());
+    *tab = nullptr;
+    if (hipMalloc((void**)tab, ht.size() * 4) != hipSuccess) return -1;
+    if (hipMemcpy(*tab, ht.data(), ht.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(*tab); *tab = nullptr; return -1; }
+    *floats = ht.size();
+    return 0;
+}
+
+int ev_resample_setup(ev_handle* h, const ev_resample_config* cfg) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_resample_setup: null config");
+    if (check_struct_size(h, "ev_resample_setup", "struct_size", cfg->struct_size, "ev_resample_config", sizeof(ev_resample_config))) return -1;
+    int up = 0, down = 0, half = 0;
+    std::vector<float> taps;
+    if (resample_check_config(h, "ev_resample_setup", *cfg, &up, &down, &half, taps)) return -1;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float* tab = nullptr; size_t floats = 0;
+    if (resample_upload_table(up, half, taps, &tab, &floats)) return fail(h, "ev_resample_setup: uploading the tap table failed");
+    if (h->rs.tab) (void)hipFree(h->rs.tab);
+    h->rs.tab = tab; h->rs.tab_floats = floats; h->rs.up = up; h->rs.down = down; h->rs.half = half;
+    h->rs.cfg = *cfg; h->rs.cfg.taps = nullptr;
+    h->rs.ready = true;
+    return 0;
+}
+
+static int resample_launch(const void* wav, int wav_is_i16, int up, int down, int half, const float* tab, const ResampleSeq* d_seqs, const ResampleTile* d_tiles,
+                           int n_tiles, int64_t total_in, float* y, hipStream_t s) {
+    if (up == 1 && down == 1) { launch_resample_copy(wav, wav_is_i16, total_in, y, s); return 0; }
+    ResampleParams p{};
+    p.wav = wav; p.wav_is_i16 = wav_is_i16; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = n_tiles;
+    p.up = up; p.down = down; p.half = half; p.row = resample_row_len(up, half); p.tab = tab; p.out = y;
+    return launch_resample_poly(p, s);
+}
+
+// cuts (first, last per utterance, from trim_scan) -> the result's lens / offsets / start / end and the gather table; returns the longest output
+static int64_t trim_plan(int B, const std::vector<ResampleSeq>& seqs, const int64_t* cuts, int pad, std::vector<TrimSeq>& ts, int64_t* lens, int64_t* offs,
+                         int64_t* start, int64_t* end) {
+    ts.resize(B);
+    int64_t o = 0, longest = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t s = cuts[2 * b], e = cuts[2 * b + 1], n = e - s + 2 * (int64_t)pad;
+        ts[b] = TrimSeq{seqs[b].out_off + s, o, e - s};
+        lens[b] = n; start[b] = s; end[b] = e;
+        if (offs) offs[b] = o;
+        o += n; longest = std::max(longest, n);
+    }
+    if (offs) offs[B] = o;
+    return longest;
+}
+
+int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* wav_lens, uint32_t flags, ev_resample_result* out) {
+    if (!h) return -1;
+    if (!wav || !wav_lens || !out) return fail(h, "ev_resample: bad argument");
+    if (check_struct_size(h, "ev_resample", "out->struct_size", out->struct_size, "ev_resample_result", sizeof(ev_resample_result))) return -1;
+    if (!h->rs.ready) return fail(h, "ev_resample: ev_resample_setup has not been called");
+    if (B < 1 || B > 65535) return fail(h, "ev_resample: B %d outside [1, 65535]", B);
+    const ev_resample_config& rc = h->rs.cfg;
+    const int up = h->rs.up, down = h->rs.down, half = h->rs.half, pad = rc.trim_pad;
+    const bool trim = rc.trim_frac > 0.f;
+    std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;
+    const int bad = resample_layout(B, wav_lens, up, down, trim ? 2 * (int64_t)pad : 0, seqs, tiles);
+    if (bad > 0) return fail(h, "ev_resample: wav_lens[%d] = %lld < 1", bad - 1, (long long)wav_lens[bad - 1]);
+    if (bad < 0) return fail(h, "ev_resample: utterance %d (%lld samples) gives more than EV_ALIGN_MAX_FRAMES * 256 = %lld output samples", -bad - 1,
+                             (long long)wav_lens[-bad - 1], (long long)RS_MAX_OUT);
+    const int64_t total_in = seqs[B - 1].in_off + seqs[B - 1].len, total_n = seqs[B - 1].out_off + seqs[B - 1].n;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    if (call_begin(h)) return -1;
+    h->rs.raw = nullptr;
+    void* d_wav = nullptr; ResampleSeq* d_seqs = nullptr; ResampleTile* d_tiles = nullptr; TrimSeq* d_ts = nullptr; int64_t* d_cuts = nullptr;
+    float *d_y = nullptr, *d_out = nullptr;
+    if (arena_plan(h, ARENA_RESAMPLE, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        d_seqs = ap.arr<ResampleSeq>(B); d_tiles = ap.arr<ResampleTile>(tiles.size());
+        d_y = ap.arr<float>((size_t)total_n);
+        if (trim) { d_ts = ap.arr<TrimSeq>(B); d_cuts = ap.arr<int64_t>(2 * (size_t)B); d_out = ap.arr<float>((size_t)total_n + 2 * (size_t)pad * B); }
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
+    std::vector<int64_t> lens((size_t)B), offs((size_t)B + 1), start((size_t)B), end((size_t)B);
+    region_begin(h, "total");
+    {
+        const bool copy = up == 1 && down == 1;
+        KScope ks(h, copy ? "resample_copy" : "resample_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)total_in * es + (double)total_n * 4.0);
+        if (resample_launch(dev_in ? wav : d_wav, wav_is_i16 != 0, up, down, half, h->rs.tab, d_seqs, d_tiles, (int)tiles.size(), total_in, d_y, h->stream))
+            return fail(h, "ev_resample: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (trim) {
+        {
+            KScope ks(h, "trim_scan", 2.0 * (double)total_n, 2.0 * (double)total_n * 4.0);
+            launch_trim_scan(d_y, d_seqs, B, rc.trim_frac, d_cuts, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        std::vector<int64_t> cuts(2 * (size_t)B);
+        HIPCHK(h, hipMemcpyAsync(cuts.data(), d_cuts, cuts.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<TrimSeq> ts;
+        const int64_t longest = trim_plan(B, seqs, cuts.data(), pad, ts, lens.data(), offs.data(), start.data(), end.data());
+        if (upload(h, d_ts, ts)) return -1;
+        {
+            KScope ks(h, "trim_gather", 0.0, 2.0 * (double)offs[B] * 4.0);
+            launch_trim_gather(d_y, d_ts, B, longest, pad, d_out, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+    } else {
+        for (int b = 0; b < B; ++b) { lens[b] = seqs[b].n; offs[b] = seqs[b].out_off; start[b] = 0; end[b] = seqs[b].n; }
+        offs[B] = total_n;
+    }
+    if (call_end(h)) return -1;
+    h->rs.lens = lens; h->rs.offs = offs; h->rs.start = start; h->rs.end = end;
+    h->rs.raw = keep ? d_y : nullptr; h->rs.raw_elems = keep ? total_n : 0;
+    reset_result(out);
+    out->batch = B; out->total_samples = offs[B]; out->wav = trim ? d_out : d_y;
+    out->wav_lens = h->rs.lens.data(); out->wav_offsets = h->rs.offs.data(); out->trim_start = h->rs.start.data(); out->trim_end = h->rs.end.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- long-form stitching (include/evhip.h: ev_stitch)
+static_assert(EV_STITCH_MAX_FADE == ST_MAX_FADE, "include/evhip.h states the ramp table's limit of ev_stitch.hip");
+void ev_default_stitch_config(ev_stitch_config* c) {
+    if (!c) return;
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_stitch_config);
+}
+
+int ev_stitch_ramp(int F, float* tab) {
+    if (F < 0 || F > EV_STITCH_MAX_FADE || (F > 0 && !tab)) return -1;
+    for (int i = 0; i < F; ++i) tab[i] = (float)(0.5 - 0.5 * cos(M_PI * ((double)i + 0.5) / (double)F));
+    return F;
+}
+
+static int stitch_check_trim(ev_handle* h, const char* who, float trim_frac, float trim_abs) {
+    if (!std::isfinite(trim_frac) || trim_frac < 0.f || !(trim_frac < 1.f)) return fail(h, "%s: trim_frac %g outside [0, 1)", who, (double)trim_frac);
+    if (!std::isfinite(trim_abs) || trim_abs < 0.f) return fail(h, "%s: trim_abs %g must be finite and >= 0", who, (double)trim_abs);
+    return 0;
+}
+
+// the config and the per-segment arrays that do not depend on the waveform: the number of documents, or -1 with the message
+static int stitch_check(ev_handle* h, const char* who, int S, const int32_t* seg_doc, const int32_t* pause_after, const ev_stitch_config* c) {
+    if (!c || !seg_doc || !pause_after) return fail(h, "%s: bad argument", who);
+    if (check_struct_size(h, who, "cfg->struct_size", c->struct_size, "ev_stitch_config", sizeof(ev_stitch_config))) return -1;
+    if (S < 1 || S > 65535) return fail(h, "%s: S %d outside [1, 65535]", who, S);
+    if (stitch_check_trim(h, who, c->trim_frac, c->trim_abs)) return -1;
+    if (c->keep < 0) return fail(h, "%s: keep %d must be >= 0", who, c->keep);
+    if (c->fade < 0 || c->fade > EV_STITCH_MAX_FADE) return fail(h, "%s: fade %d outside [0, EV_STITCH_MAX_FADE = %d]", who, c->fade, EV_STITCH_MAX_FADE);
+    if (c->lead < 0) return fail(h, "%s: lead %d must be >= 0", who, c->lead);
+    if (c->tail < 0) return fail(h, "%s: tail %d must be >= 0", who, c->tail);
+    if (seg_doc[0] != 0) return fail(h, "%s: seg_doc[0] = %d, the documents count from 0", who, seg_doc[0]);
+    for (int s = 1; s < S; ++s)
+        if (seg_doc[s] != seg_doc[s - 1] && seg_doc[s] != seg_doc[s - 1] + 1)
+            return fail(h, "%s: seg_doc[%d] = %d after %d: neither the same document nor the next", who, s, seg_doc[s], seg_doc[s - 1]);
+    for (int s = 0; s + 1 < S; ++s)
+        if (seg_doc[s + 1] == seg_doc[s] && (pause_after[s] < -EV_STITCH_MAX_FADE || pause_after[s] > EV_STITCH_MAX_PAUSE))
+            return fail(h, "%s: pause_after[%d] = %d outside [-EV_STITCH_MAX_FADE, EV_STITCH_MAX_PAUSE]", who, s, pause_after[s]);
+    return seg_doc[S - 1] + 1;
+}
+
+int ev_stitch_plan(int S, const int64_t* n, const int32_t* seg_doc, const int32_t* pause_after, const ev_stitch_config* cfg, int64_t* pos, int32_t* fl,
+                   int32_t* fr, int64_t* doc_lens) {
+    const int D = stitch_check(nullptr, "ev_stitch_plan", S, seg_doc, pause_after, cfg);
+    if (D < 0) return -1;
+    if (!n || !pos || !fl || !fr || !doc_lens) return fail(nullptr, "ev_stitch_plan: bad argument");
+    for (int s = 0; s < S; ++s)
+        if (n[s] < 0 || n[s] > EV_STITCH_MAX_DOC) return fail(nullptr, "ev_stitch_plan: n[%d] = %lld outside [0, EV_STITCH_MAX_DOC]", s, (long long)n[s]);
+    const int64_t F = cfg->fade;
+    for (int s = 0; s < S; ++s) {
+        if (s == 0 || seg_doc[s] != seg_doc[s - 1]) { pos[s] = cfg->lead; fl[s] = (int32_t)std::min(F, n[s] / 2); }
+        if (s == S - 1 || seg_doc[s + 1] != seg_doc[s]) {
+            fr[s] = (int32_t)std::min(F, n[s] / 2);
+            const int64_t len = pos[s] + n[s] + cfg->tail;
+            if (len > EV_STITCH_MAX_DOC)
+                return fail(nullptr, "ev_stitch_plan: document %d has %lld samples, more than EV_STITCH_MAX_DOC = %d", seg_doc[s], (long long)len, EV_STITCH_MAX_DOC);
+            doc_lens[seg_doc[s]] = len;
+            continue;
+        }
+        int64_t ov = 0;
+        if (pause_after[s] < 0 && n[s] > 0 && n[s + 1] > 0) ov = std::min(std::min(-(int64_t)pause_after[s], F), std::min(n[s] / 2, n[s + 1] / 2));
+        const int64_t gap = ov > 0 ? 0 : std::max((int64_t)pause_after[s], (int64_t)0);
+        pos[s + 1] = pos[s] + n[s] + gap - ov;
+        fr[s] = (int32_t)(ov > 0 ? ov : std::min(F, n[s] / 2));
+        fl[s + 1] = (int32_t)(ov > 0 ? ov : std::min(F, n[s + 1] / 2));
+    }
+    return D;
+}
+
+// the planned segments -> the mix kernel's tables and the documents' offsets (D + 1); returns the packed length
+static int64_t stitch_tables(int S, int D, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl, const int32_t* fr,
+                             const int64_t* doc_lens, std::vector<StitchMixSeg>& ms, std::vector<StitchDoc>& docs, std::vector<StitchTile>& tiles, int64_t* offs) {
+    ms.resize((size_t)S); docs.assign((size_t)D, StitchDoc{0, 0, 0, 0}); tiles.clear();
+    for (int s = 0; s < S; ++s) {
+        ms[(size_t)s] = StitchMixSeg{src[s], pos[s], (int32_t)n[s], fl[s], fr[s], 0};
+        StitchDoc& d = docs[(size_t)seg_doc[s]];
+        if (d.nseg == 0) d.seg0 = s;
+        d.nseg++;
+    }
+    int64_t o = 0;
+    for (int d = 0; d < D; ++d) {
+        docs[(size_t)d].out_off = o; docs[(size_t)d].len = doc_lens[d];
+        offs[d] = o;
+        for (int64_t t = 0; t * ST_TILE < doc_lens[d]; ++t) tiles.push_back(StitchTile{d, (int32_t)t});
+        o += doc_lens[d];
+    }
+    offs[D] = o;
+    return o;
+}
+
+int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets, const int64_t* seg_lens, const int32_t* seg_doc, const int32_t* pause_after,
+              const ev_stitch_config* cfg, uint32_t flags, ev_stitch_result* out) {
+    if (!h) return -1;
+    if (!wav || !seg_offsets || !seg_lens || !seg_doc || !pause_after || !out) return fail(h, "ev_stitch: bad argument");
+    if (check_struct_size(h, "ev_stitch", "out->struct_size", out->struct_size, "ev_stitch_result", sizeof(ev_stitch_result))) return -1;
+    ev_stitch_config dflt;
+    if (!cfg) { ev_default_stitch_config(&dflt); cfg = &dflt; }
+    const int D = stitch_check(h, "ev_stitch", S, seg_doc, pause_after, cfg);
+    if (D < 0) return -1;
+    const ev_stitch_config c = *cfg;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, trim = c.trim_frac > 0.f || c.trim_abs > 0.f, i16 = c.want_i16 != 0;
+    // the layout of the input, and each document's length before any cut: what the workspace is sized for and what EV_STITCH_MAX_DOC is judged on
+    std::vector<StitchSeg> segs((size_t)S);
+    std::vector<int64_t> bound((size_t)D, (int64_t)c.lead + c.tail);
+    int64_t lo_off = INT64_MAX, hi_end = 0, n_part = 0, max_len = 0;
+    for (int s = 0; s < S; ++s) {
+        if (seg_offsets[s] < 0) return fail(h, "ev_stitch: seg_offsets[%d] = %lld < 0", s, (long long)seg_offsets[s]);
+        if (seg_lens[s] < 1) return fail(h, "ev_stitch: seg_lens[%d] = %lld < 1", s, (long long)seg_lens[s]);
+        int64_t& bd = bound[(size_t)seg_doc[s]];
+        bd += std::min(seg_lens[s], (int64_t)EV_STITCH_MAX_DOC + 1);
+        if (s + 1 < S && seg_doc[s + 1] == seg_doc[s]) bd += std::max(pause_after[s], 0);
+        if (bd > EV_STITCH_MAX_DOC)
+            return fail(h, "ev_stitch: document %d exceeds EV_STITCH_MAX_DOC = %d samples at segment %d (lead + tail + segments + pauses, before the cut)",
+                        seg_doc[s], EV_STITCH_MAX_DOC, s);
+        segs[(size_t)s] = StitchSeg{seg_offsets[s], seg_lens[s], n_part};
+        n_part += (seg_lens[s] + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
+        lo_off = std::min(lo_off, seg_offsets[s]); hi_end = std::max(hi_end, seg_offsets[s] + seg_lens[s]); max_len = std::max(max_len, seg_lens[s]);
+    }
+    if (!dev_in) for (auto& sg : segs) sg.off -= lo_off;      // the host's samples lo_off .. hi_end are copied
+    int64_t cap_out = 0, cap_tiles = 0;
+    for (int d = 0; d < D; ++d) { cap_out += bound[(size_t)d]; cap_tiles += (bound[(size_t)d] + ST_TILE - 1) / ST_TILE; }
+    if (call_begin(h)) return -1;
+    float* d_wav = nullptr; StitchSeg* d_segs = nullptr; float *d_part = nullptr, *d_peak = nullptr; int64_t* d_cuts = nullptr;
+    StitchMixSeg* d_ms = nullptr; StitchDoc* d_docs = nullptr; StitchTile* d_tiles = nullptr; float* d_out = nullptr; int16_t* d_i16 = nullptr;
+    if (arena_plan(h, ARENA_STITCH, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.arr<float>((size_t)(hi_end - lo_off));
+        if (trim) { d_segs = ap.arr<StitchSeg>(S); d_part = ap.arr<float>((size_t)n_part); d_peak = ap.arr<float>(S); d_cuts = ap.arr<int64_t>(2 * (size_t)S); }
+        d_ms = ap.arr<StitchMixSeg>(S); d_docs = ap.arr<StitchDoc>(D); d_tiles = ap.arr<StitchTile>((size_t)cap_tiles);
+        d_out = ap.arr<float>((size_t)cap_out);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)cap_out);
+    })) return -1;
+    if (!h->stitch.tab) HIPCHK(h, hipMalloc((void**)&h->stitch.tab, (size_t)EV_STITCH_MAX_FADE * sizeof(float)));
+    h->stitch.tab_host.resize((size_t)c.fade);
+    (void)ev_stitch_ramp(c.fade, h->stitch.tab_host.data());
+    h->stitch.F = c.fade;
+    if (c.fade > 0) HIPCHK(h, hipMemcpyAsync(h->stitch.tab, h->stitch.tab_host.data(), (size_t)c.fade * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav + lo_off, (size_t)(hi_end - lo_off) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const float* x = dev_in ? wav : d_wav;
+    std::vector<int64_t> a((size_t)S, 0), b((size_t)S), n((size_t)S), src((size_t)S);
+    std::vector<float> peak((size_t)S, 0.f);
+    for (int s = 0; s < S; ++s) b[(size_t)s] = seg_lens[s];
+    region_begin(h, "total");
+    if (trim) {
+        if (upload(h, d_segs, segs)) return -1;
+        {
+            KScope ks(h, "stitch_peak", 0.0, (double)(hi_end - lo_off) * 4.0);
+            launch_stitch_peak(x, d_segs, S, max_len, d_part, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        {
+            KScope ks(h, "stitch_edges", 0.0, (double)n_part * 4.0);
+            launch_stitch_edges(x, d_segs, S, d_part, c.trim_frac, c.trim_abs, d_peak, d_cuts, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        std::vector<int64_t> cuts(2 * (size_t)S);
+        HIPCHK(h, hipMemcpyAsync(cuts.data(), d_cuts, cuts.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(peak.data(), d_peak, (size_t)S * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int s = 0; s < S; ++s) {
+            const int64_t first = cuts[2 * (size_t)s], last = cuts[2 * (size_t)s + 1];
+            a[(size_t)s] = first < 0 ? 0 : std::max((int64_t)0, first - c.keep);
+            b[(size_t)s] = first < 0 ? 0 : std::min(seg_lens[s], last + 1 + c.keep);
+        }
+    }
+    for (int s = 0; s < S; ++s) { n[(size_t)s] = b[(size_t)s] - a[(size_t)s]; src[(size_t)s] = segs[(size_t)s].off + a[(size_t)s]; }
+    std::vector<int64_t> pos((size_t)S), doc_lens((size_t)D), offs((size_t)D + 1);
+    std::vector<int32_t> fl((size_t)S), fr((size_t)S);
+    if (ev_stitch_plan(S, n.data(), seg_doc, pause_after, &c, pos.data(), fl.data(), fr.data(), doc_lens.data()) != D)
+        return fail(h, "ev_stitch: %s", ev_last_error(nullptr));
+    std::vector<StitchMixSeg> ms; std::vector<StitchDoc> docs; std::vector<StitchTile> tiles;
+    const int64_t total = stitch_tables(S, D, src.data(), n.data(), seg_doc, pos.data(), fl.data(), fr.data(), doc_lens.data(), ms, docs, tiles, offs.data());
+    if (total > cap_out || (int64_t)tiles.size() > cap_tiles) return fail(h, "ev_stitch: the plan outgrew its workspace");      // the cut only shortens
+    if (upload(h, d_ms, ms) || upload(h, d_docs, docs) || (!tiles.empty() && upload(h, d_tiles, tiles))) return -1;
+    {
+        KScope ks(h, "stitch_mix", 0.0, (double)total * (i16 ? 10.0 : 8.0));
+        if (launch_stitch_mix(x, d_ms, d_docs, d_tiles, (int64_t)tiles.size(), h->stitch.tab, c.fade, d_out, i16 ? d_i16 : nullptr, h->stream))
+            return fail(h, "ev_stitch: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    h->stitch.doc_lens = doc_lens; h->stitch.doc_offs = offs; h->stitch.pos = pos; h->stitch.start = a; h->stitch.end = b; h->stitch.peak = peak;
+    reset_result(out);
+    out->batch_docs = D; out->batch_segs = S; out->total_samples = total; out->wav = d_out; out->wav_i16 = i16 ? d_i16 : nullptr;
+    out->doc_lens = h->stitch.doc_lens.data(); out->doc_offsets = h->stitch.doc_offs.data(); out->seg_pos = h->stitch.pos.data();
+    out->seg_start = h->stitch.start.data(); out->seg_end = h->stitch.end.data(); out->seg_peak = h->stitch.peak.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- signal comparison (include/evhip.h: ev_compare)
+static_assert(EV_COMPARE_CHUNK == CMP_CHUNK, "include/evhip.h states the chunk of ev_compare.hip");
+int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_t* lens, uint32_t flags, ev_compare_result* out) {
+    if (!h) return -1;
+    if (!a) return fail(h, "ev_compare: a is NULL");
+    if (!b) return fail(h, "ev_compare: b is NULL");
+    if (!lens) return fail(h, "ev_compare: lens is NULL");
+    if (!out) return fail(h, "ev_compare: out is NULL");
+    if (check_struct_size(h, "ev_compare", "out->struct_size", out->struct_size, "ev_compare_result", sizeof(ev_compare_result))) return -1;
+    if (B < 1 || B > 65535) return fail(h, "ev_compare: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    std::vector<int64_t> coffs((size_t)B + 1, 0);
+    int64_t total = 0;
+    for (int s = 0; s < B; ++s) {      // the chunk table's size is judged before it is built
+        if (lens[s] < 1) return fail(h, "ev_compare: lens[%d] = %lld < 1", s, (long long)lens[s]);
+        if (lens[s] > (int64_t)INT_MAX * CMP_CHUNK || coffs[(size_t)s] + (lens[s] + CMP_CHUNK - 1) / CMP_CHUNK > INT_MAX)
+            return fail(h, "ev_compare: lens[%d] = %lld: more than %d chunks of %d elements in one call", s, (long long)lens[s], INT_MAX, CMP_CHUNK);
+        coffs[(size_t)s + 1] = coffs[(size_t)s] + (lens[s] + CMP_CHUNK - 1) / CMP_CHUNK;
+        total += lens[s];
+    }
+    const int64_t NC = coffs[(size_t)B];
+    std::vector<CompareChunk> chunks;
+    chunks.reserve((size_t)NC);
+    for (int64_t s = 0, off = 0; s < B; off += lens[s], ++s)
+        for (int64_t i = 0; i < lens[s]; i += CMP_CHUNK) chunks.push_back(CompareChunk{off + i, (int32_t)std::min<int64_t>(CMP_CHUNK, lens[s] - i), 0});
+    if (call_begin(h)) return -1;
+    float *d_a = nullptr, *d_b = nullptr; CompareChunk* d_chunks = nullptr; int64_t* d_coffs = nullptr; double *d_sums = nullptr, *d_maxd = nullptr;
+    int32_t *d_argd = nullptr, *d_nonf = nullptr; float* d_peak = nullptr; CompareSeg* d_seg = nullptr;
+    if (arena_plan(h, ARENA_COMPARE, [&](ArenaPlan& ap) {
+        if (!dev_in) { d_a = ap.arr<float>((size_t)total); d_b = ap.arr<float>((size_t)total); }
+        d_chunks = ap.arr<CompareChunk>((size_t)NC); d_coffs = ap.arr<int64_t>((size_t)B + 1);
+        d_sums = ap.arr<double>(4 * (size_t)NC); d_maxd = ap.arr<double>((size_t)NC);
+        d_argd = ap.arr<int32_t>((size_t)NC); d_nonf = ap.arr<int32_t>((size_t)NC); d_peak = ap.arr<float>((size_t)NC);
+        d_seg = ap.arr<CompareSeg>((size_t)B);
+    })) return -1;
+    if (!dev_in) {
+        HIPCHK(h, hipMemcpyAsync(d_a, a, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_b, b, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    if (upload(h, d_chunks, chunks) || upload(h, d_coffs, coffs)) return -1;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "compare_chunks", 8.0 * (double)total, 8.0 * (double)total + 64.0 * (double)NC);
+        if (launch_compare_chunks(dev_in ? a : d_a, dev_in ? b : d_b, d_chunks, NC, d_sums, d_maxd, d_argd, d_peak, d_nonf, h->stream))
+            return fail(h, "ev_compare: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "compare_finish", 4.0 * (double)NC, 52.0 * (double)NC + (double)B * sizeof(CompareSeg));
+        launch_compare_finish(B, d_coffs, d_sums, NC, d_maxd, d_argd, d_peak, d_nonf, d_seg, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    region_end(h, "total");
+    std::vector<CompareSeg> seg((size_t)B);
+    std::vector<double> cd2((size_t)NC), cy2((size_t)NC);
+    HIPCHK(h, hipMemcpyAsync(seg.data(), d_seg, (size_t)B * sizeof(CompareSeg), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cd2.data(), d_sums + NC, (size_t)NC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cy2.data(), d_sums + 3 * NC, (size_t)NC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    profiling_collect(h);
+    // from here on nothing fails: the previous result is replaced
+    const size_t nb = (size_t)B;
+    h->cmp.d.resize(nb); h->cmp.d2.resize(nb); h->cmp.y.resize(nb); h->cmp.y2.resize(nb); h->cmp.rel.resize(nb); h->cmp.rel_ac.resize(nb);
+    h->cmp.max_d.resize(nb); h->cmp.peak_y.resize(nb); h->cmp.arg.resize(nb); h->cmp.nonf.resize(nb);
+    for (size_t s = 0; s < nb; ++s) {
+        const CompareSeg& g = seg[s];
+        const double n = (double)lens[s], num = sqrt(g.sum[1]);
+        const double var = g.sum[3] - (g.sum[2] * g.sum[2]) / n;      // the quotient sits between the product and the difference: nothing to fuse
+        h->cmp.d[s] = g.sum[0]; h->cmp.d2[s] = g.sum[1]; h->cmp.y[s] = g.sum[2]; h->cmp.y2[s] = g.sum[3];
+        h->cmp.rel[s] = num / sqrt(std::max(g.sum[3], EV_COMPARE_FLOOR));
+        h->cmp.rel_ac[s] = num / sqrt(std::max(var, EV_COMPARE_FLOOR));
+        h->cmp.max_d[s] = (float)g.max_d; h->cmp.peak_y[s] = g.peak_y; h->cmp.arg[s] = g.arg; h->cmp.nonf[s] = g.nonfinite;
+    }
+    h->cmp.chunk_d2.swap(cd2); h->cmp.chunk_y2.swap(cy2); h->cmp.chunk_offs.swap(coffs);
+    reset_result(out);
+    out->batch = B; out->total = total;
+    out->sum_d = h->cmp.d.data(); out->sum_d2 = h->cmp.d2.data(); out->sum_y = h->cmp.y.data(); out->sum_y2 = h->cmp.y2.data();
+    out->rel_l2 = h->cmp.rel.data(); out->rel_l2_ac = h->cmp.rel_ac.data(); out->max_abs_d = h->cmp.max_d.data(); out->argmax_d = h->cmp.arg.data();
+    out->peak_y = h->cmp.peak_y.data(); out->nonfinite = h->cmp.nonf.data();
+    out->chunk_d2 = h->cmp.chunk_d2.data(); out->chunk_y2 = h->cmp.chunk_y2.data(); out->chunk_offsets = h->cmp.chunk_offs.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- FLAC encoding (include/evhip.h: ev_flac)
+void ev_default_flac_config(ev_flac_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c; c->sample_rate = 16000; c->block_size = 4096; c->max_fixed_order = 4; c->max_partition_order = 5; c->convert = EV_FLAC_WRAP;
+}
+
+int64_t ev_flac_bound(int64_t n, int block_size) {
+    if (n < 1 || n > EV_FLAC_MAX_SAMPLES || flac_block_code(block_size) < 0) return -1;
+    return flac_bound(n, block_size);
+}
+
+// the encoder's constants from a config flac_check_config has accepted; the caller adds the pointers
+static FlacParams flac_params(const ev_flac_config& c, int sr_code, int bs_code) {
+    FlacParams fp{};
+    fp.convert = c.convert; fp.block_size = c.block_size; fp.bs_code = bs_code; fp.sr_code = sr_code;
+    fp.max_fixed_order = c.max_fixed_order; fp.max_partition_order = c.max_partition_order; fp.stride = 2 * c.block_size + 24;
+    return fp;
+}
+
+int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out) {
+    if (!h) return -1;
+    if (!pcm) return fail(h, "ev_flac: pcm is NULL");
+    if (!lens) return fail(h, "ev_flac: lens is NULL");
+    if (!out) return fail(h, "ev_flac: out is NULL");
+    if (check_struct_size(h, "ev_flac", "out->struct_size", out->struct_size, "ev_flac_result", sizeof(ev_flac_result))) return -1;
+    ev_flac_config dflt;
+    if (!cfg) { ev_default_flac_config(&dflt); cfg = &dflt; }
+    if (check_struct_size(h, "ev_flac", "cfg->struct_size", cfg->struct_size, "ev_flac_config", sizeof(ev_flac_config))) return -1;
+    const ev_flac_config c = *cfg;
+    int sr_code = 0, bs_code = 0;
+    switch (flac_check_config(c, &sr_code, &bs_code)) {
+    case FLAC_OK: break;
+    case FLAC_BAD_RATE: return fail(h, "ev_flac: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
+    case FLAC_BAD_BLOCK: return fail(h, "ev_flac: block_size = %d is not one of 256, 512, 1024, 2048, 4096", c.block_size);
+    case FLAC_BAD_FIXED_ORDER: return fail(h, "ev_flac: max_fixed_order = %d outside [0, 4]", c.max_fixed_order);
+    case FLAC_BAD_PARTITION_ORDER: return fail(h, "ev_flac: max_partition_order = %d outside [0, 6]", c.max_partition_order);
+    case FLAC_BAD_CONVERT: return fail(h, "ev_flac: convert = %d is neither EV_FLAC_WRAP nor EV_FLAC_CLAMP", c.convert);
+    }
+    if (B < 1 || B > 65535) return fail(h, "ev_flac: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, i16 = pcm_is_i16 != 0;
+    const int N = c.block_size, stride = 2 * N + 24;
+    FlacPlan plan;
+    int at = 0;
+    switch (flac_plan(B, lens, N, plan, &at)) {
+    case LEN_OK: break;
+    case LEN_SHORT: return fail(h, "ev_flac: lens[%d] = %lld < 1", at, (long long)lens[at]);
+    case LEN_LONG: return fail(h, "ev_flac: lens[%d] = %lld > EV_FLAC_MAX_SAMPLES = %d", at, (long long)lens[at], EV_FLAC_MAX_SAMPLES);
+    case LEN_COUNT: return fail(h, "ev_flac: lens[%d] = %lld: more than %d frames in one call", at, (long long)lens[at], INT_MAX);
+    }
+    const int64_t total = plan.total, NF = (int64_t)plan.frames.size(), cap = plan.cap;
+    if (call_begin(h)) return -1;
+    const size_t es = i16 ? sizeof(int16_t) : sizeof(float);
+    char* d_pcm = nullptr; FlacFrame* d_frames = nullptr; int32_t* d_sizes = nullptr; uint32_t* d_desc = nullptr; uint8_t *d_scratch = nullptr, *d_hdr = nullptr, *d_bytes = nullptr;
+    int64_t* d_foffs = nullptr;
+    if (arena_plan(h, ARENA_FLAC, [&](ArenaPlan& ap) {
+        if (!dev_in) d_pcm = ap.arr<char>((size_t)total * es);
+        d_frames = ap.arr<FlacFrame>((size_t)NF); d_sizes = ap.arr<int32_t>((size_t)NF); d_desc = ap.arr<uint32_t>((size_t)NF);
+        d_foffs = ap.arr<int64_t>((size_t)NF); d_hdr = ap.arr<uint8_t>((size_t)B * FLAC_HEADER_STRIDE);
+        d_scratch = ap.arr<uint8_t>((size_t)NF * (size_t)stride + 16); d_bytes = ap.arr<uint8_t>((size_t)cap);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_pcm, pcm, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_frames, plan.frames)) return -1;
+    FlacParams fp = flac_params(c, sr_code, bs_code);
+    fp.pcm = dev_in ? pcm : d_pcm; fp.pcm_is_i16 = i16; fp.frames = d_frames; fp.scratch = d_scratch; fp.sizes = d_sizes; fp.desc = d_desc;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "flac_encode", 0.0, (double)total * (double)es + (double)NF * (double)stride);
+        if (launch_flac_encode(fp, NF, h->stream)) return fail(h, "ev_flac: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> sizes((size_t)NF); std::vector<uint32_t> desc((size_t)NF);
+    HIPCHK(h, hipMemcpyAsync(sizes.data(), d_sizes, (size_t)NF * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(desc.data(), d_desc, (size_t)NF * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the layout: per stream its header, then its frames; the header needs the stream's smallest and largest frame
+    std::vector<int64_t> soffs((size_t)B + 1, 0), foffs((size_t)NF + 1, 0);
+    std::vector<uint8_t> hdr((size_t)B * FLAC_HEADER_STRIDE, 0), kind((size_t)NF), porder((size_t)NF);
+    int64_t pos = 0, f = 0;
+    for (int b = 0; b < B; ++b) {
+        soffs[(size_t)b] = pos;
+        pos += FLAC_STREAM_HEADER;
+        int32_t lo = INT_MAX, hi = 0;
+        for (int64_t i = 0; i < plan.stream_frames[(size_t)b]; ++i, ++f) {
+            const int32_t sz = sizes[(size_t)f];
+            if (sz < 1 || sz > 2 * N + 15) return fail(h, "ev_flac: frame %lld of segment %d reports %d bytes", (long long)i, b, sz);
+            foffs[(size_t)f] = pos; pos += sz; lo = std::min(lo, sz); hi = std::max(hi, sz);
+            kind[(size_t)f] = (uint8_t)(desc[(size_t)f] & 0xFFu); porder[(size_t)f] = (uint8_t)(desc[(size_t)f] >> 8 & 0xFFu);
+        }
+        uint8_t* p = hdr.data() + (size_t)b * FLAC_HEADER_STRIDE;
+        const uint64_t n = (uint64_t)lens[b], v = (uint64_t)c.sample_rate << 44 | (uint64_t)15 << 36 | n;      // 20 + 3 + 5 + 36 bits
+        memcpy(p, "fLaC", 4);
+        p[4] = 0x80; p[5] = 0; p[6] = 0; p[7] = 0x22;
+        p[8] = p[10] = (uint8_t)(N >> 8); p[9] = p[11] = (uint8_t)(N & 0xFF);
+        p[12] = (uint8_t)(lo >> 16); p[13] = (uint8_t)(lo >> 8); p[14] = (uint8_t)lo;
+        p[15] = (uint8_t)(hi >> 16); p[16] = (uint8_t)(hi >> 8); p[17] = (uint8_t)hi;
+        for (int i = 0; i < 8; ++i) p[18 + i] = (uint8_t)(v >> (56 - 8 * i));      // p[26 .. 42): the MD5, zero
+    }
+    soffs[(size_t)B] = pos; foffs[(size_t)NF] = pos;
+    if (pos > cap) return fail(h, "ev_flac: the streams outgrew their bound");
+    HIPCHK(h, hipMemcpyAsync(d_foffs, foffs.data(), (size_t)NF * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, h->stream));
+    {
+        KScope ks(h, "flac_gather", 0.0, 2.0 * (double)pos);
+        launch_flac_gather(d_scratch, stride, d_frames, NF, d_sizes, d_foffs, d_hdr, d_bytes, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    h->flac.stream_offs.swap(soffs); h->flac.stream_frames.swap(plan.stream_frames); h->flac.frame_offs.swap(foffs); h->flac.kind.swap(kind); h->flac.porder.swap(porder);
+    reset_result(out);
+    out->batch = B; out->total_bytes = pos; out->total_frames = NF; out->bytes = d_bytes;
+    out->stream_offsets = h->flac.stream_offs.data(); out->stream_frames = h->flac.stream_frames.data(); out->frame_offsets = h->flac.frame_offs.data();
+    out->frame_kind = h->flac.kind.data(); out->frame_porder = h->flac.porder.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- loudness normalisation (include/evhip.h: ev_loudness)
+static_assert(EV_LOUDNESS_TILE == LOUD_TILE, "include/evhip.h states the tile of ev_loudness.hip");
+void ev_default_loudness_config(ev_loudness_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c; c->sample_rate = 16000; c->target_lufs = NAN; c->max_gain_db = 20.0; c->peak_ceiling = (float)pow(10.0, -1.0 / 20.0); c->want_i16 = 0;
+}
+
+int ev_loudness_design(int sample_rate, double coef[10]) {
+    if (flac_rate_code(sample_rate) < 0 || !coef) return -1;
+    const double pi = 3.14159265358979323846, fs = (double)sample_rate;
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
+        coef[0] = (Vh + Vb * K / Q + K * K) / a0; coef[1] = 2.0 * (K * K - Vh) / a0; coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+        coef[3] = 2.0 * (K * K - 1.0) / a0; coef[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+        coef[5] = 1.0; coef[6] = -2.0; coef[7] = 1.0;
+        coef[8] = 2.0 * (K * K - 1.0) / a0; coef[9] = (1.0 - K / Q + K * K) / a0;
+    }
+    return 0;
+}
+
+// the kernels' constants: the coefficients and the powers A^(LOUD_RUN 2^d), d = 0 .. 8, of the cascade's transition matrix (transposed direct form II,
+// states: the shelf's two, then the high-pass's two), squared up in long double and rounded once
+static void loudness_coef(const double coef[10], LoudCoef* lc) {
+    for (int q = 0; q < 2; ++q) {
+        for (int i = 0; i < 3; ++i) lc->b[q][i] = coef[5 * q + i];
+        for (int i = 0; i < 2; ++i) lc->a[q][i] = coef[5 * q + 3 + i];
+    }
+    const long double a1 = coef[3], a2 = coef[4], c0 = coef[5], c1 = coef[6], c2 = coef[7], d1 = coef[8], d2 = coef[9];
+    long double M[16] = {-a1, 1, 0, 0, -a2, 0, 0, 0, c1 - d1 * c0, 0, -d1, 1, c2 - d2 * c0, 0, -d2, 0}, T[16];
+    auto square = [&]() {
+        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {
+            long double acc = 0;
+            for (int k = 0; k < 4; ++k) acc += M[i * 4 + k] * M[k * 4 + j];
+            T[i * 4 + j] = acc;
+        }
+        memcpy(M, T, sizeof M);
+    };
+    int run = 1;
+    while (run < LOUD_RUN) { square(); run *= 2; }
+    for (int d = 0; d < 9; ++d) {
+        for (int i = 0; i < 16; ++i) lc->P[d][i] = (double)M[i];
+        square();
+    }
+}
+
+static double loudness_lufs(double z) { return -0.691 + 10.0 * log10(z); }      // z = 0: -inf
+
+int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_loudness_config* cfg, uint32_t flags,
+                ev_loudness_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_loudness: wav is NULL");
+    if (!lens) return fail(h, "ev_loudness: lens is NULL");
+    if (!out) return fail(h, "ev_loudness: out is NULL");
+    if (check_struct_size(h, "ev_loudness", "out->struct_size", out->struct_size, "ev_loudness_result", sizeof(ev_loudness_result))) return -1;
+    ev_loudness_config dflt;
+    if (!cfg) { ev_default_loudness_config(&dflt); cfg = &dflt; }
+    if (check_struct_size(h, "ev_loudness", "cfg->struct_size", cfg->struct_size, "ev_loudness_config", sizeof(ev_loudness_config))) return -1;
+    const ev_loudness_config c = *cfg;
+    double coef[10];
+    if (ev_loudness_design(c.sample_rate, coef))
+        return fail(h, "ev_loudness: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
+    const bool measure_only = std::isnan(c.target_lufs);
+    if (!measure_only && !(c.target_lufs >= -70.0 && c.target_lufs <= 0.0))
+        return fail(h, "ev_loudness: target_lufs = %g is neither NaN (measure only) nor in [-70, 0]", c.target_lufs);
+    if (!(std::isfinite(c.max_gain_db) && c.max_gain_db >= 0.0)) return fail(h, "ev_loudness: max_gain_db = %g is not finite and >= 0", c.max_gain_db);
+    if (!(c.peak_ceiling > 0.f && c.peak_ceiling <= 1.f)) return fail(h, "ev_loudness: peak_ceiling = %g outside (0, 1]", (double)c.peak_ceiling);
+    if (B < 1 || B > 65535) return fail(h, "ev_loudness: B = %d outside [1, 65535]", B);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0 && !measure_only;
+    const int64_t step = c.sample_rate / 10, block = 4 * step;
+    LoudPlan plan;
+    int at = 0;
+    switch (loudness_plan(B, lens, step, plan, &at)) {
+    case LEN_OK: break;
+    case LEN_SHORT: return fail(h, "ev_loudness: lens[%d] = %lld < 1", at, (long long)lens[at]);
+    case LEN_LONG: return fail(h, "ev_loudness: lens[%d] = %lld > EV_LOUDNESS_MAX_SAMPLES = %d", at, (long long)lens[at], EV_LOUDNESS_MAX_SAMPLES);
+    case LEN_COUNT: return fail(h, "ev_loudness: lens[%d] = %lld: more than %d tiles in one call", at, (long long)lens[at], INT_MAX);
+    }
+    const std::vector<LoudSeg>& segs = plan.segs;
+    const int64_t total = plan.total, NT = (int64_t)plan.tiles.size(), NB = plan.n_blocks;
+    LoudCoef lc;
+    loudness_coef(coef, &lc);
+    if (call_begin(h)) return -1;
+    const size_t es = in16 ? sizeof(int16_t) : sizeof(float);
+    char* d_in = nullptr; LoudTile* d_tiles = nullptr; LoudSeg* d_segs = nullptr; LoudCoef* d_coef = nullptr; double *d_ends = nullptr, *d_init = nullptr;
+    LoudTileOut* d_outs = nullptr; int64_t* d_offs = nullptr; float *d_gain = nullptr, *d_wav = nullptr; int16_t* d_i16 = nullptr;
+    if (arena_plan(h, ARENA_LOUDNESS, [&](ArenaPlan& ap) {
+        if (!dev_in) d_in = ap.arr<char>((size_t)total * es);
+        d_tiles = ap.arr<LoudTile>((size_t)NT); d_segs = ap.arr<LoudSeg>((size_t)B); d_coef = ap.arr<LoudCoef>(1);
+        d_ends = ap.arr<double>(4 * (size_t)NT); d_init = ap.arr<double>(4 * (size_t)NT); d_outs = ap.arr<LoudTileOut>((size_t)NT);
+        d_offs = ap.arr<int64_t>((size_t)B + 1); d_gain = ap.arr<float>((size_t)B);
+        if (!measure_only) d_wav = ap.arr<float>((size_t)total);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_in, wav, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_tiles, plan.tiles) || upload(h, d_segs, plan.segs)) return -1;
+    HIPCHK(h, hipMemcpyAsync(d_coef, &lc, sizeof lc, hipMemcpyHostToDevice, h->stream));
+    const void* x = dev_in ? wav : (const void*)d_in;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "loudness_measure", 60.0 * (double)total, 2.0 * (double)total * (double)es + (double)NT * (64.0 + sizeof(LoudTileOut)));
+        if (launch_loudness_measure(x, in16, d_tiles, NT, d_segs, B, d_coef, (int)step, d_ends, d_init, d_outs, h->stream))
+            return fail(h, "ev_loudness: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<LoudTileOut> touts((size_t)NT);
+    HIPCHK(h, hipMemcpyAsync(touts.data(), d_outs, (size_t)NT * sizeof(LoudTileOut), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the host half: step sums from the tiles' in ascending tile order, blocks, the two gates, the gain
+    std::vector<double> loud((size_t)B), rel((size_t)B), ms; std::vector<float> gain((size_t)B), peak((size_t)B); std::vector<uint8_t> fl((size_t)B), state;
+    std::vector<int64_t> nonf((size_t)B), boffs((size_t)B + 1, 0);
+    ms.reserve((size_t)NB); state.reserve((size_t)NB);
+    std::vector<double> S;
+    const double ninf = -std::numeric_limits<double>::infinity();
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lens[b], nbins = (n + step - 1) / step;
+        S.assign((size_t)nbins, 0.0);
+        float pk = 0.f; int64_t nf = 0;
+        for (int64_t t = 0; t < segs[(size_t)b].ntiles; ++t) {
+            const LoudTileOut& o = touts[(size_t)(segs[(size_t)b].tile0 + t)];
+            const int64_t pos = t * LOUD_TILE, tb0 = pos / step, nsl = (std::min<int64_t>(pos + LOUD_TILE, n) - 1) / step - tb0 + 1;
+            for (int64_t k = 0; k < nsl; ++k) S[(size_t)(tb0 + k)] += o.sum[k];
+            pk = std::max(pk, o.peak); nf += o.nonfinite;
+        }
+        const size_t j0 = ms.size();
+        if (n >= block) {
+            const int64_t nblk = (n - block) / step + 1;
+            for (int64_t j = 0; j < nblk; ++j) ms.push_back((((S[(size_t)j] + S[(size_t)j + 1]) + S[(size_t)j + 2]) + S[(size_t)j + 3]) / (double)block);
+        } else {
+            double acc = 0.0;
+            for (int64_t m = 0; m < nbins; ++m) acc += S[(size_t)m];
+            ms.push_back(acc / (double)n);
+        }
+        const size_t j1 = ms.size();
+        state.resize(j1, 0);
+        double acc = 0.0; int64_t cnt = 0;
+        for (size_t j = j0; j < j1; ++j) if (loudness_lufs(ms[j]) > -70.0) { state[j] = 1; acc += ms[j]; ++cnt; }
+        double L = ninf, gamma = ninf;
+        if (cnt > 0) {
+            gamma = loudness_lufs(acc / (double)cnt) - 10.0;
+            acc = 0.0; cnt = 0;
+            for (size_t j = j0; j < j1; ++j) if (state[j] == 1 && loudness_lufs(ms[j]) > gamma) { state[j] = 2; acc += ms[j]; ++cnt; }
+            if (cnt > 0) L = loudness_lufs(acc / (double)cnt);
+        }
+        uint8_t f = L == ninf ? EV_LOUDNESS_UNDEFINED : 0;
+        double g = 1.0;
+        if (!measure_only) {
+            if (L != ninf) g = pow(10.0, (c.target_lufs - L) / 20.0);
+            const double gmax = pow(10.0, c.max_gain_db / 20.0);
+            if (g > gmax) { g = gmax; f |= EV_LOUDNESS_BOOST_LIMITED; }
+            if (pk > 0.f) {
+                const double gpk = (double)c.peak_ceiling / (double)pk;
+                if (g > gpk) { g = gpk; f |= EV_LOUDNESS_PEAK_LIMITED; }
+            }
+        }
+        loud[(size_t)b] = L; rel[(size_t)b] = gamma; gain[(size_t)b] = (float)g; peak[(size_t)b] = pk; fl[(size_t)b] = f; nonf[(size_t)b] = nf;
+        boffs[(size_t)b + 1] = (int64_t)j1;
+    }
+    if (!measure_only) {
+        if (upload(h, d_offs, plan.offs) || upload(h, d_gain, gain)) return -1;
+        {
+            KScope ks(h, "loudness_gain", (double)total, (double)total * ((double)es + (i16 ? 6.0 : 4.0)));
+            if (launch_loudness_gain(x, in16, d_offs, B, d_gain, total, d_wav, i16 ? d_i16 : nullptr, h->stream))
+                return fail(h, "ev_loudness: the kernels do not build this shape");
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    if (call_end(h)) return -1;
+    h->loud.loud.swap(loud); h->loud.rel.swap(rel); h->loud.ms.swap(ms); h->loud.gain.swap(gain); h->loud.peak.swap(peak); h->loud.flags.swap(fl); h->loud.state.swap(state);
+    h->loud.nonf.swap(nonf); h->loud.boffs.swap(boffs);
+    reset_result(out);
+    out->batch = B; out->total = total; out->wav = measure_only ? nullptr : d_wav; out->wav_i16 = i16 ? d_i16 : nullptr;
+    out->loudness = h->loud.loud.data(); out->rel_threshold = h->loud.rel.data(); out->gain = h->loud.gain.data(); out->peak = h->loud.peak.data();
+    out->flags = h->loud.flags.data(); out->nonfinite = h->loud.nonf.data(); out->block_offsets = h->loud.boffs.data(); out->block_ms = h->loud.ms.data();
+    out->block_state = h->loud.state.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- per-kernel test entry points of the utilities (include/evhip_ops.h)
+// Each builds its kernel's tables from per-utterance HOST arrays (no struct crosses the boundary), launches on the caller's stream and waits for it
+// before the tables go.  -2: a rejected argument or shape; -1: a runtime failure.
+int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* mel_basis, const float* window, int n_fft, int hop,
+                   int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
+                   void* stream) {
+    if (!wav || !wav_lens || !mel_basis || !mel || !energy || B < 1 || B > 65535 || !stft_shape_ok(n_fft, hop, n_mels)) return -2;
+    FrameGrid g;
+    if (frame_grid_layout(B, wav_lens, n_fft / 2 + 1, hop, 64, g)) return -2;
+    char* basis = nullptr; float* melT = nullptr;
+    int rc = features_upload_tables(nullptr, n_fft, n_mels, mel_basis, window, &basis, &melT) ? -1 : 0;
+    DevTable t;
+    const size_t so = t.add(g.seqs), to = t.add(g.tiles);
+    if (rc == 0 && t.commit()) rc = -1;
+    if (rc == 0) {
+        StftParams p{};
+        p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
+        p.basis = basis; p.melT = melT; p.n_fft = n_fft; p.hop = hop; p.n_mels = n_mels; p.nmi = stft_mels_per_group(n_mels); p.n_bins = n_fft / 2 + 1;
+        p.n_btiles = stft_bin_tiles(n_fft); p.mel_clip = mel_clip; p.energy_floor = energy_floor; p.energy_mean = energy_mean; p.energy_std = energy_std;
+        p.mel = mel; p.energy = energy; p.mag = mag;
+        if (launch_stft_mel(p, (hipStream_t)stream)) rc = -2;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    if (basis) (void)hipFree(basis);
+    if (melT) (void)hipFree(melT);
+    return rc;
+}
+
+int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sample_rate, int hop, int win, float f_min, float f_max,
+                    float threshold, float silence_rms, float* f0_hz, float* aperiodicity, int32_t* tau, void* stream) {
+    if (!wav || !wav_lens || !f0_hz || !aperiodicity || B < 1 || B > 65535) return -2;
+    ev_pitch_config c;
+    ev_default_pitch_config(&c);
+    c.sample_rate = sample_rate; c.hop = hop; c.win = win; c.f_min = f_min; c.f_max = f_max; c.threshold = threshold; c.silence_rms = silence_rms;
+    int tau_min = 0, tau_max = 0;
+    if (pitch_check_config(nullptr, "ev_op_pitch_yin", c, &tau_min, &tau_max)) return -2;
+    FrameGrid g;
+    if (frame_grid_layout(B, wav_lens, 1, hop, PITCH_TF, g)) return -2;
+    DevTable t;
+    const size_t so = t.add(g.seqs), to = t.add(g.tiles);
+    if (t.commit()) return -1;
+    PitchParams p = pitch_params(c, tau_min, tau_max);
+    p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
+    p.f0 = f0_hz; p.ap = aperiodicity; p.tau = tau;
+    int rc = 0;
+    if (launch_pitch_yin(p, (hipStream_t)stream)) rc = -2;
+    else if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pitch_mean, float pitch_std, float* pitch, void* stream) {
+    if (!f0_hz || !frames || !pitch || pitch == f0_hz || B < 1 || B > 65535) return -2;
+    if (!std::isfinite(pitch_mean) || !std::isfinite(pitch_std) || !(pitch_std > 0.f)) return -2;
+    // the frame grid of utterances of frames - 1 samples at hop 1: T = frames.  The kernel reads a sequence's frame offset and count only.
+    std::vector<int64_t> lens((size_t)B);
+    for (int b = 0; b < B; ++b) lens[(size_t)b] = (int64_t)frames[b] - 1;
+    FrameGrid g;
+    if (frame_grid_layout(B, lens.data(), 0, 1, PITCH_TF, g)) return -2;
+    DevTable t;
+    const size_t so = t.add(g.seqs);
+    if (t.commit()) return -1;
+    int rc = 0;
+    launch_pitch_fill(f0_hz, t.at<StftSeq>(so), B, pitch_mean, pitch_std, pitch, (hipStream_t)stream);
+    if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+
+int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sr_in, int sr_out, const float* taps, int half_len, float* y,
+                   void* stream) {
+    if (!wav || !wav_lens || !y || B < 1 || B > 65535) return -2;
+    ev_resample_config c;
+    ev_default_resample_config(&c);
+    c.sr_in = sr_in; c.sr_out = sr_out; c.taps = taps; c.half_len = half_len;
+    int up = 0, down = 0, half = 0;
+    std::vector<float> ht;
+    if (resample_check_config(nullptr, "ev_op_resample", c, &up, &down, &half, ht)) return -2;
+    std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;
+    if (resample_layout(B, wav_lens, up, down, 0, seqs, tiles)) return -2;
+    float* tab = nullptr; size_t floats = 0;
+    if (resample_upload_table(up, half, ht, &tab, &floats)) return -1;
+    DevTable t;
+    const size_t so = t.add(seqs), to = t.add(tiles);
+    int rc = t.commit() ? -1 : 0;
+    if (rc == 0) {
+        if (resample_launch(wav, wav_is_i16 != 0, up, down, half, tab, t.at<ResampleSeq>(so), t.at<ResampleTile>(to), (int)tiles.size(),
+                            seqs[B - 1].in_off + seqs[B - 1].len, y, (hipStream_t)stream)) rc = -2;
+        else if (hipGetLastError() != hipSuccess) rc = -1;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    }
+    (void)hipFree(tab);
+    return rc;
+}
+int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int trim_pad, float* out, int64_t* out_lens, int64_t* trim_start,
+               int64_t* trim_end, void* stream) {
+    if (!y || !lens || !out || !out_lens || !trim_start || !trim_end || out == y || B < 1 || B > 65535) return -2;
+    if (!std::isfinite(trim_frac) || !(trim_frac > 0.f) || !(trim_frac < 1.f) || trim_pad < 0) return -2;
+    std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;      // y as the output of a 1 : 1 conversion (the tiles are not used)
+    if (resample_layout(B, lens, 1, 1, 2 * (int64_t)trim_pad, seqs, tiles)) return -2;
+    DevTable t;
+    const size_t cb = 2 * (size_t)B * sizeof(int64_t), so = t.add(seqs), co = t.room(cb), to = t.room((size_t)B * sizeof(TrimSeq));
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> cuts(2 * (size_t)B);
+    std::vector<TrimSeq> ts;
+    launch_trim_scan(y, t.at<ResampleSeq>(so), B, trim_frac, t.at<int64_t>(co), s);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (hipMemcpy(cuts.data(), t.at<int64_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int64_t longest = trim_plan(B, seqs, cuts.data(), trim_pad, ts, out_lens, nullptr, trim_start, trim_end);
+    if (hipMemcpy(t.at<TrimSeq>(to), ts.data(), (size_t)B * sizeof(TrimSeq), hipMemcpyHostToDevice) != hipSuccess) return -1;
+    int rc = 0;
+    launch_trim_gather(y, t.at<TrimSeq>(to), B, longest, trim_pad, out, s);
+    if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    return rc;
+}
+
+int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const int64_t* seg_lens, float trim_frac, float trim_abs, float* peak,
+                      int64_t* first, int64_t* last, void* stream) {
+    if (!wav || !seg_offsets || !seg_lens || !peak || !first || !last || S < 1 || S > 65535) return -2;
+    if (stitch_check_trim(nullptr, "ev_op_stitch_scan", trim_frac, trim_abs)) return -2;
+    std::vector<StitchSeg> segs((size_t)S);
+    int64_t n_part = 0, max_len = 0;
+    for (int s = 0; s < S; ++s) {
+        if (seg_offsets[s] < 0 || seg_lens[s] < 1) return -2;
+        segs[(size_t)s] = StitchSeg{seg_offsets[s], seg_lens[s], n_part};
+        n_part += (seg_lens[s] + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
+        max_len = std::max(max_len, seg_lens[s]);
+    }
+    DevTable t;
+    const size_t cb = 2 * (size_t)S * sizeof(int64_t);
+    const size_t so = t.add(segs), co = t.room(cb), po = t.room((size_t)S * sizeof(float)), qo = t.room((size_t)n_part * sizeof(float));
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> cuts(2 * (size_t)S);
+    int rc = 0;
+    launch_stitch_peak(wav, t.at<StitchSeg>(so), S, max_len, t.at<float>(qo), s);
+    launch_stitch_edges(wav, t.at<StitchSeg>(so), S, t.at<float>(qo), trim_frac, trim_abs, t.at<float>(po), t.at<int64_t>(co), s);
+    if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    if (rc == 0 && (hipMemcpy(cuts.data(), t.at<int64_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(peak, t.at<float>(po), (size_t)S * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
+    if (rc == 0) for (int i = 0; i < S; ++i) { first[i] = cuts[2 * (size_t)i]; last[i] = cuts[2 * (size_t)i + 1]; }
+    return rc;
+}
+int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, uint8_t* slots, int32_t* sizes,
+                      uint8_t* kind, uint8_t* porder, void* stream) {
+    ev_flac_config c;
+    if (cfg) c = *cfg; else ev_default_flac_config(&c);
+    if (!pcm || !lens || !slots || !sizes || !kind || !porder || B < 1 || B > 65535 || c.struct_size != sizeof(ev_flac_config)) return -2;
+    int sr_code = 0, bs_code = 0, at = 0;
+    FlacPlan plan;
+    if (flac_check_config(c, &sr_code, &bs_code) != FLAC_OK || (reinterpret_cast<uintptr_t>(slots) & 3)) return -2;
+    if (flac_plan(B, lens, c.block_size, plan, &at) != LEN_OK) return -2;
+    const size_t NF = plan.frames.size(), sb = NF * sizeof(int32_t);
+    DevTable t;
+    const size_t fo = t.add(plan.frames), so = t.room(sb), d_o = t.room(sb);
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    FlacParams fp = flac_params(c, sr_code, bs_code);
+    fp.pcm = pcm; fp.pcm_is_i16 = pcm_is_i16 != 0; fp.frames = t.at<FlacFrame>(fo); fp.scratch = slots; fp.sizes = t.at<int32_t>(so); fp.desc = t.at<uint32_t>(d_o);
+    std::vector<uint32_t> desc(NF);
+    int rc = 0;
+    if (launch_flac_encode(fp, (int64_t)NF, s) || hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    if (rc == 0 && (hipMemcpy(sizes, fp.sizes, sb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(desc.data(), fp.desc, sb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
+    if (rc == 0) for (size_t f = 0; f < NF; ++f) { kind[f] = (uint8_t)(desc[f] & 0xFFu); porder[f] = (uint8_t)(desc[f] >> 8 & 0xFFu); }
+    return rc;
+}
+int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl,
+                     const int32_t* fr, const float* tab, int F, int D, const int64_t* doc_lens, float* out, int16_t* out_i16, void* stream) {
+    if (!wav || !src || !n || !seg_doc || !pos || !fl || !fr || !doc_lens || !out || S < 1 || S > 65535) return -2;
+    if (F < 0 || F > EV_STITCH_MAX_FADE || (F > 0 && !tab) || seg_doc[0] != 0) return -2;
+    for (int s = 0; s < S; ++s) {
+        const bool head = s == 0 || seg_doc[s] != seg_doc[s - 1];
+        if (s > 0 && seg_doc[s] != seg_doc[s - 1] && seg_doc[s] != seg_doc[s - 1] + 1) return -2;
+        if (seg_doc[s] >= D || src[s] < 0 || n[s] < 0 || n[s] > EV_STITCH_MAX_DOC || pos[s] < 0) return -2;
+        if (doc_lens[seg_doc[s]] < 0 || doc_lens[seg_doc[s]] > EV_STITCH_MAX_DOC || pos[s] + n[s] > doc_lens[seg_doc[s]]) return -2;
+        if (fl[s] < 0 || fr[s] < 0 || fl[s] > std::min((int64_t)F, n[s]) || fr[s] > std::min((int64_t)F, n[s])) return -2;
+        if (!head && (pos[s] < pos[s - 1] || pos[s] + n[s] < pos[s - 1] + n[s - 1])) return -2;
+        if (!head && s >= 2 && seg_doc[s - 2] == seg_doc[s] && pos[s] < pos[s - 2] + n[s - 2]) return -2;
+    }
+    if (seg_doc[S - 1] + 1 != D) return -2;
+    std::vector<StitchMixSeg> ms; std::vector<StitchDoc> docs; std::vector<StitchTile> tiles; std::vector<int64_t> offs((size_t)D + 1);
+    stitch_tables(S, D, src, n, seg_doc, pos, fl, fr, doc_lens, ms, docs, tiles, offs.data());
+    DevTable t;
+    const size_t mo = t.add(ms), d_o = t.add(docs), to = t.add(tiles), fo = t.add(tab, (size_t)F * sizeof(float));
+    if (t.commit()) return -1;
+    int rc = 0;
+    if (launch_stitch_mix(wav, t.at<StitchMixSeg>(mo), t.at<StitchDoc>(d_o), t.at<StitchTile>(to), (int64_t)tiles.size(), t.at<float>(fo), F, out, out_i16,
+                          (hipStream_t)stream)) rc = -2;
+    else if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+
+// The AlignSeq table of the two aligner kernels, from per-utterance host arrays: 0, or -2
+static int op_align_table(int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row, const int32_t* frames, const int64_t* lp_off,
+                          const int64_t* tok_packed, const int64_t* frm_packed, const int64_t* bits_off, bool mas, std::vector<AlignSeq>& tab, int* max_tok,
+                          int* max_frm) {
+    if (B <= 0 || B > 65535 || !tokens || !frames || !lp_off) return -2;
+    tab.resize((size_t)B);
+    *max_tok = 0; *max_frm = 0;
+    for (int b = 0; b < B; ++b) {
+        if (tokens[b] < 1 || tokens[b] > EV_ALIGN_MAX_TOKENS || frames[b] < 1 || frames[b] > EV_ALIGN_MAX_FRAMES || lp_off[b] < 0) return -2;
+        if (mas && frames[b] < tokens[b]) return -2;          // a monotonic path gives every token at least one frame
+        AlignSeq q{};
+        q.tok_row = tok_row ? tok_row[b] : 0; q.tokens = tokens[b]; q.frm_row = frm_row ? frm_row[b] : 0; q.frames = frames[b];
+        q.lp_off = lp_off[b]; q.tok_packed = tok_packed ? tok_packed[b] : 0; q.frm_packed = frm_packed ? frm_packed[b] : 0;
+        q.bits_off = bits_off ? bits_off[b] : 0;
+        if (q.tok_row < 0 || q.frm_row < 0 || q.tok_packed < 0 || q.frm_packed < 0 || q.bits_off < 0) return -2;
+        tab[(size_t)b] = q;
+        *max_tok = std::max(*max_tok, tokens[b]); *max_frm = std::max(*max_frm, frames[b]);
+    }
+    return 0;
+}
+int ev_op_align_score(const float* text, const float* feats, int C, int B, const int32_t* tok_row, const int32_t* tokens, const int32_t* frm_row,
+                      const int32_t* frames, const int64_t* lp_off, float* log_p, void* stream) {
+    if (C <= 0 || C % 32 || !tok_row || !frm_row || !log_p) return -2;      // channels are staged 32 at a time
+    std::vector<AlignSeq> tab; int max_tok = 0, max_frm = 0;
+    if (op_align_table(B, tok_row, tokens, frm_row, frames, lp_off, nullptr, nullptr, nullptr, false, tab, &max_tok, &max_frm)) return -2;
+    DevTable t;
+    const size_t o = t.add(tab);
+    if (t.commit()) return -1;
+    launch_align_score(text, feats, C, t.at<AlignSeq>(o), B, max_frm, log_p, (hipStream_t)stream);
+    int rc = hipGetLastError() == hipSuccess ? 0 : -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int32_t* frames, const int64_t* lp_off, const int64_t* tok_packed,
+                    const int64_t* frm_packed, const int64_t* bits_off, uint32_t* bits, const float* pitch_frames, const float* energy_frames,
+                    int64_t* dur, float* pitch_tok, float* energy_tok, float* score, void* stream) {
+    if (!log_p || !tok_packed || !frm_packed || !bits_off || !bits || !dur || !score) return -2;
+    if ((pitch_frames && !pitch_tok) || (energy_frames && !energy_tok)) return -2;
+    std::vector<AlignSeq> tab; int max_tok = 0, max_frm = 0;
+    if (op_align_table(B, nullptr, tokens, nullptr, frames, lp_off, tok_packed, frm_packed, bits_off, true, tab, &max_tok, &max_frm)) return -2;
+    DevTable t;
+    const size_t o = t.add(tab);
+    if (t.commit()) return -1;
+    launch_align_mas(log_p, t.at<AlignSeq>(o), B, max_tok, bits, pitch_frames, energy_frames, dur, pitch_tok, energy_tok, score, (hipStream_t)stream);
+    int rc = hipGetLastError() == hipSuccess ? 0 : -1;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Internal launcher interface between the engine (ev_engine.cpp) and the gfx950 kernels.
+// Internal launcher interface between the host code (ev_engine.cpp, ev_audio.cpp, ev_ops.cpp) and the gfx950 kernels.
 // Not part of the public ABI (that is include/evhip.h); the ev_op_* C wrappers in
 // include/evhip_ops.h expose these launchers to the per-kernel parity tests.
 #pragma once

@@ -91,7 +91,7 @@ def test_new_entry_points_are_bound_and_declared():
     assert c.mel_clip == np.float32(1e-5) and c.energy_floor == np.float32(1e-10)
     hdr = open(os.path.join(ROOT, "include", "evhip.h")).read()
     assert "EV_FLAG_DEVICE_MEL = 16" in hdr and "typedef struct ev_features_result" in hdr
-    # the limits the Python side validates against are the header's (ev_engine.cpp asserts them against the kernel's)
+    # the limits the Python side validates against are the header's (ev_audio.cpp asserts them against the kernel's)
     import re
     for name in ("EV_FEATURES_MAX_NFFT", "EV_FEATURES_MAX_MELS", "EV_FEATURES_MAX_RUN", "EV_ALIGN_MAX_FRAMES"):
         assert int(re.search(r"#define %s\s+(\d+)" % name, hdr).group(1)) == getattr(_ffi, name), name
