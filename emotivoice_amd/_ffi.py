@@ -182,6 +182,24 @@ class ev_loudness_result(C.Structure):
     ]
 
 
+EV_LIMIT_MAX_SAMPLES, EV_LIMIT_MAX_LOOKAHEAD, EV_LIMIT_MAX_HOLD, EV_LIMIT_TILE, EV_LIMIT_MAX_LDS = 1 << 30, 1024, 8192, 4096, 160 * 1024
+
+
+class ev_limit_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sample_rate", C.c_int32), ("ceiling", C.c_float), ("lookahead", C.c_int32), ("hold", C.c_int32),
+                ("want_i16", C.c_int32)]
+
+
+class ev_limit_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64),
+        ("wav", C.c_void_p), ("wav_i16", C.c_void_p),
+        ("true_peak_in", C.POINTER(C.c_float)), ("sample_peak_in", C.POINTER(C.c_float)), ("true_peak_out", C.POINTER(C.c_float)),
+        ("sample_peak_out", C.POINTER(C.c_float)), ("min_gain", C.POINTER(C.c_float)), ("limited", C.POINTER(C.c_int64)),
+        ("nonfinite", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -262,6 +280,10 @@ SIGNATURES = {
     "ev_loudness_design": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),      # host only
     # lens is a HOST array; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_loudness": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_loudness_config), C.c_uint32, C.POINTER(ev_loudness_result)]),
+    "ev_default_limit_config": (None, [C.POINTER(ev_limit_config)]),
+    "ev_limit_design": (C.c_int, [C.c_int, _P]),      # host only
+    # lens and gains are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_limit": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(ev_limit_config), C.c_uint32, C.POINTER(ev_limit_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),
@@ -314,6 +336,9 @@ SIGNATURES = {
     # everything but wav / out / out_i16 is a HOST array
     "ev_op_stitch_scan": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     "ev_op_flac_encode": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(ev_flac_config), _P, _P, _P, _P, _P]),
+    # lens, gains and the per-segment outputs are HOST arrays; wav, r, out, out_i16 and s are device buffers
+    "ev_op_limit_peak": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "ev_op_limit_apply": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "ev_op_stitch_mix": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 

@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1004,6 +1004,160 @@ int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     return 0;
 }
 
+// ------------------------------------------------------------------- true-peak metering and limiting (include/evhip.h: ev_limit)
+static_assert(EV_LIMIT_TILE == LIMIT_TILE && EV_LIMIT_MAX_LOOKAHEAD == LIMIT_MAX_LOOKAHEAD && EV_LIMIT_MAX_HOLD == LIMIT_MAX_HOLD && EV_LIMIT_MAX_LDS == LIMIT_MAX_LDS,
+              "include/evhip.h states the tile and the limits of ev_limit.hip");
+static_assert(EV_LIMIT_LDS_BYTES(EV_LIMIT_MAX_LOOKAHEAD, EV_LIMIT_MAX_HOLD) == limit_apply_lds_bytes(LIMIT_MAX_LOOKAHEAD, LIMIT_MAX_HOLD) &&
+              EV_LIMIT_LDS_BYTES(80, 800) == limit_apply_lds_bytes(80, 800), "include/evhip.h states the LDS formula of ev_limit.hip");
+void ev_default_limit_config(ev_limit_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c; c->sample_rate = 16000; c->ceiling = (float)pow(10.0, -1.0 / 20.0); c->lookahead = 80; c->hold = 800; c->want_i16 = 0;
+}
+
+int ev_limit_design(int L, float* w) {
+    if (L < 0 || L > EV_LIMIT_MAX_LOOKAHEAD || !w) return -1;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> g((size_t)L + 1);
+    double sum = 0.0;
+    for (int j = 0; j <= L; ++j) { g[(size_t)j] = 1.0 - cos(2.0 * pi * (double)(j + 1) / (double)(L + 2)); sum += g[(size_t)j]; }
+    for (int j = 0; j <= L; ++j) w[j] = (float)(g[(size_t)j] / sum);
+    for (;;) {      // the fp32 taps must not sum above one: s <= r rests on it
+        double acc = 0.0;
+        int top = 0;
+        for (int j = 0; j <= L; ++j) { acc += (double)w[j]; if (w[j] > w[top]) top = j; }
+        if (!(acc > 1.0)) break;
+        w[top] = nextafterf(w[top], 0.0f);
+    }
+    return L + 1;
+}
+
+// the interpolator's phase table and the window as the kernels read them
+static int limit_tables(int L, double tab[LIMIT_TAB], std::vector<double>& win) {
+    float h[LIMIT_TAPS];
+    if (ev_resample_design(1, 4, LIMIT_HALO, 0.945, 9.0, h, LIMIT_TAPS) != (LIMIT_TAPS - 1) / 2) return -1;
+    limit_pack_taps(h, tab);
+    std::vector<float> w((size_t)L + 1);
+    if (ev_limit_design(L, w.data()) != L + 1) return -1;
+    win.assign(w.begin(), w.end());
+    return 0;
+}
+// the first field of a config that is out of range, in the order include/evhip.h lists them
+enum LimitBad { LIMIT_OK = 0, LIMIT_BAD_RATE, LIMIT_BAD_CEILING, LIMIT_BAD_LOOKAHEAD, LIMIT_BAD_HOLD };
+static LimitBad limit_check_config(const ev_limit_config& c) {
+    if (flac_rate_code(c.sample_rate) < 0) return LIMIT_BAD_RATE;
+    if (!(c.ceiling > 0.f && c.ceiling <= 1.f)) return LIMIT_BAD_CEILING;
+    if (c.lookahead < 0 || c.lookahead > EV_LIMIT_MAX_LOOKAHEAD) return LIMIT_BAD_LOOKAHEAD;
+    if (c.hold < 0 || c.hold > EV_LIMIT_MAX_HOLD) return LIMIT_BAD_HOLD;
+    return LIMIT_OK;
+}
+static int limit_bad_gain(int B, const float* gains) {      // -1, or the first index of a gain that is negative, NaN or infinite
+    if (gains) for (int b = 0; b < B; ++b) if (!(std::isfinite(gains[b]) && gains[b] >= 0.f)) return b;
+    return -1;
+}
+// tile records -> segment records, in ascending tile order
+static void limit_fold_peaks(const LimitPlan& plan, int B, const LimitPeakOut* t, float* sp, float* tp, int64_t* nf) {
+    for (int b = 0; b < B; ++b) {
+        float s = 0.f, p = 0.f; int64_t n = 0;
+        for (int64_t i = plan.tile0[(size_t)b]; i < plan.tile0[(size_t)b + 1]; ++i) { s = std::max(s, t[i].sample_peak); p = std::max(p, t[i].true_peak); n += t[i].nonfinite; }
+        sp[b] = s; tp[b] = p; if (nf) nf[b] = n;
+    }
+}
+static void limit_fold_gains(const LimitPlan& plan, int B, const LimitApplyOut* t, float* mn, int64_t* limited) {
+    for (int b = 0; b < B; ++b) {
+        float m = 1.0f; int64_t n = 0;
+        for (int64_t i = plan.tile0[(size_t)b]; i < plan.tile0[(size_t)b + 1]; ++i) { m = std::min(m, t[i].min_gain); n += t[i].limited; }
+        mn[b] = m; limited[b] = n;
+    }
+}
+
+int ev_limit(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* gains, const ev_limit_config* cfg, uint32_t flags,
+             ev_limit_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_limit: wav is NULL");
+    if (!lens) return fail(h, "ev_limit: lens is NULL");
+    if (!out) return fail(h, "ev_limit: out is NULL");
+    if (check_struct_size(h, "ev_limit", "out->struct_size", out->struct_size, "ev_limit_result", sizeof(ev_limit_result))) return -1;
+    ev_limit_config dflt;
+    if (!cfg) { ev_default_limit_config(&dflt); cfg = &dflt; }
+    if (check_struct_size(h, "ev_limit", "cfg->struct_size", cfg->struct_size, "ev_limit_config", sizeof(ev_limit_config))) return -1;
+    const ev_limit_config c = *cfg;
+    switch (limit_check_config(c)) {
+    case LIMIT_OK: break;
+    case LIMIT_BAD_RATE: return fail(h, "ev_limit: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
+    case LIMIT_BAD_CEILING: return fail(h, "ev_limit: ceiling = %g outside (0, 1]", (double)c.ceiling);
+    case LIMIT_BAD_LOOKAHEAD: return fail(h, "ev_limit: lookahead = %d outside [0, EV_LIMIT_MAX_LOOKAHEAD = %d]", c.lookahead, EV_LIMIT_MAX_LOOKAHEAD);
+    case LIMIT_BAD_HOLD: return fail(h, "ev_limit: hold = %d outside [0, EV_LIMIT_MAX_HOLD = %d]", c.hold, EV_LIMIT_MAX_HOLD);
+    }
+    if (B < 1 || B > 65535) return fail(h, "ev_limit: B = %d outside [1, 65535]", B);
+    LimitPlan plan;
+    int at = 0;
+    switch (limit_plan(B, lens, plan, &at)) {
+    case LEN_OK: break;
+    case LEN_SHORT: return fail(h, "ev_limit: lens[%d] = %lld < 1", at, (long long)lens[at]);
+    case LEN_LONG: return fail(h, "ev_limit: lens[%d] = %lld > EV_LIMIT_MAX_SAMPLES = %d", at, (long long)lens[at], EV_LIMIT_MAX_SAMPLES);
+    case LEN_COUNT: return fail(h, "ev_limit: lens[%d] = %lld: more than %d tiles in one call", at, (long long)lens[at], INT_MAX);
+    }
+    at = limit_bad_gain(B, gains);
+    if (at >= 0) return fail(h, "ev_limit: gains[%d] = %g is not finite and >= 0", at, (double)gains[at]);
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0;
+    const int L = c.lookahead, Hd = c.hold;
+    const int64_t total = plan.total, NT = (int64_t)plan.tiles.size();
+    double tab[LIMIT_TAB];
+    std::vector<double> win;
+    if (limit_tables(L, tab, win)) return fail(h, "ev_limit: the interpolator's design failed");
+    if (call_begin(h)) return -1;
+    const size_t es = in16 ? sizeof(int16_t) : sizeof(float);
+    char* d_in = nullptr; LimitTile* d_tiles = nullptr; double *d_tab = nullptr, *d_win = nullptr; float *d_gain = nullptr, *d_r = nullptr, *d_wav = nullptr;
+    int16_t* d_i16 = nullptr; LimitPeakOut *d_pin = nullptr, *d_pout = nullptr; LimitApplyOut* d_app = nullptr;
+    if (arena_plan(h, ARENA_LIMIT, [&](ArenaPlan& ap) {
+        if (!dev_in) d_in = ap.arr<char>((size_t)total * es);
+        d_tiles = ap.arr<LimitTile>((size_t)NT); d_tab = ap.arr<double>(LIMIT_TAB); d_win = ap.arr<double>((size_t)L + 1);
+        if (gains) d_gain = ap.arr<float>((size_t)B);
+        d_r = ap.arr<float>((size_t)total); d_wav = ap.arr<float>((size_t)total);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
+        d_pin = ap.arr<LimitPeakOut>((size_t)NT); d_pout = ap.arr<LimitPeakOut>((size_t)NT); d_app = ap.arr<LimitApplyOut>((size_t)NT);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_in, wav, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_tiles, plan.tiles) || upload(h, d_win, win)) return -1;
+    HIPCHK(h, hipMemcpyAsync(d_tab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
+    if (gains) HIPCHK(h, hipMemcpyAsync(d_gain, gains, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    const void* x = dev_in ? wav : (const void*)d_in;
+    const double meter_flops = 2.0 * LIMIT_TAB * (double)total, rec = (double)NT * sizeof(LimitPeakOut);
+    region_begin(h, "total");
+    {
+        KScope ks(h, "limit_peak", meter_flops, (double)total * ((double)es + 4.0) + rec);
+        if (launch_limit_peak(x, in16, d_gain, d_tiles, NT, d_tab, c.ceiling, d_r, d_pin, h->stream)) return fail(h, "ev_limit: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "limit_apply", 2.0 * (double)(L + 1) * (double)total, (double)total * ((double)es + 8.0 + (i16 ? 2.0 : 0.0)) + (double)NT * sizeof(LimitApplyOut));
+        if (launch_limit_apply(x, in16, d_gain, d_tiles, NT, d_r, d_win, L, Hd, d_wav, i16 ? d_i16 : nullptr, nullptr, d_app, h->stream))
+            return fail(h, "ev_limit: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "limit_measure", meter_flops, 4.0 * (double)total + rec);
+        if (launch_limit_peak(d_wav, 0, nullptr, d_tiles, NT, d_tab, c.ceiling, nullptr, d_pout, h->stream)) return fail(h, "ev_limit: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<LimitPeakOut> pin((size_t)NT), pout((size_t)NT); std::vector<LimitApplyOut> app((size_t)NT);
+    HIPCHK(h, hipMemcpyAsync(pin.data(), d_pin, (size_t)NT * sizeof(LimitPeakOut), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pout.data(), d_pout, (size_t)NT * sizeof(LimitPeakOut), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(app.data(), d_app, (size_t)NT * sizeof(LimitApplyOut), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    std::vector<float> tp_in((size_t)B), sp_in((size_t)B), tp_out((size_t)B), sp_out((size_t)B), mn((size_t)B); std::vector<int64_t> limited((size_t)B), nonf((size_t)B);
+    limit_fold_peaks(plan, B, pin.data(), sp_in.data(), tp_in.data(), nonf.data());
+    limit_fold_peaks(plan, B, pout.data(), sp_out.data(), tp_out.data(), nullptr);
+    limit_fold_gains(plan, B, app.data(), mn.data(), limited.data());
+    h->lim.tp_in.swap(tp_in); h->lim.sp_in.swap(sp_in); h->lim.tp_out.swap(tp_out); h->lim.sp_out.swap(sp_out); h->lim.min_gain.swap(mn);
+    h->lim.limited.swap(limited); h->lim.nonf.swap(nonf);
+    reset_result(out);
+    out->batch = B; out->total = total; out->wav = d_wav; out->wav_i16 = i16 ? d_i16 : nullptr;
+    out->true_peak_in = h->lim.tp_in.data(); out->sample_peak_in = h->lim.sp_in.data(); out->true_peak_out = h->lim.tp_out.data();
+    out->sample_peak_out = h->lim.sp_out.data(); out->min_gain = h->lim.min_gain.data(); out->limited = h->lim.limited.data(); out->nonfinite = h->lim.nonf.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- per-kernel test entry points of the utilities (include/evhip_ops.h)
 // Each builds its kernel's tables from per-utterance HOST arrays (no struct crosses the boundary), launches on the caller's stream and waits for it
 // before the tables go.  -2: a rejected argument or shape; -1: a runtime failure.
@@ -1246,6 +1400,54 @@ int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int3
     launch_align_mas(log_p, t.at<AlignSeq>(o), B, max_tok, bits, pitch_frames, energy_frames, dur, pitch_tok, energy_tok, score, (hipStream_t)stream);
     int rc = hipGetLastError() == hipSuccess ? 0 : -1;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+
+int ev_op_limit_peak(const void* wav, int wav_is_i16, int B, const int64_t* lens, const float* gains, float ceiling, float* r, float* sample_peak,
+                     float* true_peak, int64_t* nonfinite, void* stream) {
+    if (!wav || !lens || !sample_peak || !true_peak || !nonfinite || B < 1 || B > 65535 || !(ceiling > 0.f && ceiling <= 1.f)) return -2;
+    LimitPlan plan;
+    int at = 0;
+    if (limit_plan(B, lens, plan, &at) != LEN_OK || limit_bad_gain(B, gains) >= 0) return -2;
+    double tab[LIMIT_TAB];
+    std::vector<double> win;
+    if (limit_tables(0, tab, win)) return -1;
+    const size_t NT = plan.tiles.size();
+    DevTable t;
+    const size_t to = t.add(plan.tiles), ho = t.add(tab, sizeof tab), go = gains ? t.add(gains, (size_t)B * sizeof(float)) : 0, oo = t.room(NT * sizeof(LimitPeakOut));
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<LimitPeakOut> outs(NT);
+    int rc = 0;
+    if (launch_limit_peak(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, t.at<double>(ho), ceiling, r, t.at<LimitPeakOut>(oo), s) ||
+        hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    if (rc == 0 && hipMemcpy(outs.data(), t.at<LimitPeakOut>(oo), NT * sizeof(LimitPeakOut), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+    if (rc == 0) limit_fold_peaks(plan, B, outs.data(), sample_peak, true_peak, nonfinite);
+    return rc;
+}
+int ev_op_limit_apply(const void* wav, int wav_is_i16, int B, const int64_t* lens, const float* gains, const float* r, int lookahead, int hold, float* out,
+                      int16_t* out_i16, float* s_out, float* min_gain, int64_t* limited, void* stream) {
+    if (!wav || !lens || !r || !out || !min_gain || !limited || B < 1 || B > 65535) return -2;
+    if (lookahead < 0 || lookahead > EV_LIMIT_MAX_LOOKAHEAD || hold < 0 || hold > EV_LIMIT_MAX_HOLD) return -2;
+    LimitPlan plan;
+    int at = 0;
+    if (limit_plan(B, lens, plan, &at) != LEN_OK || limit_bad_gain(B, gains) >= 0) return -2;
+    double tab[LIMIT_TAB];
+    std::vector<double> win;
+    if (limit_tables(lookahead, tab, win)) return -1;
+    const size_t NT = plan.tiles.size();
+    DevTable t;
+    const size_t to = t.add(plan.tiles), wo = t.add(win), go = gains ? t.add(gains, (size_t)B * sizeof(float)) : 0, oo = t.room(NT * sizeof(LimitApplyOut));
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<LimitApplyOut> outs(NT);
+    int rc = 0;
+    if (launch_limit_apply(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, r, t.at<double>(wo), lookahead, hold, out, out_i16,
+                           s_out, t.at<LimitApplyOut>(oo), s) || hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    if (rc == 0 && hipMemcpy(outs.data(), t.at<LimitApplyOut>(oo), NT * sizeof(LimitApplyOut), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+    if (rc == 0) limit_fold_gains(plan, B, outs.data(), min_gain, limited);
     return rc;
 }
 

@@ -35,6 +35,7 @@ enum Arena {
     ARENA_COMPARE,     // ev_compare (scratch only: its result is host memory)
     ARENA_FLAC,        // ev_flac (like ARENA_ALIGN)
     ARENA_LOUDNESS,    // ev_loudness (likewise)
+    ARENA_LIMIT,       // ev_limit (likewise)
     ARENA_COUNT
 };
 
@@ -81,6 +82,7 @@ struct LoudnessState {       // ev_loudness
     std::vector<double> loud, rel, ms; std::vector<float> gain, peak; std::vector<uint8_t> flags, state;
     std::vector<int64_t> nonf, boffs;
 };
+struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
 
 }  // namespace evh
 
@@ -115,7 +117,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

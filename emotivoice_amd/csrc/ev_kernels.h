@@ -365,4 +365,23 @@ int launch_loudness_measure(const void* wav, int is16, const LoudTile* tiles, in
 int launch_loudness_gain(const void* wav, int is16, const int64_t* offs, int B, const float* gain, int64_t total, float* out, int16_t* out_i16,
                          hipStream_t s);
 
+// ev_limit (ev_limit.hip): packed segments -> per sample the gain r that the 4x true-peak meter requires, per tile of LIMIT_TILE samples (counted
+// from its segment's start) the sample peak, the true peak and the count of non-finite samples; then, per tile, the eroded and smoothed gain s, the
+// limited waveform, the smallest s and the count of s < 1.  The taps go in as limit_pack_taps lays them out; the window as L + 1 doubles.
+constexpr int LIMIT_TILE = 4096, LIMIT_HALO = 16, LIMIT_TAPS = 129, LIMIT_TAB = 4 * (2 * LIMIT_HALO + 1);
+constexpr int LIMIT_MAX_LOOKAHEAD = 1024, LIMIT_MAX_HOLD = 8192, LIMIT_MAX_LDS = 160 * 1024;
+struct LimitTile { int64_t src, pos, len; int32_t n, seg; };      // first sample in the packed input, the same counted in its segment, the segment's length, 1 .. LIMIT_TILE samples, the segment
+struct LimitPeakOut { float sample_peak, true_peak; int32_t nonfinite, pad; };
+struct LimitApplyOut { float min_gain; int32_t limited; };
+// r reach twice (the erosion's two copies) and the window in fp64: EV_LIMIT_LDS_BYTES of include/evhip.h
+constexpr size_t limit_apply_lds_bytes(int L, int Hd) { return 2 * sizeof(float) * (size_t)(LIMIT_TILE + 2 * L + Hd) + sizeof(double) * (size_t)(L + 1); }
+// tab[(d + LIMIT_HALO) * 4 + q] = (double)h[q - 4 d], d = -LIMIT_HALO .. LIMIT_HALO, 0 outside the taps' support: host, LIMIT_TAB doubles
+void limit_pack_taps(const float* h /* host (LIMIT_TAPS,), h[-64 .. 64] */, double* tab);
+// gains: device (B,) or null = 1; r: device, packed as the input, or null = measure only.  0, or -1 for a grid that does not exist.
+int launch_limit_peak(const void* wav, int is16, const float* gains, const LimitTile* tiles, int64_t n_tiles, const double* tab, float ceiling, float* r,
+                      LimitPeakOut* outs, hipStream_t s);
+// win: device (L + 1,) doubles; out_i16 and s_out (the gain per sample) may be null.  0, or -1 for bad parameters.
+int launch_limit_apply(const void* wav, int is16, const float* gains, const LimitTile* tiles, int64_t n_tiles, const float* r, const double* win, int L,
+                       int Hd, float* out, int16_t* out_i16, float* s_out, LimitApplyOut* outs, hipStream_t s);
+
 }  // namespace ev

@@ -126,4 +126,26 @@ inline LenBad loudness_plan(int B, const int64_t* lens, int64_t step, LoudPlan& 
     return LEN_OK;
 }
 
+// ---------------------------------------------------------------- tiles of LIMIT_TILE samples (ev_limit)
+struct LimitPlan { std::vector<ev::LimitTile> tiles; std::vector<int64_t> tile0; int64_t total = 0; };      // tile0: (B + 1,), the segment's tiles are [tile0[b], tile0[b + 1])
+inline LenBad limit_plan(int B, const int64_t* lens, LimitPlan& p, int* at) {
+    int64_t NT = 0;
+    p.total = 0;
+    for (int b = 0; b < B; ++b) {
+        *at = b;
+        if (lens[b] < 1) return LEN_SHORT;
+        if (lens[b] > EV_LIMIT_MAX_SAMPLES) return LEN_LONG;
+        p.total += lens[b]; NT += (lens[b] + ev::LIMIT_TILE - 1) / ev::LIMIT_TILE;
+        if (NT > INT_MAX) return LEN_COUNT;
+    }
+    p.tiles.clear(); p.tiles.reserve((size_t)NT);
+    p.tile0.assign((size_t)B + 1, 0);
+    for (int64_t b = 0, off = 0; b < B; off += lens[b], ++b) {
+        for (int64_t i = 0; i < lens[b]; i += ev::LIMIT_TILE)
+            p.tiles.push_back(ev::LimitTile{off + i, i, lens[b], (int32_t)std::min<int64_t>(ev::LIMIT_TILE, lens[b] - i), (int32_t)b});
+        p.tile0[(size_t)b + 1] = (int64_t)p.tiles.size();
+    }
+    return LEN_OK;
+}
+
 }  // namespace evh

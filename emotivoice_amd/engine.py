@@ -100,6 +100,7 @@ class EVEngine:
         self.last_compare: Optional[_ffi.ev_compare_result] = None
         self.last_flac: Optional[_ffi.ev_flac_result] = None
         self.last_loudness: Optional[_ffi.ev_loudness_result] = None
+        self.last_limit: Optional[_ffi.ev_limit_result] = None
 
     # -- lifecycle
     def close(self):
@@ -448,7 +449,7 @@ class EVEngine:
         flat = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in wavs]))
         return self.stitch_to_numpy(self.stitch_raw(len(wavs), flat.ctypes.data, offs, lens, seg_doc, pause_after, sc))
 
-    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None) -> Dict[str, object]:
+    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
@@ -459,7 +460,9 @@ class EVEngine:
         config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to).
         loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every document is normalised on the device after ev_stitch
         (ev_loudness: one gain per document, so the balance between its sentences stays) and before ev_flac; ``documents`` (int16 by the
-        clamping rule with config.want_int16) then hold the normalised audio and ``loudness`` the per-document figures."""
+        clamping rule with config.want_int16) then hold the normalised audio and ``loudness`` the per-document figures.
+        limiter: as ``synthesize`` takes it, per document: ev_limit after ev_stitch (and after ev_loudness's measurement when ``loudness`` is
+        given, whose pre-gain it applies) and before ev_flac; ``documents`` hold the limited audio and ``limiter`` the per-document figures."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
@@ -476,10 +479,23 @@ class EVEngine:
         up = self.shapes.upsample_factor
         mel_offs = np.array([res.mel_offsets[b] for b in range(S + 1)], np.int64)
         st = self.stitch_raw(S, res.wav, mel_offs[:-1] * up, np.diff(mel_offs) * up, seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
-        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=loudness is not None)
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=loudness is not None or limiter is not None)
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
         pcm_i16 = st.wav_i16
-        if loudness is not None:
+        if limiter is not None:
+            if empty:
+                raise ValueError("limiter: document %d is empty after the cut" % empty[0])
+            lm, lim, meas = self._measure_and_limit(st.batch_docs, st.wav, out["doc_lens"], loudness, limiter, int(sc.sample_rate), sc.want_int16,
+                                                    int16_only=sc.want_int16)
+            if "wav" in lim:
+                out["wav"], out["docs"] = lim.pop("wav"), lim.pop("wav_list")
+            if "wav_i16" in lim:
+                out["wav_i16"], out["docs_i16"] = lim.pop("wav_i16"), lim.pop("wav_i16_list")
+            if meas is not None:
+                out["loudness"] = meas
+            out["limiter"] = lim
+            pcm_i16 = lm.wav_i16
+        elif loudness is not None:
             from .loudness import as_config
             if empty:
                 raise ValueError("loudness: document %d is empty after the cut" % empty[0])
@@ -683,6 +699,83 @@ class EVEngine:
         lens = np.array([a.size for a in arrs], np.int64)
         return self.loudness_to_numpy(self.loudness_raw(len(arrs), flat.ctypes.data, is16, lens, lc))
 
+    # -- true-peak metering and limiting (ev_limit): a 4x true-peak meter, a gain per sample that holds the ceiling and the limited waveform, on the device
+    def limit_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, gains=None, config=None, flags: int = 0) -> _ffi.ev_limit_result:
+        """ev_limit (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens and gains (None: all 1) are
+        host arrays.  config: an emotivoice_amd.limiter.LimiterConfig, an _ffi.ev_limit_config or None (the library's default: 16 kHz, -1 dBTP, 80
+        and 800 samples).  The returned struct's device waveforms and host arrays stay valid until the next limit call on this engine."""
+        ln = np.ascontiguousarray(lens, np.int64)
+        if ln.size != B:
+            raise ValueError("lens must have B = %d entries" % B)
+        gn = None
+        if gains is not None:
+            gn = np.ascontiguousarray(gains, np.float32)
+            if gn.shape != (B,):
+                raise ValueError("gains must have B = %d entries" % B)
+        c = config.validate().to_struct() if hasattr(config, "to_struct") else config
+        res = _ffi.ev_limit_result()
+        res.struct_size = C.sizeof(_ffi.ev_limit_result)
+        self._check(self._lib.ev_limit(self._h, B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, ln.ctypes.data_as(C.c_void_p),
+                                       gn.ctypes.data_as(C.c_void_p) if gn is not None else None, C.byref(c) if c is not None else None, flags,
+                                       C.byref(res)))
+        res._lens = ln.copy()      # the packing of res.wav / res.wav_i16, for limit_to_numpy
+        self.last_limit = res
+        return res
+
+    def limit_to_numpy(self, res: _ffi.ev_limit_result, int16_only: bool = False, lens=None) -> Dict[str, object]:
+        """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
+        output only; without it both).  lens: the call's lens, which cut the output into wav_list / wav_i16_list (None: the ones limit_raw kept
+        with the struct)."""
+        B = res.batch
+        arr = lambda p, dt: np.ctypeslib.as_array(p, (B,)).astype(dt, copy=True)      # noqa: E731
+        out: Dict[str, object] = dict(true_peak_in=arr(res.true_peak_in, np.float32), sample_peak_in=arr(res.sample_peak_in, np.float32),
+                                      true_peak_out=arr(res.true_peak_out, np.float32), sample_peak_out=arr(res.sample_peak_out, np.float32),
+                                      min_gain=arr(res.min_gain, np.float32), limited=arr(res.limited, np.int64), nonfinite=arr(res.nonfinite, np.int64))
+        lens = np.asarray(res._lens if lens is None else lens, np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        if not (int16_only and res.wav_i16):
+            out["wav"] = self.d2h(res.wav, (int(res.total),), np.float32)
+            out["wav_list"] = [out["wav"][offs[b]:offs[b + 1]] for b in range(B)]
+        if res.wav_i16:
+            out["wav_i16"] = self.d2h(res.wav_i16, (int(res.total),), np.int16)
+            out["wav_i16_list"] = [out["wav_i16"][offs[b]:offs[b + 1]] for b in range(B)]
+        return out
+
+    def limit(self, wavs: Sequence[np.ndarray], gains=None, **config) -> Dict[str, object]:
+        """Host signals -> their peaks and the limited signals.  wavs: one 1-D array per segment, all int16 or all floating, at any rate of the
+        table; gains: one pre-gain per segment (None: 1); further keywords: the fields of emotivoice_amd.limiter.LimiterConfig.  Needs no weights."""
+        from .limiter import LimiterConfig
+        lc = LimiterConfig(**config).validate()
+        if not len(wavs):
+            raise ValueError("wavs must hold at least one segment")
+        arrs = [np.asarray(x) for x in wavs]
+        is16 = arrs[0].dtype == np.int16
+        for s, a in enumerate(arrs):
+            if a.ndim != 1 or a.size < 1 or (a.dtype == np.int16) != is16 or not (is16 or np.issubdtype(a.dtype, np.floating)):
+                raise ValueError("segment %d: non-empty 1-D arrays, all int16 or all floating" % s)
+        flat = np.ascontiguousarray(np.concatenate([a.astype(np.int16 if is16 else np.float32, copy=False) for a in arrs]))
+        lens = np.array([a.size for a in arrs], np.int64)
+        return self.limit_to_numpy(self.limit_raw(len(arrs), flat.ctypes.data, is16, lens, gains, lc))
+
+    def _measure_and_limit(self, B: int, wav_ptr: int, lens: np.ndarray, loudness, limiter, sample_rate: int, want_int16: bool, int16_only: bool = False):
+        """``loudness=`` with ``limiter=`` on a device waveform: ev_loudness measure only, the pre-gain on the host (the gain rule without its
+        sample-peak step), then ev_limit, which scales and limits in its one pass.  With ``limiter=`` alone the gains are 1.
+        -> (ev_limit_result, the limiter's dict, the loudness dict or None)."""
+        import dataclasses
+        from .limiter import as_config as limiter_config, pre_gain
+        mc = limiter_config(limiter, sample_rate, want_int16)
+        gains, meas = None, None
+        if loudness is not None:
+            from .loudness import as_config as loudness_config
+            lc = loudness_config(loudness, sample_rate)
+            only = dataclasses.replace(lc, target_lufs=float("nan"), want_int16=False)
+            meas = self.loudness_to_numpy(self.loudness_raw(B, wav_ptr, False, lens, only, _ffi.EV_FLAG_DEVICE_INPUTS))
+            pairs = [pre_gain(float(l), lc) for l in meas["loudness"]]
+            gains = np.array([g for g, _ in pairs], np.float32)
+            meas["gain"], meas["flags"] = gains.copy(), np.array([f for _, f in pairs], np.uint8)
+        lm = self.limit_raw(B, wav_ptr, False, lens, gains, mc, _ffi.EV_FLAG_DEVICE_INPUTS)
+        return lm, self.limit_to_numpy(lm, int16_only=int16_only), meas
+
     def set_forced_durations(self, durations: np.ndarray):
         d = np.ascontiguousarray(durations, np.int64)
         self._check(self._lib.ev_set_forced_durations(self._h, d.ctypes.data_as(C.c_void_p), d.size))
@@ -740,7 +833,7 @@ class EVEngine:
         return res, cu
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
@@ -751,9 +844,18 @@ class EVEngine:
         loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every utterance is normalised on the device
         (ev_loudness on the vocoder's waveform).  wav / wav_list then hold the normalised audio, want_int16 adds wav_i16 / wav_int16_list
         by the clamping rule (not EV_FLAG_WANT_INT16's wrapping cast), ``loudness`` holds the per-utterance figures, and flac encodes the
-        normalised int16: a stream decodes to wav_int16_list[b]."""
+        normalised int16: a stream decodes to wav_int16_list[b].
+        limiter: None, True, a true-peak ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: every utterance goes through ev_limit
+        on the device.  With ``loudness`` the gain to the target is no longer cut by the utterance's largest sample: ev_loudness only measures,
+        the pre-gain (emotivoice_amd.limiter.pre_gain) goes into ev_limit, and the limiter holds the peaks sample by sample; ``loudness`` then
+        holds the measurement and the pre-gain, ``limiter`` the limiter's per-utterance figures, and the audio, the int16 (clamping rule) and
+        the FLAC streams are the limiter's.  The loudness is not measured again after the limiter: it sits at or slightly below the target."""
         if flac is not None and flac is not False and not vocoder:
             raise ValueError("flac needs the vocoder's waveform")
+        if limiter is not None:
+            if not vocoder:
+                raise ValueError("limiter needs the vocoder's waveform")
+            return self._synthesize_limited(utts, alpha, want_int16, forced_durations, prosody, flac, loudness, limiter)
         if loudness is not None:
             if not vocoder:
                 raise ValueError("loudness needs the vocoder's waveform")
@@ -788,6 +890,26 @@ class EVEngine:
         out["loudness"] = norm
         if want_flac:
             out["flac_list"] = self._flac_of_result(res, flac, pcm_i16=ld.wav_i16)
+        return out
+
+    def _synthesize_limited(self, utts, alpha, want_int16, forced_durations, prosody, flac, loudness, limiter) -> Dict[str, object]:
+        """``synthesize`` with ``limiter=``: the synthesis call, ev_loudness (measure only) when a target is given, ev_limit on the device
+        waveform, D2H copies of the limited audio only."""
+        want_flac = flac is not None and flac is not False
+        res, cu = self._synthesize_call(utts, alpha, 0, forced_durations, prosody)
+        out = self.result_to_numpy(res, skip_wav=True)
+        out["cu_seqlens"] = cu
+        B, up = res.batch, self.shapes.upsample_factor
+        lm, lim, meas = self._measure_and_limit(B, res.wav, np.diff(out["mel_offsets"]) * up, loudness, limiter, int(self.shapes.sr), want_int16 or want_flac)
+        out["wav"], out["wav_list"] = lim.pop("wav"), lim.pop("wav_list")
+        i16, i16_list = lim.pop("wav_i16", None), lim.pop("wav_i16_list", None)
+        if want_int16 or want_flac:
+            out["wav_i16"], out["wav_int16_list"] = i16, i16_list
+        if meas is not None:
+            out["loudness"] = meas
+        out["limiter"] = lim
+        if want_flac:
+            out["flac_list"] = self._flac_of_result(res, flac, pcm_i16=lm.wav_i16)
         return out
 
     def vocoder(self, mels: Sequence[np.ndarray], want_int16: bool = False) -> Dict[str, object]:

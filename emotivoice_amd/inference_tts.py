@@ -188,6 +188,9 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
     if getattr(args, "loudness", None) is not None:      # every utterance normalised on the device (ev_loudness) before it is written
         import functools
         synthesize = functools.partial(eng.synthesize, loudness=float(args.loudness))
+    if getattr(args, "true_peak", None) is not None:     # the true peak held at a ceiling on the device (ev_limit); with --loudness it replaces the sample-peak limit
+        import functools
+        synthesize = functools.partial(synthesize, limiter=float(args.true_peak))
     try:
         stats = run_chunk(lines, start_idx, chunk_num, synthesize=synthesize, embed=embed, g2p=g2p, token2id=token2id,
                           id2speaker=id2speaker, output_dir=output_dir, sampling_rate=int(getattr(config, "sampling_rate", gen.shapes.sr)),
@@ -222,6 +225,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                    help="normalise every utterance on the device to this programme loudness (ITU-R BS.1770, e.g. -16), at most +20 dB and with the "
                         "sample peak held at -1 dBFS; default: the vocoder's level, untouched")
+    p.add_argument("--true-peak", type=float, default=None, metavar="DBTP",
+                   help="hold every utterance's true (inter-sample) peak at this ceiling with the look-ahead limiter on the device (e.g. -1); with "
+                        "--loudness the gain to the target is then no longer cut by the utterance's largest sample; default: no limiter")
     return p
 
 

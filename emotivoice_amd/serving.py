@@ -304,25 +304,35 @@ def _loudness_kw(loudness) -> dict:
     return {} if loudness is None else dict(loudness=loudness)
 
 
-def engine_synth_fn(engine, loudness=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
-    """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness)."""
+def _output_kw(loudness, limiter) -> dict:
+    """``loudness`` and ``limiter`` (None, True, a ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: ev_limit on every utterance) of
+    the engine_*_synth_fn factories; like ``loudness`` a service-level setting.  Both None: synthesize is called exactly as before."""
     kw = _loudness_kw(loudness)
+    if limiter is not None:
+        kw["limiter"] = limiter
+    return kw
+
+
+def engine_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
+    """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness); ``limiter``: its
+    true peak held at a ceiling (ev_limit)."""
+    kw = _output_kw(loudness, limiter)
     return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
 
 
-def engine_prosody_synth_fn(engine, loudness=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
-    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``: as
-    ``engine_synth_fn``."""
-    kw = _loudness_kw(loudness)
+def engine_prosody_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness`` and
+    ``limiter``: as ``engine_synth_fn``."""
+    kw = _output_kw(loudness, limiter)
     return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
 
 
-def engine_flac_synth_fn(engine, loudness=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_flac_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
     second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
-    streams then carry the normalised int16 (the clamping conversion)."""
-    lkw = _loudness_kw(loudness)
+    streams then carry the normalised int16 (the clamping conversion).  ``limiter``: as ``engine_synth_fn``; the streams carry the limiter's int16."""
+    lkw = _output_kw(loudness, limiter)
 
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)

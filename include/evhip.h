@@ -722,6 +722,88 @@ typedef struct ev_loudness_result {
 int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_loudness_config* cfg, uint32_t flags,
                 ev_loudness_result* out);
 
+/* True-peak metering and look-ahead limiting (ev_limit): packed segments -> their sample peak and true (inter-sample) peak, a gain per SAMPLE that
+ * holds the true peak at a ceiling, and the limited waveform, on the device: it sits between ev_loudness and ev_flac, so that one plosive no
+ * longer lowers the gain of its whole utterance (ev_loudness's step 4).  The reference has no such stage; the arithmetic is the one specified
+ * here.  The defaults (-1 dBTP, 80 samples of look-ahead and 800 of hold: 5 ms and 50 ms at 16 kHz) are starting values; none has been measured
+ * on a released checkpoint.
+ *   Pre-gain: u[n] = x[n] * gains[b], one rounded fp32 product of the fp32 sample or of (float)s / 32768.0f; where gains[b] == 1.0f (or gains is
+ *     NULL) the source bits pass through.  A non-finite u (NaN, +-inf) counts once in nonfinite[b] and enters the meter as 0.
+ *   Interpolator: h[-64 .. 64] = ev_resample_design(1, 4, 16, 0.945, 9.0): the 4x windowed sinc of ev_resample, 129 fp32 taps.
+ *   Oversampled signal: v[4 n + q] = sum_k u[k] h[4 n + q - 4 k], q = 0 .. 3, k ascending over the taps' support, u = +0 outside [0, len): an fp64
+ *     accumulation from +0.0 of the exact fp32 x fp32 products in that order, rounded once to fp32.  (An fp64 fma of an exact product equals
+ *     multiply-then-add, so contraction cannot change the bits.)
+ *   Peaks: p[n] = max(|u[n]|, |v[4 n]|, |v[4 n + 1]|, |v[4 n + 2]|, |v[4 n + 3]|); true_peak_in[b] = max_n p[n], sample_peak_in[b] = max_n |u[n]|.
+ *     Known limitation: this is the project's own 4x windowed sinc, not the table printed in BS.1770 annex 2, and it under-reads near Nyquist: a
+ *     sine at 0.4 fs reads about 3 % low, one at 0.45 fs about 23 % low (INTEGRATION.md has the table).
+ *   Required gain: r[n] = 1.0f if p[n] <= ceiling, else (float)((double)ceiling / (double)p[n]); r = 1 for every index outside [0, len).
+ *   Erosion: m[k] = min(r[k - Hd .. k + L]) for EVERY integer k, the indices before 0 and past len - 1 included: m[k] for k in [-L, 0) can be
+ *     below 1 (it is not padded with ones; that would break s <= r at a segment's first and last samples).  L = lookahead, Hd = hold.
+ *   Window (ev_limit_design, host, fp64): w[j] = 1 - cos(2 pi (j + 1) / (L + 2)), j = 0 .. L, divided by its sum (added in ascending j) and rounded
+ *     to fp32; then, while the fp64 sum of the fp32 taps in ascending j exceeds 1, the first largest tap is lowered by one ulp toward 0.
+ *   Gain: s[n] = 1.0f exactly when m[n - j] == 1.0f for all j = 0 .. L; otherwise s[n] = (float)(sum_j (double)w[j] * (double)m[n - j]), fp64,
+ *     j ascending from +0.0.  Every m[n - j] covers sample n, the taps sum to at most 1 and rounding is monotone, so s[n] <= r[n] bitwise.  The
+ *     gain starts to fall L samples before a peak, is at the required value at the peak, holds for Hd samples and is back at 1 after L more.
+ *     L = 0 does not smooth: the sample peak holds, the true peak of the output can exceed the ceiling by a few percent.
+ *   Output: y[n] = u[n] * s[n], one rounded fp32 product; where s[n] == 1.0f the bits of u pass through.  want_i16: ev_stitch's rule,
+ *     (int)(y * 32768.0f) truncated toward zero, then clamped to [-32768, 32767]; it never wraps; NaN -> 0.
+ *   true_peak_out / sample_peak_out: the same meter over y (a non-finite y enters as 0).  min_gain[b] = min_n s[n]; limited[b] = the count of
+ *     s[n] < 1.
+ * No atomics, no recursion, nothing carried from tile to tile: every value depends on (segment, index) alone, and the maxima, the minimum and the
+ * counts are exact in any order.  A segment gives the same bits alone or anywhere in a batch, from host or device memory, as int16 or as the
+ * equal floats.  Needs no weights.
+ *   The second kernel keeps, per tile of EV_LIMIT_TILE samples, r on [t0 - L - Hd, t0 + EV_LIMIT_TILE + L) twice (the erosion doubles its window
+ *     from one copy into the other) and the window as fp64 in LDS: EV_LIMIT_LDS_BYTES(L, Hd), within EV_LIMIT_MAX_LDS at the largest L and Hd. */
+#define EV_LIMIT_MAX_SAMPLES   (1 << 30)    /* per segment */
+#define EV_LIMIT_MAX_LOOKAHEAD 1024         /* samples */
+#define EV_LIMIT_MAX_HOLD      8192         /* samples */
+#define EV_LIMIT_TILE          4096         /* samples */
+#define EV_LIMIT_MAX_LDS       (160 * 1024)
+#define EV_LIMIT_REACH(L, Hd)     (EV_LIMIT_TILE + 2 * (L) + (Hd))                      /* samples of r a tile looks at */
+#define EV_LIMIT_LDS_BYTES(L, Hd) (2 * 4 * EV_LIMIT_REACH(L, Hd) + 8 * ((L) + 1))
+#ifdef __cplusplus
+static_assert(EV_LIMIT_LDS_BYTES(EV_LIMIT_MAX_LOOKAHEAD, EV_LIMIT_MAX_HOLD) <= EV_LIMIT_MAX_LDS, "ev_limit's largest tile must fit the LDS of a CU");
+static_assert(EV_LIMIT_LDS_BYTES(EV_LIMIT_MAX_LOOKAHEAD, EV_LIMIT_MAX_HOLD) == 122888, "2 * 4 * (4096 + 2048 + 8192) + 8 * 1025");
+#endif
+typedef struct ev_limit_config {
+    uint32_t struct_size;          /* sizeof(ev_limit_config); any other value is rejected */
+    int32_t  sample_rate;          /* one of 8000, 16000, 22050, 24000, 32000, 44100, 48000 (ev_flac's table) */
+    float    ceiling;              /* linear, in (0, 1]: the true peak of the output aims at it */
+    int32_t  lookahead;            /* L, samples, in [0, EV_LIMIT_MAX_LOOKAHEAD] */
+    int32_t  hold;                 /* Hd, samples, in [0, EV_LIMIT_MAX_HOLD] */
+    int32_t  want_i16;             /* != 0: also the int16 output */
+} ev_limit_config;
+void ev_default_limit_config(ev_limit_config* cfg);      /* 16000, (float)10^(-1/20) = -1 dBTP, 80, 800, 0 */
+/* Host only: the L + 1 taps of the smoothing window above.  Returns L + 1, or -1 for L outside [0, EV_LIMIT_MAX_LOOKAHEAD] or a NULL w. */
+int ev_limit_design(int L, float* w);
+
+typedef struct ev_limit_result {
+    uint32_t struct_size;          /* sizeof(ev_limit_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* samples: the sum of lens */
+    const float*   wav;            /* DEVICE, (total,), packed as the input: y */
+    const int16_t* wav_i16;        /* DEVICE, the same layout; NULL without want_i16 */
+    const float*   true_peak_in;   /* every array below: (batch,) HOST */
+    const float*   sample_peak_in;
+    const float*   true_peak_out;
+    const float*   sample_peak_out;
+    const float*   min_gain;       /* min s */
+    const int64_t* limited;        /* samples with s < 1 */
+    const int64_t* nonfinite;      /* non-finite u */
+} ev_limit_result;
+/* wav: a host pointer, or with EV_FLAG_DEVICE_INPUTS (the other flags are ignored) a device pointer on the handle's device, which must not be the
+ * wav of the previous ev_limit_result; lens is always a HOST array, so an ev_result.wav with lens = mel_lens * 256, an ev_stitch_result.wav or an
+ * ev_loudness_result.wav goes straight in, and the result's wav_i16 goes straight into ev_flac.  gains: a HOST array (B,) of pre-gains, or NULL =
+ * all 1: with ev_loudness's measurement and its gain rule without step 4, one pass scales and limits.  cfg NULL = ev_default_limit_config.
+ * Rejected before anything is launched (message naming the field or segment; the previous result stays valid): a NULL h, wav, lens or out, a
+ * wrong struct_size of cfg or out, a sample_rate outside the table, a ceiling outside (0, 1] or not finite, lookahead outside
+ * [0, EV_LIMIT_MAX_LOOKAHEAD], hold outside [0, EV_LIMIT_MAX_HOLD], B outside [1, 65535], lens[b] < 1 or > EV_LIMIT_MAX_SAMPLES, a gains[b] that
+ * is negative, NaN or infinite.  The per-tile records come back to the host once, at the end of the call; no waveform is copied to the host.
+ * The result lives in a workspace of its own and is complete when the call returns; it stays valid across every other entry point until the next
+ * ev_limit or ev_destroy -- the contract of ev_features_result. */
+int ev_limit(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* gains, const ev_limit_config* cfg, uint32_t flags,
+             ev_limit_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 

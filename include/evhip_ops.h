@@ -253,6 +253,16 @@ int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t*
 int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, uint8_t* slots, int32_t* sizes,
                       uint8_t* kind, uint8_t* porder, void* hip_stream);
 
+/* ev_limit's kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_limit).  ev_op_limit_peak: the meter on B segments of wav
+ * (int16 or fp32, packed back to back, lens[b] samples each) with the pre-gains -> r (the required gain per sample, packed as the input; NULL =
+ * measure only) and the HOST arrays sample_peak, true_peak, nonfinite (B each).  ev_op_limit_apply: r -> the gain per sample s (unless NULL), out =
+ * u * s, out_i16 (unless NULL), and the HOST arrays min_gain and limited (B each).  lens and gains (or NULL = all 1) are HOST arrays.  The calls
+ * wait for the stream.  -2 for what ev_limit rejects. */
+int ev_op_limit_peak(const void* wav, int wav_is_i16, int B, const int64_t* lens, const float* gains, float ceiling, float* r, float* sample_peak,
+                     float* true_peak, int64_t* nonfinite, void* hip_stream);
+int ev_op_limit_apply(const void* wav, int wav_is_i16, int B, const int64_t* lens, const float* gains, const float* r, int lookahead, int hold, float* out,
+                      int16_t* out_i16, float* s, float* min_gain, int64_t* limited, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
