@@ -92,7 +92,9 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
     (trim_start - trim_pad) / sr_out: add it to ``timestamps()`` to get times on the original recording's clock.  The resampler is this
     project's windowed sinc, not librosa's soxr.  Returns what ``EVEngine.align`` returns."""
     from . import _ffi
+    from .engine_audio import cut, host_array
     from .features import frames_for, pack_wavs
+    from .packing import pack_utts
     B = len(utts)
     if len(wavs) != B:
         raise ValueError("%d wavs for %d utterances" % (len(wavs), B))
@@ -112,7 +114,7 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
             engine.resample_setup(rc)
         flat, is16_in, lens_in = pack_any_rate(wavs, rc)
         rs = engine.resample_raw(B, flat.ctypes.data, is16_in, lens_in)
-        lens = np.array([rs.wav_lens[b] for b in range(B)], np.int64)
+        lens = host_array(rs.wav_lens, B, np.int64)
         for b, n in enumerate(lens):
             if n < fc.n_fft // 2 + 1:
                 raise ValueError("wavs[%d]: %d samples after resampling%s < n_fft / 2 + 1 = %d (reflect padding needs that many)"
@@ -131,18 +133,13 @@ def align_recordings(engine, utts: Sequence[dict], wavs: Sequence[np.ndarray], e
         pm, ps = check_stats(pitch_stats)
         pitch_ptr = engine.pitch_raw(B, wav_ptr, is16, lens, pm, ps, pc, flags=wav_flags).pitch
     feats = engine.features_raw(B, wav_ptr, is16, lens, mean, std, flags=wav_flags)
-    mel_lens = np.array([feats.mel_lens[b] for b in range(B)], np.int32)
-    ling = np.ascontiguousarray(np.concatenate([np.asarray(u["ling"], np.int64) for u in utts]))
-    cu = np.zeros(B + 1, np.int32)
-    cu[1:] = np.cumsum([len(u["ling"]) for u in utts])
-    spk = np.ascontiguousarray([int(u["speaker"]) for u in utts], np.int64)
-    style = np.ascontiguousarray(np.stack([np.asarray(u["style"], np.float32) for u in utts]))
-    content = np.ascontiguousarray(np.stack([np.asarray(u["content"], np.float32) for u in utts]))
+    mel_lens = host_array(feats.mel_lens, B, np.int32)
+    ling, cu, spk, style, content = pack_utts(utts)
     res = engine.align_raw(B, ling.ctypes.data, cu, spk.ctypes.data, style.ctypes.data, content.ctypes.data, feats.mel, False, mel_lens,
                            pitch_ptr, feats.energy if energy_stats is not None else None, flags=_ffi.EV_FLAG_DEVICE_MEL)
     out = engine.align_to_numpy(res)
     out["cu_seqlens"] = cu
-    out["durations_list"] = [out["durations"][cu[b]:cu[b + 1]] for b in range(B)]
+    out["durations_list"] = cut(out["durations"], cu)
     if resampled is not None:
         out.update(resampled)
     return out

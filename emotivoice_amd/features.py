@@ -108,20 +108,12 @@ def pack_wavs(wavs, n_fft: int = 1024, hop: int = 256, min_samples: Optional[int
     """Utterances back to back for ev_features: (flat array, is_int16, lens int64).  All int16 or all floating (converted to float32);
     too short (< n_fft // 2 + 1 samples) or too long (> MAX_FRAMES frames) utterances are errors that name the utterance.  ``min_samples``: another
     minimum length, for a call without reflect padding (ev_pitch: 1)."""
-    if len(wavs) == 0:
-        raise ValueError("no utterances")
-    arrs = [np.asarray(w).reshape(-1) for w in wavs]
-    is16 = arrs[0].dtype == np.int16
-    for b, a in enumerate(arrs):
-        if (a.dtype == np.int16) != is16:
-            raise ValueError("wavs[%d]: int16 and floating utterances cannot be mixed in one call" % b)
-        if not is16 and not np.issubdtype(a.dtype, np.floating):
-            raise ValueError("wavs[%d]: expected int16 or floating samples, got %s" % (b, a.dtype))
-        if min_samples is not None and a.size < min_samples:
-            raise ValueError("wavs[%d]: %d samples < %d" % (b, a.size, min_samples))
-        if min_samples is None and a.size < n_fft // 2 + 1:
-            raise ValueError("wavs[%d]: %d samples < n_fft / 2 + 1 = %d (reflect padding needs that many)" % (b, a.size, n_fft // 2 + 1))
-        if frames_for(a.size, hop) > MAX_FRAMES:
-            raise ValueError("wavs[%d]: %d frames > EV_ALIGN_MAX_FRAMES %d" % (b, frames_for(a.size, hop), MAX_FRAMES))
-    flat = np.ascontiguousarray(np.concatenate([a.astype(np.int16 if is16 else np.float32, copy=False) for a in arrs]))
-    return flat, is16, np.array([a.size for a in arrs], np.int64)
+    from .packing import pack_segments
+
+    def limit(n):
+        if min_samples is None and n < n_fft // 2 + 1:
+            return "%d samples < n_fft / 2 + 1 = %d (reflect padding needs that many)" % (n, n_fft // 2 + 1)
+        if frames_for(n, hop) > MAX_FRAMES:
+            return "%d frames > EV_ALIGN_MAX_FRAMES %d" % (frames_for(n, hop), MAX_FRAMES)
+
+    return pack_segments(wavs, min_samples=min_samples or 0, flatten=True, limit=limit)

@@ -14,7 +14,7 @@ from typing import Tuple
 
 import numpy as np
 
-from .loudness import FLAG_BOOST_LIMITED, FLAG_UNDEFINED, SAMPLE_RATES, LoudnessConfig
+from .loudness import SAMPLE_RATES, LoudnessConfig, gain_for
 
 MAX_LOOKAHEAD, MAX_HOLD = 1024, 8192      # samples: EV_LIMIT_MAX_LOOKAHEAD, EV_LIMIT_MAX_HOLD
 
@@ -98,12 +98,4 @@ def interpolator() -> np.ndarray:
 def pre_gain(loudness: float, cfg: LoudnessConfig) -> Tuple[np.float32, int]:
     """Steps 1-3 of ev_loudness's gain rule, WITHOUT step 4 (the sample-peak limit): the pre-gain that goes into ev_limit, which holds the peak
     sample by sample instead.  The same operations and flags as emotivoice_amd.loudness.gain_for with a peak of 0: (gain, flags)."""
-    cfg.validate()
-    flags = FLAG_UNDEFINED if loudness == -math.inf else 0
-    if cfg.measure_only:
-        return np.float32(1.0), flags
-    g = 1.0 if loudness == -math.inf else 10.0 ** ((float(cfg.target_lufs) - float(loudness)) / 20.0)
-    gmax = 10.0 ** (float(cfg.max_gain_db) / 20.0)
-    if g > gmax:
-        g, flags = gmax, flags | FLAG_BOOST_LIMITED
-    return np.float32(g), flags
+    return gain_for(loudness, 0.0, cfg)

@@ -131,22 +131,14 @@ def time_offset_s(trim_start: int, trim_pad: int, sr_out: int) -> float:
 def pack_wavs(wavs, config: Optional[ResampleConfig] = None):
     """Utterances back to back for ev_resample: (flat array, is_int16, lens int64).  All int16 or all floating (converted to float32); an empty
     utterance, or one whose output (with the trim's padding) exceeds EV_ALIGN_MAX_FRAMES * 256 samples, is an error that names the utterance."""
-    if len(wavs) == 0:
-        raise ValueError("no utterances")
+    from .packing import pack_segments
     if len(wavs) > 65535:
         raise ValueError("%d utterances > 65535 per call" % len(wavs))
     cfg = config or ResampleConfig()
     extra = 2 * cfg.pad() if cfg.trim else 0
-    arrs = [np.asarray(w).reshape(-1) for w in wavs]
-    is16 = arrs[0].dtype == np.int16
-    for b, a in enumerate(arrs):
-        if (a.dtype == np.int16) != is16:
-            raise ValueError("wavs[%d]: int16 and floating utterances cannot be mixed in one call" % b)
-        if not is16 and not np.issubdtype(a.dtype, np.floating):
-            raise ValueError("wavs[%d]: expected int16 or floating samples, got %s" % (b, a.dtype))
-        if a.size < 1:
-            raise ValueError("wavs[%d]: %d samples < 1" % (b, a.size))
-        if cfg.output_len(a.size) + extra > MAX_OUT:
-            raise ValueError("wavs[%d]: %d output samples > EV_ALIGN_MAX_FRAMES * 256 = %d" % (b, cfg.output_len(a.size) + extra, MAX_OUT))
-    flat = np.ascontiguousarray(np.concatenate(arrs).astype(np.int16 if is16 else np.float32, copy=False))
-    return flat, is16, np.array([a.size for a in arrs], np.int64)
+
+    def limit(n):
+        if cfg.output_len(n) + extra > MAX_OUT:
+            return "%d output samples > EV_ALIGN_MAX_FRAMES * 256 = %d" % (cfg.output_len(n) + extra, MAX_OUT)
+
+    return pack_segments(wavs, flatten=True, limit=limit)
