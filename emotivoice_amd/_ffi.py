@@ -300,6 +300,7 @@ SIGNATURES = {
     "ev_op_conv_gemm": (C.c_int, [C.POINTER(ev_conv_gemm_desc), _P]),
     "ev_op_conv_gemm_group3": (C.c_int, [C.POINTER(ev_conv_gemm_desc), C.c_int, _P]),
     "ev_op_mx_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ev_op_mx_scratch_planes": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),      # host only: six addresses / the scale stride
     "ev_op_resblock_pair_c32": (C.c_int, [C.POINTER(ev_res_pair_desc), _P]),
     "ev_op_resblock_pair_c64": (C.c_int, [C.POINTER(ev_res_pair_desc), _P]),
     "ev_op_resblock_pair_c32_mx": (C.c_int, [C.POINTER(ev_res_pair_desc), _P]),

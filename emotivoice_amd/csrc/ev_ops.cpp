@@ -38,6 +38,14 @@ int ev_op_conv_gemm_group3(const ev_conv_gemm_desc* d3, int check_only, void* st
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 size_t ev_op_mx_scratch_bytes(int M, int K) { return mx_scratch_bytes(M, K); }
+int ev_op_mx_scratch_planes(void* scratch, int M, int K, unsigned long long out[6]) {
+    if (!scratch || !out || M <= 0 || K <= 0 || K % 128) return -2;
+    const MxScratchPlanes sp = mx_scratch_planes(scratch, M, K);
+    out[0] = (unsigned long long)(uintptr_t)sp.h;
+    for (int i = 0; i < 2; ++i) { out[1 + i] = (unsigned long long)(uintptr_t)sp.q4[i]; out[3 + i] = (unsigned long long)(uintptr_t)sp.qs[i]; }
+    out[5] = sp.qs_stride;
+    return 0;
+}
 int ev_op_resblock_pair_c32(const ev_res_pair_desc* d, void* stream) {
     static_assert(sizeof(ev_res_pair_desc) == sizeof(ResPairParams), "descriptor layout must match ResPairParams");
     ResPairParams p;

@@ -13,6 +13,11 @@ of fp16's 3e-4 (tools/precision_study_mx.py: waveform 3.5e-4 against 2.3e-3 for 
 Element code (4 bits): s e e m, values +-{0, .5, 1, 1.5, 2, 3, 4, 6}; two codes per byte, element 2j in the low nibble of
 byte j (checked against the instruction on the device: tools/mfma_ubench.hip).  Scale byte b means 2^(b - 127); the block scale
 is 2^(floor(log2(amax)) - 2) (OCP MX v1.0: the largest element lands in the top binade, values above 6 saturate).
+
+Domain of the activation side ("ocp" rule, split_hi_lo, e5m2_*), on which every device quantiser is held to these functions bit for bit
+(tests/quant_probes.py, tests/test_gpu_quant_edges.py): finite values, |v| < 65520 (the fp16 hi part is finite), and v == 0 or |v| >= 2^-100.
+Non-finite values, fp32 denormals and the E8M0 clamp at 254 are outside what the engine produces; what the functions return there is not a promise
+about the device.
 """
 from __future__ import annotations
 

@@ -75,6 +75,11 @@ int ev_op_conv_gemm(const ev_conv_gemm_desc* d, void* hip_stream);
 int ev_op_conv_gemm_group3(const ev_conv_gemm_desc* d3, int check_only, void* hip_stream);
 /* scratch bytes a dtype-3 call with an [M][K] activation needs (fp16 hi plane, two fp4 code planes, two E8M0 scale planes) */
 size_t ev_op_mx_scratch_bytes(int M, int K);
+/* where a dtype-3 call with an fp32 [M][K] activation lays that activation's plane set inside its mx_scratch (what its mx_planes_kernel pass fills), row 0 of
+ * each plane: out[0] the fp16 hi plane [M][K], out[1] / out[2] the fp4 code planes of the hi / lo parts [M][K / 2], out[3] / out[4] their E8M0 scale planes
+ * (chunk-major [K / 128][out[5] / 4 rows][4], as mx_xs), all as addresses, out[5] = the scale planes' chunk stride in bytes.  Host only: nothing is launched.
+ * Returns 0, or -2 for a null argument or a shape the scratch layout does not cover (M <= 0, K % 128). */
+int ev_op_mx_scratch_planes(void* scratch, int M, int K, unsigned long long out[6]);
 
 /* Fused HiFi-GAN ResBlock1 pair for C = 32: xt = lrelu(c1(lrelu(x)) + b1); out = epi(c2(xt) + b2 + x)
  * (reference models/hifigan/models.py:50-57).  `epi` uses the ev_conv_gemm_desc fields bias (= b2), res (= x), res_dtype,
