@@ -154,6 +154,10 @@ class ev_flac_config(C.Structure):
                 ("max_partition_order", C.c_int32), ("convert", C.c_int32)]
 
 
+class ev_flac_ext(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_lpc_order", C.c_int32), ("qlp_precision", C.c_int32), ("md5", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class ev_flac_result(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_bytes", C.c_int64), ("total_frames", C.c_int64),
@@ -276,6 +280,8 @@ SIGNATURES = {
     "ev_flac_bound": (C.c_int64, [C.c_int64, C.c_int]),      # host only
     # lens is a HOST array; pcm is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_flac": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_flac_config), C.c_uint32, C.POINTER(ev_flac_result)]),
+    "ev_default_flac_ext": (None, [C.POINTER(ev_flac_ext)]),
+    "ev_flac_lpc": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_flac_config), C.POINTER(ev_flac_ext), C.c_uint32, C.POINTER(ev_flac_result)]),
     "ev_default_loudness_config": (None, [C.POINTER(ev_loudness_config)]),
     "ev_loudness_design": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),      # host only
     # lens is a HOST array; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
@@ -337,6 +343,7 @@ SIGNATURES = {
     # everything but wav / out / out_i16 is a HOST array
     "ev_op_stitch_scan": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     "ev_op_flac_encode": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(ev_flac_config), _P, _P, _P, _P, _P]),
+    "ev_op_flac_lpc": (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(ev_flac_config), C.c_int, C.c_int, _P, _P, _P, _P]),
     # lens, gains and the per-segment outputs are HOST arrays; wav, r, out, out_i16 and s are device buffers
     "ev_op_limit_peak": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     "ev_op_limit_apply": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),

@@ -726,46 +726,63 @@ static FlacParams flac_params(const ev_flac_config& c, int sr_code, int bs_code)
     return fp;
 }
 
-int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out) {
+void ev_default_flac_ext(ev_flac_ext* e) {
+    memset(e, 0, sizeof *e);
+    e->struct_size = sizeof *e; e->max_lpc_order = 8; e->qlp_precision = 12; e->md5 = 1;
+}
+
+// ev_flac (ext NULL) and ev_flac_lpc; who names the entry point in messages
+static int flac_run(ev_handle* h, const char* who, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, const ev_flac_ext* ext,
+                    uint32_t flags, ev_flac_result* out) {
     if (!h) return -1;
-    if (!pcm) return fail(h, "ev_flac: pcm is NULL");
-    if (!lens) return fail(h, "ev_flac: lens is NULL");
-    if (!out) return fail(h, "ev_flac: out is NULL");
-    if (check_struct_size(h, "ev_flac", "out->struct_size", out->struct_size, "ev_flac_result", sizeof(ev_flac_result))) return -1;
+    if (!pcm) return fail(h, "%s: pcm is NULL", who);
+    if (!lens) return fail(h, "%s: lens is NULL", who);
+    if (!out) return fail(h, "%s: out is NULL", who);
+    if (check_struct_size(h, who, "out->struct_size", out->struct_size, "ev_flac_result", sizeof(ev_flac_result))) return -1;
     ev_flac_config dflt;
     if (!cfg) { ev_default_flac_config(&dflt); cfg = &dflt; }
-    if (check_struct_size(h, "ev_flac", "cfg->struct_size", cfg->struct_size, "ev_flac_config", sizeof(ev_flac_config))) return -1;
+    if (check_struct_size(h, who, "cfg->struct_size", cfg->struct_size, "ev_flac_config", sizeof(ev_flac_config))) return -1;
     const ev_flac_config c = *cfg;
     int sr_code = 0, bs_code = 0;
     switch (flac_check_config(c, &sr_code, &bs_code)) {
     case FLAC_OK: break;
-    case FLAC_BAD_RATE: return fail(h, "ev_flac: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", c.sample_rate);
-    case FLAC_BAD_BLOCK: return fail(h, "ev_flac: block_size = %d is not one of 256, 512, 1024, 2048, 4096", c.block_size);
-    case FLAC_BAD_FIXED_ORDER: return fail(h, "ev_flac: max_fixed_order = %d outside [0, 4]", c.max_fixed_order);
-    case FLAC_BAD_PARTITION_ORDER: return fail(h, "ev_flac: max_partition_order = %d outside [0, 6]", c.max_partition_order);
-    case FLAC_BAD_CONVERT: return fail(h, "ev_flac: convert = %d is neither EV_FLAC_WRAP nor EV_FLAC_CLAMP", c.convert);
+    case FLAC_BAD_RATE: return fail(h, "%s: sample_rate = %d is not one of 8000, 16000, 22050, 24000, 32000, 44100, 48000", who, c.sample_rate);
+    case FLAC_BAD_BLOCK: return fail(h, "%s: block_size = %d is not one of 256, 512, 1024, 2048, 4096", who, c.block_size);
+    case FLAC_BAD_FIXED_ORDER: return fail(h, "%s: max_fixed_order = %d outside [0, 4]", who, c.max_fixed_order);
+    case FLAC_BAD_PARTITION_ORDER: return fail(h, "%s: max_partition_order = %d outside [0, 6]", who, c.max_partition_order);
+    case FLAC_BAD_CONVERT: return fail(h, "%s: convert = %d is neither EV_FLAC_WRAP nor EV_FLAC_CLAMP", who, c.convert);
     }
-    if (B < 1 || B > 65535) return fail(h, "ev_flac: B = %d outside [1, 65535]", B);
+    int lpc_order = 0, lpc_q = 12; bool md5 = false;
+    if (ext) {
+        if (check_struct_size(h, who, "ext->struct_size", ext->struct_size, "ev_flac_ext", sizeof(ev_flac_ext))) return -1;
+        if (ext->max_lpc_order < 0 || ext->max_lpc_order > FLAC_LPC_MAX_ORDER) return fail(h, "%s: ext->max_lpc_order = %d outside [0, %d]", who, ext->max_lpc_order, FLAC_LPC_MAX_ORDER);
+        if (ext->qlp_precision < 5 || ext->qlp_precision > 15) return fail(h, "%s: ext->qlp_precision = %d outside [5, 15]", who, ext->qlp_precision);
+        if (ext->md5 != 0 && ext->md5 != 1) return fail(h, "%s: ext->md5 = %d is neither 0 nor 1", who, ext->md5);
+        for (int i = 0; i < 4; ++i) if (ext->reserved[i] != 0) return fail(h, "%s: ext->reserved[%d] = %d is not 0", who, i, ext->reserved[i]);
+        lpc_order = ext->max_lpc_order; lpc_q = ext->qlp_precision; md5 = ext->md5 != 0;
+    }
+    if (B < 1 || B > 65535) return fail(h, "%s: B = %d outside [1, 65535]", who, B);
     const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, i16 = pcm_is_i16 != 0;
     const int N = c.block_size, stride = 2 * N + 24;
     FlacPlan plan;
     int at = 0;
     switch (flac_plan(B, lens, N, plan, &at)) {
     case LEN_OK: break;
-    case LEN_SHORT: return fail(h, "ev_flac: lens[%d] = %lld < 1", at, (long long)lens[at]);
-    case LEN_LONG: return fail(h, "ev_flac: lens[%d] = %lld > EV_FLAC_MAX_SAMPLES = %d", at, (long long)lens[at], EV_FLAC_MAX_SAMPLES);
-    case LEN_COUNT: return fail(h, "ev_flac: lens[%d] = %lld: more than %d frames in one call", at, (long long)lens[at], INT_MAX);
+    case LEN_SHORT: return fail(h, "%s: lens[%d] = %lld < 1", who, at, (long long)lens[at]);
+    case LEN_LONG: return fail(h, "%s: lens[%d] = %lld > EV_FLAC_MAX_SAMPLES = %d", who, at, (long long)lens[at], EV_FLAC_MAX_SAMPLES);
+    case LEN_COUNT: return fail(h, "%s: lens[%d] = %lld: more than %d frames in one call", who, at, (long long)lens[at], INT_MAX);
     }
     const int64_t total = plan.total, NF = (int64_t)plan.frames.size(), cap = plan.cap;
     if (call_begin(h)) return -1;
     const size_t es = i16 ? sizeof(int16_t) : sizeof(float);
     char* d_pcm = nullptr; FlacFrame* d_frames = nullptr; int32_t* d_sizes = nullptr; uint32_t* d_desc = nullptr; uint8_t *d_scratch = nullptr, *d_hdr = nullptr, *d_bytes = nullptr;
-    int64_t* d_foffs = nullptr;
+    int64_t* d_foffs = nullptr; FlacMd5Seg* d_segs = nullptr; uint32_t* d_md5 = nullptr;
     if (arena_plan(h, ARENA_FLAC, [&](ArenaPlan& ap) {
         if (!dev_in) d_pcm = ap.arr<char>((size_t)total * es);
         d_frames = ap.arr<FlacFrame>((size_t)NF); d_sizes = ap.arr<int32_t>((size_t)NF); d_desc = ap.arr<uint32_t>((size_t)NF);
         d_foffs = ap.arr<int64_t>((size_t)NF); d_hdr = ap.arr<uint8_t>((size_t)B * FLAC_HEADER_STRIDE);
         d_scratch = ap.arr<uint8_t>((size_t)NF * (size_t)stride + 16); d_bytes = ap.arr<uint8_t>((size_t)cap);
+        if (md5) { d_segs = ap.arr<FlacMd5Seg>((size_t)B); d_md5 = ap.arr<uint32_t>(4 * (size_t)B); }
     })) return -1;
     if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_pcm, pcm, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
     if (upload(h, d_frames, plan.frames)) return -1;
@@ -774,10 +791,23 @@ int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t*
     region_begin(h, "total");
     {
         KScope ks(h, "flac_encode", 0.0, (double)total * (double)es + (double)NF * (double)stride);
-        if (launch_flac_encode(fp, NF, h->stream)) return fail(h, "ev_flac: the kernel does not build this shape");
+        if (lpc_order > 0 ? launch_flac_encode_lpc(fp, FlacLpc{lpc_order, lpc_q}, NF, h->stream) : launch_flac_encode(fp, NF, h->stream))
+            return fail(h, "%s: the kernel does not build this shape", who);
     }
     HIPCHK(h, hipGetLastError());
-    std::vector<int32_t> sizes((size_t)NF); std::vector<uint32_t> desc((size_t)NF);
+    std::vector<int32_t> sizes((size_t)NF); std::vector<uint32_t> desc((size_t)NF), digest(md5 ? 4 * (size_t)B : 0);
+    if (md5) {      // one chain per segment, before the synchronisation the frame sizes need anyway
+        std::vector<FlacMd5Seg> segs((size_t)B);
+        int64_t off = 0;
+        for (int b = 0; b < B; ++b) { segs[(size_t)b] = FlacMd5Seg{off, lens[b]}; off += lens[b]; }
+        if (upload(h, d_segs, segs)) return -1;
+        {
+            KScope ks(h, "flac_md5", 0.0, (double)total * (double)es);
+            launch_flac_md5(fp, d_segs, B, d_md5, h->stream);
+        }
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(digest.data(), d_md5, digest.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipMemcpyAsync(sizes.data(), d_sizes, (size_t)NF * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(desc.data(), d_desc, (size_t)NF * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -791,7 +821,7 @@ int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t*
         int32_t lo = INT_MAX, hi = 0;
         for (int64_t i = 0; i < plan.stream_frames[(size_t)b]; ++i, ++f) {
             const int32_t sz = sizes[(size_t)f];
-            if (sz < 1 || sz > 2 * N + 15) return fail(h, "ev_flac: frame %lld of segment %d reports %d bytes", (long long)i, b, sz);
+            if (sz < 1 || sz > 2 * N + 15) return fail(h, "%s: frame %lld of segment %d reports %d bytes", who, (long long)i, b, sz);
             foffs[(size_t)f] = pos; pos += sz; lo = std::min(lo, sz); hi = std::max(hi, sz);
             kind[(size_t)f] = (uint8_t)(desc[(size_t)f] & 0xFFu); porder[(size_t)f] = (uint8_t)(desc[(size_t)f] >> 8 & 0xFFu);
         }
@@ -802,10 +832,11 @@ int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t*
         p[8] = p[10] = (uint8_t)(N >> 8); p[9] = p[11] = (uint8_t)(N & 0xFF);
         p[12] = (uint8_t)(lo >> 16); p[13] = (uint8_t)(lo >> 8); p[14] = (uint8_t)lo;
         p[15] = (uint8_t)(hi >> 16); p[16] = (uint8_t)(hi >> 8); p[17] = (uint8_t)hi;
-        for (int i = 0; i < 8; ++i) p[18 + i] = (uint8_t)(v >> (56 - 8 * i));      // p[26 .. 42): the MD5, zero
+        for (int i = 0; i < 8; ++i) p[18 + i] = (uint8_t)(v >> (56 - 8 * i));      // p[26 .. 42): the MD5, or zero
+        if (md5) for (int i = 0; i < 16; ++i) p[26 + i] = (uint8_t)(digest[4 * (size_t)b + (size_t)(i >> 2)] >> (8 * (i & 3)));
     }
     soffs[(size_t)B] = pos; foffs[(size_t)NF] = pos;
-    if (pos > cap) return fail(h, "ev_flac: the streams outgrew their bound");
+    if (pos > cap) return fail(h, "%s: the streams outgrew their bound", who);
     HIPCHK(h, hipMemcpyAsync(d_foffs, foffs.data(), (size_t)NF * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, h->stream));
     {
@@ -820,6 +851,15 @@ int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t*
     out->stream_offsets = h->flac.stream_offs.data(); out->stream_frames = h->flac.stream_frames.data(); out->frame_offsets = h->flac.frame_offs.data();
     out->frame_kind = h->flac.kind.data(); out->frame_porder = h->flac.porder.data();
     return 0;
+}
+
+int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out) {
+    return flac_run(h, "ev_flac", B, pcm, pcm_is_i16, lens, cfg, nullptr, flags, out);
+}
+
+int ev_flac_lpc(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, const ev_flac_ext* ext, uint32_t flags,
+                ev_flac_result* out) {
+    return flac_run(h, "ev_flac_lpc", B, pcm, pcm_is_i16, lens, cfg, ext, flags, out);
 }
 
 // ------------------------------------------------------------------- loudness normalisation (include/evhip.h: ev_loudness)
@@ -1325,6 +1365,31 @@ int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* len
     if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
     if (rc == 0 && (hipMemcpy(sizes, fp.sizes, sb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(desc.data(), fp.desc, sb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     if (rc == 0) for (size_t f = 0; f < NF; ++f) { kind[f] = (uint8_t)(desc[f] & 0xFFu); porder[f] = (uint8_t)(desc[f] >> 8 & 0xFFu); }
+    return rc;
+}
+int ev_op_flac_lpc(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, int max_lpc_order, int qlp_precision, int64_t* R,
+                   int32_t* shift, int32_t* coef, void* stream) {
+    ev_flac_config c;
+    if (cfg) c = *cfg; else ev_default_flac_config(&c);
+    if (!pcm || !lens || !R || !shift || !coef || B < 1 || B > 65535 || c.struct_size != sizeof(ev_flac_config)) return -2;
+    if (max_lpc_order < 0 || max_lpc_order > FLAC_LPC_MAX_ORDER || qlp_precision < 5 || qlp_precision > 15) return -2;
+    int sr_code = 0, bs_code = 0, at = 0;
+    FlacPlan plan;
+    if (flac_check_config(c, &sr_code, &bs_code) != FLAC_OK) return -2;
+    if (flac_plan(B, lens, c.block_size, plan, &at) != LEN_OK) return -2;
+    const size_t NF = plan.frames.size(), rb = NF * 13 * sizeof(int64_t), sb = NF * FLAC_LPC_MAX_ORDER * sizeof(int32_t), cb = sb * FLAC_LPC_MAX_ORDER;
+    DevTable t;
+    const size_t fo = t.add(plan.frames), ro = t.room(rb), so = t.room(sb), co = t.room(cb);
+    if (t.commit()) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    FlacParams fp = flac_params(c, sr_code, bs_code);
+    fp.pcm = pcm; fp.pcm_is_i16 = pcm_is_i16 != 0; fp.frames = t.at<FlacFrame>(fo);
+    int rc = 0;
+    if (launch_flac_lpc_analysis(fp, FlacLpc{max_lpc_order, qlp_precision}, (int64_t)NF, t.at<int64_t>(ro), t.at<int32_t>(so), t.at<int32_t>(co), s) ||
+        hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    if (rc == 0 && (hipMemcpy(R, t.at<int64_t>(ro), rb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shift, t.at<int32_t>(so), sb, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(coef, t.at<int32_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     return rc;
 }
 int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t* n, const int32_t* seg_doc, const int64_t* pos, const int32_t* fl,

@@ -345,6 +345,15 @@ struct FlacParams {
     uint32_t* desc;                                   // (n_frames,): kind | partition order << 8
 };
 int launch_flac_encode(const FlacParams& p, int64_t n_frames, hipStream_t s);      // 0, or -1 for bad parameters
+// ev_flac_lpc: the same encoder with the LPC candidates of orders 1 .. max_order (0 .. 12) at `precision` bits (5 .. 15); the analysis alone, per
+// frame R (13 int64), shift (12, -1 = no candidate) and coef (12 x 12, [order - 1][j]); and the MD5 of every segment's 16-bit samples, one wave
+// per segment (of p only pcm, pcm_is_i16 and convert are read), four little-endian words per segment.
+constexpr int FLAC_LPC_MAX_ORDER = 12;
+struct FlacLpc { int max_order, precision; };
+struct FlacMd5Seg { int64_t src, n; };      // first sample in the packed input, samples
+int launch_flac_encode_lpc(const FlacParams& p, const FlacLpc& q, int64_t n_frames, hipStream_t s);
+int launch_flac_lpc_analysis(const FlacParams& p, const FlacLpc& q, int64_t n_frames, int64_t* R, int32_t* shift, int32_t* coef, hipStream_t s);
+void launch_flac_md5(const FlacParams& p, const FlacMd5Seg* segs, int B, uint32_t* digests, hipStream_t s);
 void launch_flac_gather(const uint8_t* scratch, int stride, const FlacFrame* frames, int64_t n_frames, const int32_t* sizes, const int64_t* frame_offs,
                         const uint8_t* headers, uint8_t* out, hipStream_t s);
 

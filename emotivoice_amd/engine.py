@@ -327,12 +327,19 @@ class EVEngine(EVAudio):
         audio = {k: src.pop(k) for k in ("wav", "wav_list", "wav_i16", "wav_i16_list") if k in src}
         return audio, figures, limited, last.wav_i16 if last is not None else None
 
-    def _flac_runs(self, sel: np.ndarray, offsets: np.ndarray, wav_ptr: int, pcm_i16: Optional[int]) -> List[Optional[bytes]]:
+    def _flac_config(self, given, sample_rate: int, **kw):
+        """The FlacConfig of a ``flac=`` argument: a given one with the engine's sample rate (and ``kw``), else the defaults."""
+        import dataclasses
+        from .flac import FlacConfig
+        if isinstance(given, FlacConfig):
+            return dataclasses.replace(given, sample_rate=int(sample_rate), **kw).validate()
+        return FlacConfig(sample_rate=int(sample_rate), **kw)
+
+    def _flac_runs(self, sel: np.ndarray, offsets: np.ndarray, wav_ptr: int, pcm_i16: Optional[int], given=None) -> List[Optional[bytes]]:
         """The segments that ``sel`` selects of a packed device waveform, as FLAC: one ev_flac call per run of consecutive selected segments
         (ev_flac takes its segments back to back), from the int16 waveform ``pcm_i16`` when there is one, else from the fp32 ``wav_ptr`` with
         the wrapping conversion."""
-        from .flac import FlacConfig
-        fc = FlacConfig(sample_rate=int(self.shapes.sr), convert="wrap")
+        fc = self._flac_config(given, int(self.shapes.sr), convert="wrap")
         out: List[Optional[bytes]] = [None] * len(sel)
         edges = np.flatnonzero(np.diff(np.concatenate([[0], sel, [0]]).astype(np.int8)))      # where a run begins, where it ends, ...
         for b, e in zip(edges[::2].tolist(), edges[1::2].tolist()):
@@ -347,7 +354,8 @@ class EVEngine(EVAudio):
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
         for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
-        flac: None, True or one boolean per utterance: adds flac_list, the FLAC stream (``bytes``) of every selected utterance and None
+        flac: None, True, one boolean per utterance or an emotivoice_amd.flac.FlacConfig (every utterance, with its LPC / MD5 / block settings;
+        the sample rate is the engine's and the conversion stays the wrapping one): adds flac_list, the FLAC stream (``bytes``) of every selected utterance and None
         for the others, encoded on the device from the fp32 waveform with the wrapping conversion -- a stream decodes to
         wav_float_to_int16(wav_list[b]).
         loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every utterance is normalised on the device
@@ -359,9 +367,10 @@ class EVEngine(EVAudio):
         the pre-gain (emotivoice_amd.limiter.pre_gain) goes into ev_limit, and the limiter holds the peaks sample by sample; ``loudness`` then
         holds the measurement and the pre-gain, ``limiter`` the limiter's per-utterance figures, and the audio, the int16 (clamping rule) and
         the FLAC streams are the limiter's.  The loudness is not measured again after the limiter: it sits at or slightly below the target."""
+        from .flac import FlacConfig
         sel = None
         if flac is not None and flac is not False:
-            sel = np.ones(len(utts), bool) if flac is True else np.asarray(flac, bool)
+            sel = np.ones(len(utts), bool) if flac is True or isinstance(flac, FlacConfig) else np.asarray(flac, bool)
             if sel.shape != (len(utts),):
                 raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (len(utts), sel.shape))
         for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness)):
@@ -386,7 +395,7 @@ class EVEngine(EVAudio):
             if limited is not None:
                 out["limiter"] = limited
         if sel is not None:
-            out["flac_list"] = self._flac_runs(sel, offs, res.wav, pcm_i16)
+            out["flac_list"] = self._flac_runs(sel, offs, res.wav, pcm_i16, flac)
         return out
 
     def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None) -> Dict[str, object]:
@@ -396,7 +405,8 @@ class EVEngine(EVAudio):
         documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
         config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
-        flac=True adds flac_list, one FLAC stream (``bytes``) per document, encoded on the device from ev_stitch's int16 documents (it turns
+        flac=True or an emotivoice_amd.flac.FlacConfig (its LPC / MD5 / block settings; the sample rate is the engine's; ``md5`` costs one serial
+        chain per document) adds flac_list, one FLAC stream (``bytes``) per document, encoded on the device from ev_stitch's int16 documents (it turns
         config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to).
         loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every document is normalised on the device after ev_stitch
         (ev_loudness: one gain per document, so the balance between its sentences stays) and before ev_flac; ``documents`` (int16 by the
@@ -434,8 +444,7 @@ class EVEngine(EVAudio):
         if limited is not None:
             out["limiter"] = limited
         if flac:
-            from .flac import FlacConfig
-            fr = self.flac_raw(st.batch_docs, pcm_i16 or st.wav_i16, True, out["doc_lens"], FlacConfig(sample_rate=int(sc.sample_rate)),
+            fr = self.flac_raw(st.batch_docs, pcm_i16 or st.wav_i16, True, out["doc_lens"], self._flac_config(flac, int(sc.sample_rate)),
                                _ffi.EV_FLAG_DEVICE_INPUTS)
             out["flac_list"] = self.flac_to_numpy(fr)["streams"]
         sr = float(sc.sample_rate)

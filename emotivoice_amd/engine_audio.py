@@ -258,12 +258,20 @@ class EVAudio:
     def flac_raw(self, B: int, pcm_ptr: int, pcm_is_i16: bool, lens: np.ndarray, config=None, flags: int = 0) -> _ffi.ev_flac_result:
         """ev_flac (include/evhip.h).  pcm_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens is a host array.  config:
         an emotivoice_amd.flac.FlacConfig, an _ffi.ev_flac_config or None (the library's default).  The returned struct's device bytes and host
-        arrays stay valid until the next flac call on this engine."""
-        return self._call("flac", B, C.c_void_p(pcm_ptr), 1 if pcm_is_i16 else 0, _ptr(host_lens(lens, B)), config_ref(config), flags)
+        arrays stay valid until the next flac call on this engine.  A FlacConfig with LPC or MD5 (``to_ext()`` not None) goes to ev_flac_lpc."""
+        ext = config.validate().to_ext() if hasattr(config, "to_ext") else None
+        if ext is None:
+            return self._call("flac", B, C.c_void_p(pcm_ptr), 1 if pcm_is_i16 else 0, _ptr(host_lens(lens, B)), config_ref(config), flags)
+        res = _ffi.ev_flac_result()
+        res.struct_size = C.sizeof(_ffi.ev_flac_result)
+        self._check(self._lib.ev_flac_lpc(self._h, B, C.c_void_p(pcm_ptr), 1 if pcm_is_i16 else 0, _ptr(host_lens(lens, B)), config_ref(config), C.byref(ext),
+                                          flags, C.byref(res)))
+        self.last_flac = res
+        return res
 
     def flac_to_numpy(self, res: _ffi.ev_flac_result) -> Dict[str, object]:
         """One D2H copy of total_bytes and copies of the result's host arrays.  streams: one ``bytes`` per segment; frame_kind / frame_porder:
-        one uint8 array per segment (0 constant, 1 verbatim, 8 + o fixed; the partition order)."""
+        one uint8 array per segment (0 constant, 1 verbatim, 8 + o fixed, 32 + (o - 1) LPC; the partition order)."""
         B, NF = res.batch, int(res.total_frames)
         raw = self.d2h(res.bytes, (int(res.total_bytes),), np.uint8)
         offs, nfr = host_array(res.stream_offsets, B + 1, np.int64), host_array(res.stream_frames, B, np.int64)

@@ -327,17 +327,21 @@ def engine_prosody_synth_fn(engine, loudness=None, limiter=None) -> Callable[[Li
     return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
 
 
-def engine_flac_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
     second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
-    streams then carry the normalised int16 (the clamping conversion).  ``limiter``: as ``engine_synth_fn``; the streams carry the limiter's int16."""
+    streams then carry the normalised int16 (the clamping conversion).  ``limiter``: as ``engine_synth_fn``; the streams carry the limiter's int16.
+    ``flac_config``: an emotivoice_amd.flac.FlacConfig for every stream of this service (LPC order, precision, MD5, block size), like ``loudness``
+    a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms."""
     lkw = _output_kw(loudness, limiter)
+    if flac_config is not None:
+        flac_config.validate()
 
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)
         kw.update(lkw)
-        out = engine.synthesize(utts, flac=list(mask), **kw)
+        out = engine.synthesize(utts, flac=list(mask) if flac_config is None else flac_config, **kw)
         return [f if m else w for f, w, m in zip(out["flac_list"], out["wav_list"], mask)]
     return fn
 

@@ -583,14 +583,14 @@ int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_
  *   Stream of a segment of n samples: "fLaC"; the metadata block header 0x80 0x00 0x00 0x22 (last block, STREAMINFO, 34 bytes); STREAMINFO;
  *     the frames; nothing else.  STREAMINFO, big-endian bit fields in order: min block size = max block size = N (16 bits each); min and
  *     max frame size in bytes over this stream's frames (24 bits each); sample rate (20); channels - 1 = 0 (3); bits per sample - 1 = 15 (5);
- *     n (36); MD5 = 16 zero bytes ("not known", which the format allows: an MD5 of the PCM is one serial chain per stream).
+ *     n (36); MD5 = 16 zero bytes ("not known", which the format allows; ev_flac_lpc below can write it).
  *   Blocks: N = block_size; ceil(n / N) frames; every frame holds N samples but the last, which holds the rest (1 .. N).
  *   Frame header: 0xFF 0xF8 (sync, fixed block size); a byte of block-size code << 4 | sample-rate code; a byte 0x08 (channel code 0, sample-size
  *     code 4 = 16 bits, a reserved 0 bit); the frame's index in its stream in the format's UTF-8-like coding (1 byte below 2^7, then 2 .. 6 bytes
  *     carrying 11, 16, 21, 26, 31 bits); then, for a last frame shorter than N, its size - 1 in 8 bits (size <= 256, block-size code 6) or 16
  *     bits (code 7); CRC-8 (polynomial 0x07, initial value 0, not reflected, no final xor) of the header bytes before it.  A frame of N samples
  *     carries the table code 8 + log2(N / 256).  Sample-rate codes: 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10.
- *   Subframe: a byte type << 1 (a 0 bit, the 6-bit type, a 0 bit: no wasted bits); types CONSTANT 0, VERBATIM 1, FIXED order o = 8 + o.  No LPC.
+ *   Subframe: a byte type << 1 (a 0 bit, the 6-bit type, a 0 bit: no wasted bits); types CONSTANT 0, VERBATIM 1, FIXED order o = 8 + o (LPC: ev_flac_lpc below).
  *   Choice, for a block of m samples:
  *     1. All samples equal: CONSTANT, the sample in 16 bits (8 + 16 bits).
  *     2. Otherwise for every order o = 0 .. min(max_fixed_order, m - 1): the residual r_i, i = o .. m - 1, is the o-th finite difference
@@ -633,7 +633,7 @@ typedef struct ev_flac_result {
     const int64_t* stream_offsets; /* (batch + 1,) HOST: stream b is bytes[stream_offsets[b] .. stream_offsets[b + 1]) */
     const int64_t* stream_frames;  /* (batch,) HOST */
     const int64_t* frame_offsets;  /* (total_frames + 1,) HOST: byte offsets of the frames in bytes, stream after stream; the last entry is total_bytes */
-    const uint8_t* frame_kind;     /* (total_frames,) HOST: 0 constant, 1 verbatim, 8 + o fixed */
+    const uint8_t* frame_kind;     /* (total_frames,) HOST: 0 constant, 1 verbatim, 8 + o fixed, 32 + (o - 1) LPC (ev_flac_lpc only) */
     const uint8_t* frame_porder;   /* (total_frames,) HOST: the partition order of a fixed subframe, else 0 */
 } ev_flac_result;
 /* pcm: a host pointer, or with EV_FLAG_DEVICE_INPUTS (the other flags are ignored) a device pointer on the handle's device; lens is always a HOST
@@ -645,6 +645,45 @@ typedef struct ev_flac_result {
  * its own and is complete when the call returns; it stays valid across every other entry point until the next ev_flac or ev_destroy -- the
  * contract of ev_features_result. */
 int ev_flac(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, uint32_t flags, ev_flac_result* out);
+
+/* FLAC with LPC subframes and the MD5 signature (ev_flac_lpc): ev_flac with the extension ext.  ext NULL, or max_lpc_order = 0 and md5 = 0, gives
+ * the bytes of ev_flac.  Everything above holds; the Choice continues, for a block of m samples x_i that is not CONSTANT, with max_lpc_order > 0:
+ *     4. Window (Welch, integers, from m alone): w_i = (32767 * 4 * i * (m - 1 - i)) / (m - 1)^2, integer division, i = 0 .. m - 1 (m >= 2);
+ *        y_i = (x_i * w_i) >> 15, an arithmetic shift, so |y_i| < 2^15.
+ *     5. Autocorrelation: R[l] = sum_{i = l}^{m - 1} y_i y_{i - l}, l = 0 .. L, L = min(max_lpc_order, m - 1): exact in int64 (< 2^42), so any
+ *        order of summation gives the same value.  R[0] = 0: no LPC candidate.
+ *     6. Levinson-Durbin in fp64, one IEEE operation (round to nearest even) per rounding, no contraction: err = (double)R[0]; for it = 0 ..
+ *        L - 1: acc = (double)R[it + 1]; for j = 0 .. it - 1 in that order acc = acc - a_j * (double)R[it - j]; k = acc / err;
+ *        a'_j = a_j - k * a_{it - 1 - j} for j < it, a'_it = k; a = a'; err = err * (1 - k * k).  The recursion stops when err is not finite or
+ *        err <= 0; otherwise a are the coefficients of order o = it + 1.
+ *     7. Quantisation, per order, q = qlp_precision: c_max = max |a_j|; an order with c_max = 0 (or not finite) is skipped.  c_max = f 2^e with f
+ *        in [0.5, 1); shift = q - 1 - e; shift < 0: that order is no candidate; shift > 15 is taken as 15.
+ *        c_j = clamp(rint(a_j * 2^shift), -2^(q - 1), 2^(q - 1) - 1), rint to nearest even (the product by a power of two is one IEEE product).
+ *     8. Residual of order o: r_i = x_i - ((sum_{j = 0}^{o - 1} c_j x_{i - 1 - j}) >> shift), the sum in 64 bits, an arithmetic shift, i = o ..
+ *        m - 1.  An order with some |r_i| >= 2^31 is no candidate.
+ *     9. Cost: the partition / Rice search of rule 2 with o warm-up samples; bits_o = 8 + 16 o + 4 + 5 + q o + 2 + that cost.  The candidates
+ *        are FIXED 0 .. min(max_fixed_order, m - 1), then LPC 1 .. L; the smallest wins; on a tie FIXED wins over LPC and the smaller order wins.
+ *        Rule 3 (VERBATIM) applies to that minimum unchanged, so ev_flac_bound still holds.
+ *   LPC subframe, type 32 + (o - 1): the o warm-up samples in 16 bits each; q - 1 in 4 bits; shift in 5 bits; c_0 .. c_{o - 1} in q bits each, two's
+ *     complement (c_0 multiplies x_{i - 1}); then the residual exactly as in a FIXED subframe.  frame_kind reports 32 + (o - 1).
+ *   MD5: with md5 = 1 the last 16 bytes of STREAMINFO are the MD5 (RFC 1321) of the segment's samples as little-endian 16-bit values (for fp32
+ *     input: of the converted samples), one wave per segment, before the synchronisation that brings the frame sizes back; with md5 = 0 they are
+ *     zero.
+ * The streams have been held to a numpy restatement of these rules and to an independent decoder written from the format (tests/), not to
+ * libFLAC or ffmpeg. */
+typedef struct ev_flac_ext {
+    uint32_t struct_size;     /* sizeof(ev_flac_ext); any other value is rejected */
+    int32_t  max_lpc_order;   /* 0 (no LPC) .. 12 */
+    int32_t  qlp_precision;   /* 5 .. 15; default 12 */
+    int32_t  md5;             /* 0 / 1 */
+    int32_t  reserved[4];     /* 0 */
+} ev_flac_ext;
+void ev_default_flac_ext(ev_flac_ext* ext);      /* 8, 12, 1 */
+/* As ev_flac (arguments, rejections, the one synchronisation, the result's lifetime: the result shares ev_flac's workspace, so it stays valid until
+ * the next ev_flac or ev_flac_lpc); additionally rejected, with a message naming the field: a wrong ext->struct_size, max_lpc_order outside
+ * [0, 12], qlp_precision outside [5, 15], md5 outside {0, 1}, a non-zero reserved word. */
+int ev_flac_lpc(ev_handle* h, int B, const void* pcm, int pcm_is_i16, const int64_t* lens, const ev_flac_config* cfg, const ev_flac_ext* ext, uint32_t flags,
+                ev_flac_result* out);
 
 /* Loudness normalisation (ev_loudness): packed segments -> their programme loudness after ITU-R BS.1770 / EBU R 128 (K-weighted, gated, in LUFS),
  * their sample peak, one gain per segment that brings it to a target within two limits, and the scaled waveform, on the device: it sits between

@@ -257,6 +257,11 @@ int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t*
  * slots must be 4-byte aligned.  The call waits for the stream.  -2 for what ev_flac rejects. */
 int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, uint8_t* slots, int32_t* sizes,
                       uint8_t* kind, uint8_t* porder, void* hip_stream);
+/* ev_flac_lpc's analysis alone (rules 4 .. 7 of include/evhip.h) on the frames of the same input: per frame f, R[13 f + l] (l = 0 .. 12, zero
+ * beyond L), and per order o = 1 .. 12 shift[12 f + o - 1] (-1: no candidate) and coef[144 f + 12 (o - 1) + j]; a frame of one sample gives zeros
+ * and -1.  CONSTANT frames are analysed like any other.  R, shift and coef are HOST arrays.  -2 for what ev_flac_lpc rejects. */
+int ev_op_flac_lpc(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, const ev_flac_config* cfg, int max_lpc_order, int qlp_precision, int64_t* R,
+                   int32_t* shift, int32_t* coef, void* hip_stream);
 
 /* ev_limit's kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_limit).  ev_op_limit_peak: the meter on B segments of wav
  * (int16 or fp32, packed back to back, lens[b] samples each) with the pre-gains -> r (the required gain per sample, packed as the input; NULL =
