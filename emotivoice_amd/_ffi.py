@@ -204,6 +204,21 @@ class ev_limit_result(C.Structure):
     ]
 
 
+EV_DELIVER_F32, EV_DELIVER_S16, EV_DELIVER_ULAW, EV_DELIVER_ALAW, EV_DELIVER_TILE = 0, 1, 2, 3, 1024
+
+
+class ev_deliver_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sr_in", C.c_int32), ("sr_out", C.c_int32), ("encoding", C.c_int32), ("dither", C.c_int32),
+                ("seed", C.c_uint32), ("half_len", C.c_int32), ("taps", C.c_void_p)]
+
+
+class ev_deliver_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total_bytes", C.c_int64), ("data", C.c_void_p),
+        ("byte_offsets", C.POINTER(C.c_int64)), ("n_samples", C.POINTER(C.c_int64)), ("peak", C.POINTER(C.c_float)), ("clipped", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -290,6 +305,9 @@ SIGNATURES = {
     "ev_limit_design": (C.c_int, [C.c_int, _P]),      # host only
     # lens and gains are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_limit": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(ev_limit_config), C.c_uint32, C.POINTER(ev_limit_result)]),
+    "ev_default_deliver_config": (None, [C.POINTER(ev_deliver_config)]),
+    "ev_deliver_setup": (C.c_int, [_P, C.POINTER(ev_deliver_config)]),
+    "ev_deliver": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_uint32, C.POINTER(ev_deliver_result)]),
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

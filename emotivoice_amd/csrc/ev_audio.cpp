@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1195,6 +1195,101 @@ int ev_limit(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t
     out->batch = B; out->total = total; out->wav = d_wav; out->wav_i16 = i16 ? d_i16 : nullptr;
     out->true_peak_in = h->lim.tp_in.data(); out->sample_peak_in = h->lim.sp_in.data(); out->true_peak_out = h->lim.tp_out.data();
     out->sample_peak_out = h->lim.sp_out.data(); out->min_gain = h->lim.min_gain.data(); out->limited = h->lim.limited.data(); out->nonfinite = h->lim.nonf.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- response delivery (include/evhip.h: ev_deliver)
+static_assert(EV_DELIVER_TILE == DL_TILE && EV_DELIVER_F32 == DL_F32 && EV_DELIVER_S16 == DL_S16 && EV_DELIVER_ULAW == DL_ULAW && EV_DELIVER_ALAW == DL_ALAW,
+              "include/evhip.h states the tile and the encodings of ev_deliver.hip");
+void ev_default_deliver_config(ev_deliver_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_deliver_config);
+    c->sr_in = 16000; c->sr_out = 16000; c->encoding = EV_DELIVER_S16;
+}
+
+int ev_deliver_setup(ev_handle* h, const ev_deliver_config* cfg) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_deliver_setup: null config");
+    if (check_struct_size(h, "ev_deliver_setup", "struct_size", cfg->struct_size, "ev_deliver_config", sizeof(ev_deliver_config))) return -1;
+    if (cfg->encoding < EV_DELIVER_F32 || cfg->encoding > EV_DELIVER_ALAW)
+        return fail(h, "ev_deliver_setup: encoding = %d is not one of EV_DELIVER_F32, EV_DELIVER_S16, EV_DELIVER_ULAW, EV_DELIVER_ALAW", cfg->encoding);
+    if (cfg->dither != 0 && cfg->dither != 1) return fail(h, "ev_deliver_setup: dither = %d is not 0 (none) or 1 (TPDF)", cfg->dither);
+    if (cfg->dither && cfg->encoding == EV_DELIVER_F32) return fail(h, "ev_deliver_setup: dither = %d with encoding EV_DELIVER_F32: nothing is quantised", cfg->dither);
+    ev_resample_config rc;      // the ratio and the taps: ev_resample's own checks and default design
+    ev_default_resample_config(&rc);
+    rc.sr_in = cfg->sr_in; rc.sr_out = cfg->sr_out; rc.taps = cfg->taps; rc.half_len = cfg->half_len;
+    int up = 0, down = 0, half = 0;
+    std::vector<float> taps;
+    if (resample_check_config(h, "ev_deliver_setup", rc, &up, &down, &half, taps)) return -1;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float* tab = nullptr; size_t floats = 0;
+    if (!(up == 1 && down == 1) && resample_upload_table(up, half, taps, &tab, &floats)) return fail(h, "ev_deliver_setup: uploading the tap table failed");
+    if (h->dlv.tab) (void)hipFree(h->dlv.tab);
+    h->dlv.tab = tab; h->dlv.up = up; h->dlv.down = down; h->dlv.half = half;
+    h->dlv.cfg = *cfg; h->dlv.cfg.taps = nullptr;
+    h->dlv.ready = true;
+    return 0;
+}
+
+int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const uint32_t* seeds, uint32_t flags, ev_deliver_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_deliver: wav is NULL");
+    if (!lens) return fail(h, "ev_deliver: lens is NULL");
+    if (!out) return fail(h, "ev_deliver: out is NULL");
+    if (check_struct_size(h, "ev_deliver", "out->struct_size", out->struct_size, "ev_deliver_result", sizeof(ev_deliver_result))) return -1;
+    if (!h->dlv.ready) return fail(h, "ev_deliver: ev_deliver_setup has not been called");
+    if (B < 1 || B > 65535) return fail(h, "ev_deliver: B = %d outside [1, 65535]", B);
+    const ev_deliver_config& c = h->dlv.cfg;
+    const int up = h->dlv.up, down = h->dlv.down, half = h->dlv.half;
+    const int es_out = c.encoding == EV_DELIVER_F32 ? 4 : c.encoding == EV_DELIVER_S16 ? 2 : 1;
+    std::vector<DeliverSeq> seqs; std::vector<DeliverTile> tiles;
+    int64_t total_bytes = 0;
+    const int bad = deliver_layout(B, lens, up, down, es_out, seeds, c.seed, seqs, tiles, &total_bytes);
+    if (bad > 0) return fail(h, "ev_deliver: lens[%d] = %lld < 1", bad - 1, (long long)lens[bad - 1]);
+    if (bad < 0) return fail(h, "ev_deliver: utterance %d (lens[%d] = %lld samples) gives more than EV_ALIGN_MAX_FRAMES * 256 = %lld output samples", -bad - 1, -bad - 1,
+                             (long long)lens[-bad - 1], (long long)RS_MAX_OUT);
+    const int64_t total_in = seqs[B - 1].in_off + seqs[B - 1].len;
+    int64_t total_n = 0;
+    for (int b = 0; b < B; ++b) total_n += seqs[b].n;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, copy = up == 1 && down == 1;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    const size_t NT = tiles.size();
+    if (call_begin(h)) return -1;
+    void* d_wav = nullptr; DeliverSeq* d_seqs = nullptr; DeliverTile* d_tiles = nullptr; DeliverPart* d_parts = nullptr; DeliverOut* d_outs = nullptr;
+    uint8_t* d_data = nullptr;
+    if (arena_plan(h, ARENA_DELIVER, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        d_seqs = ap.arr<DeliverSeq>(B); d_tiles = ap.arr<DeliverTile>(NT); d_parts = ap.arr<DeliverPart>(NT); d_outs = ap.arr<DeliverOut>(B);
+        d_data = ap.arr<uint8_t>((size_t)total_bytes);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
+    DeliverParams p{};
+    p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)NT;
+    p.up = up; p.down = down; p.half = half; p.row = copy ? 0 : resample_row_len(up, half); p.tab = h->dlv.tab;
+    p.encoding = c.encoding; p.dither = c.dither; p.out = d_data; p.parts = d_parts;
+    region_begin(h, "total");
+    {
+        KScope ks(h, copy ? "deliver_copy" : "deliver_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)total_in * es + (double)total_bytes);
+        if (launch_deliver(p, h->stream)) return fail(h, "ev_deliver: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "deliver_fold", 0.0, (double)NT * sizeof(DeliverPart) + (double)B * sizeof(DeliverOut));
+        launch_deliver_fold(d_parts, d_seqs, B, d_outs, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<DeliverOut> outs((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(outs.data(), d_outs, (size_t)B * sizeof(DeliverOut), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    std::vector<int64_t> offs((size_t)B + 1), n((size_t)B), clipped((size_t)B); std::vector<float> peak((size_t)B);
+    for (int b = 0; b < B; ++b) { offs[b] = seqs[b].byte_off; n[b] = seqs[b].n; peak[b] = outs[b].peak; clipped[b] = outs[b].clipped; }
+    offs[B] = total_bytes;
+    h->dlv.offs.swap(offs); h->dlv.n.swap(n); h->dlv.clipped.swap(clipped); h->dlv.peak.swap(peak);
+    reset_result(out);
+    out->batch = B; out->total_bytes = total_bytes; out->data = d_data;
+    out->byte_offsets = h->dlv.offs.data(); out->n_samples = h->dlv.n.data(); out->peak = h->dlv.peak.data(); out->clipped = h->dlv.clipped.data();
     return 0;
 }
 

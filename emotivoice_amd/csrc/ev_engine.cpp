@@ -1027,6 +1027,7 @@ void ev_destroy(ev_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     for (int i = 0; i < ARENA_COUNT; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
     if (h->rs.tab) (void)hipFree(h->rs.tab);
+    if (h->dlv.tab) (void)hipFree(h->dlv.tab);
     if (h->stitch.tab) (void)hipFree(h->stitch.tab);
     if (h->feat.basis) (void)hipFree(h->feat.basis);
     if (h->feat.melT) (void)hipFree(h->feat.melT);

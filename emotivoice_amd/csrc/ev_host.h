@@ -36,6 +36,7 @@ enum Arena {
     ARENA_FLAC,        // ev_flac (like ARENA_ALIGN)
     ARENA_LOUDNESS,    // ev_loudness (likewise)
     ARENA_LIMIT,       // ev_limit (likewise)
+    ARENA_DELIVER,     // ev_deliver (likewise)
     ARENA_COUNT
 };
 
@@ -82,6 +83,10 @@ struct LoudnessState {       // ev_loudness
     std::vector<double> loud, rel, ms; std::vector<float> gain, peak; std::vector<uint8_t> flags, state;
     std::vector<int64_t> nonf, boffs;
 };
+struct DeliverState {       // ev_deliver.  tab: the phase-major table on the device (nullptr for sr_in == sr_out); its own, never ev_resample's
+    ev_deliver_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; float* tab = nullptr;
+    std::vector<int64_t> offs, n, clipped; std::vector<float> peak;
+};
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
 
 }  // namespace evh
@@ -117,7 +122,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

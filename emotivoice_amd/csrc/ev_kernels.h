@@ -306,6 +306,30 @@ void launch_resample_copy(const void* wav, int wav_is_i16, int64_t total, float*
 void launch_trim_scan(const float* y, const ResampleSeq* seqs, int B, float frac, int64_t* cuts /* (2 B,): first, last */, hipStream_t s);
 void launch_trim_gather(const float* y, const TrimSeq* seqs, int B, int64_t max_len, int pad, float* out, hipStream_t s);
 
+// ev_deliver (ev_deliver.hip): ev_resample's output sample, converted in registers to the response's encoding.  A tile is DL_TILE consecutive outputs
+// of one utterance, four consecutive outputs per thread, stored as one quad (4 / 8 / 16 bytes); the table is ev_resample's (resample_pack_table).  A
+// tile's run of inputs stays in LDS up to DL_MAX_RUN_BYTES, the table beside it up to DL_MAX_LDS in all.  Every tile leaves a DeliverPart; the fold
+// kernel reduces the parts of an utterance, tile0 .. tile0 + ceil(n / DL_TILE), in ascending order (a max and an integer sum: exact in any order).
+constexpr int DL_TILE = 1024, DL_MAX_RUN_BYTES = 49152, DL_MAX_LDS = 65536;
+enum { DL_F32 = 0, DL_S16 = 1, DL_ULAW = 2, DL_ALAW = 3 };
+struct DeliverSeq { int64_t in_off, len, n, byte_off, slot; uint32_t seed; int32_t tile0; };      // slot = the utterance's bytes rounded up to 16
+struct DeliverTile { int32_t seq, m0; };
+struct DeliverPart { float peak; int32_t clipped; };
+struct DeliverOut { float peak; int32_t pad; int64_t clipped; };
+struct DeliverParams {
+    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
+    const DeliverSeq* seqs; const DeliverTile* tiles; int n_tiles;
+    int up, down, half, row;                          // row = resample_row_len(up, half); up == down == 1: no filter, tab unused
+    const float* tab;                                 // (up, row) on the device
+    int encoding, dither;                             // DL_*; dither: 0 none, 1 TPDF
+    uint8_t* out;                                     // utterance b at byte_off, slot bytes
+    DeliverPart* parts;                               // (n_tiles,)
+    int run_cap;                                      // set by the launcher: floats of LDS for the run, 0 = read through L1
+};
+int64_t deliver_run_max(int up, int down, int half);            // an upper bound of a tile's run of input samples
+int launch_deliver(const DeliverParams& p, hipStream_t s);      // 0, or -1 for bad parameters
+void launch_deliver_fold(const DeliverPart* parts, const DeliverSeq* seqs, int B, DeliverOut* outs, hipStream_t s);
+
 // ev_stitch (ev_stitch.hip): segments -> documents.  The scan spreads a segment's peak over blocks of ST_PEAK_CHUNK samples and finds its edges in
 // chunks of ST_EDGE_CHUNK; the mix writes one tile of ST_TILE output samples per block with the ramp table (F <= ST_MAX_FADE floats) in LDS.
 constexpr int ST_PEAK_CHUNK = 4096, ST_EDGE_CHUNK = 1024, ST_TILE = 1024, ST_MAX_FADE = 4096;

@@ -50,6 +50,27 @@ inline int resample_layout(int B, const int64_t* wav_lens, int up, int down, int
     return 0;
 }
 
+// ---------------------------------------------------------------- outputs n = ceil(len up / down) of es bytes, 16-byte slots, tiles of DL_TILE outputs (ev_deliver)
+// the utterances' table (slots back to back, each rounded up to 16 bytes), the tile table and the total bytes; 0 or the index + 1 of the first empty
+// utterance (-(index + 1): more than RS_MAX_OUT outputs, ev_resample's limit)
+inline int deliver_layout(int B, const int64_t* lens, int up, int down, int es, const uint32_t* seeds, uint32_t seed, std::vector<ev::DeliverSeq>& seqs,
+                          std::vector<ev::DeliverTile>& tiles, int64_t* total_bytes) {
+    seqs.resize(B); tiles.clear();
+    int64_t io = 0, bo = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1) return b + 1;
+        if (lens[b] > RS_MAX_OUT * EV_RESAMPLE_MAX_RATIO) return -(b + 1);      // keeps L up inside int64
+        const int64_t n = (lens[b] * up + down - 1) / down;
+        if (n > RS_MAX_OUT) return -(b + 1);
+        const int64_t slot = (n * es + 15) / 16 * 16;
+        seqs[b] = ev::DeliverSeq{io, lens[b], n, bo, slot, seeds ? seeds[b] : seed, (int32_t)tiles.size()};
+        for (int64_t m0 = 0; m0 < n; m0 += ev::DL_TILE) tiles.push_back(ev::DeliverTile{b, (int32_t)m0});
+        io += lens[b]; bo += slot;
+    }
+    *total_bytes = bo;
+    return 0;
+}
+
 // what a table of fixed-size pieces rejects in a length: below 1, above the utility's limit, or more than INT_MAX pieces in the call so far
 enum LenBad { LEN_OK = 0, LEN_SHORT, LEN_LONG, LEN_COUNT };
 

@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _ffi
 from .config import EVShapes
+from .delivery import delivery_config
 from .engine_audio import EVAudio, cut, host_array
 from .limiter import as_config as limiter_config, pre_gain
 from .loudness import as_config as loudness_config
@@ -77,7 +78,7 @@ def make_ev_config(shapes: EVShapes, decoder_precision: str = "mx", keep_stages:
 
 class EVEngine(EVAudio):
     """One handle = one GPU + one stream + one workspace (include/evhip.h).  Not thread-safe.  The audio utilities (features, pitch, resample,
-    stitch, compare, flac, loudness, limit) are EVAudio's (engine_audio.py)."""
+    stitch, compare, flac, loudness, limit, deliver) are EVAudio's (engine_audio.py)."""
 
     def __init__(self, shapes: Optional[EVShapes] = None, device_id: int = 0, decoder_precision: Optional[str] = None,
                  keep_stages: bool = False, token_rate: str = "split", vocoder_chunk_mb: int = 0,
@@ -96,8 +97,8 @@ class EVEngine(EVAudio):
         self.device_id = device_id
         self._blob_keepalive = None
         self.last: Optional[_ffi.ev_result] = None
-        self.feature_config = self.resample_config = None      # set by features_setup() / resample_setup()
-        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit"):
+        self.feature_config = self.resample_config = self.delivery_config = self._delivery_key = None      # set by features_setup() / resample_setup() / deliver_setup()
+        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver"):
             setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
 
     # -- lifecycle
@@ -301,31 +302,56 @@ class EVEngine(EVAudio):
                                               packed, flags)
         return res, cu
 
-    def _finish(self, wav_ptr: int, lens: np.ndarray, loudness, limiter, want_int16: bool, int16_only: bool):
+    def _finish(self, wav_ptr: int, lens: np.ndarray, loudness, limiter, want_int16: bool, int16_only: bool, delivery=None):
         """The output stages between the synthesis (or ev_stitch) and ev_flac, on a packed device fp32 waveform.  loudness / limiter: a
         LoudnessConfig / LimiterConfig or None.  loudness alone: ev_loudness scales; limiter alone: ev_limit; both: ev_loudness measures only,
         the pre-gain is worked out on the host (the gain rule without its sample-peak step) and ev_limit scales and limits in its one pass.
         The last stage also writes the clamped int16 with ``want_int16``.  -> (the audio copied from the last stage: wav / wav_list and,
         where the stage made it, wav_i16 / wav_i16_list, by ``int16_only`` as ``*_to_numpy`` reads it; the loudness figures or None; the
-        limiter's figures or None; the last stage's device int16 waveform or None)."""
+        limiter's figures or None; the last stage's device int16 waveform or None; ev_deliver's result or None).
+        delivery: a DeliveryConfig or None.  With it ev_deliver runs last, on the fp32 device waveform of the stage before it (``wav_ptr`` when
+        there is none); the earlier stages then make no int16 and none of their audio is copied to the host: the delivered bytes are the audio
+        (delivered_list, delivered_rate and ``delivery`` = peak / clipped / n_samples in the returned audio)."""
         import dataclasses
         B, dev = len(lens), _ffi.EV_FLAG_DEVICE_INPUTS
         last = figures = limited = gains = None
+        if delivery is not None:
+            want_int16 = False
         if loudness is not None:
             lc = (dataclasses.replace(loudness, want_int16=loudness.want_int16 or want_int16) if limiter is None else
                   dataclasses.replace(loudness, target_lufs=float("nan"), want_int16=False))
             last = self.loudness_raw(B, wav_ptr, False, lens, lc, dev)
-            figures = self.loudness_to_numpy(last, int16_only=int16_only)
+            figures = self.loudness_to_numpy(last, int16_only=int16_only, skip_wav=delivery is not None)
         if limiter is not None:
             if loudness is not None:
                 pairs = [pre_gain(float(l), loudness) for l in figures["loudness"]]
                 gains = np.array([g for g, _ in pairs], np.float32)
                 figures["gain"], figures["flags"] = gains.copy(), np.array([f for _, f in pairs], np.uint8)
             last = self.limit_raw(B, wav_ptr, False, lens, gains, dataclasses.replace(limiter, want_int16=limiter.want_int16 or want_int16), dev)
-            limited = self.limit_to_numpy(last, int16_only=int16_only)
+            limited = self.limit_to_numpy(last, int16_only=int16_only, skip_wav=delivery is not None)
         src = limited if limited is not None else figures if figures is not None else {}
         audio = {k: src.pop(k) for k in ("wav", "wav_list", "wav_i16", "wav_i16_list") if k in src}
-        return audio, figures, limited, last.wav_i16 if last is not None else None
+        if delivery is None:
+            return audio, figures, limited, last.wav_i16 if last is not None else None, None
+        sr = int(self.shapes.sr)
+        if self._delivery_key != delivery.key(sr):
+            self.deliver_setup(delivery, sr)
+        dres = self.deliver_raw(B, last.wav if last is not None else wav_ptr, False, lens, None, dev)
+        got = self.deliver_to_numpy(dres, delivery)
+        audio = dict(delivered_list=got["delivered_list"], delivered_rate=int(delivery.sample_rate),
+                     delivery=dict(peak=got["peak"], clipped=got["clipped"], n_samples=got["n_samples"], encoding=delivery.encoding))
+        return audio, figures, limited, None, dres
+
+    def _flac_delivered(self, sel, dres, given, sample_rate: int, **kw) -> List[Optional[bytes]]:
+        """The selected utterances of an ev_deliver result (int16) as FLAC at the delivered rate: one ev_flac call per utterance, since every
+        utterance of the result starts on its own 16-byte boundary and ev_flac takes its segments back to back."""
+        fc = self._flac_config(given, int(sample_rate), **kw)
+        out: List[Optional[bytes]] = [None] * dres.batch
+        for b in range(dres.batch):
+            if sel[b]:
+                fr = self.flac_raw(1, dres.data + int(dres.byte_offsets[b]), True, [int(dres.n_samples[b])], fc, _ffi.EV_FLAG_DEVICE_INPUTS)
+                out[b] = self.flac_to_numpy(fr)["streams"][0]
+        return out
 
     def _flac_config(self, given, sample_rate: int, **kw):
         """The FlacConfig of a ``flac=`` argument: a given one with the engine's sample rate (and ``kw``), else the defaults."""
@@ -349,7 +375,7 @@ class EVEngine(EVAudio):
         return out
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
@@ -366,19 +392,27 @@ class EVEngine(EVAudio):
         on the device.  With ``loudness`` the gain to the target is no longer cut by the utterance's largest sample: ev_loudness only measures,
         the pre-gain (emotivoice_amd.limiter.pre_gain) goes into ev_limit, and the limiter holds the peaks sample by sample; ``loudness`` then
         holds the measurement and the pre-gain, ``limiter`` the limiter's per-utterance figures, and the audio, the int16 (clamping rule) and
-        the FLAC streams are the limiter's.  The loudness is not measured again after the limiter: it sits at or slightly below the target."""
+        the FLAC streams are the limiter's.  The loudness is not measured again after the limiter: it sits at or slightly below the target.
+        delivery: None, a sample rate in Hz (int16 at that rate) or an emotivoice_amd.delivery.DeliveryConfig: ev_deliver runs on the device
+        after the last of the stages above (on the vocoder's waveform when there is none) and the response is what it writes: delivered_list
+        (one float32 / int16 / uint8 array per utterance, at delivered_rate), ``delivery`` (peak, clipped, n_samples per utterance).  wav /
+        wav_list / wav_i16 are then not returned -- the 16 kHz waveform stays on the device -- and want_int16 is ignored.  With ``flac`` the
+        encoding must be "s16": ev_flac reads ev_deliver's int16 on the device at the delivered rate, a stream decodes to delivered_list[b]."""
         from .flac import FlacConfig
         sel = None
         if flac is not None and flac is not False:
             sel = np.ones(len(utts), bool) if flac is True or isinstance(flac, FlacConfig) else np.asarray(flac, bool)
             if sel.shape != (len(utts),):
                 raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (len(utts), sel.shape))
-        for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness)):
+        for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery)):
             if given is not None and not vocoder:
                 raise ValueError("%s needs the vocoder's waveform" % name)
         lc = None if loudness is None else loudness_config(loudness, int(self.shapes.sr))
         mc = None if limiter is None else limiter_config(limiter, int(self.shapes.sr))
-        staged = lc is not None or mc is not None       # the audio is the last stage's: the synthesis makes no int16 and its waveform stays on the device
+        dc = delivery_config(delivery, int(self.shapes.sr))
+        if dc is not None and sel is not None and dc.encoding != "s16":
+            raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
+        staged = lc is not None or mc is not None or dc is not None       # the audio is the last stage's: the synthesis makes no int16 and its waveform stays on the device
         flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
         out = self.result_to_numpy(res, want_int16, skip_wav=staged)
@@ -386,19 +420,25 @@ class EVEngine(EVAudio):
         offs = out["mel_offsets"] * self.shapes.upsample_factor
         pcm_i16 = None
         if staged:
-            audio, figures, limited, pcm_i16 = self._finish(res.wav, np.diff(offs), lc, mc, want_int16 or sel is not None, False)
-            out["wav"], out["wav_list"] = audio["wav"], audio["wav_list"]
-            if want_int16 or sel is not None:
-                out["wav_i16"], out["wav_int16_list"] = audio.get("wav_i16"), audio.get("wav_i16_list")
+            audio, figures, limited, pcm_i16, dres = self._finish(res.wav, np.diff(offs), lc, mc, want_int16 or sel is not None, False, dc)
+            if dc is not None:
+                out.update(audio)
+            else:
+                out["wav"], out["wav_list"] = audio["wav"], audio["wav_list"]
+                if want_int16 or sel is not None:
+                    out["wav_i16"], out["wav_int16_list"] = audio.get("wav_i16"), audio.get("wav_i16_list")
             if figures is not None:
                 out["loudness"] = figures
             if limited is not None:
                 out["limiter"] = limited
-        if sel is not None:
+        if sel is not None and dc is not None:
+            out["flac_list"] = self._flac_delivered(sel, dres, flac, dc.sample_rate, convert="wrap")
+        elif sel is not None:
             out["flac_list"] = self._flac_runs(sel, offs, res.wav, pcm_i16, flac)
         return out
 
-    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None) -> Dict[str, object]:
+    def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None,
+                        delivery=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
@@ -412,11 +452,21 @@ class EVEngine(EVAudio):
         (ev_loudness: one gain per document, so the balance between its sentences stays) and before ev_flac; ``documents`` (int16 by the
         clamping rule with config.want_int16) then hold the normalised audio and ``loudness`` the per-document figures.
         limiter: as ``synthesize`` takes it, per document: ev_limit after ev_stitch (and after ev_loudness's measurement when ``loudness`` is
-        given, whose pre-gain it applies) and before ev_flac; ``documents`` hold the limited audio and ``limiter`` the per-document figures."""
+        given, whose pre-gain it applies) and before ev_flac; ``documents`` hold the limited audio and ``limiter`` the per-document figures.
+        delivery: as ``synthesize`` takes it, per document, after the last of those stages: ``documents`` is then delivered_list (at
+        delivered_rate, in the delivery's encoding), ``delivery`` holds peak / clipped / n_samples, no 16 kHz audio is copied to the host,
+        config.want_int16 is ignored and flac (encoding "s16" only) reads ev_deliver's int16 at the delivered rate.  sentence_times are in
+        SECONDS and hold at any delivered rate; seg_pos / seg_start / seg_end / doc_lens and ``sample_rate`` stay on the engine's 16 kHz clock
+        (delivered_rate is returned next to them)."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
-        if flac and not sc.want_int16:
+        dc = delivery_config(delivery, int(self.shapes.sr))
+        if dc is not None and flac and dc.encoding != "s16":
+            raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
+        if dc is not None and sc.want_int16:
+            sc = dataclasses.replace(sc, want_int16=False).validate()
+        if flac and not sc.want_int16 and dc is None:
             sc = dataclasses.replace(sc, want_int16=True).validate()
         if int(sc.sample_rate) != int(self.shapes.sr):
             raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
@@ -430,12 +480,14 @@ class EVEngine(EVAudio):
         res, _ = self._synthesize_call(utts, alpha, 0, None, prosody)
         mel_offs = host_array(res.mel_offsets, S + 1, np.int64) * self.shapes.upsample_factor
         st = self.stitch_raw(S, res.wav, mel_offs[:-1], np.diff(mel_offs), seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
-        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=lc is not None or mc is not None)
-        stage = "limiter" if mc is not None else "loudness" if lc is not None else "flac" if flac else None
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=lc is not None or mc is not None or dc is not None)
+        stage = "limiter" if mc is not None else "loudness" if lc is not None else "delivery" if dc is not None else "flac" if flac else None
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
         if empty and stage:
             raise ValueError("%s: document %d is empty after the cut" % (stage, empty[0]))
-        audio, figures, limited, pcm_i16 = self._finish(st.wav, out["doc_lens"], lc, mc, sc.want_int16, sc.want_int16)
+        audio, figures, limited, pcm_i16, dres = self._finish(st.wav, out["doc_lens"], lc, mc, sc.want_int16, sc.want_int16, dc)
+        if dc is not None:
+            out.update(audio)
         for k, name in (("wav", "wav"), ("wav_list", "docs"), ("wav_i16", "wav_i16"), ("wav_i16_list", "docs_i16")):
             if k in audio:
                 out[name] = audio[k]
@@ -443,14 +495,16 @@ class EVEngine(EVAudio):
             out["loudness"] = figures
         if limited is not None:
             out["limiter"] = limited
-        if flac:
+        if flac and dc is not None:
+            out["flac_list"] = self._flac_delivered([True] * st.batch_docs, dres, flac, dc.sample_rate)
+        elif flac:
             fr = self.flac_raw(st.batch_docs, pcm_i16 or st.wav_i16, True, out["doc_lens"], self._flac_config(flac, int(sc.sample_rate)),
                                _ffi.EV_FLAG_DEVICE_INPUTS)
             out["flac_list"] = self.flac_to_numpy(fr)["streams"]
         sr = float(sc.sample_rate)
         start = out["seg_pos"] / sr
         end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr
-        out["documents"] = out["docs_i16"] if sc.want_int16 else out["docs"]
+        out["documents"] = out["delivered_list"] if dc is not None else out["docs_i16"] if sc.want_int16 else out["docs"]
         out["seg_doc"] = seg_doc
         out["sentence_times"] = [[(float(start[s]), float(end[s])) for s in np.nonzero(seg_doc == d)[0]] for d in range(st.batch_docs)]
         out["sample_rate"] = int(sc.sample_rate)

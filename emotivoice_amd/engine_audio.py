@@ -1,5 +1,5 @@
 """The audio utilities of the libevhip.so handle (csrc/ev_audio.cpp): ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac,
-ev_loudness and ev_limit as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
+ev_loudness, ev_limit and ev_deliver as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
 handle, ``_check`` and ``d2h`` are its own."""
 from __future__ import annotations
 
@@ -298,10 +298,11 @@ class EVAudio:
         res._lens = ln.copy()      # the packing of res.wav / res.wav_i16, for loudness_to_numpy
         return res
 
-    def loudness_to_numpy(self, res: _ffi.ev_loudness_result, int16_only: bool = False, lens=None) -> Dict[str, object]:
+    def loudness_to_numpy(self, res: _ffi.ev_loudness_result, int16_only: bool = False, lens=None, skip_wav: bool = False) -> Dict[str, object]:
         """Copies of the result's host arrays and, unless the call only measured, one D2H copy of the fp32 output (with ``int16_only`` and a
         result that has it, of the int16 output only; without it both).  block_ms / block_state: one array per segment.  lens: the call's
-        lens, which cut the output into wav_list / wav_i16_list (None: the ones loudness_raw kept with the struct)."""
+        lens, which cut the output into wav_list / wav_i16_list (None: the ones loudness_raw kept with the struct).  ``skip_wav``: the host
+        arrays only."""
         B = res.batch
         boffs = host_array(res.block_offsets, B + 1, np.int64)
         out: Dict[str, object] = dict(loudness=host_array(res.loudness, B, np.float64), rel_threshold=host_array(res.rel_threshold, B, np.float64),
@@ -309,7 +310,7 @@ class EVAudio:
                                       flags=host_array(res.flags, B, np.uint8), nonfinite=host_array(res.nonfinite, B, np.int64), block_offsets=boffs,
                                       block_ms=cut(host_array(res.block_ms, boffs[-1], np.float64), boffs),
                                       block_state=cut(host_array(res.block_state, boffs[-1], np.uint8), boffs))
-        if res.wav:
+        if res.wav and not skip_wav:
             out.update(self._wav_pair(res, res.total, offsets_of(res._lens if lens is None else lens), int16_only))
         return out
 
@@ -338,14 +339,15 @@ class EVAudio:
         res._lens = ln.copy()      # the packing of res.wav / res.wav_i16, for limit_to_numpy
         return res
 
-    def limit_to_numpy(self, res: _ffi.ev_limit_result, int16_only: bool = False, lens=None) -> Dict[str, object]:
+    def limit_to_numpy(self, res: _ffi.ev_limit_result, int16_only: bool = False, lens=None, skip_wav: bool = False) -> Dict[str, object]:
         """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
         output only; without it both).  lens: the call's lens, which cut the output into wav_list / wav_i16_list (None: the ones limit_raw kept
-        with the struct)."""
+        with the struct).  ``skip_wav``: the host arrays only."""
         out: Dict[str, object] = {k: host_array(getattr(res, k), res.batch, np.float32)
                                   for k in ("true_peak_in", "sample_peak_in", "true_peak_out", "sample_peak_out", "min_gain")}
         out["limited"], out["nonfinite"] = host_array(res.limited, res.batch, np.int64), host_array(res.nonfinite, res.batch, np.int64)
-        out.update(self._wav_pair(res, res.total, offsets_of(res._lens if lens is None else lens), int16_only))
+        if not skip_wav:
+            out.update(self._wav_pair(res, res.total, offsets_of(res._lens if lens is None else lens), int16_only))
         return out
 
     def limit(self, wavs: Sequence[np.ndarray], gains=None, **config) -> Dict[str, object]:
@@ -355,3 +357,57 @@ class EVAudio:
         lc = LimiterConfig(**config).validate()
         flat, is16, lens = pack_segments(wavs)
         return self.limit_to_numpy(self.limit_raw(len(lens), flat.ctypes.data, is16, lens, gains, lc))
+
+    # -- response delivery (ev_deliver): the waveform at the client's rate as fp32, int16 (optionally dithered), mu-law or A-law bytes, on the device
+    def deliver_setup(self, config, sr_in: int = 16000):
+        """ev_deliver_setup.  config: an emotivoice_amd.delivery.DeliveryConfig or a sample rate in Hz (int16 at that rate); sr_in: the rate of
+        the waveforms that will go in.  The setup is ev_deliver's own: it leaves resample_setup's alone.  Needs no weights."""
+        from .delivery import ENCODINGS, delivery_config
+        dc = delivery_config(config, int(sr_in))
+        if dc is None:
+            raise ValueError("deliver_setup needs a DeliveryConfig or a sample rate")
+        c = _ffi.ev_deliver_config()
+        c.struct_size = C.sizeof(_ffi.ev_deliver_config)
+        c.sr_in, c.sr_out, c.encoding, c.dither, c.seed = int(sr_in), int(dc.sample_rate), ENCODINGS[dc.encoding], 1 if dc.dither else 0, int(dc.seed)
+        taps = None
+        if dc.taps is not None:
+            taps = np.ascontiguousarray(dc.taps, np.float32).reshape(-1)
+            c.taps, c.half_len = taps.ctypes.data, (taps.size - 1) // 2
+        self._check(self._lib.ev_deliver_setup(self._h, C.byref(c)))
+        self.delivery_config, self._delivery_key = dc, dc.key(sr_in)
+
+    def deliver_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, seeds=None, flags: int = 0) -> _ffi.ev_deliver_result:
+        """ev_deliver (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens and seeds (None: the
+        config's seed for every utterance) are host arrays.  The returned struct's device bytes and host arrays stay valid until the next deliver
+        call on this engine."""
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, np.uint32)
+            if sd.shape != (B,):
+                raise ValueError("seeds must have B = %d entries" % B)
+        return self._call("deliver", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), _ptr(sd) if sd is not None else None, flags)
+
+    def deliver_to_numpy(self, res: _ffi.ev_deliver_result, config=None) -> Dict[str, object]:
+        """One D2H copy of total_bytes and copies of the result's host arrays.  delivered_list: one typed array per utterance (float32 / int16 /
+        uint8 by the encoding of ``config``, default the last deliver_setup's); peak, clipped, n_samples, byte_offsets: per utterance."""
+        dc = config or self.delivery_config
+        B = res.batch
+        raw = self.d2h(res.data, (int(res.total_bytes),), np.uint8)
+        offs, n = host_array(res.byte_offsets, B + 1, np.int64), host_array(res.n_samples, B, np.int64)
+        es = dc.sample_bytes
+        return dict(delivered_list=[raw[int(o):int(o) + int(k) * es].view(dc.dtype) for o, k in zip(offs[:-1], n)], n_samples=n, byte_offsets=offs,
+                    peak=host_array(res.peak, B, np.float32), clipped=host_array(res.clipped, B, np.int64), sample_rate=int(dc.sample_rate),
+                    encoding=dc.encoding)
+
+    def deliver(self, wavs: Sequence[np.ndarray], config, sample_rate: int = 16000, seeds=None) -> Dict[str, object]:
+        """Host signals at ``sample_rate`` -> what a client asked for.  wavs: one 1-D array per utterance, all int16 or all floating; config: an
+        emotivoice_amd.delivery.DeliveryConfig or a sample rate in Hz (int16 at that rate); seeds: one dither seed per utterance (None: the
+        config's).  The filter is this project's polyphase windowed sinc (ev_resample's), not soxr.  Needs no weights."""
+        from .delivery import delivery_config
+        dc = delivery_config(config, int(sample_rate))
+        if dc is None:
+            raise ValueError("deliver needs a DeliveryConfig or a sample rate")
+        if getattr(self, "_delivery_key", None) != dc.key(sample_rate):
+            self.deliver_setup(dc, sample_rate)
+        flat, is16, lens = pack_segments(wavs)
+        return self.deliver_to_numpy(self.deliver_raw(len(lens), flat.ctypes.data, is16, lens, seeds), dc)

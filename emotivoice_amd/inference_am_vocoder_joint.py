@@ -105,12 +105,17 @@ def synthesize_checkpoint(config, conf, checkpoint_path, out_dir, args, state_di
     eng = gen._ensure_engine()
     sr = int(getattr(config, "sampling_rate", gen.shapes.sr))
     written = 0
+    from .inference_tts import delivery_from_args, write_delivered
+    delivery = delivery_from_args(args)       # --sample-rate / --encoding / --dither: the files at that rate and encoding, converted on the device
     for s in range(0, len(todo), args.batch):
         chunk = todo[s:s + args.batch]
-        out = eng.synthesize([u for _, u in chunk])
+        out = eng.synthesize([u for _, u in chunk]) if delivery is None else eng.synthesize([u for _, u in chunk], delivery=delivery)
         os.makedirs(out_dir, exist_ok=True)
-        for (i, _), wav in zip(chunk, out["wav_list"]):
-            write_wav_int16(os.path.join(out_dir, "%d.wav" % (i + 1)), wav_float_to_int16(wav), sr)      # :130-134
+        for (i, _), wav in zip(chunk, out["wav_list" if delivery is None else "delivered_list"]):
+            if delivery is None:
+                write_wav_int16(os.path.join(out_dir, "%d.wav" % (i + 1)), wav_float_to_int16(wav), sr)      # :130-134
+            else:
+                write_delivered(os.path.join(out_dir, "%d.wav" % (i + 1)), wav, delivery)
             written += 1
     gen.close()
     return written
@@ -132,6 +137,8 @@ def main(argv=None):
                    help="no checkpoint directory: synthesise with the seeded synthetic checkpoint (named 'synthetic')")
     p.add_argument("--verify-precision", action="store_true",
                    help="with --precision mx: measure the checkpoint against a strict engine at load time and run the cheapest mode within 1e-3 of it")
+    from .inference_tts import add_delivery_arguments
+    add_delivery_arguments(p)
     args = p.parse_args(argv)
 
     config = _load_config(args.config_folder)

@@ -79,13 +79,39 @@ def load_g2p(spec: Optional[str]) -> Callable[[str], str]:
         raise RuntimeError("no G2P available (%s): pass --g2p pkg.module:function or --phoneme-input" % e)
 
 
+def delivery_from_args(args):
+    """--sample-rate / --encoding / --dither -> a DeliveryConfig, or None when none of them is given (the files are then written as before)."""
+    rate, enc, dither = getattr(args, "sample_rate", None), getattr(args, "encoding", None), bool(getattr(args, "dither", False))
+    if rate is None and enc is None and not dither:
+        return None
+    from .delivery import DeliveryConfig
+    return DeliveryConfig(sample_rate=int(rate) if rate is not None else 16000, encoding=enc or "s16", dither=dither).validate()
+
+
+def add_delivery_arguments(p: argparse.ArgumentParser):
+    p.add_argument("--sample-rate", type=int, default=None, metavar="HZ",
+                   help="write the audio at this sample rate, converted on the device (ev_deliver: e.g. 8000, 24000, 44100, 48000); default: the model's 16000")
+    p.add_argument("--encoding", default=None, choices=["s16", "f32", "ulaw", "alaw"],
+                   help="sample encoding of the files, converted on the device: 16-bit PCM, IEEE float, or G.711 mu-law / A-law; default: s16")
+    p.add_argument("--dither", action="store_true", help="TPDF dither before the rounding to 16 bits (not with --encoding f32)")
+
+
+def write_delivered(path: str, samples: np.ndarray, delivery):
+    from .delivery import wav_container
+    with open(path, "wb") as f:
+        f.write(wav_container(np.ascontiguousarray(samples).tobytes(), delivery.sample_rate, delivery.encoding))
+
+
 def run_chunk(lines: Sequence[str], start_idx: int, chunk_num: int, *, synthesize: Callable[[List[dict]], Dict[str, object]],
               embed: Callable[[str], np.ndarray], g2p: Callable[[str], str], token2id: Dict[str, int], id2speaker: Dict[int, str],
               output_dir: str, sampling_rate: int, batch: int = 32, g2p_map: Optional[Callable[[Sequence[str]], List[str]]] = None,
-              n_speaker: Optional[int] = None, log: Callable[[str], None] = print) -> Dict[str, int]:
+              n_speaker: Optional[int] = None, log: Callable[[str], None] = print, delivery=None) -> Dict[str, int]:
     """Lines [start_idx, start_idx + chunk_num) of the text file -> wav + txt files (the body of the reference's ``main``, :89-156).
     ``synthesize(list of utterance dicts) -> {"wav_list": [...]}`` is EVEngine.synthesize; ``embed(text) -> (768,)``.
+    ``delivery``: the emotivoice_amd.delivery.DeliveryConfig ``synthesize`` was bound with: the files then hold its ``delivered_list`` at the
+    delivered rate and encoding, in the RIFF container of emotivoice_amd.delivery.wav_container.
     Returns counts: written / skipped_existing / errors."""
+    key = "wav_list" if delivery is None else "delivered_list"
     n_speaker = n_speaker or len(id2speaker)          # (:88: range(conf.n_speaker))
     prompt_emb = {p: np.asarray(embed(p), np.float32) for p in PROMPTS}          # four prompts: once per process, not once per line
     stats = dict(written=0, skipped_existing=0, errors=0)
@@ -122,12 +148,12 @@ def run_chunk(lines: Sequence[str], start_idx: int, chunk_num: int, *, synthesiz
         if not utts:
             continue
         try:
-            wavs = list(synthesize(utts)["wav_list"])
+            wavs = list(synthesize(utts)[key])
         except Exception:                                                         # noqa: BLE001 -- re-run the batch a line at a time: only the
             wavs = []                                                             # offending line is lost, as in the reference (:154-156)
             for u in utts:
                 try:
-                    wavs.append(synthesize([u])["wav_list"][0])
+                    wavs.append(synthesize([u])[key][0])
                 except Exception as e:                                            # noqa: BLE001
                     log("Error: %s" % (e,))
                     stats["errors"] += 1
@@ -135,7 +161,10 @@ def run_chunk(lines: Sequence[str], start_idx: int, chunk_num: int, *, synthesiz
         for (content, wav_path, txt_path), wav in zip(keep, wavs):
             if wav is None:
                 continue
-            write_wav_int16(wav_path, wav_float_to_int16(wav), sampling_rate)     # :145-150
+            if delivery is None:
+                write_wav_int16(wav_path, wav_float_to_int16(wav), sampling_rate)     # :145-150
+            else:
+                write_delivered(wav_path, wav, delivery)
             with open(txt_path, "w", encoding="utf-8") as f:                      # :151-153
                 f.write("%s\n" % content)
             stats["written"] += 1
@@ -191,10 +220,15 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
     if getattr(args, "true_peak", None) is not None:     # the true peak held at a ceiling on the device (ev_limit); with --loudness it replaces the sample-peak limit
         import functools
         synthesize = functools.partial(synthesize, limiter=float(args.true_peak))
+    delivery = delivery_from_args(args)                   # the files at the client's rate and encoding, converted on the device (ev_deliver)
+    if delivery is not None:
+        import functools
+        synthesize = functools.partial(synthesize, delivery=delivery)
     try:
         stats = run_chunk(lines, start_idx, chunk_num, synthesize=synthesize, embed=embed, g2p=g2p, token2id=token2id,
                           id2speaker=id2speaker, output_dir=output_dir, sampling_rate=int(getattr(config, "sampling_rate", gen.shapes.sr)),
-                          batch=args.batch, g2p_map=pool.map if pool is not None else None, n_speaker=int(config.speaker_n_labels))
+                          batch=args.batch, g2p_map=pool.map if pool is not None else None, n_speaker=int(config.speaker_n_labels),
+                          **({} if delivery is None else dict(delivery=delivery)))
     finally:
         if pool is not None:
             pool.close()
@@ -228,6 +262,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--true-peak", type=float, default=None, metavar="DBTP",
                    help="hold every utterance's true (inter-sample) peak at this ceiling with the look-ahead limiter on the device (e.g. -1); with "
                         "--loudness the gain to the target is then no longer cut by the utterance's largest sample; default: no limiter")
+    add_delivery_arguments(p)
     return p
 
 

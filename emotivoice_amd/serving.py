@@ -12,7 +12,9 @@ pyrubberband time-stretching (:170-171).  Here:
   * the text front-end (G2P) and the tokenizer are host-side callables supplied by the caller (the reference's frontend.py /
     AutoTokenizer), the style encoder is the device SimBERT (emotivoice_amd/simbert.py) or any ``text -> 768-vector`` callable.
 Response formats: ``wav`` (16-bit PCM in a RIFF container) and ``pcm`` (raw little-endian int16); mp3 needs pydub / ffmpeg,
-which are not part of this package.
+which are not part of this package.  A service built with ``delivery=`` (an emotivoice_amd.delivery.DeliveryConfig: the client's sample rate
+and encoding, converted on the device by ev_deliver) answers at that rate: its utterances travel as ``bytes``, ``pcm`` / ``ulaw`` / ``alaw``
+pass them through and ``wav`` wraps them in a RIFF container of the delivered encoding.
 """
 from __future__ import annotations
 
@@ -60,12 +62,16 @@ class DynamicBatcher:
     ``flac_synth_fn(utts, alpha_or_prosodies, mask) -> list`` (``engine_flac_synth_fn``): called instead of ``synth_fn`` for a batch in which
     some request was submitted with ``response_format="flac"``; it returns, per utterance, the FLAC stream (``bytes``) where ``mask`` is True
     and the float waveform elsewhere.  The encoding thus runs on the worker thread, on the same handle.  Batches without such a request call
-    ``synth_fn`` exactly as before."""
+    ``synth_fn`` exactly as before.
+    ``delivery``: the DeliveryConfig the synth functions were built with (``engine_synth_fn(engine, delivery=...)``): they then return the
+    delivered ``bytes`` of every utterance, which resolve the Futures as they are; ``response_format`` "ulaw" / "alaw" needs it."""
 
     def __init__(self, synth_fn: Callable[[List[dict], float], Sequence[np.ndarray]], max_batch: int = 32, max_wait_ms: float = 5.0,
                  max_tokens: int = 16384, embed_batch_fn: Optional[Callable[[List[str]], np.ndarray]] = None,
                  n_vocab: Optional[int] = None, n_speaker: Optional[int] = None, max_len: int = 4096, mixed_prosody: bool = False,
-                 flac_synth_fn: Optional[Callable[[List[dict], object, List[bool]], Sequence[object]]] = None):
+                 flac_synth_fn: Optional[Callable[[List[dict], object, List[bool]], Sequence[object]]] = None, delivery=None):
+        from .delivery import delivery_config
+        self.delivery = delivery_config(delivery)
         self.mixed_prosody = mixed_prosody
         self.flac_synth_fn = flac_synth_fn
         self.synth_fn, self.max_batch, self.max_wait, self.max_tokens = synth_fn, max_batch, max_wait_ms * 1e-3, max_tokens
@@ -97,6 +103,9 @@ class DynamicBatcher:
             raise ValueError("alpha must be positive")
         if response_format == "flac" and self.flac_synth_fn is None:
             raise ValueError("response_format 'flac' needs a batcher with flac_synth_fn (engine_flac_synth_fn): FLAC is encoded on the device")
+        if response_format in ("ulaw", "alaw") and (self.delivery is None or self.delivery.encoding != response_format):
+            raise ValueError("response_format %r needs a batcher with delivery= of that encoding (emotivoice_amd.delivery.DeliveryConfig): "
+                             "G.711 is encoded on the device" % response_format)
         if prosody is not None:
             if not self.mixed_prosody:
                 raise ValueError("prosody controls need a batcher with mixed_prosody=True")
@@ -222,6 +231,10 @@ class DynamicBatcher:
                 if not isinstance(w, (bytes, bytearray)):
                     raise RuntimeError("flac_synth_fn returned %s where a FLAC stream was asked for" % type(w).__name__)
                 _resolve(r.future, result=bytes(w))
+            elif self.delivery is not None:
+                if not isinstance(w, (bytes, bytearray)):
+                    raise RuntimeError("synth_fn returned %s where delivered bytes were expected" % type(w).__name__)
+                _resolve(r.future, result=bytes(w))
             else:
                 _resolve(r.future, result=np.array(w, np.float32, copy=True))
 
@@ -313,36 +326,60 @@ def _output_kw(loudness, limiter) -> dict:
     return kw
 
 
-def engine_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
+def _delivered(delivery):
+    """``delivery`` of the engine_*_synth_fn factories (None, a sample rate in Hz or an emotivoice_amd.delivery.DeliveryConfig; like ``loudness``
+    a service-level setting, to be given to the DynamicBatcher as well) -> (the keyword for synthesize, the key of its result, what turns an
+    utterance of it into what the batcher resolves a Future with).  None: synthesize is called exactly as before."""
+    from .delivery import delivery_config
+    dc = delivery_config(delivery)
+    if dc is None:
+        return {}, "wav_list", lambda w: w
+    return dict(delivery=dc), "delivered_list", lambda w: w.tobytes()
+
+
+def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
     """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness); ``limiter``: its
-    true peak held at a ceiling (ev_limit)."""
+    true peak held at a ceiling (ev_limit); ``delivery``: every utterance converted to the client's rate and encoding on the device (ev_deliver)
+    and returned as ``bytes``."""
     kw = _output_kw(loudness, limiter)
-    return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
+    dkw, key, conv = _delivered(delivery)
+    if not dkw:
+        return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
+    return lambda utts, alpha: [conv(w) for w in engine.synthesize(utts, alpha=alpha, **kw, **dkw)[key]]
 
 
-def engine_prosody_synth_fn(engine, loudness=None, limiter=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
-    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness`` and
-    ``limiter``: as ``engine_synth_fn``."""
+def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+    """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``,
+    ``limiter`` and ``delivery``: as ``engine_synth_fn``."""
     kw = _output_kw(loudness, limiter)
-    return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
+    dkw, key, conv = _delivered(delivery)
+    if not dkw:
+        return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
+    return lambda utts, prosodies: [conv(w) for w in engine.synthesize(utts, prosody=prosodies, **kw, **dkw)[key]]
 
 
-def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
     second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
     streams then carry the normalised int16 (the clamping conversion).  ``limiter``: as ``engine_synth_fn``; the streams carry the limiter's int16.
     ``flac_config``: an emotivoice_amd.flac.FlacConfig for every stream of this service (LPC order, precision, MD5, block size), like ``loudness``
-    a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms."""
+    a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms.
+    ``delivery``: as ``engine_synth_fn``, with the encoding "s16": the streams carry ev_deliver's int16 at the delivered rate, the other
+    utterances come back as its ``bytes``."""
     lkw = _output_kw(loudness, limiter)
     if flac_config is not None:
         flac_config.validate()
+    dkw, key, conv = _delivered(delivery)
+    if dkw and dkw["delivery"].encoding != "s16":
+        raise ValueError("flac needs delivery's encoding 's16', not %r" % dkw["delivery"].encoding)
+    lkw.update(dkw)
 
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)
         kw.update(lkw)
         out = engine.synthesize(utts, flac=list(mask) if flac_config is None else flac_config, **kw)
-        return [f if m else w for f, w, m in zip(out["flac_list"], out["wav_list"], mask)]
+        return [f if m else conv(w) for f, w, m in zip(out["flac_list"], out[key], mask)]
     return fn
 
 
@@ -353,12 +390,26 @@ def engine_embed_batch_fn(engine, tokenize: Callable[[str], Sequence[int]]) -> C
     return lambda texts: engine.style_embed([np.asarray(tokenize(t), np.int64) for t in texts])
 
 
-def encode_audio(wav_f32, response_format: str, sample_rate: int) -> bytes:
-    """``flac``: the stream was encoded on the device (a batcher with ``flac_synth_fn``) and arrives as ``bytes``, which pass through."""
+def encode_audio(wav_f32, response_format: str, sample_rate: int, delivery=None) -> bytes:
+    """``flac``: the stream was encoded on the device (a batcher with ``flac_synth_fn``) and arrives as ``bytes``, which pass through.
+    ``delivery``: the DeliveryConfig of a service whose utterances were converted on the device (ev_deliver) and arrive as ``bytes``: ``pcm``
+    (encoding "s16"), ``ulaw`` and ``alaw`` pass them through when the encoding is theirs, ``wav`` wraps them with
+    emotivoice_amd.delivery.wav_container at the delivered rate."""
     if response_format == "flac":
         if isinstance(wav_f32, (bytes, bytearray)):
             return bytes(wav_f32)
         raise ValueError("response_format 'flac' is encoded on the device: it needs a batcher with flac_synth_fn (engine_flac_synth_fn)")
+    if response_format in ("ulaw", "alaw") and delivery is None:
+        raise ValueError("response_format %r needs a service with delivery= of that encoding: G.711 is encoded on the device" % response_format)
+    if delivery is not None and isinstance(wav_f32, (bytes, bytearray)):
+        from .delivery import wav_container
+        if response_format == "wav":
+            return wav_container(bytes(wav_f32), delivery.sample_rate, delivery.encoding)
+        if response_format in ("pcm", "ulaw", "alaw"):
+            if delivery.encoding != {"pcm": "s16"}.get(response_format, response_format):
+                raise ValueError("response_format %r: this service delivers %r" % (response_format, delivery.encoding))
+            return bytes(wav_f32)
+        raise ValueError("response_format %r is not available (wav, pcm, ulaw, alaw, flac); mp3 needs pydub / ffmpeg" % response_format)
     if isinstance(wav_f32, (bytes, bytearray)):
         raise ValueError("an encoded stream cannot be re-encoded as %r" % response_format)
     pcm = wav_float_to_int16(wav_f32)              # the reference's int16 epilogue (openaiapi.py:147-148)
@@ -384,6 +435,9 @@ class TTSService:
         handle with the batcher.  For the device SimBERT on the generator's own handle leave it None and give the BATCHER an
         ``embed_batch_fn``: the texts then travel with the request and are embedded on the worker thread, a batch at a time."""
         self.batcher, self.token2id, self.speaker2id, self.g2p, self.embed, self.sample_rate = batcher, token2id, speaker2id, g2p, embed, sample_rate
+        self.delivery = getattr(batcher, "delivery", None)      # a delivery-configured batcher: the service answers at its rate
+        if self.delivery is not None:
+            self.sample_rate = int(self.delivery.sample_rate)
         if embed is None and batcher.embed_batch_fn is None:
             raise ValueError("TTSService needs embed= or a batcher with embed_batch_fn=")
 
@@ -400,7 +454,7 @@ class TTSService:
         ling = np.array([self.token2id[ph] for ph in self.g2p(text).split()], np.int64)       # KeyError like openaiapi.py:128
         if ling.size == 0:
             raise ValueError("input has no phonemes")
-        extra = dict(response_format="flac") if response_format == "flac" else {}
+        extra = dict(response_format=response_format) if response_format in ("flac", "ulaw", "alaw") else {}
         if self.embed is None:
             return self.batcher.submit(ling, self.speaker2id[voice], prompt, text, alpha=1.0 / speed, prosody=prosody, **extra)
         return self.batcher.submit(ling, self.speaker2id[voice], self.embed(prompt), self.embed(text), alpha=1.0 / speed, prosody=prosody, **extra)
@@ -408,7 +462,9 @@ class TTSService:
     def speech(self, text: str, voice: str, prompt: str = "", speed: float = 1.0, response_format: str = "wav", timeout: float = 120.0,
                pitch_shift: float = 0.0, pitch_scale: float = 1.0, energy_scale: float = 1.0) -> bytes:
         fut = self.submit(text, voice, prompt, speed, pitch_shift, pitch_scale, energy_scale, response_format=response_format)
-        return encode_audio(fut.result(timeout=timeout), response_format, self.sample_rate)
+        if self.delivery is None:
+            return encode_audio(fut.result(timeout=timeout), response_format, self.sample_rate)
+        return encode_audio(fut.result(timeout=timeout), response_format, self.sample_rate, self.delivery)
 
 
 try:          # the request schema lives at module level: FastAPI resolves the handler's annotations in the module namespace

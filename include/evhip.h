@@ -843,6 +843,75 @@ typedef struct ev_limit_result {
 int ev_limit(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* gains, const ev_limit_config* cfg, uint32_t flags,
              ev_limit_result* out);
 
+/* Response delivery (ev_deliver): packed utterances at sr_in (the model's 16 kHz) -> the bytes a client asked for: the waveform at sr_out as fp32,
+ * as int16 (optionally TPDF-dithered), or as G.711 mu-law / A-law, on the device -- the last stage after ev_limit, so that an 8 kHz mu-law response
+ * leaves the device as 1/8 of the bytes of the fp32 waveform and no fp32 intermediate reaches memory unless fp32 is the encoding.  The reference has
+ * no such stage.  The filter is ev_resample's own windowed sinc (not soxr, not ffmpeg); G.711 is held to CPython's audioop and to the restatement
+ * below (no telephony endpoint was exercised); the dither generator is the integer hash specified here, checked for mean and variance only.
+ * Upsampling after the limiter can overshoot its ceiling: peak and clipped report it, the stage does not limit again.
+ *   Filter: y[m], m < n = ceil(L up / down), is EXACTLY ev_resample's output sample: the same prototype design (ev_resample_design's default for
+ *     the rate pair, or the caller's taps), the same phase-major table, the same k range, the same four interleaved fmaf partial sums combined as
+ *     (s0 + s1) + (s2 + s3), the same zero padding and x / 32768 for int16 input; sr_in == sr_out passes the sample through with no filter.  With
+ *     EV_DELIVER_F32 the bytes of an utterance therefore equal ev_resample's for the same taps.
+ *   EV_DELIVER_S16 without dither: t = y * 32768.0f (one fp32 product); s = (int)t truncated toward zero, clamped to [-32768, 32767]; NaN -> 0
+ *     (ev_stitch's rule).
+ *   EV_DELIVER_S16 with TPDF dither: on uint32 with wraparound, h(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *     For a uint64 counter c, mix(seed, c) = h(h((uint32)c + h(seed ^ (uint32)(c >> 32))) ^ seed).  ua = mix(s_b, 2 m) >> 8, ub = mix(s_b, 2 m + 1)
+ *     >> 8, d = (float)((int)ua - (int)ub) * 2^-24 (exact in fp32, |d| < 1); s = rintf(t + d): one fp32 add, ties to even, clamped, NaN -> 0.
+ *     s_b = seeds[b] when the host array seeds is given, else cfg.seed: the bits of a sample depend on (utterance, its seed, m) alone.
+ *     Known answers: mix(0, 0) = 0x00000000, mix(1, 5) = 0x820138b2, mix(12345, 2^32 + 7) = 0xe07a7e79.
+ *   EV_DELIVER_ULAW, from s (dithered or not): v = s >> 2 (arithmetic); v < 0: v = -v, mask = 0x7F, else mask = 0xFF; v = min(v, 8159) + 33; seg =
+ *     the index of the first end in {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF} with v <= end; byte = ((seg << 4) | ((v >> (seg + 1)) &
+ *     0xF)) ^ mask; no such end (v = 8192, the clipped magnitude): byte = 0x7F ^ mask, as audioop answers.
+ *   EV_DELIVER_ALAW, from s: v = s >> 3; v >= 0: mask = 0xD5, else mask = 0x55 and v = -v - 1; seg over the ends {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF,
+ *     0x3FF, 0x7FF, 0xFFF}; nibble = (v >> 1) & 0xF for seg < 2, else (v >> seg) & 0xF; byte = ((seg << 4) | nibble) ^ mask.
+ *   peak[b] = max |y| over the finite samples (before any conversion).  clipped[b] = the count of samples whose t (with dither: t + d) is below
+ *     -32768 or above 32767 (a NaN is not counted); 0 for EV_DELIVER_F32.
+ *   Layout: utterance b occupies data[byte_offsets[b] .. byte_offsets[b + 1]); its n_samples[b] * (4, 2, 1, 1) bytes come first, zeros fill the
+ *     rest; every byte_offsets[b] is a multiple of 16.
+ * The kernel writes EV_DELIVER_TILE consecutive outputs of one utterance per block, four consecutive outputs per thread as one store of 16 / 8 /
+ * 4 bytes.  No atomics and no floating sum split over threads: an utterance gives the same bytes alone or anywhere in a batch, as int16 or as
+ * the equal floats, from host or device memory; the max and the count are exact in any order.  Needs no weights. */
+#define EV_DELIVER_F32  0
+#define EV_DELIVER_S16  1
+#define EV_DELIVER_ULAW 2
+#define EV_DELIVER_ALAW 3
+#define EV_DELIVER_TILE 1024      /* outputs per block of the kernel */
+typedef struct ev_deliver_config {
+    uint32_t struct_size;          /* sizeof(ev_deliver_config); any other value is rejected */
+    int32_t  sr_in, sr_out;        /* >= 1; up and down <= EV_RESAMPLE_MAX_RATIO */
+    int32_t  encoding;             /* EV_DELIVER_* */
+    int32_t  dither;               /* 0 = none, 1 = TPDF; not with EV_DELIVER_F32 */
+    uint32_t seed;                 /* the dither's seed where ev_deliver is given no seeds */
+    int32_t  half_len;             /* with taps: (len - 1) / 2 >= 1; ignored without */
+    const float* taps;             /* HOST (2 half_len + 1) or NULL = ev_resample_design's default for the rate pair; copied */
+} ev_deliver_config;
+void ev_default_deliver_config(ev_deliver_config* cfg);      /* 16000 -> 16000, EV_DELIVER_S16, no dither, seed 0, taps NULL */
+/* Copies the taps (or designs the default ones) and builds the device table, in a workspace of its own: it does not disturb ev_resample_setup's
+ * state, nor the reverse.  Rejected (message naming the field): a wrong struct_size, sr_in or sr_out < 1, up or down > EV_RESAMPLE_MAX_RATIO, an
+ * unknown encoding or dither, dither with EV_DELIVER_F32, taps with half_len < 1, more than EV_RESAMPLE_MAX_TAPS taps, a non-finite tap.  A
+ * rejected setup leaves the previous one in place. */
+int ev_deliver_setup(ev_handle* h, const ev_deliver_config* cfg);
+
+typedef struct ev_deliver_result {
+    uint32_t struct_size;          /* sizeof(ev_deliver_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total_bytes;          /* byte_offsets[batch] */
+    const uint8_t* data;           /* DEVICE, (total_bytes,); an EV_DELIVER_S16 utterance at data + byte_offsets[b] goes straight into ev_flac as int16 */
+    const int64_t* byte_offsets;   /* (batch+1,) HOST, multiples of 16 */
+    const int64_t* n_samples;      /* (batch,) HOST: ceil(lens[b] up / down) */
+    const float*   peak;           /* (batch,) HOST */
+    const int64_t* clipped;        /* (batch,) HOST */
+} ev_deliver_result;
+/* wav / wav_is_i16 / lens / EV_FLAG_DEVICE_INPUTS as ev_limit (an ev_limit_result.wav, an ev_loudness_result.wav, an ev_stitch_result.wav or an
+ * ev_result.wav goes straight in).  seeds: a HOST array (B,) of uint32, or NULL = cfg.seed for every utterance; read only with dither.  Rejected
+ * before anything is launched (message naming the field or utterance; the previous result stays valid): a NULL h, wav, lens or out, a wrong
+ * struct_size, no ev_deliver_setup, B outside [1, 65535], lens[b] < 1, an utterance with more than EV_ALIGN_MAX_FRAMES * 256 output samples
+ * (ev_resample's limit).  The per-utterance figures come back to the host once, at the end of the call; no waveform is copied to the host.  The
+ * result lives in a workspace of its own and is complete when the call returns; it stays valid across every other entry point until the next
+ * ev_deliver or ev_destroy -- the contract of ev_limit_result. */
+int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const uint32_t* seeds, uint32_t flags, ev_deliver_result* out);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 
