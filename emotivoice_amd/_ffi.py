@@ -146,6 +146,19 @@ class ev_compare_result(C.Structure):
     ]
 
 
+EV_SCORE_MAX_FRAMES, EV_SCORE_MAX_CEPS, EV_SCORE_Q, EV_SCORE_CLAMP, EV_SCORE_LINEAR, EV_SCORE_WORKSPACE = 4096, 32, 65536, 1 << 27, 1, 1 << 30
+SCORE_INT_FIELDS = ("path_len", "n_diag", "n_a", "n_b", "n_vv", "n_vu", "n_uv", "n_uu")
+SCORE_FLOAT_FIELDS = ("sum_c", "sum_c2", "mcd_db", "f0_rmse_cents", "f0_bias_cents", "vuv_error", "warp")
+
+
+class ev_score_result(C.Structure):
+    _fields_ = ([("struct_size", C.c_uint32), ("batch", C.c_int32), ("n_ceps", C.c_int32), ("linear", C.c_int32), ("total_frames_a", C.c_int64),
+                 ("total_frames_b", C.c_int64), ("sum_dist", C.POINTER(C.c_int64))]
+                + [(k, C.POINTER(C.c_int32)) for k in SCORE_INT_FIELDS] + [(k, C.POINTER(C.c_double)) for k in SCORE_FLOAT_FIELDS]
+                + [(k, C.POINTER(C.c_int32)) for k in ("lens_a", "lens_b", "nonfinite_a", "nonfinite_b")]
+                + [("path_offsets", C.POINTER(C.c_int64)), ("path_a", C.c_void_p), ("path_b", C.c_void_p), ("cq_a", C.c_void_p), ("cq_b", C.c_void_p)])
+
+
 EV_FLAC_WRAP, EV_FLAC_CLAMP, EV_FLAC_MAX_SAMPLES = 0, 1, 1 << 30
 
 
@@ -308,6 +321,11 @@ SIGNATURES = {
     "ev_default_deliver_config": (None, [C.POINTER(ev_deliver_config)]),
     "ev_deliver_setup": (C.c_int, [_P, C.POINTER(ev_deliver_config)]),
     "ev_deliver": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_uint32, C.POINTER(ev_deliver_result)]),
+    "ev_score_design": (C.c_int, [C.c_int, C.c_int, _P]),      # host only
+    # lens is a HOST array; mel and f0_hz are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
+    "ev_score_load": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_uint32]),
+    "ev_score": (C.c_int, [_P, C.c_uint32, C.POINTER(ev_score_result)]),
+    "ev_score_plan": (C.c_int, [C.c_int, _P, _P, _P, _P]),      # host only
     "ev_set_forced_durations": (C.c_int, [_P, _P, C.c_int64]),
     "ev_vocoder": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.POINTER(ev_result)]),
     "ev_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_size_t]),

@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1290,6 +1290,255 @@ int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     reset_result(out);
     out->batch = B; out->total_bytes = total_bytes; out->data = d_data;
     out->byte_offsets = h->dlv.offs.data(); out->n_samples = h->dlv.n.data(); out->peak = h->dlv.peak.data(); out->clipped = h->dlv.clipped.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- objective scoring (include/evhip.h: ev_score)
+static_assert(EV_SCORE_MAX_FRAMES == SCORE_MAX_FRAMES && EV_SCORE_MAX_CEPS == SCORE_MAX_CEPS && EV_FEATURES_MAX_MELS == SCORE_MAX_MELS &&
+              EV_SCORE_CLAMP == SCORE_CLAMP && EV_SCORE_Q == 65536, "include/evhip.h states the limits of ev_score.hip");
+static int score_check_shape(ev_handle* h, const char* who, int n_mels, int n_ceps) {
+    if (n_mels < 1 || n_mels > EV_FEATURES_MAX_MELS) return fail(h, "%s: n_mels = %d outside [1, %d]", who, n_mels, EV_FEATURES_MAX_MELS);
+    const int top = std::min(n_mels - 1, EV_SCORE_MAX_CEPS);
+    if (n_ceps < 1 || n_ceps > top) return fail(h, "%s: n_ceps = %d outside [1, min(n_mels - 1, %d) = %d]", who, n_ceps, EV_SCORE_MAX_CEPS, top);
+    return 0;
+}
+
+int ev_score_design(int n_mels, int n_ceps, float* basis) {
+    if (!basis) return fail(nullptr, "ev_score_design: basis is NULL");
+    if (score_check_shape(nullptr, "ev_score_design", n_mels, n_ceps)) return -1;
+    const double M = (double)n_mels, g = sqrt(2.0 / M);
+    for (int d = 1; d <= n_ceps; ++d)
+        for (int m = 0; m < n_mels; ++m) basis[(size_t)(d - 1) * n_mels + m] = (float)(g * cos(M_PI * (double)d * ((double)m + 0.5) / M));
+    return 0;
+}
+
+// the words (uint32) of a pair's distances and of its decisions, in the order the warp visits them (ev_kernels.h)
+static int64_t score_dist_words(int Ta, int Tb) { return ((int64_t)Tb + 63) * score_run(Ta) * 64; }
+static int64_t score_dec_total(int Ta, int Tb) { return ((int64_t)Tb + 63) * score_dec_words(score_run(Ta)) * 64; }
+// consecutive pairs form a pass while the distances and decisions of all of them fit EV_SCORE_WORKSPACE together; the lengths are validated
+static int score_plan(int B, const int32_t* la, const int32_t* lb, int32_t* pass_of, int64_t* pass_bytes) {
+    int n = 0;
+    int64_t bytes = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t need = 4 * (score_dist_words(la[b], lb[b]) + score_dec_total(la[b], lb[b]));
+        if (n == 0 || bytes + need > EV_SCORE_WORKSPACE) { ++n; bytes = 0; }
+        bytes += need;
+        pass_of[b] = n - 1; pass_bytes[n - 1] = bytes;
+    }
+    return n;
+}
+
+int ev_score_plan(int B, const int32_t* lens_a, const int32_t* lens_b, int32_t* pass_of, int64_t* pass_bytes) {
+    if (!lens_a || !lens_b || !pass_of || !pass_bytes) return fail(nullptr, "ev_score_plan: NULL argument");
+    if (B < 1 || B > 65535) return fail(nullptr, "ev_score_plan: B = %d outside [1, 65535]", B);
+    for (int b = 0; b < B; ++b) {
+        if (lens_a[b] < 1 || lens_a[b] > EV_SCORE_MAX_FRAMES) return fail(nullptr, "ev_score_plan: lens_a[%d] = %d outside [1, %d]", b, lens_a[b], EV_SCORE_MAX_FRAMES);
+        if (lens_b[b] < 1 || lens_b[b] > EV_SCORE_MAX_FRAMES) return fail(nullptr, "ev_score_plan: lens_b[%d] = %d outside [1, %d]", b, lens_b[b], EV_SCORE_MAX_FRAMES);
+    }
+    return score_plan(B, lens_a, lens_b, pass_of, pass_bytes);
+}
+
+int ev_score_load(ev_handle* h, int side, int B, int n_mels, int n_ceps, const float* mel, const int32_t* lens, const float* f0_hz, uint32_t flags) {
+    if (!mel) return fail(h, "ev_score_load: mel is NULL");
+    if (!lens) return fail(h, "ev_score_load: lens is NULL");
+    if (side != 0 && side != 1) return fail(h, "ev_score_load: side = %d is not 0 (a, under test) or 1 (b, the yardstick)", side);
+    if (B < 1 || B > 65535) return fail(h, "ev_score_load: B = %d outside [1, 65535]", B);
+    if (score_check_shape(h, "ev_score_load", n_mels, n_ceps)) return -1;
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1 || lens[b] > EV_SCORE_MAX_FRAMES) return fail(h, "ev_score_load: lens[%d] = %d outside [1, %d]", b, lens[b], EV_SCORE_MAX_FRAMES);
+    if (!h) return fail(nullptr, "ev_score_load: h is NULL");
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
+    const int M = n_mels, D = n_ceps;
+    std::vector<int64_t> offs((size_t)B + 1, 0);
+    std::vector<ScoreTile> tiles; std::vector<ScoreSig> sigs((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        offs[(size_t)b + 1] = offs[(size_t)b] + lens[b];
+        sigs[(size_t)b] = ScoreSig{offs[(size_t)b], lens[b], 0};
+        for (int t0 = 0; t0 < lens[b]; t0 += SCORE_TF) tiles.push_back(ScoreTile{offs[(size_t)b] * M, offs[(size_t)b], lens[b], t0, b, 0});
+    }
+    const int64_t total = offs[(size_t)B];
+    std::vector<float> basis((size_t)D * M);
+    (void)ev_score_design(M, D, basis.data());
+    ScoreSide& sd = h->score.side[side];
+    if (call_begin(h)) return -1;
+    int32_t *d_cq = nullptr, *d_bad = nullptr, *d_nonf = nullptr; float *d_f0 = nullptr, *d_basis = nullptr, *d_mel = nullptr;
+    ScoreTile* d_tiles = nullptr; ScoreSig* d_sigs = nullptr;
+    sd.loaded = false;      // from here on the side's arena is rewritten
+    if (arena_plan(h, side ? ARENA_SCORE_B : ARENA_SCORE_A, [&](ArenaPlan& ap) {
+        d_cq = ap.arr<int32_t>((size_t)total * D); d_f0 = f0_hz ? ap.arr<float>((size_t)total) : nullptr;
+        d_bad = ap.arr<int32_t>((size_t)total); d_nonf = ap.arr<int32_t>((size_t)B); d_basis = ap.arr<float>((size_t)D * M);
+        d_tiles = ap.arr<ScoreTile>(tiles.size()); d_sigs = ap.arr<ScoreSig>((size_t)B);
+        d_mel = dev_in ? nullptr : ap.arr<float>((size_t)total * M);
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_mel, mel, (size_t)total * M * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (f0_hz) HIPCHK(h, hipMemcpyAsync(d_f0, f0_hz, (size_t)total * sizeof(float), dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_basis, basis) || upload(h, d_tiles, tiles) || upload(h, d_sigs, sigs)) return -1;
+    region_begin(h, "total");
+    {
+        KScope ks(h, "score_cepstra", 2.0 * (double)total * M * D, 4.0 * (double)total * (M + D + 1));
+        if (launch_score_cepstra(dev_in ? mel : d_mel, d_tiles, (int64_t)tiles.size(), d_basis, M, D, d_cq, d_bad, h->stream))
+            return fail(h, "ev_score_load: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "score_count", 0.0, 4.0 * (double)total);
+        launch_score_count(d_bad, d_sigs, B, d_nonf, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<int32_t> nonf((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(nonf.data(), d_nonf, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    sd.B = B; sd.n_mels = M; sd.n_ceps = D; sd.total = total; sd.cq = d_cq; sd.f0 = d_f0;
+    sd.lens.assign(lens, lens + B); sd.nonf.swap(nonf); sd.offs.swap(offs);
+    sd.loaded = true;
+    return 0;
+}
+
+int ev_score(ev_handle* h, uint32_t flags, ev_score_result* out) {
+    if (!out) return fail(h, "ev_score: out is NULL");
+    if (check_struct_size(h, "ev_score", "out->struct_size", out->struct_size, "ev_score_result", sizeof(ev_score_result))) return -1;
+    if (!h) return fail(nullptr, "ev_score: h is NULL");
+    const ScoreSide &sa = h->score.side[0], &sb = h->score.side[1];
+    if (!sa.loaded) return fail(h, "ev_score: side 0 (a) is not loaded: call ev_score_load(h, 0, ...)");
+    if (!sb.loaded) return fail(h, "ev_score: side 1 (b) is not loaded: call ev_score_load(h, 1, ...)");
+    if (sa.B != sb.B) return fail(h, "ev_score: the sides differ in B: %d signals on side 0, %d on side 1", sa.B, sb.B);
+    if (sa.n_mels != sb.n_mels) return fail(h, "ev_score: the sides differ in n_mels: %d on side 0, %d on side 1", sa.n_mels, sb.n_mels);
+    if (sa.n_ceps != sb.n_ceps) return fail(h, "ev_score: the sides differ in n_ceps: %d on side 0, %d on side 1", sa.n_ceps, sb.n_ceps);
+    const int B = sa.B, D = sa.n_ceps;
+    const bool linear = (flags & EV_SCORE_LINEAR) != 0;
+    const bool f0 = sa.f0 && sb.f0;
+    // the pair table; for a warp also the passes (score_plan) and, per pass and run, the pairs of a launch
+    std::vector<ScorePair> pairs((size_t)B); std::vector<int32_t> sel, pass_of((size_t)B, 0); std::vector<int64_t> pass_bytes((size_t)B, 0);
+    std::vector<int64_t> poffs((size_t)B + 1, 0);
+    int64_t rev_total = 0, path_cap = 0, ws_words = 0;
+    const int n_passes = linear ? 0 : score_plan(B, sa.lens.data(), sb.lens.data(), pass_of.data(), pass_bytes.data());
+    for (int q = 0; q < n_passes; ++q) {
+        if (pass_bytes[(size_t)q] > EV_SCORE_WORKSPACE) return fail(h, "ev_score: pass %d plans %lld bytes of workspace, more than EV_SCORE_WORKSPACE", q, (long long)pass_bytes[(size_t)q]);
+        ws_words = std::max(ws_words, pass_bytes[(size_t)q] / 4);
+    }
+    {
+        std::vector<int64_t> dist_n((size_t)n_passes + 1, 0), dec_n((size_t)n_passes + 1, 0);
+        for (int b = 0; b < B; ++b) {
+            ScorePair& p = pairs[(size_t)b];
+            p = ScorePair{};
+            p.fa_off = sa.offs[(size_t)b]; p.fb_off = sb.offs[(size_t)b]; p.Ta = sa.lens[(size_t)b]; p.Tb = sb.lens[(size_t)b];
+            p.rm = score_run(p.Ta);
+            if (linear) {
+                p.K = std::min(p.Ta, p.Tb); p.path_off = path_cap; path_cap += p.K;
+                poffs[(size_t)b + 1] = path_cap;
+                continue;
+            }
+            const size_t q = (size_t)pass_of[(size_t)b];
+            p.dist_off = dist_n[q]; p.dec_off = dec_n[q];
+            dist_n[q] += score_dist_words(p.Ta, p.Tb); dec_n[q] += score_dec_total(p.Ta, p.Tb);
+            p.rev_off = rev_total; rev_total += 2 * ((int64_t)p.Ta + p.Tb - 1);
+            path_cap += (int64_t)p.Ta + p.Tb - 1;
+        }
+        if (!linear) for (int b = 0; b < B; ++b) pairs[(size_t)b].dec_off += dist_n[(size_t)pass_of[(size_t)b]];      // a pass' decisions lie behind its distances
+    }
+    struct Launch { int pass, rm, first, n, max_steps; double cells; };      // the pairs of one pass with one run, sel[first .. first + n)
+    std::vector<Launch> launches;
+    for (int q = 0, b0 = 0; q < n_passes; ++q) {
+        int b1 = b0;
+        while (b1 < B && pass_of[(size_t)b1] == q) ++b1;
+        for (int rm = 1; rm <= 64; rm *= 2) {
+            Launch l{q, rm, (int)sel.size(), 0, 0, 0.0};
+            for (int b = b0; b < b1; ++b) {
+                const ScorePair& p = pairs[(size_t)b];
+                if (p.rm != rm) continue;
+                sel.push_back(b);
+                l.n += 1; l.max_steps = std::max(l.max_steps, p.Tb + 63); l.cells += (double)p.Ta * p.Tb;
+            }
+            if (l.n) launches.push_back(l);
+        }
+        b0 = b1;
+    }
+    if (call_begin(h)) return -1;
+    ScorePair* d_pairs = nullptr; int32_t *d_sel = nullptr, *d_rev = nullptr, *d_cqa = nullptr, *d_cqb = nullptr, *d_pa = nullptr, *d_pb = nullptr;
+    ScoreWarp* d_warp = nullptr; ScoreSums* d_sums = nullptr; uint32_t* d_ws = nullptr;
+    if (arena_plan(h, ARENA_SCORE, [&](ArenaPlan& ap) {
+        d_pairs = ap.arr<ScorePair>((size_t)B); d_sel = ap.arr<int32_t>((size_t)B); d_warp = ap.arr<ScoreWarp>((size_t)B); d_sums = ap.arr<ScoreSums>((size_t)B);
+        d_cqa = ap.arr<int32_t>((size_t)sa.total * D); d_cqb = ap.arr<int32_t>((size_t)sb.total * D);
+        d_pa = ap.arr<int32_t>((size_t)path_cap); d_pb = ap.arr<int32_t>((size_t)path_cap);
+        d_rev = ap.arr<int32_t>((size_t)rev_total); d_ws = ap.arr<uint32_t>((size_t)ws_words);
+    })) return -1;
+    HIPCHK(h, hipMemcpyAsync(d_cqa, sa.cq, (size_t)sa.total * D * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_cqb, sb.cq, (size_t)sb.total * D * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    if (upload(h, d_pairs, pairs)) return -1;
+    if (!sel.empty() && upload(h, d_sel, sel)) return -1;
+    region_begin(h, "total");
+    std::vector<ScoreWarp> warp((size_t)B);
+    if (!linear) {
+        // the stream orders the passes, which reuse the workspace; inside a pass every run's distances, then every run's warp
+        for (size_t l0 = 0; l0 < launches.size();) {
+            size_t l1 = l0;
+            while (l1 < launches.size() && launches[l1].pass == launches[l0].pass) ++l1;
+            for (size_t li = l0; li < l1; ++li) {
+                const Launch& l = launches[li];
+                KScope ks(h, "score_dist", 3.0 * l.cells * D, 4.0 * l.cells);
+                if (launch_score_dist(d_cqa, d_cqb, D, d_pairs, d_sel + l.first, l.n, l.rm, l.max_steps, d_ws, h->stream))
+                    return fail(h, "ev_score: the distance kernel does not build this shape");
+            }
+            HIPCHK(h, hipGetLastError());
+            for (size_t li = l0; li < l1; ++li) {
+                const Launch& l = launches[li];
+                KScope ks(h, "score_dtw", 8.0 * l.cells, 4.5 * l.cells);
+                if (launch_score_dtw(l.rm, d_pairs, d_sel + l.first, l.n, d_ws, d_ws, d_rev, d_warp, h->stream))
+                    return fail(h, "ev_score: the warp kernel does not build this shape");
+            }
+            HIPCHK(h, hipGetLastError());
+            l0 = l1;
+        }
+        HIPCHK(h, hipMemcpyAsync(warp.data(), d_warp, (size_t)B * sizeof(ScoreWarp), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // the paths' lengths lay the result out
+        int64_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            ScorePair& p = pairs[(size_t)b];
+            if (warp[(size_t)b].K < std::max(p.Ta, p.Tb) || warp[(size_t)b].K > p.Ta + p.Tb - 1) {
+                (void)call_end(h);      // the call is closed; its workspace has been rewritten, so no result is valid after this failure
+                return fail(h, "ev_score: pair %d: the backtrack returned a path of %d cells for %d x %d frames", b, warp[(size_t)b].K, p.Ta, p.Tb);
+            }
+            p.K = warp[(size_t)b].K; p.path_off = off; off += p.K;
+            poffs[(size_t)b + 1] = off;
+        }
+        if (upload(h, d_pairs, pairs)) return -1;
+    }
+    {
+        KScope ks(h, "score_sums", 0.0, 16.0 * (double)poffs[(size_t)B]);
+        launch_score_sums(d_pairs, B, linear ? 1 : 0, d_cqa, d_cqb, D, d_rev, d_warp, f0 ? sa.f0 : nullptr, f0 ? sb.f0 : nullptr, d_pa, d_pb, d_sums, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<ScoreSums> sums((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(sums.data(), d_sums, (size_t)B * sizeof(ScoreSums), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    // from here on nothing fails: the previous result is replaced
+    ScoreState& st = h->score;
+    const size_t nb = (size_t)B;
+    st.sum_dist.resize(nb); st.K.resize(nb); st.sum_c.resize(nb); st.sum_c2.resize(nb); st.mcd.resize(nb); st.rmse.resize(nb); st.bias.resize(nb);
+    st.vuv.resize(nb); st.warp.resize(nb);
+    for (auto& c : st.cnt) c.resize(nb);
+    for (size_t b = 0; b < nb; ++b) {
+        const ScoreSums& g = sums[b];
+        const int K = pairs[b].K;
+        const int32_t cnt[7] = {g.n_diag, g.n_a, g.n_b, g.n_vv, g.n_vu, g.n_uv, g.n_uu};
+        for (int k = 0; k < 7; ++k) st.cnt[k][b] = cnt[k];
+        st.sum_dist[b] = g.sum_dist; st.K[b] = K; st.sum_c[b] = g.sum_c; st.sum_c2[b] = g.sum_c2;
+        st.mcd[b] = (10.0 / log(10.0)) * sqrt(2.0) * ((double)g.sum_dist / 65536.0) / (double)K;
+        st.rmse[b] = g.n_vv ? sqrt(g.sum_c2 / (double)g.n_vv) : (double)NAN;
+        st.bias[b] = g.n_vv ? g.sum_c / (double)g.n_vv : (double)NAN;
+        st.vuv[b] = (double)(g.n_vu + g.n_uv) / (double)K;
+        st.warp[b] = (double)(g.n_a + g.n_b) / (double)K;
+    }
+    st.lens_a = sa.lens; st.lens_b = sb.lens; st.nonf_a = sa.nonf; st.nonf_b = sb.nonf; st.path_offs.swap(poffs);
+    reset_result(out);
+    out->batch = B; out->n_ceps = D; out->linear = linear ? 1 : 0; out->total_frames_a = sa.total; out->total_frames_b = sb.total;
+    out->sum_dist = st.sum_dist.data(); out->path_len = st.K.data();
+    out->n_diag = st.cnt[0].data(); out->n_a = st.cnt[1].data(); out->n_b = st.cnt[2].data();
+    out->n_vv = st.cnt[3].data(); out->n_vu = st.cnt[4].data(); out->n_uv = st.cnt[5].data(); out->n_uu = st.cnt[6].data();
+    out->sum_c = st.sum_c.data(); out->sum_c2 = st.sum_c2.data(); out->mcd_db = st.mcd.data(); out->f0_rmse_cents = st.rmse.data();
+    out->f0_bias_cents = st.bias.data(); out->vuv_error = st.vuv.data(); out->warp = st.warp.data();
+    out->lens_a = st.lens_a.data(); out->lens_b = st.lens_b.data(); out->nonfinite_a = st.nonf_a.data(); out->nonfinite_b = st.nonf_b.data();
+    out->path_offsets = st.path_offs.data(); out->path_a = d_pa; out->path_b = d_pb; out->cq_a = d_cqa; out->cq_b = d_cqb;
     return 0;
 }
 

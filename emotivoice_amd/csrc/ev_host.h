@@ -37,6 +37,9 @@ enum Arena {
     ARENA_LOUDNESS,    // ev_loudness (likewise)
     ARENA_LIMIT,       // ev_limit (likewise)
     ARENA_DELIVER,     // ev_deliver (likewise)
+    ARENA_SCORE_A,     // ev_score_load(0): the side's integer cepstra and F0 track, until the side is replaced
+    ARENA_SCORE_B,     // ev_score_load(1) (likewise)
+    ARENA_SCORE,       // ev_score (like ARENA_ALIGN; the distance and decision workspaces too)
     ARENA_COUNT
 };
 
@@ -87,6 +90,16 @@ struct DeliverState {       // ev_deliver.  tab: the phase-major table on the de
     ev_deliver_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; float* tab = nullptr;
     std::vector<int64_t> offs, n, clipped; std::vector<float> peak;
 };
+struct ScoreSide {       // a side of ev_score as ev_score_load left it: cq (total, D) and f0 (total,) or null live in the side's arena
+    bool loaded = false; int B = 0, n_mels = 0, n_ceps = 0; int64_t total = 0;
+    const int32_t* cq = nullptr; const float* f0 = nullptr;
+    std::vector<int32_t> lens, nonf; std::vector<int64_t> offs;
+};
+struct ScoreState {       // ev_score: the two sides and the host halves of the last result
+    ScoreSide side[2];
+    std::vector<int64_t> sum_dist, path_offs; std::vector<int32_t> K, cnt[7], lens_a, lens_b, nonf_a, nonf_b;
+    std::vector<double> sum_c, sum_c2, mcd, rmse, bias, vuv, warp;
+};
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
 
 }  // namespace evh
@@ -122,7 +135,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

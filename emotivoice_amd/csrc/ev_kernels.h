@@ -417,4 +417,36 @@ int launch_limit_peak(const void* wav, int is16, const float* gains, const Limit
 int launch_limit_apply(const void* wav, int is16, const float* gains, const LimitTile* tiles, int64_t n_tiles, const float* r, const double* win, int L,
                        int Hd, float* out, int16_t* out_i16, float* s_out, LimitApplyOut* outs, hipStream_t s);
 
+// ev_score (ev_score.hip): log-mel -> integer cepstra (one side at a time), then per pair the local distances, the time warp and the sums along
+// its path.  The distances and the 2-bit decisions are stored in the order the warp's wavefront visits them: lane l of the wave owns rows
+// [l * rm, (l + 1) * rm) of a and works on column s - l at step s, so cell (i, j) lives at step s = j + i / rm, run index r = i % rm, lane l = i / rm:
+// dist[(s * rm + r) * 64 + l] and bit pair r % 16 of dec[(s * W + r / 16) * 64 + l], W = score_dec_words(rm).  rm is the pair's own (score_run).
+constexpr int SCORE_MAX_FRAMES = 4096, SCORE_MAX_CEPS = 32, SCORE_MAX_MELS = 128, SCORE_TF = 64, SCORE_CLAMP = 1 << 27;
+constexpr int score_run(int Ta) { int rm = 1; while (rm * 64 < Ta) rm *= 2; return rm; }      // 1 .. 64 for Ta <= SCORE_MAX_FRAMES
+constexpr int score_dec_words(int rm) { return rm > 16 ? rm / 16 : 1; }
+struct ScoreTile { int64_t mel_off, frm_off; int32_t T, t0, sig, pad; };      // the signal's first mel element / packed frame, its frames, the tile's first frame, the signal
+struct ScoreSig { int64_t frm_off; int32_t T, pad; };
+struct ScorePair {
+    int64_t fa_off, fb_off;         // first packed frame of the pair's signals
+    int64_t dist_off, dec_off;      // into this pass' workspace (uint32 elements): the pass' distances, then its decisions
+    int64_t rev_off;                // the backtrack's path, written from the end of Ta + Tb - 1 slots
+    int64_t path_off;               // the finished path (score_sums)
+    int32_t Ta, Tb, rm, K;          // K: known for a linear score, read back from ScoreWarp otherwise
+};
+struct ScoreWarp { int64_t sum_dist; int32_t K, pad; };
+struct ScoreSums { int64_t sum_dist; double sum_c, sum_c2; int32_t n_diag, n_a, n_b, n_vv, n_vu, n_uv, n_uu, pad; };
+// basis: device (D, M) fp32; bad: (total_frames,) 0 / 1, a frame with a non-finite mel value; cq: (total_frames, D)
+int launch_score_cepstra(const float* mel, const ScoreTile* tiles, int64_t n_tiles, const float* basis, int M, int D, int32_t* cq, int32_t* bad, hipStream_t s);
+void launch_score_count(const int32_t* bad, const ScoreSig* sigs, int B, int32_t* nonfinite /* (B,) */, hipStream_t s);
+// sel: device (n,) indices of the pairs of one pass whose run is rm; max_steps over them (steps = Tb + 63).  dist and dec are one workspace:
+// a pair's dist_off and dec_off are both counted from its start
+int launch_score_dist(const int32_t* cqa, const int32_t* cqb, int D, const ScorePair* pairs, const int32_t* sel, int n, int rm, int max_steps, uint32_t* dist,
+                      hipStream_t s);
+// sel: device (n,) indices of the pairs whose run is rm
+int launch_score_dtw(int rm, const ScorePair* pairs, const int32_t* sel, int n, const uint32_t* dist, uint32_t* dec, int32_t* rev, ScoreWarp* warp, hipStream_t s);
+// f0a / f0b: packed as the frames, both or neither; linear: the path is (k, k), k < K, and the distances are computed here; otherwise the path is
+// read from rev and sum_dist from warp
+void launch_score_sums(const ScorePair* pairs, int B, int linear, const int32_t* cqa, const int32_t* cqb, int D, const int32_t* rev, const ScoreWarp* warp,
+                       const float* f0a, const float* f0b, int32_t* path_a, int32_t* path_b, ScoreSums* out, hipStream_t s);
+
 }  // namespace ev

@@ -1,5 +1,5 @@
 """The audio utilities of the libevhip.so handle (csrc/ev_audio.cpp): ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac,
-ev_loudness, ev_limit and ev_deliver as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
+ev_loudness, ev_limit, ev_deliver and ev_score as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
 handle, ``_check`` and ``d2h`` are its own."""
 from __future__ import annotations
 
@@ -411,3 +411,65 @@ class EVAudio:
             self.deliver_setup(dc, sample_rate)
         flat, is16, lens = pack_segments(wavs)
         return self.deliver_to_numpy(self.deliver_raw(len(lens), flat.ctypes.data, is16, lens, seeds), dc)
+
+    # -- objective scoring (ev_score): MCD, F0 error and voiced / unvoiced error of a signal against a yardstick of another length, on the device
+    def score_load_raw(self, side: int, B: int, n_mels: int, n_ceps: int, mel_ptr: int, lens: np.ndarray, f0_ptr: int = 0, flags: int = 0) -> None:
+        """ev_score_load (include/evhip.h): side 0 = a (under test), 1 = b (the yardstick).  mel_ptr ((n_mels, T_b) per signal, back to back) and
+        f0_ptr (Hz, 0 = none) are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS -- an ev_features_result.mel and an
+        ev_pitch_result.f0_hz go straight in; lens is a host array of frames.  The side stays loaded until it is replaced."""
+        ln = np.ascontiguousarray(lens, np.int32)
+        if ln.size < B:          # the library reads B entries; it rejects B < 1 itself
+            raise ValueError("lens must have B = %d entries" % B)
+        self._check(self._lib.ev_score_load(self._h, int(side), B, int(n_mels), int(n_ceps), C.c_void_p(mel_ptr), _ptr(ln),
+                                            C.c_void_p(f0_ptr) if f0_ptr else None, flags))
+
+    def score_raw(self, linear: bool = False) -> _ffi.ev_score_result:
+        """ev_score on the two loaded sides.  The returned struct's device arrays and host arrays stay valid until the next score call on this engine."""
+        return self._call("score", _ffi.EV_SCORE_LINEAR if linear else 0)
+
+    def score_to_numpy(self, res: _ffi.ev_score_result, with_paths: bool = True, with_cq: bool = False) -> Dict[str, object]:
+        """Copies of the result's host arrays; with ``with_paths`` one D2H copy of each path array (path_list: one (K_b, 2) int32 array per pair, the
+        frame of a and the frame of b); with ``with_cq`` the integer cepstra of both sides (cq_a_list / cq_b_list: (T_b, n_ceps) each)."""
+        B, D = res.batch, res.n_ceps
+        out: Dict[str, object] = dict(batch=B, n_ceps=D, linear=bool(res.linear), sum_dist=host_array(res.sum_dist, B, np.int64))
+        for k in _ffi.SCORE_INT_FIELDS + ("lens_a", "lens_b", "nonfinite_a", "nonfinite_b"):
+            out[k] = host_array(getattr(res, k), B, np.int32)
+        for k in _ffi.SCORE_FLOAT_FIELDS:
+            out[k] = host_array(getattr(res, k), B, np.float64)
+        offs = out["path_offsets"] = host_array(res.path_offsets, B + 1, np.int64)
+        if with_paths:
+            pa, pb = self.d2h(res.path_a, (int(offs[-1]),), np.int32), self.d2h(res.path_b, (int(offs[-1]),), np.int32)
+            out["path_list"] = [np.stack([x, y], 1) for x, y in zip(cut(pa, offs), cut(pb, offs))]
+        if with_cq:
+            for side, total, lens in (("a", res.total_frames_a, out["lens_a"]), ("b", res.total_frames_b, out["lens_b"])):
+                cq = self.d2h(getattr(res, "cq_" + side), (int(total) * D,), np.int32)
+                out["cq_%s_list" % side] = [c.reshape(-1, D) for c in cut(cq, offsets_of(lens) * D)]
+        return out
+
+    def score_load(self, side: int, feats: Sequence[np.ndarray], f0=None, n_ceps: int = 13) -> None:
+        """Host arrays into one side: feats, one (n_mels, T_b) natural-log mel per signal (what features() returns); f0: one (T_b,) track in Hz per
+        signal (0 or non-finite = unvoiced, what pitch() returns as f0_list) or None."""
+        if not len(feats):
+            raise ValueError("feats must hold at least one signal")
+        mels = [np.asarray(m, np.float32) for m in feats]
+        n_mels = mels[0].shape[0]
+        if any(m.ndim != 2 or m.shape[0] != n_mels for m in mels):
+            raise ValueError("every entry of feats must be (n_mels, T) with the same n_mels")
+        lens = np.array([m.shape[1] for m in mels], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in mels]))
+        f0_flat = None
+        if f0 is not None:
+            if len(f0) != len(mels) or any(np.asarray(t).shape != (n,) for t, n in zip(f0, lens)):
+                raise ValueError("f0 must hold one (T_b,) track per signal")
+            f0_flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float32) for t in f0]))
+        self.score_load_raw(side, len(mels), n_mels, n_ceps, flat.ctypes.data, lens, f0_flat.ctypes.data if f0_flat is not None else 0)
+
+    def score(self, feats_a: Sequence[np.ndarray], feats_b: Sequence[np.ndarray], f0_a=None, f0_b=None, linear: bool = False, n_ceps: int = 13,
+              with_cq: bool = False) -> Dict[str, object]:
+        """Host features of a (under test) against b (the yardstick), pair by pair: mel-cepstral distortion along the DTW path (``linear``: along
+        (k, k)), and with both F0 tracks the F0 error in cents and the voiced / unvoiced error rate.  Returns per-pair numpy arrays (sum_dist,
+        path_len, n_diag, n_a, n_b, n_vv, n_vu, n_uv, n_uu, sum_c, sum_c2, mcd_db, f0_rmse_cents, f0_bias_cents, vuv_error, warp, nonfinite_a,
+        nonfinite_b) and path_list.  An MFCC-style MCD on the engine's own log-mel: the figures compare among themselves only.  Needs no weights."""
+        self.score_load(0, feats_a, f0_a, n_ceps)
+        self.score_load(1, feats_b, f0_b, n_ceps)
+        return self.score_to_numpy(self.score_raw(linear), with_cq=with_cq)

@@ -912,6 +912,104 @@ typedef struct ev_deliver_result {
  * ev_deliver or ev_destroy -- the contract of ev_limit_result. */
 int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const uint32_t* seeds, uint32_t flags, ev_deliver_result* out);
 
+/* Objective scoring (ev_score): how close a signal a (under test: a synthesised utterance) is to a signal b (the yardstick: a recording of the
+ * same sentence) when the two differ in length and timing -- mel-cepstral distortion, F0 error in cents and the voiced / unvoiced error rate
+ * along a dynamic-time-warping path, on the device.  ev_compare is the measure for signals of equal length; with EV_SCORE_LINEAR the same scores
+ * are taken without a warp (an mx against a strict rendering with forced durations).  The reference has no such stage.  The scores are specified on
+ * integers, so that a restatement in numpy and Python integers reproduces every decision and every sum; nothing depends on how a square root or a
+ * cosine is rounded.  This is an MFCC-style MCD on the engine's own log-mel (ev_features), NOT SPTK's warped mel-cepstrum: the figures compare
+ * among themselves only, and nobody has set them against a published MCD.
+ * The calls are two-step because an ev_features_result is valid only until the next ev_features: ev_score_load copies what scoring needs of one
+ * side (the integer cepstra, the F0 track) into a workspace of ev_score's own, ev_score scores the two loaded sides pair by pair.
+ *   1 Basis.  basis[d-1][m] = (float)(sqrt(2.0 / M) * cos(pi * d * (m + 0.5) / M)), d = 1 .. D = n_ceps, m = 0 .. M-1 = n_mels - 1, evaluated in fp64
+ *     (the cosine's argument as ((pi * d) * (m + 0.5)) / M) and rounded once: rows 1 .. D of the orthonormal DCT-II; c0 is left out.
+ *     ev_score_design writes the table, ev_score_load uses the same one.
+ *   2 Integer cepstra.  mel is packed as ev_features_result.mel: per signal (n_mels, T) row-major, fp32 natural-log mel.  For frame t and
+ *     coefficient d: x = sum_m (double)mel[m][t] * (double)basis[d-1][m], m ascending from x = +0.0; each product is exact in fp64, each addition
+ *     one fp64 rounding, no product fused with a sum.  cq[t][d-1] = clamp(llrint(x * 65536.0), -2^27, 2^27), ties to even; a non-finite x gives
+ *     cq = 0.  A frame that holds a non-finite mel value counts once in nonfinite_a[b] / nonfinite_b[b].
+ *   3 Local distance.  For frame i of a and frame j of b: s = sum_d (int64)(cqa[i][d] - cqb[j][d])^2 (differences below 2^28, so s < 2^61 for
+ *     D <= 32: exact); dist(i, j) = the largest integer r with r * r <= s.
+ *   4 DTW.  A[0][0] = dist(0, 0); A[i][j] = dist(i, j) + min(A[i-1][j-1], A[i-1][j], A[i][j-1]), cells outside the grid infinite.  Values stay
+ *     below 2^44.  The predecessor of (i, j): the diagonal (i-1, j-1) if A[i-1][j-1] <= A[i-1][j] and A[i-1][j-1] <= A[i][j-1]; otherwise
+ *     (i-1, j), an "a-step", if A[i-1][j] <= A[i][j-1]; otherwise (i, j-1), a "b-step".  The path runs from (Ta-1, Tb-1) back to (0, 0) and is
+ *     reported ascending, K cells.  With EV_SCORE_LINEAR there is no DP: K = min(Ta, Tb), the cells are (k, k).
+ *   5 Sums along the path.  sum_dist (int64) = the sum of dist over the path's cells; without EV_SCORE_LINEAR that is A[Ta-1][Tb-1].  n_diag, n_a,
+ *     n_b: the step counts, K = 1 + n_diag + n_a + n_b.  With f0_hz loaded on both sides a frame is voiced iff its f0 is finite and > 0; n_vv,
+ *     n_vu, n_uv, n_uu (a's state first) sum to K; over the vv cells c = 1200 * log2((double)fa / (double)fb), and sum_c, sum_c2 (of c * c) are
+ *     fp64 sums from +0.0 in ascending path order.  The counts are exact; log2 is not specified bit for bit, so the two sums are specified to
+ *     1e-9 relative (sum_c: 1e-9 * sum |c|).  With f0_hz NULL on either side the four counts are 0 and the sums +0.0.
+ *   6 Ratios (host, C double, in the order written):
+ *     mcd_db = (10 / ln 10) * sqrt(2) * ((double)sum_dist / 65536) / K
+ *     f0_rmse_cents = sqrt(sum_c2 / n_vv), f0_bias_cents = sum_c / n_vv; both NaN when n_vv = 0
+ *     vuv_error = (n_vu + n_uv) / K;  warp = (n_a + n_b) / K
+ * No atomics, no synchronisation between blocks; every loop runs over a length the host has validated.  The distance and decision workspaces
+ * together stay within EV_SCORE_WORKSPACE bytes: a batch that needs more runs in passes of whole pairs.  Every decision is an integer one, so a
+ * pair gives the same bits alone or anywhere in a batch, from host or device memory, on every precision mode.  Needs no weights and no
+ * ev_features_setup. */
+#define EV_SCORE_MAX_FRAMES 4096     /* frames per signal (65 s at 16 kHz / 256) */
+#define EV_SCORE_MAX_CEPS   32
+#define EV_SCORE_Q          65536    /* cepstra are held as integers in units of 1 / 65536 nat */
+#define EV_SCORE_CLAMP      (1 << 27)
+#define EV_SCORE_LINEAR     0x1u     /* flag of ev_score: no warp, path (k, k), k < min(Ta, Tb) */
+#define EV_SCORE_WORKSPACE  (1ll << 30)
+typedef struct ev_score_result {
+    uint32_t struct_size;          /* sizeof(ev_score_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int32_t  n_ceps;
+    int32_t  linear;               /* 1: scored with EV_SCORE_LINEAR */
+    int64_t  total_frames_a;       /* lens_a[0] + .. + lens_a[batch - 1] */
+    int64_t  total_frames_b;
+    const int64_t* sum_dist;       /* every array: HOST, (batch,) unless stated */
+    const int32_t* path_len;       /* K */
+    const int32_t* n_diag;
+    const int32_t* n_a;
+    const int32_t* n_b;
+    const int32_t* n_vv;
+    const int32_t* n_vu;
+    const int32_t* n_uv;
+    const int32_t* n_uu;
+    const double*  sum_c;
+    const double*  sum_c2;
+    const double*  mcd_db;
+    const double*  f0_rmse_cents;
+    const double*  f0_bias_cents;
+    const double*  vuv_error;
+    const double*  warp;
+    const int32_t* lens_a;
+    const int32_t* lens_b;
+    const int32_t* nonfinite_a;
+    const int32_t* nonfinite_b;
+    const int64_t* path_offsets;   /* (batch+1,) HOST: pair b owns path entries path_offsets[b] .. path_offsets[b + 1], path_len[b] of them */
+    const int32_t* path_a;         /* DEVICE, (path_offsets[batch],): the path's frames of a, ascending */
+    const int32_t* path_b;         /* DEVICE, likewise for b */
+    const int32_t* cq_a;           /* DEVICE, (total_frames_a, n_ceps): step 2 of side a, signal after signal */
+    const int32_t* cq_b;           /* DEVICE, (total_frames_b, n_ceps) */
+} ev_score_result;
+/* HOST, needs no handle: basis (n_ceps, n_mels) row-major, step 1.  0, or -1 for a NULL basis, n_mels outside [1, EV_FEATURES_MAX_MELS] or n_ceps
+ * outside [1, min(n_mels - 1, EV_SCORE_MAX_CEPS)]. */
+int ev_score_design(int n_mels, int n_ceps, float* basis);
+/* Loads side 0 (a, under test) or 1 (b, the yardstick): steps 1 and 2 of B signals and a copy of their F0 tracks.  mel as step 2 states; lens[b] frames
+ * per signal, always a HOST array; f0_hz: (lens[0] + .. + lens[B - 1],) Hz as ev_pitch_result.f0_hz, or NULL.  EV_FLAG_DEVICE_INPUTS covers mel and
+ * f0_hz (an ev_features_result.mel and an ev_pitch_result.f0_hz of the same batch go straight in); the other flags are ignored.  Rejected before
+ * anything is launched (message naming the field or signal; the side stays as it was): a NULL h, mel or lens, side not 0 or 1, B outside [1, 65535],
+ * lens[b] outside [1, EV_SCORE_MAX_FRAMES], n_mels outside [1, EV_FEATURES_MAX_MELS], n_ceps outside [1, min(n_mels - 1, EV_SCORE_MAX_CEPS)].  The
+ * call synchronises; a loaded side stays loaded, across every other entry point, until it is replaced or ev_destroy. */
+int ev_score_load(ev_handle* h, int side /* 0 = a (under test), 1 = b (yardstick) */, int B, int n_mels, int n_ceps,
+                  const float* mel, const int32_t* lens, const float* f0_hz /* or NULL */, uint32_t flags);
+/* Scores pair b = (signal b of side 0, signal b of side 1), steps 3 to 6.  flags: EV_SCORE_LINEAR or 0.  Rejected before anything is launched
+ * (message naming the field or side; the previous result stays valid): a NULL h or out, a wrong struct_size, a side that is not loaded, sides that
+ * differ in B, n_mels or n_ceps.  The call synchronises (as ev_compare): the HOST arrays are complete when it returns; the result, cq_a and cq_b
+ * included, lives in a workspace of its own and stays valid across every other entry point, ev_score_load included, until the next ev_score or
+ * ev_destroy.  A call that fails after its launches began (a HIP error) has rewritten that workspace: no result is valid after it. */
+int ev_score(ev_handle* h, uint32_t flags, ev_score_result* out);
+/* HOST, needs no handle: how ev_score lays a batch of pairs (lens_a[b] x lens_b[b] frames) out in passes.  A pair's distances take
+ * (lens_b + 63) * rm * 64 * 4 bytes and its decisions (lens_b + 63) * max(rm / 16, 1) * 64 * 4, rm the power of two from 1 with rm * 64 >= lens_a;
+ * consecutive pairs share a pass while their sum stays within EV_SCORE_WORKSPACE.  pass_of: (B,) out, the pass of every pair; pass_bytes: (B,) out,
+ * its first n entries the bytes of every pass -- ev_score's workspace for distances and decisions is ONE buffer of their maximum.  Returns the
+ * number of passes n, or -1 (a NULL argument, B outside [1, 65535], a length outside [1, EV_SCORE_MAX_FRAMES]). */
+int ev_score_plan(int B, const int32_t* lens_a, const int32_t* lens_b, int32_t* pass_of, int64_t* pass_bytes);
+
 /* Durations for EV_FLAG_FORCED_DURATIONS: (total_tokens,) int64 HOST pointer, copied. */
 int ev_set_forced_durations(ev_handle* h, const int64_t* durations, int64_t n);
 
