@@ -13,6 +13,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 // every term and every sum of the specification is rounded on its own: no d * d + s as one fma
@@ -34,15 +35,6 @@ __device__ inline void take(Acc& c, float xa, float xb, int i) {
     const double ad = fabs(d);
     if (ad > c.md) { c.md = ad; c.ix = i; }
     c.py = fmaxf(c.py, ok ? fabsf(xb) : 0.f);
-}
-
-// lane j's value in every lane (j the same in all of them)
-__device__ inline double lane_value(double v, int j) {
-    union { double d; int i[2]; } u;
-    u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], j);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], j);
-    return u.d;
 }
 
 }  // namespace
@@ -131,6 +123,8 @@ __global__ __launch_bounds__(64) void compare_finish_kernel(const int64_t* __res
         py = fmaxf(py, peak[c]);
         nf += nonf[c];
     }
+    // (max, first index) has a tie-break of its own.  py and nf stay inside its butterfly: folded after it by wave_max_f32 / wave_sum_i64, the
+    // kernel measured 0.6 % slower.
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const double m2 = __shfl_xor(md, o, 64);

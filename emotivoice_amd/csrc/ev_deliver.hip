@@ -2,11 +2,11 @@
 // include/evhip.h states the specification.
 //
 // deliver: one block = DL_TILE consecutive outputs of one utterance, 256 threads, four CONSECUTIVE outputs per thread.  Output m is ev_resample's
-// sample, term for term: the same phase-major table (resample_pack_table), the same k range, four interleaved fmaf partial sums over (k - k_lo) mod 4
-// combined as (s0 + s1) + (s2 + s3); only the distribution of the outputs over threads differs.  The tile's run of inputs is kept in LDS as fp32 (zero
-// outside the utterance) when it fits, the table beside it when both fit (16 -> 44.1 kHz: 57 KB + 1.6 KB); what does not fit is read through L1 with
-// the same bounds.  up == down == 1 is the same kernel without the filter.  The four samples are converted in registers and leave as one store: a
-// dword of four law bytes, 8 bytes of four int16, 16 bytes of four fp32 -- every utterance starts on a 16-byte boundary and a tile on a multiple of
+// sample, term for term: the same phase-major table (resample_pack_table), the same k range (polyphase_taps) and the same sum (polyphase_sum,
+// ev_audio_dev.h); only the distribution of the outputs over threads differs.  The tile's run of inputs is kept in LDS as fp32 (zero outside the
+// utterance) when it fits, the table beside it when both fit (16 -> 44.1 kHz: 57 KB + 1.6 KB); what does not fit is read through L1 with the same
+// bounds (polyphase_lds decides, as for ev_resample).  up == down == 1 is the same kernel without the filter.
+// The four samples are converted in registers and leave as one store: a dword of four law bytes, 8 bytes of four int16, 16 bytes of four fp32 -- every utterance starts on a 16-byte boundary and a tile on a multiple of
 // DL_TILE outputs, so the stores are aligned; the quad that holds the utterance's last sample writes zeros behind it and up to the end of the slot.
 // Each block leaves its max |y| over finite samples and its count of clipped samples; deliver_fold reduces an utterance's tiles (a max and an integer
 // sum: exact in any order).
@@ -14,14 +14,12 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
 
 namespace {
-
-__host__ __device__ inline int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && (a < 0)) ? q - 1 : q; }      // b > 0
-__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 
 __device__ inline uint32_t dl_hash(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
@@ -65,8 +63,6 @@ __device__ inline uint32_t dl_alaw(int s) {
 
 }  // namespace
 
-int64_t deliver_run_max(int up, int down, int half) { return ((int64_t)(DL_TILE - 1) * down + 2 * (int64_t)half) / up + 2; }
-
 // PAD (only with RUN_LDS): the run is kept with one unused float after every 32.  Neighbouring lanes are four outputs = 4 down / up inputs apart;
 // at down >= 2 up that is 8 floats or more, which would put a wave's reads on a quarter of the banks or fewer.
 template <bool FILTER, bool RUN_LDS, bool TAB_LDS, bool PAD>
@@ -80,23 +76,14 @@ __global__ __launch_bounds__(256) void deliver_kernel(const DeliverParams p) {
     const DeliverSeq sq = p.seqs[tl.seq];
     const int64_t L = sq.len, up = p.up, down = p.down, half = p.half;
     const int m0 = tl.m0, m1 = (int)min((int64_t)m0 + DL_TILE, sq.n) - 1;      // the tile's outputs m0 .. m1
-    const float* wf = reinterpret_cast<const float*>(p.wav) + sq.in_off;
-    const int16_t* wi = reinterpret_cast<const int16_t*>(p.wav) + sq.in_off;
     float* run = reinterpret_cast<float*>(smem);
     float* ltab = run + (RUN_LDS ? p.run_cap : 0);
     int64_t k_first = 0;
     if (FILTER) {
         k_first = ceil_div((int64_t)m0 * down - half, up);
         const int64_t k_last = floor_div((int64_t)m1 * down + half, up);
-        if (RUN_LDS) {
-            const int NS = (int)(k_last - k_first + 1);      // < deliver_run_max, and at(NS - 1) < run_cap
-            for (int i = tid; i < NS; i += 256) {
-                const int64_t s = k_first + i;
-                float v = 0.f;
-                if (s >= 0 && s < L) v = p.wav_is_i16 ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
-                run[at(i)] = v;
-            }
-        }
+        if (RUN_LDS)      // k_last - k_first + 1 < polyphase_run_max, and at() of the last one < run_cap
+            stage_run<256>([&](int i) -> float& { return run[at(i)]; }, p.wav, p.wav_is_i16, sq.in_off, L, k_first, (int)(k_last - k_first + 1));
         if (TAB_LDS) {
             const int NT = p.up * p.row;
             for (int i = tid; i < NT; i += 256) ltab[i] = p.tab[i];
@@ -111,40 +98,16 @@ __global__ __launch_bounds__(256) void deliver_kernel(const DeliverParams p) {
         y[r] = 0.f;
         if (m > m1) continue;
         if (!FILTER) {
-            y[r] = p.wav_is_i16 ? (float)wi[m] * (1.0f / 32768.0f) : wf[m];
+            y[r] = load_sample(p.wav, p.wav_is_i16, sq.in_off + m);
             continue;
         }
-        const int64_t md = (int64_t)m * down;
-        const int64_t k_lo = ceil_div(md - half, up), k_hi = floor_div(md + half, up);
-        const int nk = (int)(k_hi - k_lo + 1);
-        const int ph = (int)(md % up);
+        int64_t k_lo;
+        int nk, ph;
+        polyphase_taps(m, up, down, half, &k_lo, &nk, &ph);
         const float* h = (TAB_LDS ? ltab : p.tab) + (size_t)ph * p.row;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        if (RUN_LDS) {
-            const int x0 = (int)(k_lo - k_first);
-            auto x = [&](int j) -> float { return run[at(x0 + j)]; };
-            int j = 0;
-            for (; j + 4 <= nk; j += 4) {
-                s0 = fmaf(x(j), h[j], s0); s1 = fmaf(x(j + 1), h[j + 1], s1); s2 = fmaf(x(j + 2), h[j + 2], s2); s3 = fmaf(x(j + 3), h[j + 3], s3);
-            }
-            if (j < nk) { s0 = fmaf(x(j), h[j], s0); ++j; }
-            if (j < nk) { s1 = fmaf(x(j), h[j], s1); ++j; }
-            if (j < nk) { s2 = fmaf(x(j), h[j], s2); }
-        } else {
-            auto x = [&](int j) -> float {
-                const int64_t k = k_lo + j;
-                if (k < 0 || k >= L) return 0.f;
-                return p.wav_is_i16 ? (float)wi[k] * (1.0f / 32768.0f) : wf[k];
-            };
-            int j = 0;
-            for (; j + 4 <= nk; j += 4) {
-                s0 = fmaf(x(j), h[j], s0); s1 = fmaf(x(j + 1), h[j + 1], s1); s2 = fmaf(x(j + 2), h[j + 2], s2); s3 = fmaf(x(j + 3), h[j + 3], s3);
-            }
-            if (j < nk) { s0 = fmaf(x(j), h[j], s0); ++j; }
-            if (j < nk) { s1 = fmaf(x(j), h[j], s1); ++j; }
-            if (j < nk) { s2 = fmaf(x(j), h[j], s2); }
-        }
-        y[r] = (s0 + s1) + (s2 + s3);
+        const int x0 = (int)(k_lo - k_first);
+        y[r] = RUN_LDS ? polyphase_sum([&](int j) { return run[at(x0 + j)]; }, h, nk)
+                       : polyphase_sum([&](int j) { return sample_or_zero(p.wav, p.wav_is_i16, sq.in_off, L, k_lo + j); }, h, nk);
     }
     // the conversion, in registers; lanes past m1 carry zeros (the slot's padding)
     float pk = 0.f;
@@ -181,8 +144,8 @@ __global__ __launch_bounds__(256) void deliver_kernel(const DeliverParams p) {
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { pk = fmaxf(pk, __shfl_xor(pk, o, 64)); cl += __shfl_xor(cl, o, 64); }
+    pk = wave_max_f32(pk);
+    cl = wave_sum_i32(cl);
     if (lane == 0) { s_pk[w] = pk; s_cl[w] = cl; }
     __syncthreads();
     if (tid == 0) p.parts[blockIdx.x] = DeliverPart{fmaxf(fmaxf(s_pk[0], s_pk[1]), fmaxf(s_pk[2], s_pk[3])), (s_cl[0] + s_cl[1]) + (s_cl[2] + s_cl[3])};
@@ -193,11 +156,11 @@ __global__ __launch_bounds__(64) void deliver_fold_kernel(const DeliverPart* __r
     const DeliverSeq sq = seqs[blockIdx.x];
     const int nt = (int)((sq.n + DL_TILE - 1) / DL_TILE);
     float pk = 0.f;
-    long long cl = 0;
+    int64_t cl = 0;
     for (int i = threadIdx.x; i < nt; i += 64) { const DeliverPart t = parts[sq.tile0 + i]; pk = fmaxf(pk, t.peak); cl += t.clipped; }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { pk = fmaxf(pk, __shfl_xor(pk, o, 64)); cl += __shfl_xor(cl, o, 64); }
-    if (threadIdx.x == 0) outs[blockIdx.x] = DeliverOut{pk, 0, (int64_t)cl};
+    pk = wave_max_f32(pk);
+    cl = wave_sum_i64(cl);
+    if (threadIdx.x == 0) outs[blockIdx.x] = DeliverOut{pk, 0, cl};
 }
 
 int launch_deliver(const DeliverParams& p, hipStream_t s) {
@@ -211,18 +174,13 @@ int launch_deliver(const DeliverParams& p, hipStream_t s) {
     }
     if (p.half < 1 || p.row != resample_row_len(p.up, p.half) || !p.tab) return -1;
     const bool pad = p.down >= 2 * p.up;
-    const int64_t run_len = deliver_run_max(p.up, p.down, p.half), run_max = pad ? run_len + run_len / 32 + 1 : run_len;      // floats of LDS, the unused ones included
-    const size_t tab_bytes = resample_table_floats(p.up, p.half) * sizeof(float);
-    const bool run_lds = (size_t)run_max * sizeof(float) <= (size_t)DL_MAX_RUN_BYTES;
-    const size_t run_bytes = run_lds ? (size_t)run_max * sizeof(float) : 0;
-    const bool tab_lds = run_bytes + tab_bytes <= (size_t)DL_MAX_LDS;
-    const size_t lds = run_bytes + (tab_lds ? tab_bytes : 0);
-    q.run_cap = run_lds ? (int)run_max : 0;
-    void (*fn)(const DeliverParams) = run_lds ? (tab_lds ? (pad ? deliver_kernel<true, true, true, true> : deliver_kernel<true, true, true, false>)
-                                                         : (pad ? deliver_kernel<true, true, false, true> : deliver_kernel<true, true, false, false>))
-                                              : (tab_lds ? deliver_kernel<true, false, true, false> : deliver_kernel<true, false, false, false>);
-    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(fn, g, b, lds, s, q);
+    const PolyphaseLds l = polyphase_lds(DL_TILE, p.up, p.down, p.half, pad);
+    q.run_cap = l.run_cap;
+    void (*fn)(const DeliverParams) = l.run_lds ? (l.tab_lds ? (pad ? deliver_kernel<true, true, true, true> : deliver_kernel<true, true, true, false>)
+                                                             : (pad ? deliver_kernel<true, true, false, true> : deliver_kernel<true, true, false, false>))
+                                                : (l.tab_lds ? deliver_kernel<true, false, true, false> : deliver_kernel<true, false, false, false>);
+    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes) != hipSuccess) return -1;
+    hipLaunchKernelGGL(fn, g, b, l.bytes, s, q);
     return 0;
 }
 

@@ -284,8 +284,9 @@ void launch_pitch_fill(const float* f0, const StftSeq* seqs, int B, float mean, 
 
 // ev_resample (ev_resample.hip): polyphase sample-rate conversion, then the silence trim.  A tile is RS_TM consecutive outputs of one utterance.  The
 // taps go in as a phase-major table (resample_pack_table): row p = (m down) mod up holds h[i], i = p (mod up), from the largest i <= half downwards,
-// zero-filled to resample_row_len (odd).  A tile's run of inputs stays in LDS up to RS_MAX_RUN_BYTES, the table beside it up to RS_MAX_LDS in all.
-constexpr int RS_TM = 256, RS_MAX_RUN_BYTES = 49152, RS_MAX_LDS = 65536;
+// zero-filled to resample_row_len (odd).  A tile's run of inputs stays in LDS up to POLY_MAX_RUN_BYTES, the table beside it up to POLY_MAX_LDS in all
+// (polyphase_lds: ev_deliver's kernel takes the same decision with its own tile).
+constexpr int RS_TM = 256, POLY_MAX_RUN_BYTES = 49152, POLY_MAX_LDS = 65536;
 struct ResampleSeq { int64_t in_off, len, out_off, n; };      // input offset / length, output offset / length n = ceil(len up / down)
 struct ResampleTile { int32_t seq, m0; };                     // one block: utterance and first output
 struct TrimSeq { int64_t src_off, dst_off, cut; };            // the cut y[src_off .. src_off + cut) goes to out[dst_off + pad ..)
@@ -300,7 +301,10 @@ struct ResampleParams {
 int resample_row_len(int up, int half);
 size_t resample_table_floats(int up, int half);
 void resample_pack_table(int up, int half, const float* taps /* host (2 half + 1,) */, float* out /* host, resample_table_floats */);
-int64_t resample_run_max(int up, int down, int half);           // an upper bound of a tile's run of input samples
+int64_t polyphase_run_max(int tile, int up, int down, int half);      // an upper bound of the run of input samples under a tile of `tile` outputs
+// Where a tile's run and the table go.  padded: the run keeps one unused float after every 32 (ev_deliver at down >= 2 up).
+struct PolyphaseLds { bool run_lds, tab_lds; int run_cap; size_t bytes; };      // run_cap: floats of LDS for the run, 0 = read through L1; bytes: dynamic LDS
+PolyphaseLds polyphase_lds(int tile, int up, int down, int half, bool padded);
 int launch_resample_poly(const ResampleParams& p, hipStream_t s);      // 0, or -1 for bad parameters
 void launch_resample_copy(const void* wav, int wav_is_i16, int64_t total, float* out, hipStream_t s);      // sr_in == sr_out
 void launch_trim_scan(const float* y, const ResampleSeq* seqs, int B, float frac, int64_t* cuts /* (2 B,): first, last */, hipStream_t s);
@@ -308,9 +312,9 @@ void launch_trim_gather(const float* y, const TrimSeq* seqs, int B, int64_t max_
 
 // ev_deliver (ev_deliver.hip): ev_resample's output sample, converted in registers to the response's encoding.  A tile is DL_TILE consecutive outputs
 // of one utterance, four consecutive outputs per thread, stored as one quad (4 / 8 / 16 bytes); the table is ev_resample's (resample_pack_table).  A
-// tile's run of inputs stays in LDS up to DL_MAX_RUN_BYTES, the table beside it up to DL_MAX_LDS in all.  Every tile leaves a DeliverPart; the fold
+// tile's run of inputs stays in LDS and the table beside it by ev_resample's rule (polyphase_lds).  Every tile leaves a DeliverPart; the fold
 // kernel reduces the parts of an utterance, tile0 .. tile0 + ceil(n / DL_TILE), in ascending order (a max and an integer sum: exact in any order).
-constexpr int DL_TILE = 1024, DL_MAX_RUN_BYTES = 49152, DL_MAX_LDS = 65536;
+constexpr int DL_TILE = 1024;
 enum { DL_F32 = 0, DL_S16 = 1, DL_ULAW = 2, DL_ALAW = 3 };
 struct DeliverSeq { int64_t in_off, len, n, byte_off, slot; uint32_t seed; int32_t tile0; };      // slot = the utterance's bytes rounded up to 16
 struct DeliverTile { int32_t seq, m0; };
@@ -326,7 +330,6 @@ struct DeliverParams {
     DeliverPart* parts;                               // (n_tiles,)
     int run_cap;                                      // set by the launcher: floats of LDS for the run, 0 = read through L1
 };
-int64_t deliver_run_max(int up, int down, int half);            // an upper bound of a tile's run of input samples
 int launch_deliver(const DeliverParams& p, hipStream_t s);      // 0, or -1 for bad parameters
 void launch_deliver_fold(const DeliverPart* parts, const DeliverSeq* seqs, int B, DeliverOut* outs, hipStream_t s);
 

@@ -19,38 +19,16 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
 
 namespace {
 
-__device__ inline float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline float wave_min_f32(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ inline bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// one rounded fp32 product, never fused with anything
-#pragma clang fp contract(off)
-__device__ inline float mul_rn(float a, float b) { return a * b; }
-#pragma clang fp contract(fast)
-
 // u of the specification: the source bits where the gain is one
 __device__ inline float limit_load(const void* wav, int is16, int64_t i, float g) {
-    const float x = is16 ? (float)reinterpret_cast<const int16_t*>(wav)[i] / 32768.0f : reinterpret_cast<const float*>(wav)[i];
+    const float x = load_sample(wav, is16, i);
     return g == 1.0f ? x : mul_rn(x, g);
 }
 
@@ -190,10 +168,7 @@ __global__ __launch_bounds__(256) void limit_apply_kernel(const void* __restrict
                 const float u = limit_load(wav, is16, tl.src + n, g), s = sv[e];
                 const float y = s == 1.0f ? u : mul_rn(u, s);
                 out[tl.src + n] = y;
-                if (out_i16) {      // NaN -> 0; else truncation toward zero, then the clamp: the same integers as the clamp in float first
-                    const float v = fminf(fmaxf(mul_rn(y, 32768.0f), -32768.0f), 32767.0f);
-                    out_i16[tl.src + n] = y != y ? (int16_t)0 : (int16_t)(int)v;
-                }
+                if (out_i16) out_i16[tl.src + n] = y != y ? (int16_t)0 : s16_trunc(y);      // NaN -> 0
                 if (s_out) s_out[tl.src + n] = s;
                 mn = fminf(mn, s);
                 ct += s < 1.0f ? 1 : 0;

@@ -10,6 +10,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
@@ -43,17 +44,7 @@ __global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchParams p) {
     float* dsh = reinterpret_cast<float*>(cs + PITCH_TF * NLP);
     float* e0 = dsh + PITCH_TF * NLP;
     float* run = e0 + PITCH_TF;
-    {
-        const int64_t L = sq.len, first = (int64_t)t0 * hop - S / 2;
-        const float* wf = reinterpret_cast<const float*>(p.wav) + sq.wav_off;
-        const int16_t* wi = reinterpret_cast<const int16_t*>(p.wav) + sq.wav_off;
-        for (int i = tid; i < NS; i += 256) {
-            const int64_t s = first + i;
-            float v = 0.f;
-            if (s >= 0 && s < L) v = p.wav_is_i16 ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
-            run[i] = v;
-        }
-    }
+    stage_run<256>([&](int i) -> float& { return run[i]; }, p.wav, p.wav_is_i16, sq.wav_off, sq.len, (int64_t)t0 * hop - S / 2, NS);
     __syncthreads();
     const int NG = (NL + 63) >> 6;
     for (int it = w; it < PITCH_TF * NG; it += 4) {
@@ -79,8 +70,7 @@ __global__ __launch_bounds__(256) void pitch_yin_kernel(const PitchParams p) {
         const float* a = run + f * hop;
         float acc = 0.f;
         for (int j = lane; j < W; j += 64) acc = fmaf(a[j], a[j], acc);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        acc = wave_sum_f32(acc);
         if (lane == 0) e0[f] = acc;
     }
     __syncthreads();

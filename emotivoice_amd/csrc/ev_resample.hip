@@ -5,24 +5,18 @@
 // fp32 (zero outside the utterance) when it fits; a run that does not fit (a large down / up, or a long custom filter) is read through L1 with the
 // same bounds.  The taps live in a phase-major table: row p = (m down) mod up lists h[i], i = p (mod up), from the largest i <= half downwards, which
 // is the order k ascends in; rows are padded to an odd length so that lanes on different phases fall on different LDS banks.  The table is copied
-// into LDS when it fits beside the run (44.1 -> 16 kHz: 57 KB), else read through L1 (it stays L2-resident).  Whichever way, output m sums its
-// products in four interleaved partial sums over (k - k_lo) mod 4, k ascending, combined as (s0 + s1) + (s2 + s3): its bits depend on (utterance, m).
+// into LDS when it fits beside the run (44.1 -> 16 kHz: 57 KB), else read through L1 (it stays L2-resident); polyphase_lds decides both.  Whichever
+// way, output m is polyphase_sum (ev_audio_dev.h, where the order of the sum is stated): its bits depend on (utterance, m).
 // trim_scan: one block per utterance, the peak first, then the first and the last index above peak * frac (max and min reductions: exact in any order).
 // trim_gather: the padded cuts at their final offsets.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
-
-namespace {
-
-__host__ __device__ inline int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && (a < 0)) ? q - 1 : q; }      // b > 0
-__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
-
-}  // namespace
 
 int resample_row_len(int up, int half) { return ((2 * half) / up + 1) | 1; }
 size_t resample_table_floats(int up, int half) { return (size_t)up * (size_t)resample_row_len(up, half); }
@@ -36,7 +30,17 @@ void resample_pack_table(int up, int half, const float* taps, float* out) {
         }
     }
 }
-int64_t resample_run_max(int up, int down, int half) { return ((int64_t)(RS_TM - 1) * down + 2 * (int64_t)half) / up + 2; }
+int64_t polyphase_run_max(int tile, int up, int down, int half) { return ((int64_t)(tile - 1) * down + 2 * (int64_t)half) / up + 2; }
+PolyphaseLds polyphase_lds(int tile, int up, int down, int half, bool padded) {
+    const int64_t run = polyphase_run_max(tile, up, down, half), cap = padded ? run + run / 32 + 1 : run;      // floats of LDS, the unused ones included
+    const size_t run_bytes = (size_t)cap * sizeof(float), tab_bytes = resample_table_floats(up, half) * sizeof(float);
+    PolyphaseLds r;
+    r.run_lds = run_bytes <= (size_t)POLY_MAX_RUN_BYTES;
+    r.tab_lds = (r.run_lds ? run_bytes : 0) + tab_bytes <= (size_t)POLY_MAX_LDS;
+    r.run_cap = r.run_lds ? (int)cap : 0;
+    r.bytes = (r.run_lds ? run_bytes : 0) + (r.tab_lds ? tab_bytes : 0);
+    return r;
+}
 
 template <bool RUN_LDS, bool TAB_LDS>
 __global__ __launch_bounds__(RS_TM) void resample_poly_kernel(const ResampleParams p) {
@@ -49,17 +53,8 @@ __global__ __launch_bounds__(RS_TM) void resample_poly_kernel(const ResamplePara
     const int64_t k_first = ceil_div((int64_t)m0 * down - half, up), k_last = floor_div((int64_t)m1 * down + half, up);
     float* run = reinterpret_cast<float*>(smem);
     float* ltab = run + (RUN_LDS ? p.run_cap : 0);
-    const float* wf = reinterpret_cast<const float*>(p.wav) + sq.in_off;
-    const int16_t* wi = reinterpret_cast<const int16_t*>(p.wav) + sq.in_off;
-    if (RUN_LDS) {
-        const int NS = (int)(k_last - k_first + 1);      // <= run_cap (resample_run_max)
-        for (int i = tid; i < NS; i += RS_TM) {
-            const int64_t s = k_first + i;
-            float v = 0.f;
-            if (s >= 0 && s < L) v = p.wav_is_i16 ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
-            run[i] = v;
-        }
-    }
+    if (RUN_LDS)      // k_last - k_first + 1 <= run_cap (polyphase_run_max)
+        stage_run<RS_TM>([&](int i) -> float& { return run[i]; }, p.wav, p.wav_is_i16, sq.in_off, L, k_first, (int)(k_last - k_first + 1));
     if (TAB_LDS) {
         const int NT = p.up * p.row;
         for (int i = tid; i < NT; i += RS_TM) ltab[i] = p.tab[i];
@@ -67,44 +62,18 @@ __global__ __launch_bounds__(RS_TM) void resample_poly_kernel(const ResamplePara
     if (RUN_LDS || TAB_LDS) __syncthreads();
     const int m = m0 + tid;
     if (m > m1) return;
-    const int64_t md = (int64_t)m * down;
-    const int64_t k_lo = ceil_div(md - half, up), k_hi = floor_div(md + half, up);
-    const int nk = (int)(k_hi - k_lo + 1);
-    const int ph = (int)(md % up);
+    int64_t k_lo;
+    int nk, ph;
+    polyphase_taps(m, up, down, half, &k_lo, &nk, &ph);
     const float* h = (TAB_LDS ? ltab : p.tab) + (size_t)ph * p.row;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (RUN_LDS) {
-        const float* x = run + (k_lo - k_first);
-        int j = 0;
-        for (; j + 4 <= nk; j += 4) {
-            s0 = fmaf(x[j], h[j], s0); s1 = fmaf(x[j + 1], h[j + 1], s1); s2 = fmaf(x[j + 2], h[j + 2], s2); s3 = fmaf(x[j + 3], h[j + 3], s3);
-        }
-        if (j < nk) { s0 = fmaf(x[j], h[j], s0); ++j; }
-        if (j < nk) { s1 = fmaf(x[j], h[j], s1); ++j; }
-        if (j < nk) { s2 = fmaf(x[j], h[j], s2); }
-    } else {
-        auto x = [&](int j) -> float {
-            const int64_t k = k_lo + j;
-            if (k < 0 || k >= L) return 0.f;
-            return p.wav_is_i16 ? (float)wi[k] * (1.0f / 32768.0f) : wf[k];
-        };
-        int j = 0;
-        for (; j + 4 <= nk; j += 4) {
-            s0 = fmaf(x(j), h[j], s0); s1 = fmaf(x(j + 1), h[j + 1], s1); s2 = fmaf(x(j + 2), h[j + 2], s2); s3 = fmaf(x(j + 3), h[j + 3], s3);
-        }
-        if (j < nk) { s0 = fmaf(x(j), h[j], s0); ++j; }
-        if (j < nk) { s1 = fmaf(x(j), h[j], s1); ++j; }
-        if (j < nk) { s2 = fmaf(x(j), h[j], s2); }
-    }
-    p.out[sq.out_off + m] = (s0 + s1) + (s2 + s3);
+    const float* x = run + (k_lo - k_first);
+    p.out[sq.out_off + m] = RUN_LDS ? polyphase_sum([&](int j) { return x[j]; }, h, nk)
+                                    : polyphase_sum([&](int j) { return sample_or_zero(p.wav, p.wav_is_i16, sq.in_off, L, k_lo + j); }, h, nk);
 }
 
 // sr_in == sr_out: the packed input and the packed output have one layout
 __global__ __launch_bounds__(256) void resample_copy_kernel(const void* __restrict__ wav, int wav_is_i16, int64_t total, float* __restrict__ out) {
-    const float* wf = reinterpret_cast<const float*>(wav);
-    const int16_t* wi = reinterpret_cast<const int16_t*>(wav);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
-        out[i] = wav_is_i16 ? (float)wi[i] * (1.0f / 32768.0f) : wf[i];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) out[i] = load_sample(wav, wav_is_i16, i);
 }
 
 // cuts[2 b] = first index with |y| > peak * frac, cuts[2 b + 1] = the last one; no such index: 0, 0
@@ -117,8 +86,7 @@ __global__ __launch_bounds__(256) void trim_scan_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float pk = 0.f;
     for (int64_t i = tid; i < sq.n; i += 256) pk = fmaxf(pk, fabsf(v[i]));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o, 64));
+    pk = wave_max_f32(pk);
     if (lane == 0) s_peak[w] = pk;
     __syncthreads();
     pk = fmaxf(fmaxf(s_peak[0], s_peak[1]), fmaxf(s_peak[2], s_peak[3]));
@@ -126,11 +94,8 @@ __global__ __launch_bounds__(256) void trim_scan_kernel(const float* __restrict_
     int64_t lo = INT64_MAX, hi = -1;
     for (int64_t i = tid; i < sq.n; i += 256)
         if (fabsf(v[i]) > thr) { lo = min(lo, i); hi = i; }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        lo = min(lo, (int64_t)__shfl_xor((long long)lo, o, 64));
-        hi = max(hi, (int64_t)__shfl_xor((long long)hi, o, 64));
-    }
+    lo = wave_min_i64(lo);
+    hi = wave_max_i64(hi);
     if (lane == 0) { s_lo[w] = lo; s_hi[w] = hi; }
     __syncthreads();
     if (tid == 0) {
@@ -159,22 +124,13 @@ __global__ __launch_bounds__(256) void trim_gather_kernel(const float* __restric
 
 int launch_resample_poly(const ResampleParams& p, hipStream_t s) {
     if (p.n_tiles <= 0 || p.up < 1 || p.down < 1 || p.half < 1 || p.row != resample_row_len(p.up, p.half)) return -1;
-    const int64_t run_max = resample_run_max(p.up, p.down, p.half);
-    const size_t tab_bytes = resample_table_floats(p.up, p.half) * sizeof(float);
-    const bool run_lds = (size_t)run_max * sizeof(float) <= (size_t)RS_MAX_RUN_BYTES;
-    const size_t run_bytes = run_lds ? (size_t)run_max * sizeof(float) : 0;
-    const bool tab_lds = run_bytes + tab_bytes <= (size_t)RS_MAX_LDS;
-    const size_t lds = run_bytes + (tab_lds ? tab_bytes : 0);
+    const PolyphaseLds l = polyphase_lds(RS_TM, p.up, p.down, p.half, false);
     ResampleParams q = p;
-    q.run_cap = run_lds ? (int)run_max : 0;
-    const void* fn = run_lds ? (tab_lds ? (const void*)resample_poly_kernel<true, true> : (const void*)resample_poly_kernel<true, false>)
-                             : (tab_lds ? (const void*)resample_poly_kernel<false, true> : (const void*)resample_poly_kernel<false, false>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    const dim3 g((unsigned)p.n_tiles), b(RS_TM);
-    if (run_lds && tab_lds) hipLaunchKernelGGL((resample_poly_kernel<true, true>), g, b, lds, s, q);
-    else if (run_lds) hipLaunchKernelGGL((resample_poly_kernel<true, false>), g, b, lds, s, q);
-    else if (tab_lds) hipLaunchKernelGGL((resample_poly_kernel<false, true>), g, b, lds, s, q);
-    else hipLaunchKernelGGL((resample_poly_kernel<false, false>), g, b, lds, s, q);
+    q.run_cap = l.run_cap;
+    void (*fn)(const ResampleParams) = l.run_lds ? (l.tab_lds ? resample_poly_kernel<true, true> : resample_poly_kernel<true, false>)
+                                                 : (l.tab_lds ? resample_poly_kernel<false, true> : resample_poly_kernel<false, false>);
+    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes) != hipSuccess) return -1;
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.n_tiles), dim3(RS_TM), l.bytes, s, q);
     return 0;
 }
 

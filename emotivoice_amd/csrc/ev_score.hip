@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 // every product and every sum of the specification is rounded on its own
@@ -47,20 +48,6 @@ __device__ inline uint64_t sq_dist(const int32_t* a, const int32_t* b, int D) {
         s += (uint64_t)((int64_t)e * (int64_t)e);
     }
     return s;
-}
-
-__device__ inline double lane_value(double v, int j) {
-    union { double d; int i[2]; } u;
-    u.d = v;
-    u.i[0] = __builtin_amdgcn_readlane(u.i[0], j);
-    u.i[1] = __builtin_amdgcn_readlane(u.i[1], j);
-    return u.d;
-}
-
-__device__ inline int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 }  // namespace
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(64) void score_count_kernel(const int32_t* __restri
     const ScoreSig sg = sigs[blockIdx.x];
     int n = 0;
     for (int t = threadIdx.x; t < sg.T; t += 64) n += bad[sg.frm_off + t];
-    n = wave_sum(n);
+    n = wave_sum_i32(n);
     if (threadIdx.x == 0) nonfinite[blockIdx.x] = n;
 }
 
@@ -260,10 +247,9 @@ __global__ __launch_bounds__(64) void score_sums_kernel(const ScorePair* __restr
             for (int t = 0; t < 64; ++t) { sc += lane_value(c, t); sc2 += lane_value(c2, t); }
         }
     }
-    n_diag = wave_sum(n_diag); n_a = wave_sum(n_a); n_b = wave_sum(n_b);
-    n_vv = wave_sum(n_vv); n_vu = wave_sum(n_vu); n_uv = wave_sum(n_uv); n_uu = wave_sum(n_uu);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sd += (int64_t)__shfl_xor((long long)sd, o, 64);
+    n_diag = wave_sum_i32(n_diag); n_a = wave_sum_i32(n_a); n_b = wave_sum_i32(n_b);
+    n_vv = wave_sum_i32(n_vv); n_vu = wave_sum_i32(n_vu); n_uv = wave_sum_i32(n_uv); n_uu = wave_sum_i32(n_uu);
+    sd = wave_sum_i64(sd);
     if (lane == 0) {
         ScoreSums r;
         r.sum_dist = linear ? sd : warp[blockIdx.x].sum_dist;

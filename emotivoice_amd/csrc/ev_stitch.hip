@@ -9,38 +9,17 @@
 // stitch_mix: one block per ST_TILE output samples of one document, 256 threads x 4 samples.  The ramp table sits in LDS.  The block finds the first
 //   segment that reaches into its tile by a binary search (the segments' ends pos + n are non-decreasing in a document, as are their starts) and
 //   walks forward while segments start inside the tile; a sample's contributions are formed in segment order, at most two (ev_stitch_plan's clamps).
+//   The specification's products and its sum are rounded one by one: mul_rn / add_rn (ev_audio_dev.h).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
 
 namespace {
-
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline int64_t wave_min_i64(int64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, (int64_t)__shfl_xor((long long)v, o, 64));
-    return v;
-}
-__device__ inline int64_t wave_max_i64(int64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, (int64_t)__shfl_xor((long long)v, o, 64));
-    return v;
-}
-
-// The specification's products and its sum are rounded one by one.  The header's __fmul_rn / __fadd_rn are plain operators compiled with contraction
-// allowed, so a product followed by a sum would still fuse into an fma after inlining; these two carry no such licence.
-#pragma clang fp contract(off)
-__device__ inline float mul_rn(float a, float b) { return a * b; }
-__device__ inline float add_rn(float a, float b) { return a + b; }
-#pragma clang fp contract(fast)
 
 // r(i, L) of the specification: i < L <= F <= ST_MAX_FADE, so (2 i + 1) F < 2^26 and the 32-bit quotient is the int64 one
 __device__ inline float ramp(int64_t i, int L, int F, const float* tab) {
@@ -63,7 +42,7 @@ __global__ __launch_bounds__(256) void stitch_peak_kernel(const float* __restric
         const int64_t i = base + r * 256 + tid;
         if (i < sg.len) pk = fmaxf(pk, fabsf(v[i]));
     }
-    pk = wave_max(pk);
+    pk = wave_max_f32(pk);
     if ((tid & 63) == 0) s_pk[tid >> 6] = pk;
     __syncthreads();
     if (tid == 0) part[sg.part_off + blockIdx.x] = fmaxf(fmaxf(s_pk[0], s_pk[1]), fmaxf(s_pk[2], s_pk[3]));
@@ -80,7 +59,7 @@ __global__ __launch_bounds__(256) void stitch_edges_kernel(const float* __restri
     const int64_t n_part = (sg.len + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
     float pk = 0.f;
     for (int64_t i = tid; i < n_part; i += 256) pk = fmaxf(pk, part[sg.part_off + i]);
-    pk = wave_max(pk);
+    pk = wave_max_f32(pk);
     if (lane == 0) s_pk[w] = pk;
     __syncthreads();
     pk = fmaxf(fmaxf(s_pk[0], s_pk[1]), fmaxf(s_pk[2], s_pk[3]));
@@ -157,10 +136,7 @@ __global__ __launch_bounds__(256) void stitch_mix_kernel(const float* __restrict
         const int64_t p = t0 + r * 256 + tid;
         if (p < t1) {
             out[dc.out_off + p] = acc[r];
-            if (out_i16) {      // truncation toward zero, then the clamp: the same integers as the clamp in float first
-                const float v = fminf(fmaxf(mul_rn(acc[r], 32768.0f), -32768.0f), 32767.0f);
-                out_i16[dc.out_off + p] = (int16_t)(int)v;
-            }
+            if (out_i16) out_i16[dc.out_off + p] = s16_trunc(acc[r]);
         }
     }
 }

@@ -52,9 +52,9 @@ def _noise(seed, n):
     return x
 
 
-def _run(eng, wavs, dc, seeds=None):
+def _run(eng, wavs, dc, seeds=None, sr_in=SR):
     """EVEngine.deliver plus the raw bytes of the result."""
-    out = eng.deliver(wavs, dc, SR, seeds)
+    out = eng.deliver(wavs, dc, sr_in, seeds)
     out["raw"] = eng.d2h(eng.last_deliver.data, (int(eng.last_deliver.total_bytes),), np.uint8)
     return out
 
@@ -92,6 +92,41 @@ def test_rate_pair_equals_the_oracle_byte_for_byte(ctx, sr_out):
             for b, y in enumerate(rs):
                 assert out["delivered_list"][b].tobytes() == y.tobytes(), b
     assert clipped > 0      # the inputs reach the clamp
+
+
+# The forms of the kernel that the rate pairs above do not reach: a long custom filter or a large rate ratio pushes the table, the tile's run of
+# inputs, or both out of LDS.  (case, sr_in, sr_out, half of the custom taps or None for the default design, input lengths whose output lengths are
+# 1, 2, 1023, 1024, 1025, and where the launcher must put (run, padded, table).)
+THROUGH_L1 = ((0, 16000, 8000, 4900, (1, 3, 2046, 2048, 2050), (True, True, False)),
+              (1, 24000, 16000, 5000, (1, 3, 1534, 1536, 1537), (True, False, False)),
+              (2, 48000, 1000, None, (1, 49, 49104, 49152, 49153), (False, False, True)),
+              (3, 50000, 1000, 8200, (1, 51, 51150, 51200, 51201), (False, False, False)))
+
+
+def _placement(up, down, half, tile=1024, max_run_bytes=49152, max_lds=65536):
+    """launch_deliver's choice restated: (run in LDS, run padded, table in LDS)."""
+    pad = down >= 2 * up
+    run = ((tile - 1) * down + 2 * half) // up + 2
+    run_bytes = 4 * (run + run // 32 + 1 if pad else run)
+    run_lds = run_bytes <= max_run_bytes
+    tab_bytes = 4 * up * (((2 * half) // up + 1) | 1)
+    return run_lds, run_lds and pad, (run_bytes if run_lds else 0) + tab_bytes <= max_lds
+
+
+@pytest.mark.parametrize("case,sr_in,sr_out,half,lens,placement", THROUGH_L1)
+def test_forms_that_read_through_l1_equal_the_oracle_byte_for_byte(ctx, case, sr_in, sr_out, half, lens, placement):
+    from emotivoice_amd import _ffi
+    from emotivoice_amd.delivery import DeliveryConfig
+    eng = ctx["eng"]
+    up, down = ro.ratio(sr_in, sr_out)
+    taps = None if half is None else (0.01 * np.random.default_rng(200 + case).standard_normal(2 * half + 1)).astype(np.float32)
+    used_half = ro.design(sr_in, sr_out)[3] if half is None else half
+    assert _ffi.EV_DELIVER_TILE == 1024 and _placement(up, down, used_half) == placement      # a new tile or LDS limit must not uncover the case
+    assert [ro.output_len(L, up, down) for L in lens] == [1, 2, 1023, 1024, 1025]
+    wavs = [_noise(300 + 10 * case + i, L) for i, L in enumerate(lens)]
+    s16 = [do.deliver(x, sr_in, sr_out, do.S16, taps=taps) for x in wavs]
+    for enc, want in ((do.S16, s16), (do.F32, [do.convert(w["y"], do.F32) for w in s16])):      # the oracle's y once: F32 is its bytes
+        _check(_run(eng, wavs, DeliveryConfig(sr_out, enc, taps=taps), sr_in=sr_in), want, enc)
 
 
 def test_every_int16_code_through_the_copy_path(ctx):
