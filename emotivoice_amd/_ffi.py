@@ -232,6 +232,21 @@ class ev_deliver_result(C.Structure):
     ]
 
 
+EV_DENOISE_MAX_R, EV_DENOISE_BIAS_FRAMES = 8, 88
+
+
+class ev_denoise_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("want_i16", C.c_int32), ("strength", C.c_float),
+                ("window", C.c_void_p)]
+
+
+class ev_denoise_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64), ("wav", C.c_void_p), ("wav_i16", C.c_void_p),
+        ("lens_out", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -321,6 +336,11 @@ SIGNATURES = {
     "ev_default_deliver_config": (None, [C.POINTER(ev_deliver_config)]),
     "ev_deliver_setup": (C.c_int, [_P, C.POINTER(ev_deliver_config)]),
     "ev_deliver": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_uint32, C.POINTER(ev_deliver_result)]),
+    "ev_default_denoise_config": (None, [C.POINTER(ev_denoise_config)]),
+    "ev_denoise_setup": (C.c_int, [_P, C.POINTER(ev_denoise_config), _P]),      # bias: a HOST array or None
+    "ev_denoise_bias": (C.c_int, [_P, _P]),
+    # lens and strengths are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_denoise": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_uint32, C.POINTER(ev_denoise_result)]),
     "ev_score_design": (C.c_int, [C.c_int, C.c_int, _P]),      # host only
     # lens is a HOST array; mel and f0_hz are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
     "ev_score_load": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_uint32]),
@@ -383,6 +403,9 @@ SIGNATURES = {
     # lens, gains and the per-segment outputs are HOST arrays; wav, r, out, out_i16 and s are device buffers
     "ev_op_limit_peak": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     "ev_op_limit_apply": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    # wav_lens, frames and window are HOST arrays (the wrappers pack the tables)
+    "ev_op_stft_gain": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "ev_op_istft": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "ev_op_stitch_mix": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 

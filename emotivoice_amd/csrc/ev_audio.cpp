@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1293,6 +1293,186 @@ int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     return 0;
 }
 
+// ------------------------------------------------------------------- vocoder bias removal (include/evhip.h: ev_denoise)
+static_assert(EV_DENOISE_MAX_R == DN_MAX_R, "include/evhip.h states the limit of ev_denoise.hip");
+void ev_default_denoise_config(ev_denoise_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof(ev_denoise_config);
+    c->n_fft = 1024; c->hop = 256; c->strength = 0.01f;
+}
+
+static int denoise_check_shape(ev_handle* h, const char* who, int n_fft, int hop) {
+    if (features_check_config(h, who, n_fft, hop, 1)) return -1;
+    if (n_fft % hop || n_fft / hop > DN_MAX_R) return fail(h, "%s: hop %d must divide n_fft %d with n_fft / hop <= %d", who, hop, n_fft, DN_MAX_R);
+    return 0;
+}
+
+// the three tables of a shape, packed on the host and uploaded; one allocation each, freed with denoise_free_tables
+struct DenoiseTables { char* basis = nullptr; char* ibasis = nullptr; float* env = nullptr; };
+static void denoise_free_tables(DenoiseTables& t) {
+    if (t.basis) (void)hipFree(t.basis);
+    if (t.ibasis) (void)hipFree(t.ibasis);
+    if (t.env) (void)hipFree(t.env);
+    t = DenoiseTables{};
+}
+static int denoise_upload_tables(int n_fft, int hop, const float* window, DenoiseTables& t) {      // 0, or -1 with nothing left behind
+    std::vector<uint16_t> hb(stft_basis_halfs(n_fft)), hi(istft_basis_halfs(n_fft, hop));
+    std::vector<float> he(istft_envelope_floats(n_fft, hop));
+    stft_pack_basis(n_fft, window, hb.data());
+    istft_pack_basis(n_fft, hop, window, hi.data());
+    istft_pack_envelope(n_fft, hop, window, he.data());
+    hipError_t e = hipMalloc((void**)&t.basis, hb.size() * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&t.ibasis, hi.size() * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&t.env, he.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(t.basis, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.ibasis, hi.data(), hi.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.env, he.data(), he.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { denoise_free_tables(t); return -1; }
+    return 0;
+}
+
+static StftGainParams stft_gain_params(const void* wav, int wav_is_i16, const StftSeq* seqs, const StftTile* tiles, size_t n_tiles, const void* basis, int n_fft,
+                                       int hop) {
+    StftGainParams p{};
+    p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = seqs; p.tiles = tiles; p.n_tiles = (int)n_tiles; p.basis = basis;
+    p.n_fft = n_fft; p.hop = hop; p.n_bins = n_fft / 2 + 1; p.n_btiles = stft_bin_tiles(n_fft); p.k_pad = denoise_k_pad(n_fft);
+    return p;
+}
+
+static int denoise_bad_value(int n, const float* v) {      // -1, or the first index of a value that is negative, NaN or infinite
+    for (int i = 0; i < n; ++i) if (!(v[i] >= 0.f) || !std::isfinite(v[i])) return i;
+    return -1;
+}
+
+int ev_denoise_setup(ev_handle* h, const ev_denoise_config* cfg, const float* bias) {
+    if (!h) return -1;
+    if (!cfg) return fail(h, "ev_denoise_setup: null config");
+    if (check_struct_size(h, "ev_denoise_setup", "struct_size", cfg->struct_size, "ev_denoise_config", sizeof(ev_denoise_config))) return -1;
+    if (denoise_check_shape(h, "ev_denoise_setup", cfg->n_fft, cfg->hop)) return -1;
+    if (!(cfg->strength >= 0.f) || !std::isfinite(cfg->strength)) return fail(h, "ev_denoise_setup: strength must be >= 0 and finite");
+    const int n_bins = cfg->n_fft / 2 + 1;
+    if (bias) {
+        const int bad = denoise_bad_value(n_bins, bias);
+        if (bad >= 0) return fail(h, "ev_denoise_setup: bias[%d] must be >= 0 and finite", bad);
+    } else if (!h->wt.count("voc.post.w")) {
+        return fail(h, "ev_denoise_setup: bias is NULL and no weights are loaded to measure one with");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    DenoiseTables t;
+    float* d_bias = nullptr;
+    if (denoise_upload_tables(cfg->n_fft, cfg->hop, cfg->window, t)) return fail(h, "ev_denoise_setup: uploading the tables failed");
+    if (hipMalloc((void**)&d_bias, (size_t)n_bins * 4) != hipSuccess) { denoise_free_tables(t); return fail(h, "ev_denoise_setup: no memory for the bias"); }
+    int rc = 0;
+    if (bias) {
+        if (hipMemcpy(d_bias, bias, (size_t)n_bins * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(h, "ev_denoise_setup: uploading the bias failed");
+    } else {      // the vocoder's answer to a zero mel; the magnitudes of its frame 0 go straight into d_bias
+        const int32_t frames = EV_DENOISE_BIAS_FRAMES;
+        std::vector<float> mel((size_t)h->cfg.n_mels * frames, 0.f);
+        ev_result r;
+        rc = ev_vocoder(h, 1, mel.data(), 0, &frames, 0, &r);
+        const int64_t L = rc ? 0 : r.total_samples;
+        if (!rc && L < cfg->n_fft / 2 + 1) rc = fail(h, "ev_denoise_setup: the vocoder's %lld samples are fewer than n_fft / 2 + 1", (long long)L);
+        if (!rc) {
+            const StftSeq sq{0, L, 0, (int32_t)(L / cfg->hop + 1), 0};
+            const StftTile tile{0, 0};
+            DevTable dt;
+            const size_t so = dt.add(&sq, sizeof sq), to = dt.add(&tile, sizeof tile);
+            if (dt.commit()) rc = fail(h, "ev_denoise_setup: no memory for the bias measurement");
+            if (!rc) {
+                StftGainParams p = stft_gain_params(r.wav, 0, dt.at<StftSeq>(so), dt.at<StftTile>(to), 1, t.basis, cfg->n_fft, cfg->hop);
+                p.mag = d_bias; p.mag_frames = 1;
+                if (launch_stft_gain(p, h->stream)) rc = fail(h, "ev_denoise_setup: the kernel does not build this shape");
+                if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "ev_denoise_setup: measuring the bias failed");
+            }
+        }
+    }
+    if (rc) { denoise_free_tables(t); (void)hipFree(d_bias); return -1; }
+    DenoiseTables old{h->dn.basis, h->dn.ibasis, h->dn.env};
+    denoise_free_tables(old);
+    if (h->dn.bias) (void)hipFree(h->dn.bias);
+    h->dn.basis = t.basis; h->dn.ibasis = t.ibasis; h->dn.env = t.env; h->dn.bias = d_bias;
+    h->dn.cfg = *cfg; h->dn.cfg.window = nullptr;
+    h->dn.ready = true;
+    return 0;
+}
+
+int ev_denoise_bias(ev_handle* h, float* out) {
+    if (!h) return -1;
+    if (!out) return fail(h, "ev_denoise_bias: out is NULL");
+    if (!h->dn.ready) return fail(h, "ev_denoise_bias: ev_denoise_setup has not been called");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out, h->dn.bias, (size_t)(h->dn.cfg.n_fft / 2 + 1) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* strengths, uint32_t flags, ev_denoise_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_denoise: wav is NULL");
+    if (!lens) return fail(h, "ev_denoise: lens is NULL");
+    if (!out) return fail(h, "ev_denoise: out is NULL");
+    if (check_struct_size(h, "ev_denoise", "out->struct_size", out->struct_size, "ev_denoise_result", sizeof(ev_denoise_result))) return -1;
+    if (!h->dn.ready) return fail(h, "ev_denoise: ev_denoise_setup has not been called");
+    if (B < 1 || B > 65535) return fail(h, "ev_denoise: B = %d outside [1, 65535]", B);
+    const ev_denoise_config& c = h->dn.cfg;
+    const int n_fft = c.n_fft, hop = c.hop, KP = denoise_k_pad(n_fft);
+    if (strengths) {
+        const int bad = denoise_bad_value(B, strengths);
+        if (bad >= 0) return fail(h, "ev_denoise: strengths[%d] must be >= 0 and finite", bad);
+    }
+    FrameGrid g;
+    const int bad = frame_grid_layout(B, lens, n_fft / 2 + 1, hop, 64, g);
+    if (bad > 0) return fail(h, "ev_denoise: lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", bad - 1, (long long)lens[bad - 1], n_fft / 2 + 1);
+    if (bad < 0) return fail(h, "ev_denoise: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(lens[-bad - 1] / hop + 1), EV_ALIGN_MAX_FRAMES);
+    std::vector<IstftSeq> iseqs; std::vector<StftTile> itiles;
+    const int64_t total_out = istft_layout(B, g.lens.data(), n_fft, hop, iseqs, itiles);
+    const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    std::vector<float> st((size_t)B);
+    for (int b = 0; b < B; ++b) st[b] = strengths ? strengths[b] : c.strength;
+    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, want16 = c.want_i16 != 0;
+    const size_t es = wav_is_i16 ? 2 : 4;
+    if (call_begin(h)) return -1;
+    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_st = nullptr, *d_out = nullptr;
+    uint16_t *d_hi = nullptr, *d_lo = nullptr; int16_t* d_i16 = nullptr;
+    if (arena_plan(h, ARENA_DENOISE, [&](ArenaPlan& ap) {
+        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_iseqs = ap.arr<IstftSeq>(B); d_itiles = ap.arr<StftTile>(itiles.size());
+        d_st = ap.arr<float>(B);
+        d_hi = ap.arr<uint16_t>((size_t)total_frames * KP); d_lo = ap.arr<uint16_t>((size_t)total_frames * KP);
+        d_out = ap.arr<float>((size_t)total_out); d_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
+    })) return -1;
+    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
+    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) || upload(h, d_st, st)) return -1;
+    region_begin(h, "total");
+    {
+        StftGainParams p = stft_gain_params(dev_in ? wav : d_wav, wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->dn.basis, n_fft, hop);
+        p.bias = h->dn.bias; p.strengths = d_st; p.spec_hi = d_hi; p.spec_lo = d_lo;
+        const double tile_frames = (double)64 * (double)g.tiles.size();
+        KScope ks(h, "stft_gain", 2.0 * 3.0 * tile_frames * n_fft * 2.0 * p.n_bins, (double)total_in * es + 4.0 * (double)total_frames * KP);
+        if (launch_stft_gain(p, h->stream)) return fail(h, "ev_denoise: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (!itiles.empty()) {
+        IstftParams p{};
+        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->dn.ibasis; p.env = h->dn.env;
+        p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = KP; p.out = d_out; p.out_i16 = d_i16;
+        KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)itiles.size() * (double)p.R * KP * hop,
+                  4.0 * (double)total_frames * KP + (double)total_out * (want16 ? 6.0 : 4.0));
+        if (launch_istft_ola(p, h->stream)) return fail(h, "ev_denoise: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    std::vector<int64_t> lo((size_t)B), offs((size_t)B + 1);
+    for (int b = 0; b < B; ++b) { lo[b] = iseqs[b].out_len; offs[b] = iseqs[b].out_off; }
+    offs[B] = total_out;
+    h->dn.lens.swap(lo); h->dn.offs.swap(offs);
+    reset_result(out);
+    out->batch = B; out->total = total_out; out->wav = d_out; out->wav_i16 = d_i16;
+    out->lens_out = h->dn.lens.data(); out->offsets = h->dn.offs.data();
+    return 0;
+}
+
 // ------------------------------------------------------------------- objective scoring (include/evhip.h: ev_score)
 static_assert(EV_SCORE_MAX_FRAMES == SCORE_MAX_FRAMES && EV_SCORE_MAX_CEPS == SCORE_MAX_CEPS && EV_FEATURES_MAX_MELS == SCORE_MAX_MELS &&
               EV_SCORE_CLAMP == SCORE_CLAMP && EV_SCORE_Q == 65536, "include/evhip.h states the limits of ev_score.hip");
@@ -1567,6 +1747,48 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
     }
     if (basis) (void)hipFree(basis);
     if (melT) (void)hipFree(melT);
+    return rc;
+}
+
+int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* window, int n_fft, int hop, const float* bias,
+                    const float* strengths, void* spec_hi, void* spec_lo, float* mag, void* stream) {
+    if (!wav || !wav_lens || B < 1 || B > 65535 || !denoise_shape_ok(n_fft, hop)) return -2;
+    if (!mag && (!bias || !strengths || !spec_hi || !spec_lo)) return -2;
+    FrameGrid g;
+    if (frame_grid_layout(B, wav_lens, n_fft / 2 + 1, hop, 64, g)) return -2;
+    std::vector<uint16_t> hb(stft_basis_halfs(n_fft));
+    stft_pack_basis(n_fft, window, hb.data());
+    DevTable t;
+    const size_t so = t.add(g.seqs), to = t.add(g.tiles), bo = t.add(hb);
+    if (t.commit()) return -1;
+    StftGainParams p = stft_gain_params(wav, wav_is_i16, t.at<StftSeq>(so), t.at<StftTile>(to), g.tiles.size(), t.at<char>(bo), n_fft, hop);
+    p.bias = bias; p.strengths = strengths; p.spec_hi = (uint16_t*)spec_hi; p.spec_lo = (uint16_t*)spec_lo;
+    p.mag = mag; p.mag_frames = EV_ALIGN_MAX_FRAMES;
+    int rc = launch_stft_gain(p, (hipStream_t)stream) ? -2 : 0;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
+    return rc;
+}
+
+int ev_op_istft(const void* spec_hi, const void* spec_lo, int B, const int32_t* frames, const float* window, int n_fft, int hop, float* out,
+                int16_t* out_i16, void* stream) {
+    if (!spec_hi || !spec_lo || !frames || !out || B < 1 || B > 65535 || !denoise_shape_ok(n_fft, hop)) return -2;
+    for (int b = 0; b < B; ++b) if (frames[b] < 1 || frames[b] > EV_ALIGN_MAX_FRAMES) return -2;
+    std::vector<IstftSeq> seqs; std::vector<StftTile> tiles;
+    istft_layout(B, frames, n_fft, hop, seqs, tiles);
+    if (tiles.empty()) return 0;      // one frame per utterance: no output
+    std::vector<uint16_t> hi(istft_basis_halfs(n_fft, hop));
+    std::vector<float> he(istft_envelope_floats(n_fft, hop));
+    istft_pack_basis(n_fft, hop, window, hi.data());
+    istft_pack_envelope(n_fft, hop, window, he.data());
+    DevTable t;
+    const size_t so = t.add(seqs), to = t.add(tiles), bo = t.add(hi), eo = t.add(he);
+    if (t.commit()) return -1;
+    IstftParams p{};
+    p.spec_hi = (const uint16_t*)spec_hi; p.spec_lo = (const uint16_t*)spec_lo; p.seqs = t.at<IstftSeq>(so); p.tiles = t.at<StftTile>(to);
+    p.n_tiles = (int)tiles.size(); p.ibasis = t.at<char>(bo); p.env = t.at<float>(eo);
+    p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = denoise_k_pad(n_fft); p.out = out; p.out_i16 = out_i16;
+    int rc = launch_istft_ola(p, (hipStream_t)stream) ? -2 : 0;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
     return rc;
 }
 

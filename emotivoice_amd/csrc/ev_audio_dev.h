@@ -1,5 +1,6 @@
-// Device parts shared by the audio kernels (ev_pitch, ev_resample, ev_stitch, ev_compare, ev_loudness, ev_limit, ev_deliver, ev_score): wave
-// reductions, the element rules that decide a bit, and the polyphase filter of ev_resample and ev_deliver.  Everything is inline with internal
+// Device parts shared by the audio kernels (ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_loudness, ev_limit, ev_deliver, ev_score,
+// ev_denoise): wave reductions, the element rules that decide a bit, the polyphase filter of ev_resample and ev_deliver, and the windowed DFT of
+// ev_features and ev_denoise.  Everything is inline with internal
 // linkage: the library exports nothing from here.  Include it before a file-wide `#pragma clang fp contract`: it leaves contraction at the default
 // (fast), as a file without pragmas has it.
 #pragma once
@@ -116,6 +117,70 @@ __device__ inline float sample_or_zero(const void* wav, int is16, int64_t in_off
 template <int THREADS, class D>
 __device__ inline void stage_run(D dst, const void* wav, int is16, int64_t in_off, int64_t L, int64_t first, int NS) {
     for (int i = threadIdx.x; i < NS; i += THREADS) dst(i) = sample_or_zero(wav, is16, in_off, L, first + i);
+}
+
+// ---- the windowed DFT of ev_features and ev_denoise: a GEMM with overlapping rows.  Row t of the A operand is padded[hop t .. hop t + n_fft), so a
+// tile of STFT_TF frames is ONE run of (STFT_TF - 1) hop + n_fft samples, kept in LDS as fp16 hi / lo planes (x = hi + 2^-11 lo).
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int STFT_TF = 64;      // frames per block
+constexpr int STFT_TB = 32;      // bins per basis tile (64 GEMM columns: re and im of the same bins)
+
+// LDS index of sample i of the block's run: 8 halfs of padding after every 256 samples, so that the 16 frames of an A fragment (hop apart:
+// 512 bytes at hop 256) start 16 bytes apart modulo the bank width.  A fragment's 8 samples start at a multiple of 8 and never straddle a pad.
+__host__ __device__ inline int stft_spad(int i) { return i + 8 * (i >> 8); }
+
+// a block of 256 threads stages samples first .. first + NS - 1 of the utterance wav[wav_off .. wav_off + L) as the two planes: reflected at
+// both ends, int16 converted (x / 32768), zero where the reflection still falls outside (frames of the tile that are never written)
+__device__ inline void stft_stage_planes(_Float16* sh, _Float16* sl, const void* wav, int is16, int64_t wav_off, int64_t L, int64_t first, int NS) {
+    const float* wf = reinterpret_cast<const float*>(wav) + wav_off;
+    const int16_t* wi = reinterpret_cast<const int16_t*>(wav) + wav_off;
+    for (int i = threadIdx.x; i < NS; i += 256) {
+        int64_t s = first + i;
+        if (s < 0) s = -s;
+        if (s >= L) s = 2 * (L - 1) - s;
+        float v = 0.f;
+        if (s >= 0 && s < L) v = is16 ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
+        const _Float16 h = (_Float16)v;
+        sh[stft_spad(i)] = h;
+        sl[stft_spad(i)] = (_Float16)((v - (float)h) * 2048.0f);
+    }
+}
+
+// One wave's share of one basis tile: its 32 frames (two 16-row tiles, A fragments at aoff[a] + 32 step) times the re and im columns of its 16
+// bins.  bp: the wave's packed basis (stft_pack_basis) at its lane; per 32-sample step 2 A fragments (hi, lo) from LDS, 4 B fragments (prefetched
+// one step ahead) and 12 MFMAs.  acc[a][c] takes hi x hi, accl[a][c] the two cross terms (in units of 2^-11); c = 0 re, 1 im.
+__device__ inline void stft_tile_gemm(const _Float16* sh, const _Float16* sl, const half8* bp, int KS, const int aoff[2], f4 acc[2][2], f4 accl[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) { acc[a][c] = f4{0.f, 0.f, 0.f, 0.f}; accl[a][c] = f4{0.f, 0.f, 0.f, 0.f}; }
+    half8 bn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bn[q] = bp[q * 64];
+    for (int ks = 0; ks < KS; ++ks) {
+        half8 b[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) b[q] = bn[q];
+        if (ks + 1 < KS) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bn[q] = bp[(size_t)(ks + 1) * 256 + q * 64];
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int at = stft_spad(aoff[a] + ks * 32);
+            const half8 ah = *reinterpret_cast<const half8*>(sh + at);
+            const half8 al = *reinterpret_cast<const half8*>(sl + at);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, b[2 * c], acc[a][c], 0, 0, 0);
+                accl[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, b[2 * c + 1], accl[a][c], 0, 0, 0);
+                accl[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, b[2 * c], accl[a][c], 0, 0, 0);
+            }
+        }
+    }
 }
 
 }  // namespace

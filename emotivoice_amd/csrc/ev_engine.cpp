@@ -1029,6 +1029,8 @@ void ev_destroy(ev_handle* h) {
     if (h->rs.tab) (void)hipFree(h->rs.tab);
     if (h->dlv.tab) (void)hipFree(h->dlv.tab);
     if (h->stitch.tab) (void)hipFree(h->stitch.tab);
+    for (void* t : {(void*)h->dn.basis, (void*)h->dn.ibasis, (void*)h->dn.env, (void*)h->dn.bias})
+        if (t) (void)hipFree(t);
     if (h->feat.basis) (void)hipFree(h->feat.basis);
     if (h->feat.melT) (void)hipFree(h->feat.melT);
     if (h->sblob) (void)hipFree(h->sblob);

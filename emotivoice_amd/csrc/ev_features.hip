@@ -5,34 +5,29 @@
 // padded[hop t .. hop t + n_fft), so a tile of 64 frames is ONE run of 63 hop + n_fft samples, kept in LDS for the block's life as fp16
 // hi / lo planes (x = hi + 2^-11 lo, the split of conv_gemm_split_kernel); reflect padding and the int16 conversion happen on load.
 // The basis is packed on the host (stft_pack_basis) in MFMA operand order: a wave's B fragment is one coalesced 16-byte load per lane.
+// The staging of the run and a wave's share of one basis tile (stft_stage_planes, stft_tile_gemm) are in ev_audio_dev.h: ev_denoise's forward
+// kernel runs the same code.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include <vector>
 
+#include "ev_audio_dev.h"
 #include "ev_kernels.h"
 
 namespace ev {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int FT_TF = 64;            // frames per block
-constexpr int FT_TB = 32;            // bins per basis tile (64 GEMM columns: re and im of the same bins)
-constexpr int FT_MAGP = FT_TF + 1;   // pitch of the [bin][frame] magnitude tile
-
-// LDS index of sample i of the block's run: 8 halfs of padding after every 256 samples, so that the 16 frames of an A fragment (hop apart:
-// 512 bytes at hop 256) start 16 bytes apart modulo the bank width.  A fragment's 8 samples start at a multiple of 8 and never straddle a pad.
-__host__ __device__ inline int spad(int i) { return i + 8 * (i >> 8); }
+constexpr int FT_TF = STFT_TF, FT_TB = STFT_TB;      // frames per block, bins per basis tile (ev_audio_dev.h)
+constexpr int FT_MAGP = FT_TF + 1;                   // pitch of the [bin][frame] magnitude tile
 
 }  // namespace
 
 int stft_run_samples(int n_fft, int hop) { return (FT_TF - 1) * hop + n_fft; }
 size_t stft_lds_bytes(int n_fft, int hop) {
-    const int nsp = spad(stft_run_samples(n_fft, hop)) + 8;
+    const int nsp = stft_spad(stft_run_samples(n_fft, hop)) + 8;
     return (size_t)nsp * 2 * sizeof(_Float16) + (size_t)FT_TB * FT_MAGP * sizeof(float);
 }
 int stft_shape_ok(int n_fft, int hop, int n_mels) {
@@ -92,25 +87,11 @@ __global__ __launch_bounds__(256) void stft_mel_kernel(const StftParams p) {
     const StftTile tl = p.tiles[blockIdx.x];
     const StftSeq sq = p.seqs[tl.seq];
     const int t0 = tl.t0, T = sq.frames, n_fft = p.n_fft, hop = p.hop;
-    const int NS = (FT_TF - 1) * hop + n_fft, NSP = spad(NS) + 8;
+    const int NS = (FT_TF - 1) * hop + n_fft, NSP = stft_spad(NS) + 8;
     _Float16* sh = reinterpret_cast<_Float16*>(smem);
     _Float16* sl = sh + NSP;
     float* magT = reinterpret_cast<float*>(sl + NSP);
-    {
-        const int64_t L = sq.len, first = (int64_t)t0 * hop - n_fft / 2;
-        const float* wf = reinterpret_cast<const float*>(p.wav) + sq.wav_off;
-        const int16_t* wi = reinterpret_cast<const int16_t*>(p.wav) + sq.wav_off;
-        for (int i = tid; i < NS; i += 256) {
-            int64_t s = first + i;
-            if (s < 0) s = -s;
-            if (s >= L) s = 2 * (L - 1) - s;
-            float v = 0.f;                                   // past the last frame of the utterance: frames of the tile that are not written
-            if (s >= 0 && s < L) v = p.wav_is_i16 ? (float)wi[s] * (1.0f / 32768.0f) : wf[s];
-            const _Float16 h = (_Float16)v;
-            sh[spad(i)] = h;
-            sl[spad(i)] = (_Float16)((v - (float)h) * 2048.0f);
-        }
-    }
+    stft_stage_planes(sh, sl, p.wav, p.wav_is_i16, sq.wav_off, sq.len, (int64_t)t0 * hop - n_fft / 2, NS);
     __syncthreads();
     const int fr = lane & 15, g = lane >> 4, nb = w & 1, mh = w >> 1;
     const int KS = n_fft / 32;
@@ -124,35 +105,7 @@ __global__ __launch_bounds__(256) void stft_mel_kernel(const StftParams p) {
     const half8* basis = reinterpret_cast<const half8*>(p.basis);
     for (int nt = 0; nt < p.n_btiles; ++nt) {
         f4 acc[2][2], accl[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) { acc[a][c] = f4{0.f, 0.f, 0.f, 0.f}; accl[a][c] = f4{0.f, 0.f, 0.f, 0.f}; }
-        const half8* bp = basis + (size_t)(nt * 2 + nb) * KS * 256 + lane;
-        half8 bn[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bn[q] = bp[q * 64];
-        for (int ks = 0; ks < KS; ++ks) {
-            half8 b[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = bn[q];
-            if (ks + 1 < KS) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) bn[q] = bp[(size_t)(ks + 1) * 256 + q * 64];
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int at = spad(aoff[a] + ks * 32);
-                const half8 ah = *reinterpret_cast<const half8*>(sh + at);
-                const half8 al = *reinterpret_cast<const half8*>(sl + at);
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, b[2 * c], acc[a][c], 0, 0, 0);
-                    accl[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, b[2 * c + 1], accl[a][c], 0, 0, 0);
-                    accl[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, b[2 * c], accl[a][c], 0, 0, 0);
-                }
-            }
-        }
+        stft_tile_gemm(sh, sl, basis + (size_t)(nt * 2 + nb) * KS * 256 + lane, KS, aoff, acc, accl);
         __syncthreads();          // the previous tile's magnitudes have been read
         const int bin = nt * FT_TB + nb * 16 + fr;
 #pragma unroll

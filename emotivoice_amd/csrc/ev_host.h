@@ -40,6 +40,7 @@ enum Arena {
     ARENA_SCORE_A,     // ev_score_load(0): the side's integer cepstra and F0 track, until the side is replaced
     ARENA_SCORE_B,     // ev_score_load(1) (likewise)
     ARENA_SCORE,       // ev_score (like ARENA_ALIGN; the distance and decision workspaces too)
+    ARENA_DENOISE,     // ev_denoise (like ARENA_ALIGN; the spectrum scratch too)
     ARENA_COUNT
 };
 
@@ -100,6 +101,10 @@ struct ScoreState {       // ev_score: the two sides and the host halves of the 
     std::vector<int64_t> sum_dist, path_offs; std::vector<int32_t> K, cnt[7], lens_a, lens_b, nonf_a, nonf_b;
     std::vector<double> sum_c, sum_c2, mcd, rmse, bias, vuv, warp;
 };
+struct DenoiseState {       // ev_denoise.  basis, ibasis, env, bias: its own tables on the device (one allocation each), never ev_features'
+    ev_denoise_config cfg{}; bool ready = false; char* basis = nullptr; char* ibasis = nullptr; float* env = nullptr; float* bias = nullptr;
+    std::vector<int64_t> lens, offs;
+};
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
 
 }  // namespace evh
@@ -135,7 +140,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score; evh::DenoiseState dn;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

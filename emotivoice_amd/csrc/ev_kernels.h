@@ -262,6 +262,45 @@ void stft_pack_basis(int n_fft, const float* window /* host (n_fft,) or null = p
 void stft_pack_mel(int n_fft, int n_mels, const float* mel_basis /* host (n_mels, n_bins) */, float* out /* host, stft_melT_floats */);
 int launch_stft_mel(const StftParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
 
+// ev_denoise (ev_denoise.hip): wav -> STFT -> gain per cell -> inverse STFT.  The two kernels meet in a scratch of fp16 hi / lo planes
+// (x = hi + 2^-11 lo), [total_frames][k_pad]: column 2 k is g Re, 2 k + 1 is g Im of bin k, k_pad = denoise_k_pad = 2 n_bins rounded up to 32 with
+// zero padding columns.  Utterances and forward tiles are the StftSeq / StftTile of ev_features.  Limits: stft_shape_ok, n_fft % hop == 0 and
+// R = n_fft / hop <= DN_MAX_R.
+constexpr int DN_MAX_R = 8, DN_TJ = 64, DN_TN = 128;      // chunks (of hop output samples) and output columns per block of the inverse
+struct StftGainParams {
+    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
+    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
+    const void* basis;                                // stft_pack_basis, on the device
+    const float* bias;                                // (n_bins,) device
+    const float* strengths;                           // (B,) device
+    int n_fft, hop, n_bins, n_btiles, k_pad;
+    uint16_t *spec_hi, *spec_lo;                      // the scratch planes; frame t of an utterance is row frm_off + t
+    float* mag; int mag_frames;                       // not null: the other mode -- fp32 magnitudes (row frm_off + t, n_bins columns) of frames t < mag_frames
+};
+struct IstftSeq { int64_t frm_off, out_off, out_len; int32_t frames, reserved; };      // first scratch row, first output sample, hop (frames - 1), T
+struct IstftParams {
+    const uint16_t *spec_hi, *spec_lo;
+    const IstftSeq* seqs; const StftTile* tiles; int n_tiles;      // a tile: utterance and first chunk j0 (chunk j = untrimmed samples hop j .. hop j + hop)
+    const void* ibasis;                               // istft_pack_basis, on the device
+    const float* env;                                 // istft_pack_envelope, on the device
+    int n_fft, hop, R, k_pad;
+    float* out; int16_t* out_i16;                     // packed at out_off; out_i16 may be null
+};
+int denoise_shape_ok(int n_fft, int hop);
+int denoise_k_pad(int n_fft);
+size_t istft_basis_halfs(int n_fft, int hop);
+size_t istft_envelope_floats(int n_fft, int hop);
+// Inverse basis planes.  Row q k_pad + 2 k + part (q = 0 .. R - 1: the frame j - R + 1 + q of chunk j), column n: float32(c_k cos / -c_k sin(2 pi k m / n_fft))
+// * window[m] at m = (R - 1 - q) hop + n, c_k = 1 for k = 0 and n_fft / 2, else 2; zero in the padding rows and columns.
+// Order: [16-column tile][k step of 32][hi, lo][lane][8]: lane l holds rows 32 step + 8 (l >> 4) + j of column (l & 15).
+void istft_pack_basis(int n_fft, int hop, const float* window /* host (n_fft,) or null = periodic hann */, uint16_t* out /* host, istft_basis_halfs */);
+// env[(qa R + qb) hop + n]: the float32 window-sum envelope at phase n of a chunk that the frames q = qa .. qb reach, summed in ascending q as the
+// reference's window_sumsquare sums it (float32 accumulator, float64 squares); 0 for qa > qb
+void istft_pack_envelope(int n_fft, int hop, const float* window, float* out /* host, istft_envelope_floats */);
+size_t stft_gain_lds_bytes(int n_fft, int hop);
+int launch_stft_gain(const StftGainParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
+int launch_istft_ola(const IstftParams& p, hipStream_t s);
+
 // ev_pitch (ev_pitch.hip): wav -> per-frame F0 (YIN), then the continuous fill and the standardisation.  The utterance and tile tables are the
 // StftSeq / StftTile of ev_features, with tiles of PITCH_TF frames.  Limits of the kernel: win <= PITCH_MAX_WIN, 1 <= hop <= win, 4 <= tau_min <
 // tau_max, tau_max + 1 <= win, and the tile's LDS (pitch_lds_bytes: its run of samples and three numbers per (frame, lag)) within PITCH_MAX_LDS.

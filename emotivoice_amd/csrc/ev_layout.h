@@ -32,6 +32,23 @@ inline int frame_grid_layout(int B, const int64_t* wav_lens, int64_t min_len, in
     return 0;
 }
 
+// ---------------------------------------------------------------- chunks of hop output samples, tiles of DN_TJ chunks (ev_denoise's inverse)
+// Utterance b has frames[b] = T frames at consecutive rows of the scratch and hop (T - 1) output samples: the untrimmed samples n_fft / 2 ..
+// n_fft / 2 + hop (T - 1), which lie in chunks (n_fft / 2) / hop .. (n_fft / 2 + hop (T - 1) - 1) / hop.  An utterance of one frame has no output
+// and no tile.  Returns the total of output samples.
+inline int64_t istft_layout(int B, const int32_t* frames, int n_fft, int hop, std::vector<ev::IstftSeq>& seqs, std::vector<ev::StftTile>& tiles) {
+    seqs.resize(B); tiles.clear();
+    int64_t fo = 0, oo = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = (int64_t)hop * (frames[b] - 1);
+        seqs[b] = ev::IstftSeq{fo, oo, n, frames[b], 0};
+        if (n > 0)
+            for (int64_t j = (n_fft / 2) / hop; j <= (n_fft / 2 + n - 1) / hop; j += ev::DN_TJ) tiles.push_back(ev::StftTile{b, (int32_t)j});
+        fo += frames[b]; oo += n;
+    }
+    return oo;
+}
+
 // ---------------------------------------------------------------- outputs n = ceil(len up / down), tiles of RS_TM outputs (ev_resample)
 constexpr int64_t RS_MAX_OUT = (int64_t)EV_ALIGN_MAX_FRAMES * 256;
 // output lengths, offsets and the tile table of a batch; 0 or the index + 1 of the first empty utterance (-(index + 1): too long with `extra` added)

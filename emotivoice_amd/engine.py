@@ -9,6 +9,7 @@ import numpy as np
 from . import _ffi
 from .config import EVShapes
 from .delivery import delivery_config
+from .denoise import denoise_config, removed_db
 from .engine_audio import EVAudio, cut, host_array
 from .limiter import as_config as limiter_config, pre_gain
 from .loudness import as_config as loudness_config
@@ -78,7 +79,7 @@ def make_ev_config(shapes: EVShapes, decoder_precision: str = "mx", keep_stages:
 
 class EVEngine(EVAudio):
     """One handle = one GPU + one stream + one workspace (include/evhip.h).  Not thread-safe.  The audio utilities (features, pitch, resample,
-    stitch, compare, flac, loudness, limit, deliver) are EVAudio's (engine_audio.py)."""
+    stitch, compare, flac, loudness, limit, deliver, score, denoise) are EVAudio's (engine_audio.py)."""
 
     def __init__(self, shapes: Optional[EVShapes] = None, device_id: int = 0, decoder_precision: Optional[str] = None,
                  keep_stages: bool = False, token_rate: str = "split", vocoder_chunk_mb: int = 0,
@@ -98,7 +99,9 @@ class EVEngine(EVAudio):
         self._blob_keepalive = None
         self.last: Optional[_ffi.ev_result] = None
         self.feature_config = self.resample_config = self.delivery_config = self._delivery_key = None      # set by features_setup() / resample_setup() / deliver_setup()
-        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver"):
+        self.denoise_config = self._denoise_key = None      # set by denoise_setup()
+        self._denoise_own_bias: Dict[tuple, np.ndarray] = {}      # the vocoder's own bias per (n_fft, hop), measured by denoise_setup on the loaded weights
+        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise"):
             setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
 
     # -- lifecycle
@@ -128,11 +131,15 @@ class EVEngine(EVAudio):
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.ev_load_weights(self._h, C.cast(buf, C.c_void_p), len(blob),
                                               manifest_json.encode() if manifest_json else None))
+        self._denoise_own_bias.clear()
+        self._denoise_key = None
 
     def load_blob_device(self, dptr: int, nbytes: int, keepalive=None):
         """Borrow a blob that already lives in device memory (e.g. after an RCCL broadcast)."""
         self._blob_keepalive = keepalive
         self._check(self._lib.ev_load_weights_device(self._h, C.c_void_p(dptr), nbytes, None))
+        self._denoise_own_bias.clear()
+        self._denoise_key = None
 
     # -- SimBERT prompt / content encoder (ev_style_*)
     def style_load(self, blob: bytes, cfg: dict):
@@ -302,7 +309,37 @@ class EVEngine(EVAudio):
                                               packed, flags)
         return res, cu
 
-    def _finish(self, wav_ptr: int, lens: np.ndarray, loudness, limiter, want_int16: bool, int16_only: bool, delivery=None):
+    def _denoise_ready(self, denoise):
+        """Before a synthesis whose waveform ev_denoise will read: measure the vocoder's own bias now if the config asks for it and none is
+        kept, because measuring runs the vocoder and would replace that waveform."""
+        if denoise is not None and denoise.bias is None and (int(denoise.n_fft), int(denoise.hop)) not in self._denoise_own_bias:
+            self.denoise_setup(denoise)
+
+    def _denoise_stage(self, wav_ptr: int, lens: np.ndarray, denoise, want_int16: bool, int16_only: bool, last_stage: bool):
+        """ev_denoise as the first output stage, on a packed device fp32 waveform: (ev_denoise_result, its host figures -- lens_out, offsets, with
+        ``denoise.report`` removed_db from ev_compare on the two device waveforms, and the audio when it is the last stage)."""
+        import dataclasses
+        dev = _ffi.EV_FLAG_DEVICE_INPUTS
+        dc = dataclasses.replace(denoise, want_int16=bool(last_stage and (denoise.want_int16 or want_int16))).validate()
+        if self._denoise_key != dc.key():
+            self.denoise_setup(dc)
+        B = len(lens)
+        res = self.denoise_raw(B, wav_ptr, False, lens, None, dev)
+        got = self.denoise_to_numpy(res, int16_only=int16_only, skip_wav=not last_stage)
+        if dc.report:
+            if np.array_equal(got["lens_out"], np.asarray(lens, np.int64)):      # the same packing on both sides: one call
+                cmp = self.compare_to_numpy(self.compare_raw(B, res.wav, wav_ptr, lens, dev))
+                got["removed_db"] = removed_db(cmp["sum_d2"], cmp["sum_y2"])
+            else:                                                                 # a length was cut to whole hops: utterance by utterance
+                offs_in, rd = np.concatenate([[0], np.cumsum(np.asarray(lens, np.int64))]), []
+                for b in range(B):
+                    cmp = self.compare_to_numpy(self.compare_raw(1, res.wav + 4 * int(got["offsets"][b]), wav_ptr + 4 * int(offs_in[b]),
+                                                                 got["lens_out"][b:b + 1], dev))
+                    rd.append(removed_db(cmp["sum_d2"], cmp["sum_y2"])[0])
+                got["removed_db"] = np.array(rd, np.float64)
+        return res, got
+
+    def _finish(self, wav_ptr: int, lens: np.ndarray, loudness, limiter, want_int16: bool, int16_only: bool, delivery=None, denoise=None):
         """The output stages between the synthesis (or ev_stitch) and ev_flac, on a packed device fp32 waveform.  loudness / limiter: a
         LoudnessConfig / LimiterConfig or None.  loudness alone: ev_loudness scales; limiter alone: ev_limit; both: ev_loudness measures only,
         the pre-gain is worked out on the host (the gain rule without its sample-peak step) and ev_limit scales and limits in its one pass.
@@ -314,9 +351,12 @@ class EVEngine(EVAudio):
         (delivered_list, delivered_rate and ``delivery`` = peak / clipped / n_samples in the returned audio)."""
         import dataclasses
         B, dev = len(lens), _ffi.EV_FLAG_DEVICE_INPUTS
-        last = figures = limited = gains = None
+        last = figures = limited = gains = denoised = None
         if delivery is not None:
             want_int16 = False
+        if denoise is not None:      # first: the later stages measure and shape the audio that is delivered
+            last, denoised = self._denoise_stage(wav_ptr, lens, denoise, want_int16, int16_only, loudness is None and limiter is None and delivery is None)
+            wav_ptr, lens = last.wav, denoised["lens_out"]
         if loudness is not None:
             lc = (dataclasses.replace(loudness, want_int16=loudness.want_int16 or want_int16) if limiter is None else
                   dataclasses.replace(loudness, target_lufs=float("nan"), want_int16=False))
@@ -329,8 +369,10 @@ class EVEngine(EVAudio):
                 figures["gain"], figures["flags"] = gains.copy(), np.array([f for _, f in pairs], np.uint8)
             last = self.limit_raw(B, wav_ptr, False, lens, gains, dataclasses.replace(limiter, want_int16=limiter.want_int16 or want_int16), dev)
             limited = self.limit_to_numpy(last, int16_only=int16_only, skip_wav=delivery is not None)
-        src = limited if limited is not None else figures if figures is not None else {}
+        src = limited if limited is not None else figures if figures is not None else denoised if denoised is not None else {}
         audio = {k: src.pop(k) for k in ("wav", "wav_list", "wav_i16", "wav_i16_list") if k in src}
+        if denoised is not None:
+            audio["denoise"] = denoised
         if delivery is None:
             return audio, figures, limited, last.wav_i16 if last is not None else None, None
         sr = int(self.shapes.sr)
@@ -340,6 +382,8 @@ class EVEngine(EVAudio):
         got = self.deliver_to_numpy(dres, delivery)
         audio = dict(delivered_list=got["delivered_list"], delivered_rate=int(delivery.sample_rate),
                      delivery=dict(peak=got["peak"], clipped=got["clipped"], n_samples=got["n_samples"], encoding=delivery.encoding))
+        if denoised is not None:
+            audio["denoise"] = denoised
         return audio, figures, limited, None, dres
 
     def _flac_delivered(self, sel, dres, given, sample_rate: int, **kw) -> List[Optional[bytes]]:
@@ -375,7 +419,8 @@ class EVEngine(EVAudio):
         return out
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
-                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None) -> Dict[str, object]:
+                   forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None,
+                   denoise=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
@@ -397,30 +442,41 @@ class EVEngine(EVAudio):
         after the last of the stages above (on the vocoder's waveform when there is none) and the response is what it writes: delivered_list
         (one float32 / int16 / uint8 array per utterance, at delivered_rate), ``delivery`` (peak, clipped, n_samples per utterance).  wav /
         wav_list / wav_i16 are then not returned -- the 16 kHz waveform stays on the device -- and want_int16 is ignored.  With ``flac`` the
-        encoding must be "s16": ev_flac reads ev_deliver's int16 on the device at the delivered rate, a stream decodes to delivered_list[b]."""
+        encoding must be "s16": ev_flac reads ev_deliver's int16 on the device at the delivered rate, a stream decodes to delivered_list[b].
+        denoise: None, True, a strength, a dict of DenoiseConfig's fields or an emotivoice_amd.denoise.DenoiseConfig: ev_denoise runs FIRST, on the
+        vocoder's waveform -- strength times the magnitude spectrum of the vocoder's answer to an all-zero mel (measured once per engine, or
+        config.bias) is subtracted from every STFT cell -- so that loudness is measured on the audio that is delivered; the lengths do not change
+        (a waveform of whole frames).  Alone it is the last stage: wav / wav_list hold its output, want_int16 and flac its clamped int16.
+        ``denoise`` in the result holds lens_out and, with report=True, removed_db: per utterance the removed energy relative to the input
+        (ev_compare on the two device waveforms).  The default strength 0.01 is an unmeasured starting value (emotivoice_amd.denoise)."""
         from .flac import FlacConfig
         sel = None
         if flac is not None and flac is not False:
             sel = np.ones(len(utts), bool) if flac is True or isinstance(flac, FlacConfig) else np.asarray(flac, bool)
             if sel.shape != (len(utts),):
                 raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (len(utts), sel.shape))
-        for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery)):
+        for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery), ("denoise", denoise)):
             if given is not None and not vocoder:
                 raise ValueError("%s needs the vocoder's waveform" % name)
         lc = None if loudness is None else loudness_config(loudness, int(self.shapes.sr))
         mc = None if limiter is None else limiter_config(limiter, int(self.shapes.sr))
         dc = delivery_config(delivery, int(self.shapes.sr))
+        nc = denoise_config(denoise, int(self.shapes.sr))
         if dc is not None and sel is not None and dc.encoding != "s16":
             raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
-        staged = lc is not None or mc is not None or dc is not None       # the audio is the last stage's: the synthesis makes no int16 and its waveform stays on the device
+        staged = lc is not None or mc is not None or dc is not None or nc is not None       # the audio is the last stage's: the synthesis makes no int16 and its waveform stays on the device
         flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
+        self._denoise_ready(nc)
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
         out = self.result_to_numpy(res, want_int16, skip_wav=staged)
         out["cu_seqlens"] = cu
         offs = out["mel_offsets"] * self.shapes.upsample_factor
         pcm_i16 = None
         if staged:
-            audio, figures, limited, pcm_i16, dres = self._finish(res.wav, np.diff(offs), lc, mc, want_int16 or sel is not None, False, dc)
+            audio, figures, limited, pcm_i16, dres = self._finish(res.wav, np.diff(offs), lc, mc, want_int16 or sel is not None, False, dc, nc)
+            if nc is not None:      # whole frames in, whole frames out: every offset above still holds
+                assert np.array_equal(audio["denoise"]["lens_out"], np.diff(offs)), "ev_denoise changed a length of whole frames"
+                out["denoise"] = audio.pop("denoise")
             if dc is not None:
                 out.update(audio)
             else:
@@ -438,7 +494,7 @@ class EVEngine(EVAudio):
         return out
 
     def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None,
-                        delivery=None) -> Dict[str, object]:
+                        delivery=None, denoise=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
@@ -457,11 +513,15 @@ class EVEngine(EVAudio):
         delivered_rate, in the delivery's encoding), ``delivery`` holds peak / clipped / n_samples, no 16 kHz audio is copied to the host,
         config.want_int16 is ignored and flac (encoding "s16" only) reads ev_deliver's int16 at the delivered rate.  sentence_times are in
         SECONDS and hold at any delivered rate; seg_pos / seg_start / seg_end / doc_lens and ``sample_rate`` stay on the engine's 16 kHz clock
-        (delivered_rate is returned next to them)."""
+        (delivered_rate is returned next to them).
+        denoise: as ``synthesize`` takes it, per document: ev_denoise right after ev_stitch and before the other stages.  Its output has whole
+        hops: a document whose length is no multiple of the hop (256) loses the up to 255 samples after its last whole hop, doc_lens then holds
+        the new lengths and ``denoise`` lens_out (and removed_db with report=True)."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
         dc = delivery_config(delivery, int(self.shapes.sr))
+        nc = denoise_config(denoise, int(self.shapes.sr))
         if dc is not None and flac and dc.encoding != "s16":
             raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
         if dc is not None and sc.want_int16:
@@ -477,15 +537,20 @@ class EVEngine(EVAudio):
         if S > 65535:
             raise ValueError("%d sentences exceed the 65535 segments of one ev_stitch call; split the documents over several calls" % S)
         seg_doc, pause_after = plan_document(seg_doc, pauses, sc.sample_rate)
+        self._denoise_ready(nc)
         res, _ = self._synthesize_call(utts, alpha, 0, None, prosody)
         mel_offs = host_array(res.mel_offsets, S + 1, np.int64) * self.shapes.upsample_factor
         st = self.stitch_raw(S, res.wav, mel_offs[:-1], np.diff(mel_offs), seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
-        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=lc is not None or mc is not None or dc is not None)
-        stage = "limiter" if mc is not None else "loudness" if lc is not None else "delivery" if dc is not None else "flac" if flac else None
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=lc is not None or mc is not None or dc is not None or nc is not None)
+        stage = ("denoise" if nc is not None else "limiter" if mc is not None else "loudness" if lc is not None else "delivery" if dc is not None else
+                 "flac" if flac else None)
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
         if empty and stage:
             raise ValueError("%s: document %d is empty after the cut" % (stage, empty[0]))
-        audio, figures, limited, pcm_i16, dres = self._finish(st.wav, out["doc_lens"], lc, mc, sc.want_int16, sc.want_int16, dc)
+        audio, figures, limited, pcm_i16, dres = self._finish(st.wav, out["doc_lens"], lc, mc, sc.want_int16, sc.want_int16, dc, nc)
+        if nc is not None:
+            out["denoise"] = audio.pop("denoise")
+            out["doc_lens"], out["doc_offsets"] = out["denoise"]["lens_out"], out["denoise"]["offsets"]
         if dc is not None:
             out.update(audio)
         for k, name in (("wav", "wav"), ("wav_list", "docs"), ("wav_i16", "wav_i16"), ("wav_i16_list", "docs_i16")):

@@ -1,5 +1,5 @@
 """The audio utilities of the libevhip.so handle (csrc/ev_audio.cpp): ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac,
-ev_loudness, ev_limit, ev_deliver and ev_score as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
+ev_loudness, ev_limit, ev_deliver, ev_score and ev_denoise as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
 handle, ``_check`` and ``d2h`` are its own."""
 from __future__ import annotations
 
@@ -411,6 +411,65 @@ class EVAudio:
             self.deliver_setup(dc, sample_rate)
         flat, is16, lens = pack_segments(wavs)
         return self.deliver_to_numpy(self.deliver_raw(len(lens), flat.ctypes.data, is16, lens, seeds), dc)
+
+    # -- vocoder bias removal (ev_denoise): STFT, a gain per cell from the vocoder's zero-mel spectrum, inverse STFT, on the device
+    def denoise_setup(self, config=None):
+        """ev_denoise_setup.  config: an emotivoice_amd.denoise.DenoiseConfig (default: strength 0.01, 1024 / 256).  With config.bias None the
+        engine measures its own vocoder's bias, which needs the weights and runs the vocoder once -- it replaces ``last`` and the waveform of the
+        last synthesis, so it must not happen between a synthesis and the stages that read its device waveform; the measured bias is kept and
+        passed back on later setups until other weights are loaded.  ``denoise_bias()`` reads it.  The setup is ev_denoise's own: it leaves
+        features_setup's alone."""
+        from .denoise import DenoiseConfig
+        dc = (config or DenoiseConfig()).validate()
+        c = _ffi.ev_denoise_config()
+        self._lib.ev_default_denoise_config(C.byref(c))
+        c.n_fft, c.hop, c.strength, c.want_i16 = int(dc.n_fft), int(dc.hop), float(dc.strength), 1 if dc.want_int16 else 0
+        own = getattr(self, "_denoise_own_bias", None)      # (n_fft, hop) -> the bias measured on the loaded weights: measured once, then passed back
+        shape = (int(dc.n_fft), int(dc.hop))
+        bias = (own or {}).get(shape) if dc.bias is None else np.ascontiguousarray(dc.bias, np.float32)
+        self._check(self._lib.ev_denoise_setup(self._h, C.byref(c), _ptr(bias) if bias is not None else None))
+        self.denoise_config, self._denoise_key = dc, dc.key()
+        if dc.bias is None and bias is None and own is not None:
+            own[shape] = self.denoise_bias()
+
+    def denoise_bias(self) -> np.ndarray:
+        """ev_denoise_bias: the (n_fft / 2 + 1,) float32 bias in use -- what to keep beside a checkpoint and pass back as DenoiseConfig.bias."""
+        if self.denoise_config is None:
+            raise ValueError("denoise_setup has not been called")
+        out = np.empty(int(self.denoise_config.n_fft) // 2 + 1, np.float32)
+        self._check(self._lib.ev_denoise_bias(self._h, _ptr(out)))
+        return out
+
+    def denoise_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, strengths=None, flags: int = 0) -> _ffi.ev_denoise_result:
+        """ev_denoise (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens and strengths (None: the
+        config's strength for every utterance) are host arrays.  The returned struct's device waveforms and host arrays stay valid until the next
+        denoise call on this engine."""
+        st = None
+        if strengths is not None:
+            st = np.ascontiguousarray(strengths, np.float32)
+            if st.shape != (B,):
+                raise ValueError("strengths must have B = %d entries" % B)
+        return self._call("denoise", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), _ptr(st) if st is not None else None, flags)
+
+    def denoise_to_numpy(self, res: _ffi.ev_denoise_result, int16_only: bool = False, skip_wav: bool = False) -> Dict[str, object]:
+        """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
+        output only; without it both).  ``skip_wav``: the host arrays only."""
+        B = res.batch
+        out: Dict[str, object] = dict(lens_out=host_array(res.lens_out, B, np.int64), offsets=host_array(res.offsets, B + 1, np.int64))
+        if not skip_wav:
+            out.update(self._wav_pair(res, res.total, out["offsets"], int16_only))
+        return out
+
+    def denoise(self, wavs: Sequence[np.ndarray], config=None, strengths=None) -> Dict[str, object]:
+        """Host signals -> the signals with the vocoder's bias removed.  wavs: one 1-D array per utterance, all int16 or all floating, each of
+        n_fft / 2 + 1 samples or more; config: None, a strength or an emotivoice_amd.denoise.DenoiseConfig; strengths: one per utterance (None:
+        the config's).  Every output has hop * (len // hop) samples."""
+        from .denoise import DenoiseConfig, denoise_config
+        dc = denoise_config(config) or DenoiseConfig().validate()
+        if getattr(self, "_denoise_key", None) != dc.key():
+            self.denoise_setup(dc)
+        flat, is16, lens = pack_segments(wavs, min_samples=int(dc.n_fft) // 2 + 1)
+        return self.denoise_to_numpy(self.denoise_raw(len(lens), flat.ctypes.data, is16, lens, strengths))
 
     # -- objective scoring (ev_score): MCD, F0 error and voiced / unvoiced error of a signal against a yardstick of another length, on the device
     def score_load_raw(self, side: int, B: int, n_mels: int, n_ceps: int, mel_ptr: int, lens: np.ndarray, f0_ptr: int = 0, flags: int = 0) -> None:

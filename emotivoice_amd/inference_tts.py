@@ -214,9 +214,12 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
         lines = f.readlines()
     eng = gen._ensure_engine()
     synthesize = eng.synthesize
-    if getattr(args, "loudness", None) is not None:      # every utterance normalised on the device (ev_loudness) before it is written
+    if getattr(args, "denoise", None) is not None:       # the vocoder's stationary bias removed on the device (ev_denoise), before every other output stage
         import functools
-        synthesize = functools.partial(eng.synthesize, loudness=float(args.loudness))
+        synthesize = functools.partial(synthesize, denoise=float(args.denoise))
+    if getattr(args, "loudness", None) is not None:     # every utterance normalised on the device (ev_loudness) before it is written
+        import functools
+        synthesize = functools.partial(synthesize, loudness=float(args.loudness))
     if getattr(args, "true_peak", None) is not None:     # the true peak held at a ceiling on the device (ev_limit); with --loudness it replaces the sample-peak limit
         import functools
         synthesize = functools.partial(synthesize, limiter=float(args.true_peak))
@@ -262,6 +265,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--true-peak", type=float, default=None, metavar="DBTP",
                    help="hold every utterance's true (inter-sample) peak at this ceiling with the look-ahead limiter on the device (e.g. -1); with "
                         "--loudness the gain to the target is then no longer cut by the utterance's largest sample; default: no limiter")
+    p.add_argument("--denoise", type=float, default=None, metavar="STRENGTH",
+                   help="remove the vocoder's stationary bias on the device before the other output stages: STRENGTH times the magnitude spectrum of "
+                        "its answer to an all-zero mel is subtracted from every STFT cell (e.g. 0.01, an unmeasured starting value); default: off")
     add_delivery_arguments(p)
     return p
 

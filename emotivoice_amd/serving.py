@@ -317,12 +317,16 @@ def _loudness_kw(loudness) -> dict:
     return {} if loudness is None else dict(loudness=loudness)
 
 
-def _output_kw(loudness, limiter) -> dict:
-    """``loudness`` and ``limiter`` (None, True, a ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: ev_limit on every utterance) of
-    the engine_*_synth_fn factories; like ``loudness`` a service-level setting.  Both None: synthesize is called exactly as before."""
+def _output_kw(loudness, limiter, denoise=None) -> dict:
+    """``loudness``, ``limiter`` (None, True, a ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: ev_limit on every utterance) and
+    ``denoise`` (None, a strength or an emotivoice_amd.denoise.DenoiseConfig: ev_denoise on every utterance, before the other stages) of the
+    engine_*_synth_fn factories; like ``loudness`` service-level settings.  All None: synthesize is called exactly as before."""
     kw = _loudness_kw(loudness)
     if limiter is not None:
         kw["limiter"] = limiter
+    if denoise is not None:
+        from .denoise import denoise_config
+        kw["denoise"] = denoise_config(denoise)
     return kw
 
 
@@ -337,28 +341,28 @@ def _delivered(delivery):
     return dict(delivery=dc), "delivered_list", lambda w: w.tobytes()
 
 
-def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
+def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
     """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness); ``limiter``: its
     true peak held at a ceiling (ev_limit); ``delivery``: every utterance converted to the client's rate and encoding on the device (ev_deliver)
-    and returned as ``bytes``."""
-    kw = _output_kw(loudness, limiter)
+    and returned as ``bytes``; ``denoise``: the vocoder's stationary bias removed from every utterance on the device (ev_denoise), first in the chain."""
+    kw = _output_kw(loudness, limiter, denoise)
     dkw, key, conv = _delivered(delivery)
     if not dkw:
         return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
     return lambda utts, alpha: [conv(w) for w in engine.synthesize(utts, alpha=alpha, **kw, **dkw)[key]]
 
 
-def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
     """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``,
-    ``limiter`` and ``delivery``: as ``engine_synth_fn``."""
-    kw = _output_kw(loudness, limiter)
+    ``limiter``, ``delivery`` and ``denoise``: as ``engine_synth_fn``."""
+    kw = _output_kw(loudness, limiter, denoise)
     dkw, key, conv = _delivered(delivery)
     if not dkw:
         return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
     return lambda utts, prosodies: [conv(w) for w in engine.synthesize(utts, prosody=prosodies, **kw, **dkw)[key]]
 
 
-def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None, denoise=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
     second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
@@ -366,8 +370,8 @@ def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, 
     ``flac_config``: an emotivoice_amd.flac.FlacConfig for every stream of this service (LPC order, precision, MD5, block size), like ``loudness``
     a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms.
     ``delivery``: as ``engine_synth_fn``, with the encoding "s16": the streams carry ev_deliver's int16 at the delivered rate, the other
-    utterances come back as its ``bytes``."""
-    lkw = _output_kw(loudness, limiter)
+    utterances come back as its ``bytes``.  ``denoise``: as ``engine_synth_fn``; the streams carry the denoised audio."""
+    lkw = _output_kw(loudness, limiter, denoise)
     if flac_config is not None:
         flac_config.validate()
     dkw, key, conv = _delivered(delivery)

@@ -912,6 +912,72 @@ typedef struct ev_deliver_result {
  * ev_deliver or ev_destroy -- the contract of ev_limit_result. */
 int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const uint32_t* seeds, uint32_t flags, ev_deliver_result* out);
 
+/* Vocoder bias removal (ev_denoise): the stationary tone and hiss a GAN vocoder emits even for an all-zero mel, subtracted from the magnitude
+ * spectrum of every utterance on the device -- the `Denoiser` of the Tacotron 2 / WaveGlow / FastPitch recipes.  It runs first in the output
+ * chain, on the vocoder's (or ev_stitch's) waveform, before ev_loudness, ev_limit and ev_deliver.  The arithmetic is that of the reference's
+ * STFT class (models/prompt_tts_modified/stft.py: transform, clamp(mag - s bias, 0), inverse with window-sum normalisation), against which it is
+ * tested; NVIDIA's Denoiser code itself was not available.  The default strength 0.01 is FastPitch's published value for HiFi-GAN, an UNMEASURED
+ * starting value here: nobody has listened to a released checkpoint with it, and no audible improvement is claimed.
+ *   1 Input.  x[i], i < L: the fp32 sample, or s / 32768 for int16.  padded[i] = x reflected by n_fft / 2 at both ends (numpy's "reflect": the edge
+ *     sample is not repeated), which needs L >= n_fft / 2 + 1.  T = L / hop + 1 frames (integer division); frame t is padded[hop t .. hop t + n_fft).
+ *   2 Basis.  Exactly ev_features' (step 2 there): float32(cos / -sin(2 pi k n / n_fft)) * float32 window[n], k = 0 .. n_fft / 2; window NULL =
+ *     periodic hann evaluated in float64 and rounded to float32.  Re[t][k], Im[t][k] = frame t times the two rows of bin k, operands split as
+ *     x = hi + 2^-11 lo in fp16 (lo x lo dropped), products accumulated in fp32 by the matrix cores.
+ *   3 Gain.  mag = sqrtf(Re^2 + Im^2); g = mag > 0 ? max(mag - s_b * bias[k], 0) / mag : 0, in fp32, s_b = strengths[b] or cfg.strength; mag == 0
+ *     (and a NaN) gives a zero cell.  The cell becomes g Re, g Im, again split into fp16 hi / lo planes in a scratch in device memory
+ *     ([frame][k_pad], k_pad = 2 (n_fft / 2 + 1) rounded up to 32): |g Re| and |g Im| must stay below 65504, which holds for |x| <= 100.
+ *   4 Inverse.  The untrimmed signal u[i], i < n_fft + hop (T - 1): u[i] = sum over the frames t with 0 <= i - hop t < n_fft, t ascending, of
+ *     sum_k c_k (g Re[t][k] cos(2 pi k m / n_fft) - g Im[t][k] sin(2 pi k m / n_fft)) * window[m], m = i - hop t, c_k = 1 for k = 0 and n_fft / 2,
+ *     else 2 (the weights of the real inverse DFT; the reference's pinv basis equals this wherever Im[0] = Im[n_fft / 2] = 0, which a gain on a real
+ *     signal's spectrum preserves).  The table entries are float32(c_k cos / -c_k sin) * float32 window[m]; one GEMM row per chunk of hop samples
+ *     over the R = n_fft / hop frames that reach it, so the overlap-add is the GEMM's own fp32 accumulation in one fixed order.
+ *   5 Envelope.  env[i] = the reference's window_sumsquare: a float32 accumulator from 0, += (double)window[m]^2 over the same frames, t ascending
+ *     (window NULL: the square of the float64 hann before its rounding to float32, as the reference squares scipy's float64 window).
+ *     y = u * (1.0f / n_fft) (one fp32 product; the reference's pinv scale hop / n_fft and its final n_fft / hop cancel), then y = y / env[i]
+ *     where env[i] > FLT_MIN (the reference's tiny), else y unchanged.
+ *   6 Trim.  out[i] = y[i + n_fft / 2], i < hop (L / hop): the output length is L rounded down to a multiple of hop (the reference's), so a
+ *     waveform of whole frames -- every ev_result.wav -- keeps its length.
+ *   7 int16 (want_i16): ev_loudness' rule -- t = out * 32768.0f (one fp32 product), clamped to [-32768, 32767], truncated toward zero; NaN -> 0.
+ * Strength 0 is the identity up to the float32 round trip (about 1e-7 of the peak).  No atomics and nothing carried between blocks: an
+ * utterance gives the same bits alone, anywhere in a batch and in any batch, as int16 or as the equal floats, from host or device memory.
+ * Shapes: n_fft a multiple of 128 up to EV_FEATURES_MAX_NFFT, hop a multiple of 8 dividing n_fft with n_fft / hop <= EV_DENOISE_MAX_R, and
+ * ev_features' limit EV_FEATURES_MAX_RUN on 63 hop + n_fft.  The scratch takes 4 k_pad bytes per frame (about 130 MB at 32 x 16 s). */
+#define EV_DENOISE_MAX_R 8             /* n_fft / hop */
+#define EV_DENOISE_BIAS_FRAMES 88      /* the zero mel ev_denoise_setup vocodes to measure the bias (the Denoiser's choice) */
+typedef struct ev_denoise_config {
+    uint32_t struct_size;          /* sizeof(ev_denoise_config); any other value is rejected */
+    int32_t  n_fft, hop;
+    int32_t  want_i16;             /* also write the clamped int16 waveform */
+    float    strength;             /* >= 0 and finite: s_b where ev_denoise is given no strengths */
+    const float* window;           /* HOST (n_fft,) or NULL = periodic hann; copied */
+} ev_denoise_config;
+void ev_default_denoise_config(ev_denoise_config* cfg);      /* 1024, 256, no int16, strength 0.01, window NULL */
+/* Builds the tables in a workspace of its own (it leaves ev_features_setup alone) and takes the bias: `bias` is a HOST array (n_fft / 2 + 1,) of
+ * finite values >= 0, or NULL -- then the engine measures its own: it runs ev_vocoder on an all-zero mel of EV_DENOISE_BIAS_FRAMES frames (which
+ * needs weights and replaces the last ev_result) and keeps the magnitudes (step 3's mag) of frame 0 of that waveform on the device.  Rejected
+ * (message naming the field): a wrong struct_size, a shape outside the limits above, a negative or non-finite strength or bias value.  A
+ * rejected setup leaves the previous one in place. */
+int ev_denoise_setup(ev_handle* h, const ev_denoise_config* cfg, const float* bias);
+/* Copies the bias in use to out, HOST (n_fft / 2 + 1,): what to store beside a checkpoint and pass back to ev_denoise_setup, bit for bit. */
+int ev_denoise_bias(ev_handle* h, float* out);
+
+typedef struct ev_denoise_result {
+    uint32_t struct_size;          /* sizeof(ev_denoise_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* offsets[batch] */
+    const float*   wav;            /* DEVICE, (total,) utterances back to back: what ev_loudness / ev_limit / ev_deliver / ev_flac take */
+    const int16_t* wav_i16;        /* DEVICE, the same layout; NULL without want_i16 */
+    const int64_t* lens_out;       /* (batch,) HOST: hop * (lens[b] / hop) */
+    const int64_t* offsets;        /* (batch+1,) HOST */
+} ev_denoise_result;
+/* wav / wav_is_i16 / lens / EV_FLAG_DEVICE_INPUTS as ev_limit (an ev_result.wav with lens = mel_lens * 256 or an ev_stitch_result.wav goes straight
+ * in).  strengths: a HOST array (B,) of finite values >= 0, or NULL = cfg.strength for every utterance.  Rejected before anything is launched
+ * (message naming the field or utterance; the previous result stays valid): a NULL h, wav, lens or out, a wrong struct_size, no ev_denoise_setup,
+ * B outside [1, 65535], lens[b] < n_fft / 2 + 1, an utterance of more than EV_ALIGN_MAX_FRAMES frames, a bad strength.  The result lives in a
+ * workspace of its own and is complete when the call returns; it stays valid across every other entry point until the next ev_denoise or
+ * ev_destroy -- the contract of ev_limit_result. */
+int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* strengths, uint32_t flags, ev_denoise_result* out);
+
 /* Objective scoring (ev_score): how close a signal a (under test: a synthesised utterance) is to a signal b (the yardstick: a recording of the
  * same sentence) when the two differ in length and timing -- mel-cepstral distortion, F0 error in cents and the voiced / unvoiced error rate
  * along a dynamic-time-warping path, on the device.  ev_compare is the measure for signals of equal length; with EV_SCORE_LINEAR the same scores

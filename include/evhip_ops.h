@@ -218,6 +218,18 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
                    int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
                    void* hip_stream);
 
+/* ev_denoise's two kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_denoise).  ev_op_stft_gain: steps 1-3, wav (B utterances
+ * back to back, fp32 or int16), bias (n_fft / 2 + 1,) and strengths (B,) -> the scratch planes spec_hi / spec_lo, fp16 (sum_b T_b, k_pad) each, T_b =
+ * wav_lens[b] / hop + 1, k_pad = 2 (n_fft / 2 + 1) rounded up to 32: column 2 k holds g Re, 2 k + 1 g Im of bin k, value = hi + lo / 2048, padding columns
+ * zero.  With mag not NULL it writes the fp32 magnitudes (sum_b T_b, n_fft / 2 + 1) instead and reads neither bias nor strengths nor the planes.
+ * ev_op_istft: steps 4-7, the planes of T_b = frames[b] frames per utterance -> out (sum_b hop (T_b - 1),) fp32 and, unless NULL, out_i16.  wav_lens,
+ * frames and window (n_fft,) or NULL are HOST arrays: the calls pack their tables, wait for the stream and free them.  -2 for what a kernel would
+ * mishandle: a shape outside ev_denoise's limits, wav_lens[b] < n_fft / 2 + 1, T_b outside [1, 16384], B outside [1, 65535]. */
+int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* window, int n_fft, int hop, const float* bias,
+                    const float* strengths, void* spec_hi, void* spec_lo, float* mag, void* hip_stream);
+int ev_op_istft(const void* spec_hi, const void* spec_lo, int B, const int32_t* frames, const float* window, int n_fft, int hop, float* out,
+                int16_t* out_i16, void* hip_stream);
+
 /* ev_pitch's two kernels on caller-provided DEVICE buffers (semantics: include/evhip.h, ev_pitch).  ev_op_pitch_yin: steps 1-5, wav (B utterances back
  * to back, fp32 or int16) -> f0_hz and aperiodicity (sum_b T_b,), T_b = wav_lens[b] / hop + 1, and, unless NULL, the chosen lag tau (-1 = unvoiced).
  * ev_op_pitch_fill: steps 6-7, f0_hz (sum_b frames[b],) -> pitch of the same shape; pitch must not be f0_hz.  wav_lens / frames are HOST arrays; the

@@ -1,0 +1,278 @@
+"""Vocoder bias removal on the CPU: the float64 oracle (tests/denoise_oracle.py) against the fixtures of the reference's own STFT class
+(tests/golden/denoise, made by make_golden_denoise.py), the identity at strength 0, the output lengths, the envelope table against the
+reference's window_sumsquare, the configuration, and the place of ev_denoise in the output chain of EVEngine against the stand-in library of
+tests/fake_evhip.py with a trivial ev_denoise added: it ADDS 1/8 and cuts every utterance to whole hops."""
+import ctypes as C
+import glob
+import os
+
+import numpy as np
+import pytest
+
+import denoise_oracle as do
+import fake_evhip as fk
+from conftest import GOLDEN_DIR
+from emotivoice_amd import _ffi
+from emotivoice_amd.denoise import DEFAULT_STRENGTH, DenoiseConfig, denoise_config, out_len, removed_db
+
+DN_DIR = os.path.join(GOLDEN_DIR, "denoise")
+FIXTURES = sorted(glob.glob(os.path.join(DN_DIR, "dn_[a-g]_*.npz")))
+DEV = _ffi.EV_FLAG_DEVICE_INPUTS
+# the reference accumulates n_fft = 1024 float32 products per cell and per sample: sqrt(1024) * 2^-24 of the peak
+REF_BOUND = 32 * 2.0 ** -24
+
+
+def test_the_fixtures_are_the_ones_the_issue_lists():
+    names = [os.path.basename(p)[:-4] for p in FIXTURES]
+    assert names == ["dn_a_l513", "dn_b_l2048", "dn_c_l20011", "dn_d_l20011_i16", "dn_e_l20011_s0", "dn_f_l20011_s30", "dn_g_l8192_zeros"]
+    gs = [dict(np.load(p)) for p in FIXTURES]
+    assert [g["wav"].size for g in gs] == [513, 2048, 20011, 20011, 20011, 20011, 8192]
+    assert gs[3]["wav"].dtype == np.int16 and all(g["wav"].dtype == np.float32 for g in gs[:3])
+    assert [round(float(g["strength"]), 3) for g in gs] == [0.1, 0.1, 0.1, 0.1, 0.0, 30.0, 0.1]
+    assert np.all(gs[6]["wav"][2048:6144] == 0)
+    assert all(os.path.getsize(p) < 1_000_000 for p in glob.glob(os.path.join(DN_DIR, "*.npz")))
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[:-4])
+def test_oracle_against_the_reference(path):
+    """The reference's float32 transform -> clamp -> inverse lies within its own float32 error of the float64 closed form, the recorded ref_err is
+    that error, and the output has hop * (L // hop) samples."""
+    g = dict(np.load(path))
+    y64 = do.denoise64(g["wav"], g["bias"], float(g["strength"]))
+    assert y64.size == g["ref_out"].size == out_len(g["wav"].size) == 256 * (g["wav"].size // 256)
+    e = do.peak_error(g["ref_out"], y64)
+    print(os.path.basename(path), "E(ref)", e)
+    assert e == pytest.approx(float(g["ref_err"]), rel=1e-6) and e <= REF_BOUND
+
+
+def test_oracle_inverse_against_the_references_inverse():
+    g = dict(np.load(os.path.join(DN_DIR, "dn_h_inverse_t9.npz")))
+    assert np.all(g["im"][:, 0] == 0) and np.all(g["im"][:, -1] == 0)
+    y64 = do.istft64(g["re"].astype(np.float64), g["im"].astype(np.float64))
+    e = do.peak_error(g["ref_out"], y64)
+    assert y64.size == 2048 and e == pytest.approx(float(g["ref_err"]), rel=1e-6) and e <= REF_BOUND
+    # the weights 1, 2, ..., 2, 1 matter: the all-two basis is far outside
+    assert do.peak_error(g["ref_out"], do.istft64(g["re"].astype(np.float64), g["im"].astype(np.float64), all_two=True)) > 100 * REF_BOUND
+
+
+def test_strength_zero_is_the_identity_edges_included():
+    """3 x 2^-24 of the peak: the float32 rounding of the three tables (forward basis, inverse basis, envelope: half an ulp, 2^-24 relative, each)
+    is all that separates the float64 round trip from the input."""
+    for path in (FIXTURES[0], FIXTURES[2]):
+        g = dict(np.load(path))
+        y = do.denoise64(g["wav"], g["bias"], 0.0)
+        assert do.peak_error(y, g["wav"][:y.size]) <= 3 * 2.0 ** -24
+    z = np.zeros(1024, np.float32)
+    assert np.all(do.denoise64(z, np.ones(513, np.float32), 1.0) == 0)          # mag == 0: zero cells, no NaN
+
+
+def test_envelope_table_is_the_references_window_sumsquare():
+    """Bit for bit, for every T of the fixture (1, 3 and 4 frames: both ends reach into every chunk)."""
+    ref = dict(np.load(os.path.join(DN_DIR, "dn_envelope.npz")))
+    tab = do.envelope_table()
+    assert tab.shape == (4, 4, 256) and tab.dtype == np.float32
+    for key, ws in ref.items():
+        T = int(key[1:])
+        assert np.array_equal(do.envelope_from_table(tab, T), ws) and np.array_equal(do.envelope_f32(T), ws), key
+    interior = ref["T79"][1024:-1024].reshape(-1, 256)
+    assert np.all(interior == tab[0, 3][None, :]) and abs(float(tab[0, 3].mean()) - 1.5) < 1e-6      # constant in between: 4 hann^2 sum to 1.5
+    # another shape, against the plain statement
+    t2 = do.envelope_table(512, 128)
+    for T in (1, 2, 5, 11):
+        assert np.array_equal(do.envelope_from_table(t2, T, 512, 128), do.envelope_f32(T, 512, 128))
+
+
+def test_config_validation():
+    assert DenoiseConfig().validate().strength == DEFAULT_STRENGTH == 0.01
+    assert denoise_config(None) is None and denoise_config(False) is None
+    assert denoise_config(True).strength == 0.01 and denoise_config(0.1).strength == 0.1 and denoise_config(0).strength == 0.0
+    c = denoise_config(dict(strength=0.2, report=True))
+    assert (c.strength, c.report, c.n_fft, c.hop, c.want_int16) == (0.2, True, 1024, 256, False)
+    given = DenoiseConfig(strength=0.3, bias=np.ones(513, np.float32))
+    assert denoise_config(given) is given
+    assert given.key() != DenoiseConfig(strength=0.3).key() and DenoiseConfig(0.3).key() == DenoiseConfig(0.3, report=True).key()
+    for bad in (DenoiseConfig(strength=-0.1), DenoiseConfig(strength=float("nan")), DenoiseConfig(strength=float("inf")), DenoiseConfig(strength=True),
+                DenoiseConfig(n_fft=1000), DenoiseConfig(n_fft=4096), DenoiseConfig(hop=96), DenoiseConfig(hop=64), DenoiseConfig(n_fft=2048, hop=512),
+                DenoiseConfig(bias=np.ones(512, np.float32)), DenoiseConfig(bias=-np.ones(513, np.float32)), DenoiseConfig(bias=np.full(513, np.nan))):
+        with pytest.raises(ValueError):
+            bad.validate()
+    for bad in ("0.1", [0.1], object()):
+        with pytest.raises(ValueError):
+            denoise_config(bad)
+    DenoiseConfig(n_fft=512, hop=128).validate()
+    DenoiseConfig(n_fft=2048, hop=256).validate()
+    assert out_len(20011) == 19968 and out_len(513) == 512 and out_len(255) == 0
+    assert removed_db([1.0, 0.0], [100.0, 4.0]).tolist() == [-20.0, -np.inf]
+
+
+def test_cli_has_the_denoise_flag():
+    from emotivoice_amd.inference_tts import build_parser
+    p = build_parser()
+    assert p.parse_args(["-t", "x"]).denoise is None
+    assert p.parse_args(["-t", "x", "--denoise", "0.01"]).denoise == 0.01
+
+
+# ---------------------------------------------------------------- the chain, against the stand-in library
+TOKENS = (3, 5, 2)
+LENS = [t * fk.UP for t in TOKENS]
+OFFS = np.concatenate([[0], np.cumsum(LENS)])
+N = int(OFFS[-1])
+EIGHTH = np.float32(0.125)
+
+
+class DenoiseLib(fk.FakeLib):
+    setup = None
+
+    def ev_default_denoise_config(self, ref):
+        c = ref._obj
+        c.struct_size, c.n_fft, c.hop, c.strength = C.sizeof(_ffi.ev_denoise_config), 1024, 256, 0.01
+
+    def ev_denoise_setup(self, h, ref, bias):
+        self.setup = fk._cfg(ref)
+        self.log.append(dict(name="ev_denoise_setup", cfg=dict(self.setup), bias=None if bias is None else fk._host(bias, C.c_float, 513).tolist()))
+        if bias is None:      # measuring runs the vocoder: whatever the synthesis left is gone
+            self.log.append(dict(name="ev_vocoder(zero mel)"))
+            if "synth.wav" in self.bufs:
+                self.bufs["synth.wav"][:] = np.nan
+        return 0
+
+    def ev_denoise_bias(self, h, out):
+        self.log.append(dict(name="ev_denoise_bias"))
+        half = np.full(513, 0.5, np.float32)
+        C.memmove(out, half.ctypes.data, half.nbytes)
+        return 0
+
+    def ev_denoise(self, h, B, wav, is_i16, lens, strengths, flags, ref):
+        ln = fk._host(lens, C.c_int64, B)
+        x, src = self._read(wav, is_i16, ln)
+        self.log.append(dict(name="ev_denoise", B=B, flags=int(flags), lens=ln.tolist(), is_i16=int(is_i16), src=src, strengths=strengths, cfg=dict(self.setup)))
+        offs = np.concatenate([[0], np.cumsum(ln)])
+        lo = ln // 256 * 256
+        out = np.concatenate([x[a:a + n] + EIGHTH for a, n in zip(offs[:-1], lo)])
+        res = ref._obj
+        res.batch, res.total = B, int(lo.sum())
+        return self._fill("denoise", ref, wav=out, wav_i16=fk.to_i16(out) if self.setup["want_i16"] else None, lens_out=lo.astype(np.int64),
+                          offsets=np.concatenate([[0], np.cumsum(lo)]).astype(np.int64))
+
+    def ev_compare(self, h, B, a, b, lens, flags, ref):
+        ln = fk._host(lens, C.c_int64, B)
+        self.log.append(dict(name="ev_compare", B=B, flags=int(flags), lens=ln.tolist(), a=self.where(a), b=self.where(b)))
+        z, zi = np.zeros(B), np.zeros(B, np.int64)
+        res = ref._obj
+        res.batch, res.total = B, int(ln.sum())
+        return self._fill("compare", ref, sum_d=z, sum_d2=np.full(B, 1.0), sum_y=z, sum_y2=np.full(B, 100.0), rel_l2=z, rel_l2_ac=z, max_abs_d=np.zeros(B, np.float32),
+                          argmax_d=zi, peak_y=np.zeros(B, np.float32), nonfinite=zi, chunk_offsets=np.arange(B + 1, dtype=np.int64), chunk_d2=z, chunk_y2=z)
+
+
+def utterances():
+    return [dict(ling=np.arange(t) + 1, speaker=b, style=np.zeros(768, np.float32), content=np.zeros(768, np.float32)) for b, t in enumerate(TOKENS)]
+
+
+@pytest.fixture
+def eng(monkeypatch):
+    lib = DenoiseLib()
+    monkeypatch.setattr(_ffi, "lib", lambda: lib)
+    from emotivoice_amd.engine import EVEngine
+    e = EVEngine()
+    e.fake = lib
+    yield e
+    e.close()
+
+
+def test_denoise_runs_first_and_the_bias_is_measured_before_the_synthesis(eng):
+    lib = eng.fake
+    out = eng.synthesize(utterances(), denoise=0.1, loudness=-16.0, limiter=-1.0, want_int16=True, flac=True)
+    assert lib.names() == ["ev_denoise_setup", "ev_vocoder(zero mel)", "ev_denoise_bias", "ev_synthesize", "ev_denoise", "ev_loudness", "ev_limit", "ev_flac"]
+    assert lib.calls("ev_denoise_setup")[0]["bias"] is None      # measured once, before the synthesis
+    (dn,), (ld,), (lim,) = lib.calls("ev_denoise"), lib.calls("ev_loudness"), lib.calls("ev_limit")
+    assert (dn["B"], dn["flags"], dn["lens"], dn["is_i16"], dn["src"], dn["strengths"]) == (3, DEV, LENS, 0, ("synth.wav", 0), None)
+    assert abs(dn["cfg"]["strength"] - 0.1) < 1e-7 and dn["cfg"]["want_i16"] == 0      # not the last stage: no int16
+    assert ld["src"] == ("denoise.wav", 0) and lim["src"] == ("denoise.wav", 0) and lim["cfg"]["want_i16"] == 1
+    assert lib.calls("ev_flac")[0]["src"] == ("limit.wav_i16", 0)
+    assert np.all(np.isfinite(out["wav"])) and out["denoise"]["lens_out"].tolist() == LENS and "loudness" in out and "limiter" in out
+    # a later call with another setup measures nothing: the kept bias is passed back
+    n = len(lib.log)
+    eng.synthesize(utterances(), denoise=0.2, want_int16=True)
+    assert [e["name"] for e in lib.log[n:] if e["name"] != "ev_memcpy_d2h"] == ["ev_synthesize", "ev_denoise_setup", "ev_denoise"]
+    assert lib.calls("ev_denoise_setup")[-1]["bias"] == [0.5] * 513 and lib.calls("ev_denoise_setup")[-1]["cfg"]["want_i16"] == 1
+
+
+def test_denoise_alone_is_the_last_stage(eng):
+    lib = eng.fake
+    out = eng.synthesize(utterances(), denoise=DenoiseConfig(strength=0.2, bias=np.full(513, 0.25, np.float32), report=True), want_int16=True, flac=[True, False, True])
+    assert "ev_vocoder(zero mel)" not in lib.names() and lib.names()[:3] == ["ev_synthesize", "ev_denoise_setup", "ev_denoise"]
+    (st,) = lib.calls("ev_denoise_setup")
+    assert st["bias"] == [0.25] * 513 and st["cfg"]["want_i16"] == 1 and abs(st["cfg"]["strength"] - 0.2) < 1e-7
+    want = fk.ramp(N) + EIGHTH
+    assert np.array_equal(out["wav"], want) and np.array_equal(out["wav_i16"], fk.to_i16(want))
+    assert all(np.array_equal(w, want[a:b]) for w, a, b in zip(out["wav_list"], OFFS[:-1], OFFS[1:]))
+    (cmp,) = lib.calls("ev_compare")
+    assert (cmp["a"], cmp["b"], cmp["lens"], cmp["flags"]) == (("denoise.wav", 0), ("synth.wav", 0), LENS, DEV)
+    assert out["denoise"]["removed_db"].tolist() == [-20.0] * 3
+    assert [e["src"] for e in lib.calls("ev_flac")] == [("denoise.wav_i16", 0), ("denoise.wav_i16", 2 * int(OFFS[2]))]
+    assert out["flac_list"][1] is None and out["flac_list"][0] == b"fLaC" + fk.to_i16(want).tobytes()[:8]
+
+
+def test_delivery_reads_the_denoised_waveform(eng):
+    from emotivoice_amd.delivery import DeliveryConfig
+    import test_deliver_chain as tdc
+
+    class Both(DenoiseLib, tdc.DeliverLib):
+        pass
+    lib = Both()
+    lib.log, lib.bufs = eng.fake.log, eng.fake.bufs
+    eng._lib = eng.fake = lib
+    out = eng.synthesize(utterances(), denoise=DenoiseConfig(bias=np.ones(513, np.float32)), delivery=DeliveryConfig(8000, "s16"))
+    (dl,) = lib.calls("ev_deliver")
+    assert dl["src"] == ("denoise.wav", 0) and lib.calls("ev_denoise")[0]["cfg"]["want_i16"] == 0
+    assert "wav" not in out and "denoise" in out and [e["src"][0] for e in lib.calls("ev_memcpy_d2h")] == ["deliver.data"]
+
+
+def test_synthesize_long_denoises_after_the_stitch_and_cuts_to_whole_hops(eng, monkeypatch):
+    from emotivoice_amd.longform import StitchConfig
+    lib = eng.fake
+    u = utterances()
+    out = eng.synthesize_long([dict(utts=u[:2]), (u[2:], None)], config=StitchConfig(want_int16=True), denoise=DenoiseConfig(bias=np.ones(513, np.float32)), flac=True)
+    assert lib.names() == ["ev_synthesize", "ev_stitch", "ev_denoise_setup", "ev_denoise", "ev_flac"]
+    (dn,) = lib.calls("ev_denoise")
+    assert dn["src"] == ("stitch.wav", 0) and dn["lens"] == [2048, 512] and dn["cfg"]["want_i16"] == 1
+    assert lib.calls("ev_flac")[0]["src"] == ("denoise.wav_i16", 0) and lib.calls("ev_flac")[0]["lens"] == [2048, 512]
+    want = fk.to_i16(-fk.ramp(N) + EIGHTH)
+    assert all(np.array_equal(d, want[a:b]) for d, a, b in zip(out["documents"], (0, 2048), (2048, 2560)))
+    assert out["doc_lens"].tolist() == [2048, 512]
+
+
+def test_without_denoise_the_transcript_is_the_one_of_the_plain_library(monkeypatch):
+    """denoise=None, the default, issues exactly the calls it issued before: the stand-in WITHOUT ev_denoise (it would raise on any call of it)
+    logs the same entries with the same arguments."""
+    logs = []
+    for lib in (fk.FakeLib(), DenoiseLib()):
+        monkeypatch.setattr(_ffi, "lib", lambda lib=lib: lib)
+        from emotivoice_amd.engine import EVEngine
+        e = EVEngine()
+        e.synthesize(utterances(), loudness=-16.0, limiter=-1.0, want_int16=True, flac=True)
+        e.synthesize(utterances(), denoise=None, flac=[True, False, True])
+        e.synthesize_long([dict(utts=utterances())], flac=True, denoise=None)
+        logs.append([repr(x) for x in lib.log])
+        e.close()
+    assert logs[0] == logs[1] and not any("denoise" in x for x in logs[1])
+
+
+def test_serving_passes_denoise_through():
+    from emotivoice_amd.serving import engine_flac_synth_fn, engine_prosody_synth_fn, engine_synth_fn
+
+    class Engine:
+        def __init__(self):
+            self.calls = []
+
+        def synthesize(self, utts, **kw):
+            self.calls.append(kw)
+            return dict(wav_list=[np.zeros(4, np.float32)] * len(utts), flac_list=[b"fLaC"] * len(utts))
+    e = Engine()
+    engine_synth_fn(e)([{}], 1.0)
+    engine_synth_fn(e, denoise=0.05)([{}], 1.0)
+    engine_prosody_synth_fn(e, denoise=DenoiseConfig(0.2))([{}], [None])
+    engine_flac_synth_fn(e, denoise=0.05)([{}], 1.0, [True])
+    assert "denoise" not in e.calls[0] and e.calls[1]["denoise"].strength == 0.05 and e.calls[2]["denoise"].strength == 0.2 and e.calls[3]["denoise"].strength == 0.05
+    with pytest.raises(ValueError):
+        engine_synth_fn(e, denoise=-1.0)
