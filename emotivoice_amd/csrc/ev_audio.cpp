@@ -22,27 +22,46 @@ template <typename T> int upload(ev_handle* h, T* dst, const std::vector<T>& v) 
     return 0;
 }
 
+// The waveform a utility call reads: the caller's own pointer with EV_FLAG_DEVICE_INPUTS, else a staging buffer in the utility's arena that copy() fills
+// on the handle's stream.  `bytes` is what the kernel reads of it.
+struct WavIn {
+    const void* src; size_t bytes; bool dev; void* stage = nullptr;
+    WavIn(const void* p, int64_t elements, int wav_is_i16, uint32_t flags)
+        : src(p), bytes((size_t)elements * (wav_is_i16 ? 2 : 4)), dev((flags & EV_FLAG_DEVICE_INPUTS) != 0) {}
+    void plan(ArenaPlan& ap) { stage = dev ? nullptr : ap.take(bytes); }
+    int copy(ev_handle* h) const {
+        if (!dev) HIPCHK(h, hipMemcpyAsync(stage, src, bytes, hipMemcpyHostToDevice, h->stream));
+        return 0;
+    }
+    const void* ptr() const { return dev ? src : stage; }
+};
+
 // The device side of a per-kernel test entry point (the end of this file): ONE allocation that holds the host tables appended with add() and the
 // scratch reserved with room(), each at an aligned offset.  commit() allocates and uploads, at<T>() turns an offset into its pointer, and the end
 // of the scope frees -- after the wrapper has waited for the stream.
 struct DevTable {
     struct Part { size_t off; const void* src; size_t bytes; };
-    std::vector<Part> parts; size_t size = 0; char* base = nullptr;
-    DevTable() = default;
-    DevTable(const DevTable&) = delete;
-    DevTable& operator=(const DevTable&) = delete;
-    ~DevTable() { if (base) (void)hipFree(base); }
+    std::vector<Part> parts; size_t size = 0; DevMem mem;
     size_t room(size_t bytes) { const size_t off = align_up(size, 256); size = off + bytes; return off; }
     size_t add(const void* src, size_t bytes) { const size_t off = room(bytes); parts.push_back(Part{off, src, bytes}); return off; }
     template <typename T> size_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
     int commit() {      // 0, or -1
-        if (hipMalloc((void**)&base, size + 16) != hipSuccess) { base = nullptr; return -1; }
+        if (mem.alloc(size + 16) != hipSuccess) return -1;
         for (const Part& p : parts)
-            if (p.bytes && hipMemcpy(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
+            if (p.bytes && hipMemcpy(mem.as<char>() + p.off, p.src, p.bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
         return 0;
     }
-    template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+    template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(mem.as<char>() + off); }
 };
+
+// The end of a per-kernel test entry point, after its last launch: -2 for a launch the wrapper refused, -1 (over -2) for a launch error or a failed
+// wait for the stream, else 0.  The tables may go once it has returned.
+int op_finish(int launch_rc, hipStream_t s) {
+    int rc = launch_rc ? -2 : 0;
+    if (hipGetLastError() != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    return rc;
+}
 
 }  // namespace
 
@@ -65,24 +84,17 @@ static int features_check_config(ev_handle* h, const char* who, int n_fft, int h
     return 0;
 }
 
-// packs the basis planes on the host and uploads them; *basis / *melT are hipMalloc'ed
-static int features_upload_tables(ev_handle* h, int n_fft, int n_mels, const float* mel_basis, const float* window, char** basis, float** melT) {
+// packs the basis planes on the host and uploads them into fresh allocations; nothing half-built is left behind
+static int features_upload_tables(ev_handle* h, int n_fft, int n_mels, const float* mel_basis, const float* window, DevMem& basis, DevMem& melT) {
     std::vector<uint16_t> hb(stft_basis_halfs(n_fft));
     std::vector<float> hm(stft_melT_floats(n_fft));
     stft_pack_basis(n_fft, window, hb.data());
     stft_pack_mel(n_fft, n_mels, mel_basis, hm.data());
-    *basis = nullptr; *melT = nullptr;
-    hipError_t e = hipMalloc((void**)basis, hb.size() * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)melT, hm.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(*basis, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(*melT, hm.data(), hm.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {       // nothing half-built is left behind
-        if (*basis) (void)hipFree(*basis);
-        if (*melT) (void)hipFree(*melT);
-        *basis = nullptr; *melT = nullptr;
-        return fail(h, "ev_features: uploading the basis planes failed: %s", hipGetErrorString(e));
-    }
-    return 0;
+    hipError_t e = dev_upload(basis, hb);
+    if (e == hipSuccess) e = dev_upload(melT, hm);
+    if (e == hipSuccess) return 0;
+    basis.reset();
+    return fail(h, "ev_features: uploading the basis planes failed: %s", hipGetErrorString(e));
 }
 
 int ev_features_setup(ev_handle* h, const ev_features_config* cfg) {
@@ -95,10 +107,9 @@ int ev_features_setup(ev_handle* h, const ev_features_config* cfg) {
     if (!(cfg->energy_floor >= 0.f) || !std::isfinite(cfg->energy_floor)) return fail(h, "ev_features_setup: energy_floor must be >= 0 and finite");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->feat.ready = false;
-    if (h->feat.basis) { HIPCHK(h, hipFree(h->feat.basis)); h->feat.basis = nullptr; }
-    if (h->feat.melT) { HIPCHK(h, hipFree(h->feat.melT)); h->feat.melT = nullptr; }
-    if (features_upload_tables(h, cfg->n_fft, cfg->n_mels, cfg->mel_basis, cfg->window, &h->feat.basis, &h->feat.melT)) return -1;
+    DevMem basis, melT;
+    if (features_upload_tables(h, cfg->n_fft, cfg->n_mels, cfg->mel_basis, cfg->window, basis, melT)) return -1;
+    h->feat.basis = std::move(basis); h->feat.melT = std::move(melT);
     h->feat.cfg = *cfg; h->feat.cfg.mel_basis = nullptr; h->feat.cfg.window = nullptr;
     h->feat.ready = true;
     return 0;
@@ -120,29 +131,28 @@ int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     if (bad > 0) return fail(h, "ev_features: wav_lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", bad - 1, (long long)wav_lens[bad - 1], fc.n_fft / 2 + 1);
     if (bad < 0) return fail(h, "ev_features: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / fc.hop + 1), EV_ALIGN_MAX_FRAMES);
     const int64_t total_frames = g.offs[B], total_samples = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
-    const size_t es = wav_is_i16 ? 2 : 4;
+    const bool keep = h->cfg.keep_stages != 0;
+    WavIn in(wav, total_samples, wav_is_i16, flags);
     if (call_begin(h)) return -1;
     h->feat.mag = nullptr;
-    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_mel = nullptr, *d_energy = nullptr, *d_mag = nullptr;
+    StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_mel = nullptr, *d_energy = nullptr, *d_mag = nullptr;
     if (arena_plan(h, ARENA_FEATURES, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        in.plan(ap);
         d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size());
         d_mel = ap.arr<float>((size_t)total_frames * fc.n_mels); d_energy = ap.arr<float>((size_t)total_frames);
         d_mag = keep ? ap.arr<float>((size_t)total_frames * n_bins) : nullptr;
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
     region_begin(h, "total");
     {
         StftParams p{};
-        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
-        p.basis = h->feat.basis; p.melT = h->feat.melT; p.n_fft = fc.n_fft; p.hop = fc.hop; p.n_mels = fc.n_mels; p.nmi = stft_mels_per_group(fc.n_mels);
+        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
+        p.basis = h->feat.basis.get(); p.melT = h->feat.melT.as<float>(); p.n_fft = fc.n_fft; p.hop = fc.hop; p.n_mels = fc.n_mels; p.nmi = stft_mels_per_group(fc.n_mels);
         p.n_bins = n_bins; p.n_btiles = stft_bin_tiles(fc.n_fft); p.mel_clip = fc.mel_clip; p.energy_floor = fc.energy_floor;
         p.energy_mean = energy_mean; p.energy_std = energy_std; p.mel = d_mel; p.energy = d_energy; p.mag = d_mag;
         const double tile_frames = 64.0 * (double)g.tiles.size();
         KScope ks(h, "stft_mel", 2.0 * 3.0 * tile_frames * fc.n_fft * 2.0 * n_bins + 2.0 * tile_frames * n_bins * fc.n_mels,
-                  (double)total_samples * es + (double)total_frames * (fc.n_mels + 1) * 4.0);
+                  (double)in.bytes + (double)total_frames * (fc.n_mels + 1) * 4.0);
         if (launch_stft_mel(p, h->stream)) return fail(h, "ev_features: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -211,23 +221,21 @@ int ev_pitch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t
     if (bad > 0) return fail(h, "ev_pitch: wav_lens[%d] = %lld < 1", bad - 1, (long long)wav_lens[bad - 1]);
     if (bad < 0) return fail(h, "ev_pitch: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(wav_lens[-bad - 1] / pc.hop + 1), EV_ALIGN_MAX_FRAMES);
     const int64_t total_frames = g.offs[B], total_samples = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
-    const size_t es = wav_is_i16 ? 2 : 4;
+    WavIn in(wav, total_samples, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_pitch = nullptr, *d_f0 = nullptr, *d_ap = nullptr;
+    StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float *d_pitch = nullptr, *d_f0 = nullptr, *d_ap = nullptr;
     if (arena_plan(h, ARENA_PITCH, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.take((size_t)total_samples * es);
+        in.plan(ap);
         d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size());
         d_pitch = ap.arr<float>((size_t)total_frames); d_f0 = ap.arr<float>((size_t)total_frames); d_ap = ap.arr<float>((size_t)total_frames);
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_samples * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
     region_begin(h, "total");
     {
         PitchParams p = pitch_params(pc, tau_min, tau_max);
-        p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
+        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
         p.f0 = d_f0; p.ap = d_ap; p.tau = nullptr;
-        KScope ks(h, "pitch_yin", 3.0 * (double)total_frames * (tau_max + 2.0) * pc.win, (double)total_samples * es + (double)total_frames * 8.0);
+        KScope ks(h, "pitch_yin", 3.0 * (double)total_frames * (tau_max + 2.0) * pc.win, (double)in.bytes + (double)total_frames * 8.0);
         if (launch_pitch_yin(p, h->stream)) return fail(h, "ev_pitch: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -315,15 +323,11 @@ static int resample_check_config(ev_handle* h, const char* who, const ev_resampl
     return 0;
 }
 
-// the table on the device (hipMalloc'ed); nothing half-built is left behind
-static int resample_upload_table(int up, int half, const std::vector<float>& taps, float** tab, size_t* floats) {
+// the phase-major table, packed on the host and uploaded into a fresh allocation; nothing half-built is left behind
+static int resample_upload_table(int up, int half, const std::vector<float>& taps, DevMem& tab) {
     std::vector<float> ht(resample_table_floats(up, half));
     resample_pack_table(up, half, taps.data(), ht.data());
-    *tab = nullptr;
-    if (hipMalloc((void**)tab, ht.size() * 4) != hipSuccess) return -1;
-    if (hipMemcpy(*tab, ht.data(), ht.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(*tab); *tab = nullptr; return -1; }
-    *floats = ht.size();
-    return 0;
+    return dev_upload(tab, ht) == hipSuccess ? 0 : -1;
 }
 
 int ev_resample_setup(ev_handle* h, const ev_resample_config* cfg) {
@@ -335,10 +339,9 @@ int ev_resample_setup(ev_handle* h, const ev_resample_config* cfg) {
     if (resample_check_config(h, "ev_resample_setup", *cfg, &up, &down, &half, taps)) return -1;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float* tab = nullptr; size_t floats = 0;
-    if (resample_upload_table(up, half, taps, &tab, &floats)) return fail(h, "ev_resample_setup: uploading the tap table failed");
-    if (h->rs.tab) (void)hipFree(h->rs.tab);
-    h->rs.tab = tab; h->rs.tab_floats = floats; h->rs.up = up; h->rs.down = down; h->rs.half = half;
+    DevMem tab;
+    if (resample_upload_table(up, half, taps, tab)) return fail(h, "ev_resample_setup: uploading the tap table failed");
+    h->rs.tab = std::move(tab); h->rs.tab_floats = resample_table_floats(up, half); h->rs.up = up; h->rs.down = down; h->rs.half = half;
     h->rs.cfg = *cfg; h->rs.cfg.taps = nullptr;
     h->rs.ready = true;
     return 0;
@@ -384,26 +387,25 @@ int ev_resample(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     if (bad < 0) return fail(h, "ev_resample: utterance %d (%lld samples) gives more than EV_ALIGN_MAX_FRAMES * 256 = %lld output samples", -bad - 1,
                              (long long)wav_lens[-bad - 1], (long long)RS_MAX_OUT);
     const int64_t total_in = seqs[B - 1].in_off + seqs[B - 1].len, total_n = seqs[B - 1].out_off + seqs[B - 1].n;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, keep = h->cfg.keep_stages != 0;
-    const size_t es = wav_is_i16 ? 2 : 4;
+    const bool keep = h->cfg.keep_stages != 0;
+    WavIn in(wav, total_in, wav_is_i16, flags);
     if (call_begin(h)) return -1;
     h->rs.raw = nullptr;
-    void* d_wav = nullptr; ResampleSeq* d_seqs = nullptr; ResampleTile* d_tiles = nullptr; TrimSeq* d_ts = nullptr; int64_t* d_cuts = nullptr;
+    ResampleSeq* d_seqs = nullptr; ResampleTile* d_tiles = nullptr; TrimSeq* d_ts = nullptr; int64_t* d_cuts = nullptr;
     float *d_y = nullptr, *d_out = nullptr;
     if (arena_plan(h, ARENA_RESAMPLE, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        in.plan(ap);
         d_seqs = ap.arr<ResampleSeq>(B); d_tiles = ap.arr<ResampleTile>(tiles.size());
         d_y = ap.arr<float>((size_t)total_n);
         if (trim) { d_ts = ap.arr<TrimSeq>(B); d_cuts = ap.arr<int64_t>(2 * (size_t)B); d_out = ap.arr<float>((size_t)total_n + 2 * (size_t)pad * B); }
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
     std::vector<int64_t> lens((size_t)B), offs((size_t)B + 1), start((size_t)B), end((size_t)B);
     region_begin(h, "total");
     {
         const bool copy = up == 1 && down == 1;
-        KScope ks(h, copy ? "resample_copy" : "resample_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)total_in * es + (double)total_n * 4.0);
-        if (resample_launch(dev_in ? wav : d_wav, wav_is_i16 != 0, up, down, half, h->rs.tab, d_seqs, d_tiles, (int)tiles.size(), total_in, d_y, h->stream))
+        KScope ks(h, copy ? "resample_copy" : "resample_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)in.bytes + (double)total_n * 4.0);
+        if (resample_launch(in.ptr(), wav_is_i16 != 0, up, down, half, h->rs.tab.as<float>(), d_seqs, d_tiles, (int)tiles.size(), total_in, d_y, h->stream))
             return fail(h, "ev_resample: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -536,7 +538,7 @@ int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets,
     const int D = stitch_check(h, "ev_stitch", S, seg_doc, pause_after, cfg);
     if (D < 0) return -1;
     const ev_stitch_config c = *cfg;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, trim = c.trim_frac > 0.f || c.trim_abs > 0.f, i16 = c.want_i16 != 0;
+    const bool trim = c.trim_frac > 0.f || c.trim_abs > 0.f, i16 = c.want_i16 != 0;
     // the layout of the input, and each document's length before any cut: what the workspace is sized for and what EV_STITCH_MAX_DOC is judged on
     std::vector<StitchSeg> segs((size_t)S);
     std::vector<int64_t> bound((size_t)D, (int64_t)c.lead + c.tail);
@@ -554,26 +556,27 @@ int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets,
         n_part += (seg_lens[s] + ST_PEAK_CHUNK - 1) / ST_PEAK_CHUNK;
         lo_off = std::min(lo_off, seg_offsets[s]); hi_end = std::max(hi_end, seg_offsets[s] + seg_lens[s]); max_len = std::max(max_len, seg_lens[s]);
     }
-    if (!dev_in) for (auto& sg : segs) sg.off -= lo_off;      // the host's samples lo_off .. hi_end are copied
+    for (auto& sg : segs) sg.off -= lo_off;      // the call reads the samples lo_off .. hi_end, and a host's are copied
+    WavIn in(wav + lo_off, hi_end - lo_off, 0, flags);
     int64_t cap_out = 0, cap_tiles = 0;
     for (int d = 0; d < D; ++d) { cap_out += bound[(size_t)d]; cap_tiles += (bound[(size_t)d] + ST_TILE - 1) / ST_TILE; }
     if (call_begin(h)) return -1;
-    float* d_wav = nullptr; StitchSeg* d_segs = nullptr; float *d_part = nullptr, *d_peak = nullptr; int64_t* d_cuts = nullptr;
+    StitchSeg* d_segs = nullptr; float *d_part = nullptr, *d_peak = nullptr; int64_t* d_cuts = nullptr;
     StitchMixSeg* d_ms = nullptr; StitchDoc* d_docs = nullptr; StitchTile* d_tiles = nullptr; float* d_out = nullptr; int16_t* d_i16 = nullptr;
     if (arena_plan(h, ARENA_STITCH, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.arr<float>((size_t)(hi_end - lo_off));
+        in.plan(ap);
         if (trim) { d_segs = ap.arr<StitchSeg>(S); d_part = ap.arr<float>((size_t)n_part); d_peak = ap.arr<float>(S); d_cuts = ap.arr<int64_t>(2 * (size_t)S); }
         d_ms = ap.arr<StitchMixSeg>(S); d_docs = ap.arr<StitchDoc>(D); d_tiles = ap.arr<StitchTile>((size_t)cap_tiles);
         d_out = ap.arr<float>((size_t)cap_out);
         if (i16) d_i16 = ap.arr<int16_t>((size_t)cap_out);
     })) return -1;
-    if (!h->stitch.tab) HIPCHK(h, hipMalloc((void**)&h->stitch.tab, (size_t)EV_STITCH_MAX_FADE * sizeof(float)));
+    if (!h->stitch.tab) HIPCHK(h, h->stitch.tab.alloc((size_t)EV_STITCH_MAX_FADE * sizeof(float)));
     h->stitch.tab_host.resize((size_t)c.fade);
     (void)ev_stitch_ramp(c.fade, h->stitch.tab_host.data());
     h->stitch.F = c.fade;
-    if (c.fade > 0) HIPCHK(h, hipMemcpyAsync(h->stitch.tab, h->stitch.tab_host.data(), (size_t)c.fade * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav + lo_off, (size_t)(hi_end - lo_off) * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    const float* x = dev_in ? wav : d_wav;
+    if (c.fade > 0) HIPCHK(h, hipMemcpyAsync(h->stitch.tab.get(), h->stitch.tab_host.data(), (size_t)c.fade * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (in.copy(h)) return -1;
+    const float* x = static_cast<const float*>(in.ptr());
     std::vector<int64_t> a((size_t)S, 0), b((size_t)S), n((size_t)S), src((size_t)S);
     std::vector<float> peak((size_t)S, 0.f);
     for (int s = 0; s < S; ++s) b[(size_t)s] = seg_lens[s];
@@ -611,7 +614,7 @@ int ev_stitch(ev_handle* h, int S, const float* wav, const int64_t* seg_offsets,
     if (upload(h, d_ms, ms) || upload(h, d_docs, docs) || (!tiles.empty() && upload(h, d_tiles, tiles))) return -1;
     {
         KScope ks(h, "stitch_mix", 0.0, (double)total * (i16 ? 10.0 : 8.0));
-        if (launch_stitch_mix(x, d_ms, d_docs, d_tiles, (int64_t)tiles.size(), h->stitch.tab, c.fade, d_out, i16 ? d_i16 : nullptr, h->stream))
+        if (launch_stitch_mix(x, d_ms, d_docs, d_tiles, (int64_t)tiles.size(), h->stitch.tab.as<float>(), c.fade, d_out, i16 ? d_i16 : nullptr, h->stream))
             return fail(h, "ev_stitch: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -634,7 +637,6 @@ int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_
     if (!out) return fail(h, "ev_compare: out is NULL");
     if (check_struct_size(h, "ev_compare", "out->struct_size", out->struct_size, "ev_compare_result", sizeof(ev_compare_result))) return -1;
     if (B < 1 || B > 65535) return fail(h, "ev_compare: B = %d outside [1, 65535]", B);
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0;
     std::vector<int64_t> coffs((size_t)B + 1, 0);
     int64_t total = 0;
     for (int s = 0; s < B; ++s) {      // the chunk table's size is judged before it is built
@@ -649,25 +651,22 @@ int ev_compare(ev_handle* h, int B, const float* a, const float* b, const int64_
     chunks.reserve((size_t)NC);
     for (int64_t s = 0, off = 0; s < B; off += lens[s], ++s)
         for (int64_t i = 0; i < lens[s]; i += CMP_CHUNK) chunks.push_back(CompareChunk{off + i, (int32_t)std::min<int64_t>(CMP_CHUNK, lens[s] - i), 0});
+    WavIn ia(a, total, 0, flags), ib(b, total, 0, flags);
     if (call_begin(h)) return -1;
-    float *d_a = nullptr, *d_b = nullptr; CompareChunk* d_chunks = nullptr; int64_t* d_coffs = nullptr; double *d_sums = nullptr, *d_maxd = nullptr;
+    CompareChunk* d_chunks = nullptr; int64_t* d_coffs = nullptr; double *d_sums = nullptr, *d_maxd = nullptr;
     int32_t *d_argd = nullptr, *d_nonf = nullptr; float* d_peak = nullptr; CompareSeg* d_seg = nullptr;
     if (arena_plan(h, ARENA_COMPARE, [&](ArenaPlan& ap) {
-        if (!dev_in) { d_a = ap.arr<float>((size_t)total); d_b = ap.arr<float>((size_t)total); }
+        ia.plan(ap); ib.plan(ap);
         d_chunks = ap.arr<CompareChunk>((size_t)NC); d_coffs = ap.arr<int64_t>((size_t)B + 1);
         d_sums = ap.arr<double>(4 * (size_t)NC); d_maxd = ap.arr<double>((size_t)NC);
         d_argd = ap.arr<int32_t>((size_t)NC); d_nonf = ap.arr<int32_t>((size_t)NC); d_peak = ap.arr<float>((size_t)NC);
         d_seg = ap.arr<CompareSeg>((size_t)B);
     })) return -1;
-    if (!dev_in) {
-        HIPCHK(h, hipMemcpyAsync(d_a, a, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_b, b, (size_t)total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    if (upload(h, d_chunks, chunks) || upload(h, d_coffs, coffs)) return -1;
+    if (ia.copy(h) || ib.copy(h) || upload(h, d_chunks, chunks) || upload(h, d_coffs, coffs)) return -1;
     region_begin(h, "total");
     {
         KScope ks(h, "compare_chunks", 8.0 * (double)total, 8.0 * (double)total + 64.0 * (double)NC);
-        if (launch_compare_chunks(dev_in ? a : d_a, dev_in ? b : d_b, d_chunks, NC, d_sums, d_maxd, d_argd, d_peak, d_nonf, h->stream))
+        if (launch_compare_chunks(static_cast<const float*>(ia.ptr()), static_cast<const float*>(ib.ptr()), d_chunks, NC, d_sums, d_maxd, d_argd, d_peak, d_nonf, h->stream))
             return fail(h, "ev_compare: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -762,7 +761,7 @@ static int flac_run(ev_handle* h, const char* who, int B, const void* pcm, int p
         lpc_order = ext->max_lpc_order; lpc_q = ext->qlp_precision; md5 = ext->md5 != 0;
     }
     if (B < 1 || B > 65535) return fail(h, "%s: B = %d outside [1, 65535]", who, B);
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, i16 = pcm_is_i16 != 0;
+    const bool i16 = pcm_is_i16 != 0;
     const int N = c.block_size, stride = 2 * N + 24;
     FlacPlan plan;
     int at = 0;
@@ -773,24 +772,23 @@ static int flac_run(ev_handle* h, const char* who, int B, const void* pcm, int p
     case LEN_COUNT: return fail(h, "%s: lens[%d] = %lld: more than %d frames in one call", who, at, (long long)lens[at], INT_MAX);
     }
     const int64_t total = plan.total, NF = (int64_t)plan.frames.size(), cap = plan.cap;
+    WavIn in(pcm, total, pcm_is_i16, flags);
     if (call_begin(h)) return -1;
-    const size_t es = i16 ? sizeof(int16_t) : sizeof(float);
-    char* d_pcm = nullptr; FlacFrame* d_frames = nullptr; int32_t* d_sizes = nullptr; uint32_t* d_desc = nullptr; uint8_t *d_scratch = nullptr, *d_hdr = nullptr, *d_bytes = nullptr;
+    FlacFrame* d_frames = nullptr; int32_t* d_sizes = nullptr; uint32_t* d_desc = nullptr; uint8_t *d_scratch = nullptr, *d_hdr = nullptr, *d_bytes = nullptr;
     int64_t* d_foffs = nullptr; FlacMd5Seg* d_segs = nullptr; uint32_t* d_md5 = nullptr;
     if (arena_plan(h, ARENA_FLAC, [&](ArenaPlan& ap) {
-        if (!dev_in) d_pcm = ap.arr<char>((size_t)total * es);
+        in.plan(ap);
         d_frames = ap.arr<FlacFrame>((size_t)NF); d_sizes = ap.arr<int32_t>((size_t)NF); d_desc = ap.arr<uint32_t>((size_t)NF);
         d_foffs = ap.arr<int64_t>((size_t)NF); d_hdr = ap.arr<uint8_t>((size_t)B * FLAC_HEADER_STRIDE);
         d_scratch = ap.arr<uint8_t>((size_t)NF * (size_t)stride + 16); d_bytes = ap.arr<uint8_t>((size_t)cap);
         if (md5) { d_segs = ap.arr<FlacMd5Seg>((size_t)B); d_md5 = ap.arr<uint32_t>(4 * (size_t)B); }
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_pcm, pcm, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_frames, plan.frames)) return -1;
+    if (in.copy(h) || upload(h, d_frames, plan.frames)) return -1;
     FlacParams fp = flac_params(c, sr_code, bs_code);
-    fp.pcm = dev_in ? pcm : d_pcm; fp.pcm_is_i16 = i16; fp.frames = d_frames; fp.scratch = d_scratch; fp.sizes = d_sizes; fp.desc = d_desc;
+    fp.pcm = in.ptr(); fp.pcm_is_i16 = i16; fp.frames = d_frames; fp.scratch = d_scratch; fp.sizes = d_sizes; fp.desc = d_desc;
     region_begin(h, "total");
     {
-        KScope ks(h, "flac_encode", 0.0, (double)total * (double)es + (double)NF * (double)stride);
+        KScope ks(h, "flac_encode", 0.0, (double)in.bytes + (double)NF * (double)stride);
         if (lpc_order > 0 ? launch_flac_encode_lpc(fp, FlacLpc{lpc_order, lpc_q}, NF, h->stream) : launch_flac_encode(fp, NF, h->stream))
             return fail(h, "%s: the kernel does not build this shape", who);
     }
@@ -802,7 +800,7 @@ static int flac_run(ev_handle* h, const char* who, int B, const void* pcm, int p
         for (int b = 0; b < B; ++b) { segs[(size_t)b] = FlacMd5Seg{off, lens[b]}; off += lens[b]; }
         if (upload(h, d_segs, segs)) return -1;
         {
-            KScope ks(h, "flac_md5", 0.0, (double)total * (double)es);
+            KScope ks(h, "flac_md5", 0.0, (double)in.bytes);
             launch_flac_md5(fp, d_segs, B, d_md5, h->stream);
         }
         HIPCHK(h, hipGetLastError());
@@ -934,7 +932,7 @@ int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     if (!(std::isfinite(c.max_gain_db) && c.max_gain_db >= 0.0)) return fail(h, "ev_loudness: max_gain_db = %g is not finite and >= 0", c.max_gain_db);
     if (!(c.peak_ceiling > 0.f && c.peak_ceiling <= 1.f)) return fail(h, "ev_loudness: peak_ceiling = %g outside (0, 1]", (double)c.peak_ceiling);
     if (B < 1 || B > 65535) return fail(h, "ev_loudness: B = %d outside [1, 65535]", B);
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0 && !measure_only;
+    const bool in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0 && !measure_only;
     const int64_t step = c.sample_rate / 10, block = 4 * step;
     LoudPlan plan;
     int at = 0;
@@ -948,25 +946,24 @@ int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     const int64_t total = plan.total, NT = (int64_t)plan.tiles.size(), NB = plan.n_blocks;
     LoudCoef lc;
     loudness_coef(coef, &lc);
+    WavIn in(wav, total, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    const size_t es = in16 ? sizeof(int16_t) : sizeof(float);
-    char* d_in = nullptr; LoudTile* d_tiles = nullptr; LoudSeg* d_segs = nullptr; LoudCoef* d_coef = nullptr; double *d_ends = nullptr, *d_init = nullptr;
+    LoudTile* d_tiles = nullptr; LoudSeg* d_segs = nullptr; LoudCoef* d_coef = nullptr; double *d_ends = nullptr, *d_init = nullptr;
     LoudTileOut* d_outs = nullptr; int64_t* d_offs = nullptr; float *d_gain = nullptr, *d_wav = nullptr; int16_t* d_i16 = nullptr;
     if (arena_plan(h, ARENA_LOUDNESS, [&](ArenaPlan& ap) {
-        if (!dev_in) d_in = ap.arr<char>((size_t)total * es);
+        in.plan(ap);
         d_tiles = ap.arr<LoudTile>((size_t)NT); d_segs = ap.arr<LoudSeg>((size_t)B); d_coef = ap.arr<LoudCoef>(1);
         d_ends = ap.arr<double>(4 * (size_t)NT); d_init = ap.arr<double>(4 * (size_t)NT); d_outs = ap.arr<LoudTileOut>((size_t)NT);
         d_offs = ap.arr<int64_t>((size_t)B + 1); d_gain = ap.arr<float>((size_t)B);
         if (!measure_only) d_wav = ap.arr<float>((size_t)total);
         if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_in, wav, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_tiles, plan.tiles) || upload(h, d_segs, plan.segs)) return -1;
+    if (in.copy(h) || upload(h, d_tiles, plan.tiles) || upload(h, d_segs, plan.segs)) return -1;
     HIPCHK(h, hipMemcpyAsync(d_coef, &lc, sizeof lc, hipMemcpyHostToDevice, h->stream));
-    const void* x = dev_in ? wav : (const void*)d_in;
+    const void* x = in.ptr();
     region_begin(h, "total");
     {
-        KScope ks(h, "loudness_measure", 60.0 * (double)total, 2.0 * (double)total * (double)es + (double)NT * (64.0 + sizeof(LoudTileOut)));
+        KScope ks(h, "loudness_measure", 60.0 * (double)total, 2.0 * (double)in.bytes + (double)NT * (64.0 + sizeof(LoudTileOut)));
         if (launch_loudness_measure(x, in16, d_tiles, NT, d_segs, B, d_coef, (int)step, d_ends, d_init, d_outs, h->stream))
             return fail(h, "ev_loudness: the kernels do not build this shape");
     }
@@ -1027,7 +1024,7 @@ int ev_loudness(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     if (!measure_only) {
         if (upload(h, d_offs, plan.offs) || upload(h, d_gain, gain)) return -1;
         {
-            KScope ks(h, "loudness_gain", (double)total, (double)total * ((double)es + (i16 ? 6.0 : 4.0)));
+            KScope ks(h, "loudness_gain", (double)total, (double)in.bytes + (double)total * (i16 ? 6.0 : 4.0));
             if (launch_loudness_gain(x, in16, d_offs, B, d_gain, total, d_wav, i16 ? d_i16 : nullptr, h->stream))
                 return fail(h, "ev_loudness: the kernels do not build this shape");
         }
@@ -1139,38 +1136,37 @@ int ev_limit(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t
     }
     at = limit_bad_gain(B, gains);
     if (at >= 0) return fail(h, "ev_limit: gains[%d] = %g is not finite and >= 0", at, (double)gains[at]);
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0;
+    const bool in16 = wav_is_i16 != 0, i16 = c.want_i16 != 0;
     const int L = c.lookahead, Hd = c.hold;
     const int64_t total = plan.total, NT = (int64_t)plan.tiles.size();
     double tab[LIMIT_TAB];
     std::vector<double> win;
     if (limit_tables(L, tab, win)) return fail(h, "ev_limit: the interpolator's design failed");
+    WavIn in(wav, total, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    const size_t es = in16 ? sizeof(int16_t) : sizeof(float);
-    char* d_in = nullptr; LimitTile* d_tiles = nullptr; double *d_tab = nullptr, *d_win = nullptr; float *d_gain = nullptr, *d_r = nullptr, *d_wav = nullptr;
+    LimitTile* d_tiles = nullptr; double *d_tab = nullptr, *d_win = nullptr; float *d_gain = nullptr, *d_r = nullptr, *d_wav = nullptr;
     int16_t* d_i16 = nullptr; LimitPeakOut *d_pin = nullptr, *d_pout = nullptr; LimitApplyOut* d_app = nullptr;
     if (arena_plan(h, ARENA_LIMIT, [&](ArenaPlan& ap) {
-        if (!dev_in) d_in = ap.arr<char>((size_t)total * es);
+        in.plan(ap);
         d_tiles = ap.arr<LimitTile>((size_t)NT); d_tab = ap.arr<double>(LIMIT_TAB); d_win = ap.arr<double>((size_t)L + 1);
         if (gains) d_gain = ap.arr<float>((size_t)B);
         d_r = ap.arr<float>((size_t)total); d_wav = ap.arr<float>((size_t)total);
         if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
         d_pin = ap.arr<LimitPeakOut>((size_t)NT); d_pout = ap.arr<LimitPeakOut>((size_t)NT); d_app = ap.arr<LimitApplyOut>((size_t)NT);
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_in, wav, (size_t)total * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_tiles, plan.tiles) || upload(h, d_win, win)) return -1;
+    if (in.copy(h) || upload(h, d_tiles, plan.tiles) || upload(h, d_win, win)) return -1;
     HIPCHK(h, hipMemcpyAsync(d_tab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
     if (gains) HIPCHK(h, hipMemcpyAsync(d_gain, gains, (size_t)B * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    const void* x = dev_in ? wav : (const void*)d_in;
+    const void* x = in.ptr();
     const double meter_flops = 2.0 * LIMIT_TAB * (double)total, rec = (double)NT * sizeof(LimitPeakOut);
     region_begin(h, "total");
     {
-        KScope ks(h, "limit_peak", meter_flops, (double)total * ((double)es + 4.0) + rec);
+        KScope ks(h, "limit_peak", meter_flops, (double)in.bytes + (double)total * 4.0 + rec);
         if (launch_limit_peak(x, in16, d_gain, d_tiles, NT, d_tab, c.ceiling, d_r, d_pin, h->stream)) return fail(h, "ev_limit: the kernels do not build this shape");
     }
     HIPCHK(h, hipGetLastError());
     {
-        KScope ks(h, "limit_apply", 2.0 * (double)(L + 1) * (double)total, (double)total * ((double)es + 8.0 + (i16 ? 2.0 : 0.0)) + (double)NT * sizeof(LimitApplyOut));
+        KScope ks(h, "limit_apply", 2.0 * (double)(L + 1) * (double)total, (double)in.bytes + (double)total * (8.0 + (i16 ? 2.0 : 0.0)) + (double)NT * sizeof(LimitApplyOut));
         if (launch_limit_apply(x, in16, d_gain, d_tiles, NT, d_r, d_win, L, Hd, d_wav, i16 ? d_i16 : nullptr, nullptr, d_app, h->stream))
             return fail(h, "ev_limit: the kernels do not build this shape");
     }
@@ -1223,10 +1219,9 @@ int ev_deliver_setup(ev_handle* h, const ev_deliver_config* cfg) {
     if (resample_check_config(h, "ev_deliver_setup", rc, &up, &down, &half, taps)) return -1;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    float* tab = nullptr; size_t floats = 0;
-    if (!(up == 1 && down == 1) && resample_upload_table(up, half, taps, &tab, &floats)) return fail(h, "ev_deliver_setup: uploading the tap table failed");
-    if (h->dlv.tab) (void)hipFree(h->dlv.tab);
-    h->dlv.tab = tab; h->dlv.up = up; h->dlv.down = down; h->dlv.half = half;
+    DevMem tab;
+    if (!(up == 1 && down == 1) && resample_upload_table(up, half, taps, tab)) return fail(h, "ev_deliver_setup: uploading the tap table failed");
+    h->dlv.tab = std::move(tab); h->dlv.up = up; h->dlv.down = down; h->dlv.half = half;
     h->dlv.cfg = *cfg; h->dlv.cfg.taps = nullptr;
     h->dlv.ready = true;
     return 0;
@@ -1252,26 +1247,25 @@ int ev_deliver(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     const int64_t total_in = seqs[B - 1].in_off + seqs[B - 1].len;
     int64_t total_n = 0;
     for (int b = 0; b < B; ++b) total_n += seqs[b].n;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, copy = up == 1 && down == 1;
-    const size_t es = wav_is_i16 ? 2 : 4;
+    const bool copy = up == 1 && down == 1;
     const size_t NT = tiles.size();
+    WavIn in(wav, total_in, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    void* d_wav = nullptr; DeliverSeq* d_seqs = nullptr; DeliverTile* d_tiles = nullptr; DeliverPart* d_parts = nullptr; DeliverOut* d_outs = nullptr;
+    DeliverSeq* d_seqs = nullptr; DeliverTile* d_tiles = nullptr; DeliverPart* d_parts = nullptr; DeliverOut* d_outs = nullptr;
     uint8_t* d_data = nullptr;
     if (arena_plan(h, ARENA_DELIVER, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        in.plan(ap);
         d_seqs = ap.arr<DeliverSeq>(B); d_tiles = ap.arr<DeliverTile>(NT); d_parts = ap.arr<DeliverPart>(NT); d_outs = ap.arr<DeliverOut>(B);
         d_data = ap.arr<uint8_t>((size_t)total_bytes);
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles)) return -1;
     DeliverParams p{};
-    p.wav = dev_in ? wav : d_wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)NT;
-    p.up = up; p.down = down; p.half = half; p.row = copy ? 0 : resample_row_len(up, half); p.tab = h->dlv.tab;
+    p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)NT;
+    p.up = up; p.down = down; p.half = half; p.row = copy ? 0 : resample_row_len(up, half); p.tab = h->dlv.tab.as<float>();
     p.encoding = c.encoding; p.dither = c.dither; p.out = d_data; p.parts = d_parts;
     region_begin(h, "total");
     {
-        KScope ks(h, copy ? "deliver_copy" : "deliver_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)total_in * es + (double)total_bytes);
+        KScope ks(h, copy ? "deliver_copy" : "deliver_poly", copy ? 0.0 : 2.0 * (double)total_n * (2.0 * half / up + 1.0), (double)in.bytes + (double)total_bytes);
         if (launch_deliver(p, h->stream)) return fail(h, "ev_deliver: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
@@ -1307,28 +1301,14 @@ static int denoise_check_shape(ev_handle* h, const char* who, int n_fft, int hop
     return 0;
 }
 
-// the three tables of a shape, packed on the host and uploaded; one allocation each, freed with denoise_free_tables
-struct DenoiseTables { char* basis = nullptr; char* ibasis = nullptr; float* env = nullptr; };
-static void denoise_free_tables(DenoiseTables& t) {
-    if (t.basis) (void)hipFree(t.basis);
-    if (t.ibasis) (void)hipFree(t.ibasis);
-    if (t.env) (void)hipFree(t.env);
-    t = DenoiseTables{};
-}
-static int denoise_upload_tables(int n_fft, int hop, const float* window, DenoiseTables& t) {      // 0, or -1 with nothing left behind
+// the three tables of a shape, packed on the host and uploaded, one allocation each: 0, or -1 (the caller's locals free what was built)
+static int denoise_upload_tables(int n_fft, int hop, const float* window, DevMem& basis, DevMem& ibasis, DevMem& env) {
     std::vector<uint16_t> hb(stft_basis_halfs(n_fft)), hi(istft_basis_halfs(n_fft, hop));
     std::vector<float> he(istft_envelope_floats(n_fft, hop));
     stft_pack_basis(n_fft, window, hb.data());
     istft_pack_basis(n_fft, hop, window, hi.data());
     istft_pack_envelope(n_fft, hop, window, he.data());
-    hipError_t e = hipMalloc((void**)&t.basis, hb.size() * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&t.ibasis, hi.size() * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&t.env, he.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(t.basis, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t.ibasis, hi.data(), hi.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t.env, he.data(), he.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { denoise_free_tables(t); return -1; }
-    return 0;
+    return dev_upload(basis, hb) == hipSuccess && dev_upload(ibasis, hi) == hipSuccess && dev_upload(env, he) == hipSuccess ? 0 : -1;
 }
 
 static StftGainParams stft_gain_params(const void* wav, int wav_is_i16, const StftSeq* seqs, const StftTile* tiles, size_t n_tiles, const void* basis, int n_fft,
@@ -1359,39 +1339,29 @@ int ev_denoise_setup(ev_handle* h, const ev_denoise_config* cfg, const float* bi
     }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    DenoiseTables t;
-    float* d_bias = nullptr;
-    if (denoise_upload_tables(cfg->n_fft, cfg->hop, cfg->window, t)) return fail(h, "ev_denoise_setup: uploading the tables failed");
-    if (hipMalloc((void**)&d_bias, (size_t)n_bins * 4) != hipSuccess) { denoise_free_tables(t); return fail(h, "ev_denoise_setup: no memory for the bias"); }
-    int rc = 0;
+    DevMem basis, ibasis, env, d_bias;
+    if (denoise_upload_tables(cfg->n_fft, cfg->hop, cfg->window, basis, ibasis, env)) return fail(h, "ev_denoise_setup: uploading the tables failed");
     if (bias) {
-        if (hipMemcpy(d_bias, bias, (size_t)n_bins * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(h, "ev_denoise_setup: uploading the bias failed");
+        if (dev_upload(d_bias, bias, (size_t)n_bins * 4) != hipSuccess) return fail(h, "ev_denoise_setup: uploading the bias failed");
     } else {      // the vocoder's answer to a zero mel; the magnitudes of its frame 0 go straight into d_bias
+        if (d_bias.alloc((size_t)n_bins * 4) != hipSuccess) return fail(h, "ev_denoise_setup: no memory for the bias");
         const int32_t frames = EV_DENOISE_BIAS_FRAMES;
         std::vector<float> mel((size_t)h->cfg.n_mels * frames, 0.f);
         ev_result r;
-        rc = ev_vocoder(h, 1, mel.data(), 0, &frames, 0, &r);
-        const int64_t L = rc ? 0 : r.total_samples;
-        if (!rc && L < cfg->n_fft / 2 + 1) rc = fail(h, "ev_denoise_setup: the vocoder's %lld samples are fewer than n_fft / 2 + 1", (long long)L);
-        if (!rc) {
-            const StftSeq sq{0, L, 0, (int32_t)(L / cfg->hop + 1), 0};
-            const StftTile tile{0, 0};
-            DevTable dt;
-            const size_t so = dt.add(&sq, sizeof sq), to = dt.add(&tile, sizeof tile);
-            if (dt.commit()) rc = fail(h, "ev_denoise_setup: no memory for the bias measurement");
-            if (!rc) {
-                StftGainParams p = stft_gain_params(r.wav, 0, dt.at<StftSeq>(so), dt.at<StftTile>(to), 1, t.basis, cfg->n_fft, cfg->hop);
-                p.mag = d_bias; p.mag_frames = 1;
-                if (launch_stft_gain(p, h->stream)) rc = fail(h, "ev_denoise_setup: the kernel does not build this shape");
-                if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "ev_denoise_setup: measuring the bias failed");
-            }
-        }
+        if (ev_vocoder(h, 1, mel.data(), 0, &frames, 0, &r)) return -1;
+        const int64_t L = r.total_samples;
+        if (L < cfg->n_fft / 2 + 1) return fail(h, "ev_denoise_setup: the vocoder's %lld samples are fewer than n_fft / 2 + 1", (long long)L);
+        const StftSeq sq{0, L, 0, (int32_t)(L / cfg->hop + 1), 0};
+        const StftTile tile{0, 0};
+        DevTable dt;
+        const size_t so = dt.add(&sq, sizeof sq), to = dt.add(&tile, sizeof tile);
+        if (dt.commit()) return fail(h, "ev_denoise_setup: no memory for the bias measurement");
+        StftGainParams p = stft_gain_params(r.wav, 0, dt.at<StftSeq>(so), dt.at<StftTile>(to), 1, basis.get(), cfg->n_fft, cfg->hop);
+        p.mag = d_bias.as<float>(); p.mag_frames = 1;
+        if (launch_stft_gain(p, h->stream)) return fail(h, "ev_denoise_setup: the kernel does not build this shape");
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, "ev_denoise_setup: measuring the bias failed");
     }
-    if (rc) { denoise_free_tables(t); (void)hipFree(d_bias); return -1; }
-    DenoiseTables old{h->dn.basis, h->dn.ibasis, h->dn.env};
-    denoise_free_tables(old);
-    if (h->dn.bias) (void)hipFree(h->dn.bias);
-    h->dn.basis = t.basis; h->dn.ibasis = t.ibasis; h->dn.env = t.env; h->dn.bias = d_bias;
+    h->dn.basis = std::move(basis); h->dn.ibasis = std::move(ibasis); h->dn.env = std::move(env); h->dn.bias = std::move(d_bias);
     h->dn.cfg = *cfg; h->dn.cfg.window = nullptr;
     h->dn.ready = true;
     return 0;
@@ -1403,7 +1373,7 @@ int ev_denoise_bias(ev_handle* h, float* out) {
     if (!h->dn.ready) return fail(h, "ev_denoise_bias: ev_denoise_setup has not been called");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out, h->dn.bias, (size_t)(h->dn.cfg.n_fft / 2 + 1) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out, h->dn.bias.get(), (size_t)(h->dn.cfg.n_fft / 2 + 1) * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1430,32 +1400,31 @@ int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
     std::vector<float> st((size_t)B);
     for (int b = 0; b < B; ++b) st[b] = strengths ? strengths[b] : c.strength;
-    const bool dev_in = (flags & EV_FLAG_DEVICE_INPUTS) != 0, want16 = c.want_i16 != 0;
-    const size_t es = wav_is_i16 ? 2 : 4;
+    const bool want16 = c.want_i16 != 0;
+    WavIn in(wav, total_in, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    void* d_wav = nullptr; StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_st = nullptr, *d_out = nullptr;
+    StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_st = nullptr, *d_out = nullptr;
     uint16_t *d_hi = nullptr, *d_lo = nullptr; int16_t* d_i16 = nullptr;
     if (arena_plan(h, ARENA_DENOISE, [&](ArenaPlan& ap) {
-        d_wav = dev_in ? nullptr : ap.take((size_t)total_in * es);
+        in.plan(ap);
         d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_iseqs = ap.arr<IstftSeq>(B); d_itiles = ap.arr<StftTile>(itiles.size());
         d_st = ap.arr<float>(B);
         d_hi = ap.arr<uint16_t>((size_t)total_frames * KP); d_lo = ap.arr<uint16_t>((size_t)total_frames * KP);
         d_out = ap.arr<float>((size_t)total_out); d_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
     })) return -1;
-    if (!dev_in) HIPCHK(h, hipMemcpyAsync(d_wav, wav, (size_t)total_in * es, hipMemcpyHostToDevice, h->stream));
-    if (upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) || upload(h, d_st, st)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) || upload(h, d_st, st)) return -1;
     region_begin(h, "total");
     {
-        StftGainParams p = stft_gain_params(dev_in ? wav : d_wav, wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->dn.basis, n_fft, hop);
-        p.bias = h->dn.bias; p.strengths = d_st; p.spec_hi = d_hi; p.spec_lo = d_lo;
+        StftGainParams p = stft_gain_params(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->dn.basis.get(), n_fft, hop);
+        p.bias = h->dn.bias.as<float>(); p.strengths = d_st; p.spec_hi = d_hi; p.spec_lo = d_lo;
         const double tile_frames = (double)64 * (double)g.tiles.size();
-        KScope ks(h, "stft_gain", 2.0 * 3.0 * tile_frames * n_fft * 2.0 * p.n_bins, (double)total_in * es + 4.0 * (double)total_frames * KP);
+        KScope ks(h, "stft_gain", 2.0 * 3.0 * tile_frames * n_fft * 2.0 * p.n_bins, (double)in.bytes + 4.0 * (double)total_frames * KP);
         if (launch_stft_gain(p, h->stream)) return fail(h, "ev_denoise: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
     if (!itiles.empty()) {
         IstftParams p{};
-        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->dn.ibasis; p.env = h->dn.env;
+        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->dn.ibasis.get(); p.env = h->dn.env.as<float>();
         p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = KP; p.out = d_out; p.out_i16 = d_i16;
         KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)itiles.size() * (double)p.R * KP * hop,
                   4.0 * (double)total_frames * KP + (double)total_out * (want16 ? 6.0 : 4.0));
@@ -1731,23 +1700,16 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
     if (!wav || !wav_lens || !mel_basis || !mel || !energy || B < 1 || B > 65535 || !stft_shape_ok(n_fft, hop, n_mels)) return -2;
     FrameGrid g;
     if (frame_grid_layout(B, wav_lens, n_fft / 2 + 1, hop, 64, g)) return -2;
-    char* basis = nullptr; float* melT = nullptr;
-    int rc = features_upload_tables(nullptr, n_fft, n_mels, mel_basis, window, &basis, &melT) ? -1 : 0;
+    DevMem basis, melT;
     DevTable t;
     const size_t so = t.add(g.seqs), to = t.add(g.tiles);
-    if (rc == 0 && t.commit()) rc = -1;
-    if (rc == 0) {
-        StftParams p{};
-        p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
-        p.basis = basis; p.melT = melT; p.n_fft = n_fft; p.hop = hop; p.n_mels = n_mels; p.nmi = stft_mels_per_group(n_mels); p.n_bins = n_fft / 2 + 1;
-        p.n_btiles = stft_bin_tiles(n_fft); p.mel_clip = mel_clip; p.energy_floor = energy_floor; p.energy_mean = energy_mean; p.energy_std = energy_std;
-        p.mel = mel; p.energy = energy; p.mag = mag;
-        if (launch_stft_mel(p, (hipStream_t)stream)) rc = -2;
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    }
-    if (basis) (void)hipFree(basis);
-    if (melT) (void)hipFree(melT);
-    return rc;
+    if (features_upload_tables(nullptr, n_fft, n_mels, mel_basis, window, basis, melT) || t.commit()) return -1;
+    StftParams p{};
+    p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
+    p.basis = basis.get(); p.melT = melT.as<float>(); p.n_fft = n_fft; p.hop = hop; p.n_mels = n_mels; p.nmi = stft_mels_per_group(n_mels); p.n_bins = n_fft / 2 + 1;
+    p.n_btiles = stft_bin_tiles(n_fft); p.mel_clip = mel_clip; p.energy_floor = energy_floor; p.energy_mean = energy_mean; p.energy_std = energy_std;
+    p.mel = mel; p.energy = energy; p.mag = mag;
+    return op_finish(launch_stft_mel(p, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* window, int n_fft, int hop, const float* bias,
@@ -1764,9 +1726,7 @@ int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_l
     StftGainParams p = stft_gain_params(wav, wav_is_i16, t.at<StftSeq>(so), t.at<StftTile>(to), g.tiles.size(), t.at<char>(bo), n_fft, hop);
     p.bias = bias; p.strengths = strengths; p.spec_hi = (uint16_t*)spec_hi; p.spec_lo = (uint16_t*)spec_lo;
     p.mag = mag; p.mag_frames = EV_ALIGN_MAX_FRAMES;
-    int rc = launch_stft_gain(p, (hipStream_t)stream) ? -2 : 0;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(launch_stft_gain(p, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int ev_op_istft(const void* spec_hi, const void* spec_lo, int B, const int32_t* frames, const float* window, int n_fft, int hop, float* out,
@@ -1787,9 +1747,7 @@ int ev_op_istft(const void* spec_hi, const void* spec_lo, int B, const int32_t* 
     p.spec_hi = (const uint16_t*)spec_hi; p.spec_lo = (const uint16_t*)spec_lo; p.seqs = t.at<IstftSeq>(so); p.tiles = t.at<StftTile>(to);
     p.n_tiles = (int)tiles.size(); p.ibasis = t.at<char>(bo); p.env = t.at<float>(eo);
     p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = denoise_k_pad(n_fft); p.out = out; p.out_i16 = out_i16;
-    int rc = launch_istft_ola(p, (hipStream_t)stream) ? -2 : 0;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(launch_istft_ola(p, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sample_rate, int hop, int win, float f_min, float f_max,
@@ -1808,11 +1766,7 @@ int ev_op_pitch_yin(const void* wav, int wav_is_i16, int B, const int64_t* wav_l
     PitchParams p = pitch_params(c, tau_min, tau_max);
     p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
     p.f0 = f0_hz; p.ap = aperiodicity; p.tau = tau;
-    int rc = 0;
-    if (launch_pitch_yin(p, (hipStream_t)stream)) rc = -2;
-    else if (hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(launch_pitch_yin(p, (hipStream_t)stream), (hipStream_t)stream);
 }
 int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pitch_mean, float pitch_std, float* pitch, void* stream) {
     if (!f0_hz || !frames || !pitch || pitch == f0_hz || B < 1 || B > 65535) return -2;
@@ -1825,11 +1779,8 @@ int ev_op_pitch_fill(const float* f0_hz, int B, const int32_t* frames, float pit
     DevTable t;
     const size_t so = t.add(g.seqs);
     if (t.commit()) return -1;
-    int rc = 0;
     launch_pitch_fill(f0_hz, t.at<StftSeq>(so), B, pitch_mean, pitch_std, pitch, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(0, (hipStream_t)stream);
 }
 
 int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, int sr_in, int sr_out, const float* taps, int half_len, float* y,
@@ -1843,19 +1794,13 @@ int ev_op_resample(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
     if (resample_check_config(nullptr, "ev_op_resample", c, &up, &down, &half, ht)) return -2;
     std::vector<ResampleSeq> seqs; std::vector<ResampleTile> tiles;
     if (resample_layout(B, wav_lens, up, down, 0, seqs, tiles)) return -2;
-    float* tab = nullptr; size_t floats = 0;
-    if (resample_upload_table(up, half, ht, &tab, &floats)) return -1;
+    DevMem tab;
+    if (resample_upload_table(up, half, ht, tab)) return -1;
     DevTable t;
     const size_t so = t.add(seqs), to = t.add(tiles);
-    int rc = t.commit() ? -1 : 0;
-    if (rc == 0) {
-        if (resample_launch(wav, wav_is_i16 != 0, up, down, half, tab, t.at<ResampleSeq>(so), t.at<ResampleTile>(to), (int)tiles.size(),
-                            seqs[B - 1].in_off + seqs[B - 1].len, y, (hipStream_t)stream)) rc = -2;
-        else if (hipGetLastError() != hipSuccess) rc = -1;
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    }
-    (void)hipFree(tab);
-    return rc;
+    if (t.commit()) return -1;
+    return op_finish(resample_launch(wav, wav_is_i16 != 0, up, down, half, tab.as<float>(), t.at<ResampleSeq>(so), t.at<ResampleTile>(to), (int)tiles.size(),
+                                     seqs[B - 1].in_off + seqs[B - 1].len, y, (hipStream_t)stream), (hipStream_t)stream);
 }
 int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int trim_pad, float* out, int64_t* out_lens, int64_t* trim_start,
                int64_t* trim_end, void* stream) {
@@ -1870,15 +1815,12 @@ int ev_op_trim(const float* y, int B, const int64_t* lens, float trim_frac, int 
     std::vector<int64_t> cuts(2 * (size_t)B);
     std::vector<TrimSeq> ts;
     launch_trim_scan(y, t.at<ResampleSeq>(so), B, trim_frac, t.at<int64_t>(co), s);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (op_finish(0, s)) return -1;
     if (hipMemcpy(cuts.data(), t.at<int64_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     const int64_t longest = trim_plan(B, seqs, cuts.data(), trim_pad, ts, out_lens, nullptr, trim_start, trim_end);
     if (hipMemcpy(t.at<TrimSeq>(to), ts.data(), (size_t)B * sizeof(TrimSeq), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    int rc = 0;
     launch_trim_gather(y, t.at<TrimSeq>(to), B, longest, trim_pad, out, s);
-    if (hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(0, s);
 }
 
 int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const int64_t* seg_lens, float trim_frac, float trim_abs, float* peak,
@@ -1899,11 +1841,9 @@ int ev_op_stitch_scan(const float* wav, int S, const int64_t* seg_offsets, const
     if (t.commit()) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<int64_t> cuts(2 * (size_t)S);
-    int rc = 0;
     launch_stitch_peak(wav, t.at<StitchSeg>(so), S, max_len, t.at<float>(qo), s);
     launch_stitch_edges(wav, t.at<StitchSeg>(so), S, t.at<float>(qo), trim_frac, trim_abs, t.at<float>(po), t.at<int64_t>(co), s);
-    if (hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    int rc = op_finish(0, s);
     if (rc == 0 && (hipMemcpy(cuts.data(), t.at<int64_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(peak, t.at<float>(po), (size_t)S * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     if (rc == 0) for (int i = 0; i < S; ++i) { first[i] = cuts[2 * (size_t)i]; last[i] = cuts[2 * (size_t)i + 1]; }
@@ -1926,9 +1866,7 @@ int ev_op_flac_encode(const void* pcm, int pcm_is_i16, int B, const int64_t* len
     FlacParams fp = flac_params(c, sr_code, bs_code);
     fp.pcm = pcm; fp.pcm_is_i16 = pcm_is_i16 != 0; fp.frames = t.at<FlacFrame>(fo); fp.scratch = slots; fp.sizes = t.at<int32_t>(so); fp.desc = t.at<uint32_t>(d_o);
     std::vector<uint32_t> desc(NF);
-    int rc = 0;
-    if (launch_flac_encode(fp, (int64_t)NF, s) || hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    int rc = op_finish(launch_flac_encode(fp, (int64_t)NF, s), s);
     if (rc == 0 && (hipMemcpy(sizes, fp.sizes, sb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(desc.data(), fp.desc, sb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     if (rc == 0) for (size_t f = 0; f < NF; ++f) { kind[f] = (uint8_t)(desc[f] & 0xFFu); porder[f] = (uint8_t)(desc[f] >> 8 & 0xFFu); }
     return rc;
@@ -1950,10 +1888,7 @@ int ev_op_flac_lpc(const void* pcm, int pcm_is_i16, int B, const int64_t* lens, 
     hipStream_t s = (hipStream_t)stream;
     FlacParams fp = flac_params(c, sr_code, bs_code);
     fp.pcm = pcm; fp.pcm_is_i16 = pcm_is_i16 != 0; fp.frames = t.at<FlacFrame>(fo);
-    int rc = 0;
-    if (launch_flac_lpc_analysis(fp, FlacLpc{max_lpc_order, qlp_precision}, (int64_t)NF, t.at<int64_t>(ro), t.at<int32_t>(so), t.at<int32_t>(co), s) ||
-        hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    int rc = op_finish(launch_flac_lpc_analysis(fp, FlacLpc{max_lpc_order, qlp_precision}, (int64_t)NF, t.at<int64_t>(ro), t.at<int32_t>(so), t.at<int32_t>(co), s), s);
     if (rc == 0 && (hipMemcpy(R, t.at<int64_t>(ro), rb, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(shift, t.at<int32_t>(so), sb, hipMemcpyDeviceToHost) != hipSuccess ||
                     hipMemcpy(coef, t.at<int32_t>(co), cb, hipMemcpyDeviceToHost) != hipSuccess)) rc = -1;
     return rc;
@@ -1977,12 +1912,8 @@ int ev_op_stitch_mix(const float* wav, int S, const int64_t* src, const int64_t*
     DevTable t;
     const size_t mo = t.add(ms), d_o = t.add(docs), to = t.add(tiles), fo = t.add(tab, (size_t)F * sizeof(float));
     if (t.commit()) return -1;
-    int rc = 0;
-    if (launch_stitch_mix(wav, t.at<StitchMixSeg>(mo), t.at<StitchDoc>(d_o), t.at<StitchTile>(to), (int64_t)tiles.size(), t.at<float>(fo), F, out, out_i16,
-                          (hipStream_t)stream)) rc = -2;
-    else if (hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(launch_stitch_mix(wav, t.at<StitchMixSeg>(mo), t.at<StitchDoc>(d_o), t.at<StitchTile>(to), (int64_t)tiles.size(), t.at<float>(fo), F, out,
+                                       out_i16, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 // The AlignSeq table of the two aligner kernels, from per-utterance host arrays: 0, or -2
@@ -2014,9 +1945,7 @@ int ev_op_align_score(const float* text, const float* feats, int C, int B, const
     const size_t o = t.add(tab);
     if (t.commit()) return -1;
     launch_align_score(text, feats, C, t.at<AlignSeq>(o), B, max_frm, log_p, (hipStream_t)stream);
-    int rc = hipGetLastError() == hipSuccess ? 0 : -1;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(0, (hipStream_t)stream);
 }
 int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int32_t* frames, const int64_t* lp_off, const int64_t* tok_packed,
                     const int64_t* frm_packed, const int64_t* bits_off, uint32_t* bits, const float* pitch_frames, const float* energy_frames,
@@ -2029,9 +1958,7 @@ int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int3
     const size_t o = t.add(tab);
     if (t.commit()) return -1;
     launch_align_mas(log_p, t.at<AlignSeq>(o), B, max_tok, bits, pitch_frames, energy_frames, dur, pitch_tok, energy_tok, score, (hipStream_t)stream);
-    int rc = hipGetLastError() == hipSuccess ? 0 : -1;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
-    return rc;
+    return op_finish(0, (hipStream_t)stream);
 }
 
 int ev_op_limit_peak(const void* wav, int wav_is_i16, int B, const int64_t* lens, const float* gains, float ceiling, float* r, float* sample_peak,
@@ -2049,10 +1976,8 @@ int ev_op_limit_peak(const void* wav, int wav_is_i16, int B, const int64_t* lens
     if (t.commit()) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<LimitPeakOut> outs(NT);
-    int rc = 0;
-    if (launch_limit_peak(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, t.at<double>(ho), ceiling, r, t.at<LimitPeakOut>(oo), s) ||
-        hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    int rc = op_finish(launch_limit_peak(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, t.at<double>(ho), ceiling, r,
+                                         t.at<LimitPeakOut>(oo), s), s);
     if (rc == 0 && hipMemcpy(outs.data(), t.at<LimitPeakOut>(oo), NT * sizeof(LimitPeakOut), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     if (rc == 0) limit_fold_peaks(plan, B, outs.data(), sample_peak, true_peak, nonfinite);
     return rc;
@@ -2073,10 +1998,8 @@ int ev_op_limit_apply(const void* wav, int wav_is_i16, int B, const int64_t* len
     if (t.commit()) return -1;
     hipStream_t s = (hipStream_t)stream;
     std::vector<LimitApplyOut> outs(NT);
-    int rc = 0;
-    if (launch_limit_apply(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, r, t.at<double>(wo), lookahead, hold, out, out_i16,
-                           s_out, t.at<LimitApplyOut>(oo), s) || hipGetLastError() != hipSuccess) rc = -1;
-    if (hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    int rc = op_finish(launch_limit_apply(wav, wav_is_i16 != 0, gains ? t.at<float>(go) : nullptr, t.at<LimitTile>(to), (int64_t)NT, r, t.at<double>(wo), lookahead, hold,
+                                          out, out_i16, s_out, t.at<LimitApplyOut>(oo), s), s);
     if (rc == 0 && hipMemcpy(outs.data(), t.at<LimitApplyOut>(oo), NT * sizeof(LimitApplyOut), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     if (rc == 0) limit_fold_gains(plan, B, outs.data(), min_gain, limited);
     return rc;

@@ -56,10 +56,10 @@ int check_struct_size(ev_handle* h, const char* who, const char* field, uint32_t
 // ---------------------------------------------------------------- arena
 int arena_reserve(ev_handle* h, int idx, size_t bytes) {
     if (bytes <= h->arena_bytes[idx]) return 0;
-    if (h->arena[idx]) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->arena[idx])); h->arena[idx] = nullptr; h->arena_bytes[idx] = 0; }
+    if (h->arena[idx]) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->arena[idx].reset(); h->arena_bytes[idx] = 0; }
     bytes = align_up(bytes + bytes / 8, 1 << 20);
-    HIPCHK(h, hipMalloc((void**)&h->arena[idx], bytes));
-    HIPCHK(h, hipMemsetAsync(h->arena[idx], 0, bytes, h->stream));
+    HIPCHK(h, h->arena[idx].alloc(bytes));
+    HIPCHK(h, hipMemsetAsync(h->arena[idx].get(), 0, bytes, h->stream));
     h->arena_bytes[idx] = bytes;
     return 0;
 }
@@ -164,11 +164,8 @@ int parse_blob(ev_handle* h, const char* host_hdr, size_t nbytes, bool style = f
         if (is_style == style) it = h->wt.erase(it); else ++it;
     }
     h->scalar_cache.clear();
-    if (!style) {
-        if (h->pe_dev) { (void)hipFree(h->pe_dev); h->pe_dev = nullptr; }
-        h->pe_cap = 0;
-    }
-    char* base = style ? h->sblob : h->wblob;
+    if (!style) { h->pe_dev.reset(); h->pe_cap = 0; }
+    char* base = style ? h->sblob.as<char>() : h->wblob;
     for (uint32_t i = 0; i < count; ++i) {
         BlobEntry e;
         memcpy(&e, host_hdr + 16 + (size_t)i * sizeof(BlobEntry), sizeof e);
@@ -218,14 +215,13 @@ int ensure_pe(ev_handle* h, int need) {
     const int C = h->cfg.hidden, packed = (int)pw->dims[0];
     int cap = std::max(need, std::max(packed, 2 * h->pe_cap));
     cap = (int)align_up((size_t)cap, 1024);
-    float* nb = nullptr;
-    HIPCHK(h, hipMalloc((void**)&nb, (size_t)cap * C * 4));
+    DevMem nb;
+    HIPCHK(h, nb.alloc((size_t)cap * C * 4));
     const int have = std::min(packed, cap);
-    HIPCHK(h, hipMemcpyAsync(nb, pw->ptr, (size_t)have * C * 4, hipMemcpyDeviceToDevice, h->stream));
-    launch_pe_extend(nb, reinterpret_cast<const float*>(dw->ptr), have, cap, C, h->stream);
+    HIPCHK(h, hipMemcpyAsync(nb.get(), pw->ptr, (size_t)have * C * 4, hipMemcpyDeviceToDevice, h->stream));
+    launch_pe_extend(nb.as<float>(), reinterpret_cast<const float*>(dw->ptr), have, cap, C, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->pe_dev) HIPCHK(h, hipFree(h->pe_dev));
-    h->pe_dev = nb; h->pe_cap = cap;
+    h->pe_dev = std::move(nb); h->pe_cap = cap;
     return 0;
 }
 
@@ -1025,24 +1021,13 @@ void ev_destroy(ev_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < ARENA_COUNT; ++i) if (h->arena[i]) (void)hipFree(h->arena[i]);
-    if (h->rs.tab) (void)hipFree(h->rs.tab);
-    if (h->dlv.tab) (void)hipFree(h->dlv.tab);
-    if (h->stitch.tab) (void)hipFree(h->stitch.tab);
-    for (void* t : {(void*)h->dn.basis, (void*)h->dn.ibasis, (void*)h->dn.env, (void*)h->dn.bias})
-        if (t) (void)hipFree(t);
-    if (h->feat.basis) (void)hipFree(h->feat.basis);
-    if (h->feat.melT) (void)hipFree(h->feat.melT);
-    if (h->sblob) (void)hipFree(h->sblob);
     if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->pe_dev) (void)hipFree(h->pe_dev);
-    if (h->wblob && h->wblob_owned) (void)hipFree(h->wblob);
     for (auto e : h->evt_pool) (void)hipEventDestroy(e);
     for (auto& kv : h->region_evt) { (void)hipEventDestroy(kv.second.first); (void)hipEventDestroy(kv.second.second); }
     for (int j = 0; j < 2; ++j) { if (h->aux[j]) (void)hipStreamDestroy(h->aux[j]); if (h->ev_join[j]) (void)hipEventDestroy(h->ev_join[j]); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;      // the device memory goes with its owners (DevMem), after the wait above
 }
 
 int ev_set_stream(ev_handle* h, void* s) {
@@ -1055,10 +1040,9 @@ int ev_set_stream(ev_handle* h, void* s) {
 int ev_load_weights(ev_handle* h, const void* blob, size_t nbytes, const char*) {
     if (!h || !blob) return fail(h, "ev_load_weights: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->wblob && h->wblob_owned) HIPCHK(h, hipFree(h->wblob));
     h->wblob = nullptr;
-    HIPCHK(h, hipMalloc((void**)&h->wblob, nbytes));
-    h->wblob_owned = true; h->wbytes = nbytes;
+    HIPCHK(h, h->wblob_own.alloc(nbytes));
+    h->wblob = h->wblob_own.as<char>(); h->wbytes = nbytes;
     HIPCHK(h, hipMemcpy(h->wblob, blob, nbytes, hipMemcpyHostToDevice));
     return parse_blob(h, (const char*)blob, nbytes, false);
 }
@@ -1066,8 +1050,8 @@ int ev_load_weights(ev_handle* h, const void* blob, size_t nbytes, const char*) 
 int ev_load_weights_device(ev_handle* h, const void* dptr, size_t nbytes, const char*) {
     if (!h || !dptr) return fail(h, "ev_load_weights_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->wblob && h->wblob_owned) HIPCHK(h, hipFree(h->wblob));
-    h->wblob = (char*)dptr; h->wblob_owned = false; h->wbytes = nbytes;
+    h->wblob_own.reset();
+    h->wblob = (char*)dptr; h->wbytes = nbytes;
     if (nbytes < 16) return fail(h, "weight blob too small");
     uint32_t count = 0;
     char hdr[16];
@@ -1338,7 +1322,7 @@ static int synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* c
     float alphas[2];
     if (get_scalar(h, "enc.alpha", &alphas[0]) || get_scalar(h, "dec.alpha", &alphas[1])) return -1;
     { KScope ks(h, "embed_pe", 0, (double)NT * C * 12.0);
-      launch_embed_pe(tb.d_ling, h->d_cu, h->d_tok_seq, h->d_tok_pos, tok_emb, c.n_vocab, h->pe_dev, alphas[0], (float*)tb.x.p, keep ? (float*)tb.tokemb_tap.p : nullptr, Rt, C, h->stream); }
+      launch_embed_pe(tb.d_ling, h->d_cu, h->d_tok_seq, h->d_tok_pos, tok_emb, c.n_vocab, h->pe_dev.as<float>(), alphas[0], (float*)tb.x.p, keep ? (float*)tb.tokemb_tap.p : nullptr, Rt, C, h->stream); }
     if (run_stack(h, "enc", c.enc_layers, DT_F32, trc, tb.x, tb.hb, tb.qkv, tb.ctx, tb.ffn, tb.y, nullptr, keep ? &tb.ltaps : nullptr)) return -1;
     HIPCHK(h, hipGetLastError());
     region_end(h, "encoder");
@@ -1404,7 +1388,7 @@ static int synthesize(ev_handle* h, int B, const int64_t* ling, const int32_t* c
         max_frames = std::max(max_frames, h->mel_lens[b]);
     }
     if (ensure_pe(h, max_frames)) return -1;
-    const float* pe = h->pe_dev;
+    const float* pe = h->pe_dev.as<float>();
 
     // ---------------- phase 2: frame-rate arena (placed after the token arena)
     struct FrmBufs { Buf x, hb, qkv, ctx, ffn, y, mel32, mel16, up_tap, y_tap; std::vector<Buf> ltaps; float* d_mel; } fb;
@@ -1619,7 +1603,7 @@ int ev_align(ev_handle* h, int B, const int64_t* ling, const int32_t* cu, const 
     float enc_alpha;
     if (get_scalar(h, "enc.alpha", &enc_alpha)) return -1;
     { KScope ks(h, "embed_pe", 0, (double)NT * C * 12.0);
-      launch_embed_pe(ab.d_ling, h->d_cu, h->d_tok_seq, h->d_tok_pos, tok_emb, c.n_vocab, h->pe_dev, enc_alpha, (float*)ab.x.p, nullptr, Rt, C, h->stream); }
+      launch_embed_pe(ab.d_ling, h->d_cu, h->d_tok_seq, h->d_tok_pos, tok_emb, c.n_vocab, h->pe_dev.as<float>(), enc_alpha, (float*)ab.x.p, nullptr, Rt, C, h->stream); }
     if (run_stack(h, "enc", c.enc_layers, DT_F32, trc, ab.x, ab.hb, ab.qkv, ab.ctx, ab.ffn, ab.y, nullptr, nullptr)) return -1;
     WPTR(wcond, float, "proj.wcond"); WPTR(bproj, float, "proj.b"); WPTR(wproj, char, "proj.w32");
     { KScope ks(h, "cond_vector", 2.0 * B * C * (C + 2.0 * c.bert_dim), 0);
@@ -1677,11 +1661,10 @@ int ev_style_load_weights(ev_handle* h, const ev_bert_config* cfg, const void* b
     if (cfg->hidden % 128 || cfg->hidden > 1024 || cfg->heads <= 0 || cfg->hidden / cfg->heads != 64 || cfg->intermediate % 64 || cfg->layers <= 0)
         return fail(h, "ev_style_load_weights: only hidden %% 128 == 0 (<= 1024) with 64-wide heads is built (BERT-base: 768 / 12)");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->sblob) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->sblob)); h->sblob = nullptr; }
-    h->style_loaded = false;
-    HIPCHK(h, hipMalloc((void**)&h->sblob, nbytes));
+    if (h->sblob) HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->style_loaded = false; h->sbytes = 0;
+    HIPCHK(h, dev_upload(h->sblob, blob, nbytes));
     h->sbytes = nbytes;
-    HIPCHK(h, hipMemcpy(h->sblob, blob, nbytes, hipMemcpyHostToDevice));
     if (parse_blob(h, (const char*)blob, nbytes, true)) return -1;
     const WeightEntry* we = W(h, "sb.emb.word");
     if (!we) return -1;
@@ -1814,9 +1797,9 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
     if (!strcmp(name, "feat_mag"))
         return stage_copy(h, name, h->feat.mag, (size_t)h->feat.mag_elems * 4, h->feat.mag != nullptr, "no ev_features call with keep_stages yet", host_dst, cap);
     if (!strcmp(name, "resample_taps"))
-        return stage_copy(h, name, h->rs.tab, h->rs.tab_floats * 4, h->rs.ready, "ev_resample_setup has not been called", host_dst, cap);
+        return stage_copy(h, name, h->rs.tab.get(), h->rs.tab_floats * 4, h->rs.ready, "ev_resample_setup has not been called", host_dst, cap);
     if (!strcmp(name, "stitch_ramp"))
-        return stage_copy(h, name, h->stitch.tab, (size_t)std::max(h->stitch.F, 0) * 4, h->stitch.F >= 0, "no ev_stitch call yet", host_dst, cap);
+        return stage_copy(h, name, h->stitch.tab.get(), (size_t)std::max(h->stitch.F, 0) * 4, h->stitch.F >= 0, "no ev_stitch call yet", host_dst, cap);
     if (!strcmp(name, "resample_raw"))
         return stage_copy(h, name, h->rs.raw, (size_t)h->rs.raw_elems * 4, h->rs.raw != nullptr, "no ev_resample call with keep_stages yet", host_dst, cap);
     if (!strcmp(name, "log_p_attn")) {     // ev_align: the (T_b, N_b) blocks of the utterances, concatenated
@@ -1842,14 +1825,13 @@ int64_t ev_get_stage(ev_handle* h, const char* name, void* host_dst, size_t cap)
     const size_t need = (size_t)nrows * t.C * 4;
     if (!host_dst) return (int64_t)need;
     if (cap < need) return fail(h, "ev_get_stage(%s): need %zu bytes, cap %zu", name, need, cap);
-    float* d_tmp = nullptr; int64_t* d_scr = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_tmp, need));
-    HIPCHK(h, hipMalloc((void**)&d_scr, (3 * (size_t)h->B + 8) * 8));
-    int rc = pack_level(h, t.ptr, t.dtype, t.ld, t.C, t.shift, t.level == 0, d_tmp, d_scr);
-    if (rc == 0 && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, "ev_get_stage: gather failed");
-    if (rc == 0 && hipMemcpy(host_dst, d_tmp, need, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, "ev_get_stage: D2H failed");
-    (void)hipFree(d_tmp); (void)hipFree(d_scr);
-    return rc ? -1 : (int64_t)need;
+    DevMem tmp, scr;
+    HIPCHK(h, tmp.alloc(need));
+    HIPCHK(h, scr.alloc((3 * (size_t)h->B + 8) * 8));
+    if (pack_level(h, t.ptr, t.dtype, t.ld, t.C, t.shift, t.level == 0, tmp.as<float>(), scr.as<int64_t>())) return -1;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, "ev_get_stage: gather failed");
+    if (hipMemcpy(host_dst, tmp.get(), need, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, "ev_get_stage: D2H failed");
+    return (int64_t)need;
 }
 
 }  // extern "C"

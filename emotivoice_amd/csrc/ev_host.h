@@ -44,6 +44,36 @@ enum Arena {
     ARENA_COUNT
 };
 
+// One hipMalloc allocation and its owner: move-only, freed when the owner goes or takes another.  The caller has waited for whatever still reads it.
+class DevMem {
+    void* p_ = nullptr;
+public:
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { reset(); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    hipError_t alloc(size_t bytes) {      // replaces what it held; holds nothing after a failure
+        reset();
+        const hipError_t e = hipMalloc(&p_, bytes);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    void* get() const { return p_; }
+    template <typename T> T* as() const { return static_cast<T*>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+// host bytes into a fresh allocation, with a synchronous copy; `out` holds nothing after a failure
+inline hipError_t dev_upload(DevMem& out, const void* src, size_t bytes) {
+    hipError_t e = out.alloc(bytes);
+    if (e == hipSuccess && bytes) e = hipMemcpy(out.get(), src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) out.reset();
+    return e;
+}
+template <typename T> hipError_t dev_upload(DevMem& out, const std::vector<T>& v) { return dev_upload(out, v.data(), v.size() * sizeof(T)); }
+
 struct WeightEntry { int dtype; int ndim; uint64_t dims[4]; const char* ptr; uint64_t nbytes; };
 
 struct Buf {              // activation buffer with PAD_ROWS of slack on both sides
@@ -64,18 +94,18 @@ struct AlignState {       // ev_align; kept apart from the synthesis' mel_lens /
     const float* lp = nullptr; int64_t lp_elems = 0;
 };
 struct FeaturesState {       // ev_features.  basis, melT: the basis planes on the device; mag: the "feat_mag" stage of the last call
-    ev_features_config cfg{}; bool ready = false; char* basis = nullptr; float* melT = nullptr;
+    ev_features_config cfg{}; bool ready = false; DevMem basis, melT;
     std::vector<int32_t> mel_lens; std::vector<int64_t> mel_offs;
     const float* mag = nullptr; int64_t mag_elems = 0;
 };
 struct PitchState { std::vector<int32_t> mel_lens; std::vector<int64_t> mel_offs; };       // ev_pitch
 struct ResampleState {       // ev_resample.  tab: the phase-major table on the device; raw: the "resample_raw" stage of the last call
-    ev_resample_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; float* tab = nullptr; size_t tab_floats = 0;
+    ev_resample_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; DevMem tab; size_t tab_floats = 0;
     std::vector<int64_t> lens, offs, start, end;
     const float* raw = nullptr; int64_t raw_elems = 0;
 };
 struct StitchState {       // ev_stitch.  tab: the ramp table of the last call (device, EV_STITCH_MAX_FADE floats once allocated; its host copy feeds the upload)
-    float* tab = nullptr; int F = -1; std::vector<float> tab_host;
+    DevMem tab; int F = -1; std::vector<float> tab_host;
     std::vector<int64_t> doc_lens, doc_offs, pos, start, end; std::vector<float> peak;
 };
 struct CompareState {       // ev_compare: its result, all of it host memory
@@ -87,8 +117,8 @@ struct LoudnessState {       // ev_loudness
     std::vector<double> loud, rel, ms; std::vector<float> gain, peak; std::vector<uint8_t> flags, state;
     std::vector<int64_t> nonf, boffs;
 };
-struct DeliverState {       // ev_deliver.  tab: the phase-major table on the device (nullptr for sr_in == sr_out); its own, never ev_resample's
-    ev_deliver_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; float* tab = nullptr;
+struct DeliverState {       // ev_deliver.  tab: the phase-major table on the device (empty for sr_in == sr_out); its own, never ev_resample's
+    ev_deliver_config cfg{}; bool ready = false; int up = 1, down = 1, half = 0; DevMem tab;
     std::vector<int64_t> offs, n, clipped; std::vector<float> peak;
 };
 struct ScoreSide {       // a side of ev_score as ev_score_load left it: cq (total, D) and f0 (total,) or null live in the side's arena
@@ -102,7 +132,7 @@ struct ScoreState {       // ev_score: the two sides and the host halves of the 
     std::vector<double> sum_c, sum_c2, mcd, rmse, bias, vuv, warp;
 };
 struct DenoiseState {       // ev_denoise.  basis, ibasis, env, bias: its own tables on the device (one allocation each), never ev_features'
-    ev_denoise_config cfg{}; bool ready = false; char* basis = nullptr; char* ibasis = nullptr; float* env = nullptr; float* bias = nullptr;
+    ev_denoise_config cfg{}; bool ready = false; DevMem basis, ibasis, env, bias;
     std::vector<int64_t> lens, offs;
 };
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
@@ -117,14 +147,14 @@ struct ev_handle {
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     std::string err;
     // weights
-    char* wblob = nullptr; bool wblob_owned = false; size_t wbytes = 0;
+    evh::DevMem wblob_own; char* wblob = nullptr; size_t wbytes = 0;      // wblob: the blob in use, wblob_own's (ev_load_weights) or the caller's (ev_load_weights_device)
     std::map<std::string, evh::WeightEntry> wt;
     std::map<std::string, float> scalar_cache;   // host copies of 1-element tensors (biases of the Linear(C,1) heads, PE alphas)
-    float* pe_dev = nullptr; int pe_cap = 0;     // positional table, extended on demand beyond the packed length
+    evh::DevMem pe_dev; int pe_cap = 0;     // positional table, extended on demand beyond the packed length
     // SimBERT style encoder (ev_style_load_weights / ev_style_embed): its own blob, merged into `wt` under the "sb." prefix
-    char* sblob = nullptr; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
+    evh::DevMem sblob; size_t sbytes = 0; ev_bert_config bcfg{}; bool style_loaded = false;
     // arenas (evh::Arena)
-    char* arena[evh::ARENA_COUNT] = {}; size_t arena_bytes[evh::ARENA_COUNT] = {};
+    evh::DevMem arena[evh::ARENA_COUNT]; size_t arena_bytes[evh::ARENA_COUNT] = {};
     char* tok_ks = nullptr; size_t tok_ks_bytes = 0;          // split-K partial sums of the token-rate conv-FFN (tok_splitk); inside ARENA_TOKEN
     char* pinned = nullptr; size_t pinned_bytes = 0;
     // persistent outputs (host side)
@@ -173,7 +203,7 @@ struct ArenaPlan {   // two-pass: the dry pass measures, the second pass hands o
     ev_handle* h; int idx; bool dry; size_t off = 0;
     char* take(size_t bytes) {
         off = align_up(off, 256);
-        char* p = dry ? nullptr : h->arena[idx] + off;
+        char* p = dry ? nullptr : h->arena[idx].as<char>() + off;
         off += bytes;
         return p;
     }

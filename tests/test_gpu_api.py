@@ -212,3 +212,91 @@ def test_grouped_level_launches_equal_one_launch_per_conv_bitwise(ctx):
     grouped = [r for r in recs if r["name"] == "voc_conv_gemm_mx" and r["taps"] == 21]
     assert len(grouped) == 10, len(grouped)          # stages 0 and 1: five grouped levels each
     one.close()
+
+
+def test_setups_replace_each_other_and_engines_destroy_clean():
+    """The four utilities that keep tables on the device (ev_features, ev_resample, ev_deliver, ev_denoise) on one engine without weights: a
+    second setup replaces the first, the first again gives the first call's bits, and a setup the library rejects leaves the one before it at
+    work.  Then ev_destroy with such tables, without any, and a fresh engine that still works.  B = 2 at the smallest shapes the kernels take."""
+    from emotivoice_amd import _ffi
+    from emotivoice_amd.delivery import DeliveryConfig
+    from emotivoice_amd.denoise import DenoiseConfig
+    from emotivoice_amd.engine import EVEngine, EVError
+    from emotivoice_amd.features import FeatureConfig
+    from emotivoice_amd.resample import ResampleConfig
+    rng = np.random.default_rng(7)
+
+    def wavs(n):
+        return [(0.3 * rng.standard_normal(k)).astype(np.float32) for k in (n, n - 9)]
+
+    def bias(n_fft):
+        return np.linspace(0.0, 0.5, n_fft // 2 + 1).astype(np.float32)
+
+    def same(a, b):
+        return len(a) == len(b) and all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
+
+    w_feat, w_rs, w_dlv, w_dn = wavs(200), wavs(500), wavs(500), wavs(300)
+    eng = EVEngine()
+    lib = eng._lib
+
+    def features(e=None):
+        r = (e or eng).features(w_feat)
+        return r["mel_list"] + r["energy_list"]
+
+    # a config the library's own checks reject, straight through the C entry (the Python wrappers would refuse it before the call)
+    def bad_features():
+        c = _ffi.ev_features_config()
+        lib.ev_default_features_config(C.byref(c))
+        c.n_fft, c.hop, c.n_mels = 128, 32, 0
+        return lib.ev_features_setup(eng._h, C.byref(c)), "n_mels"
+
+    def bad_resample():
+        c = _ffi.ev_resample_config()
+        lib.ev_default_resample_config(C.byref(c))
+        c.sr_in, c.sr_out = 48000, 0
+        return lib.ev_resample_setup(eng._h, C.byref(c)), "sr_out"
+
+    def bad_deliver():
+        c = _ffi.ev_deliver_config()
+        c.struct_size = C.sizeof(_ffi.ev_deliver_config)
+        c.sr_in, c.sr_out, c.encoding = 16000, 8000, 7
+        return lib.ev_deliver_setup(eng._h, C.byref(c)), "encoding"
+
+    def bad_denoise():
+        c = _ffi.ev_denoise_config()
+        lib.ev_default_denoise_config(C.byref(c))
+        c.n_fft, c.hop = 128, 48          # a multiple of 8 that does not divide n_fft
+        b = bias(128)
+        return lib.ev_denoise_setup(eng._h, C.byref(c), b.ctypes.data_as(C.c_void_p)), "hop"
+
+    # per utility: the two configs, the setup, the call under a config (no setup of its own: the config is the one just set up), the rejected setup
+    groups = (
+        ("features", [FeatureConfig(n_fft=128, hop=32, n_mels=8), FeatureConfig(n_fft=256, hop=64, n_mels=8)],
+         eng.features_setup, lambda c: features(), bad_features),
+        ("resample", [ResampleConfig(sr_in=48000, sr_out=16000), ResampleConfig(sr_in=22050, sr_out=16000)],
+         eng.resample_setup, lambda c: eng.resample(w_rs, c.sr_in, sr_out=c.sr_out)["wav_list"], bad_resample),
+        ("deliver", [DeliveryConfig(sample_rate=8000, encoding="ulaw"), DeliveryConfig(sample_rate=24000, encoding="s16")],
+         lambda c: eng.deliver_setup(c, 16000), lambda c: eng.deliver(w_dlv, c, 16000)["delivered_list"], bad_deliver),
+        ("denoise", [DenoiseConfig(strength=0.5, n_fft=128, hop=32, bias=bias(128)), DenoiseConfig(strength=0.5, n_fft=256, hop=64, bias=bias(256))],
+         eng.denoise_setup, lambda c: eng.denoise(w_dn, c)["wav_list"], bad_denoise))
+    firsts = {}
+    for name, (c0, c1), setup, call, bad in groups:
+        setup(c0)
+        first = [x.copy() for x in call(c0)]
+        setup(c1)
+        second = [x.copy() for x in call(c1)]
+        assert len(first) >= 2 and all(x.size and np.all(np.isfinite(x.astype(np.float64))) for x in first + second), name
+        assert not same(first, second), name              # the second setup really is another one
+        setup(c0)
+        assert same(call(c0), first), name                # the first again: the first's bits
+        rc, word = bad()
+        assert rc != 0 and word in lib.ev_last_error(eng._h).decode(), name
+        assert same(call(c0), first), name                # the rejected setup left the tables alone
+        firsts[name] = first
+    eng.close()                                           # ev_destroy with every table owned
+    EVEngine().close()                                    # ... and with none
+    third = EVEngine()
+    third.features_setup(groups[0][1][0])
+    assert same(features(third), firsts["features"])
+    third.close()
+
