@@ -8,17 +8,18 @@ import numpy as np
 
 from . import _ffi
 from .config import EVShapes
-from .delivery import delivery_config
-from .denoise import denoise_config, removed_db
 from .engine_audio import EVAudio, cut, host_array
-from .limiter import as_config as limiter_config, pre_gain
-from .loudness import as_config as loudness_config
+from .output_chain import resolve as resolve_chain, run as run_chain
 from .packing import pack_utts
 
 
 class EVError(RuntimeError):
     pass
 
+
+# the chain's audio keys (output_chain.AUDIO_KEYS) under the names each entry point returns them
+SYNTHESIZE_NAMES = (("wav", "wav"), ("wav_list", "wav_list"), ("wav_i16", "wav_i16"), ("wav_i16_list", "wav_int16_list"))
+SYNTHESIZE_LONG_NAMES = (("wav", "wav"), ("wav_list", "docs"), ("wav_i16", "wav_i16"), ("wav_i16_list", "docs_i16"))
 
 _PREC = {"f16": _ffi.EV_PREC_F16, "f32": _ffi.EV_PREC_F32, "x3": _ffi.EV_PREC_X3, "mx": _ffi.EV_PREC_MX}
 
@@ -98,11 +99,7 @@ class EVEngine(EVAudio):
         self.device_id = device_id
         self._blob_keepalive = None
         self.last: Optional[_ffi.ev_result] = None
-        self.feature_config = self.resample_config = self.delivery_config = self._delivery_key = None      # set by features_setup() / resample_setup() / deliver_setup()
-        self.denoise_config = self._denoise_key = None      # set by denoise_setup()
-        self._denoise_own_bias: Dict[tuple, np.ndarray] = {}      # the vocoder's own bias per (n_fft, hop), measured by denoise_setup on the loaded weights
-        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise"):
-            setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
+        EVAudio.__init__(self)      # the utilities' setups, their keys and ``last_<utility>``
 
     # -- lifecycle
     def close(self):
@@ -131,15 +128,13 @@ class EVEngine(EVAudio):
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._check(self._lib.ev_load_weights(self._h, C.cast(buf, C.c_void_p), len(blob),
                                               manifest_json.encode() if manifest_json else None))
-        self._denoise_own_bias.clear()
-        self._denoise_key = None
+        self._weights_changed()
 
     def load_blob_device(self, dptr: int, nbytes: int, keepalive=None):
         """Borrow a blob that already lives in device memory (e.g. after an RCCL broadcast)."""
         self._blob_keepalive = keepalive
         self._check(self._lib.ev_load_weights_device(self._h, C.c_void_p(dptr), nbytes, None))
-        self._denoise_own_bias.clear()
-        self._denoise_key = None
+        self._weights_changed()
 
     # -- SimBERT prompt / content encoder (ev_style_*)
     def style_load(self, blob: bytes, cfg: dict):
@@ -315,109 +310,6 @@ class EVEngine(EVAudio):
         if denoise is not None and denoise.bias is None and (int(denoise.n_fft), int(denoise.hop)) not in self._denoise_own_bias:
             self.denoise_setup(denoise)
 
-    def _denoise_stage(self, wav_ptr: int, lens: np.ndarray, denoise, want_int16: bool, int16_only: bool, last_stage: bool):
-        """ev_denoise as the first output stage, on a packed device fp32 waveform: (ev_denoise_result, its host figures -- lens_out, offsets, with
-        ``denoise.report`` removed_db from ev_compare on the two device waveforms, and the audio when it is the last stage)."""
-        import dataclasses
-        dev = _ffi.EV_FLAG_DEVICE_INPUTS
-        dc = dataclasses.replace(denoise, want_int16=bool(last_stage and (denoise.want_int16 or want_int16))).validate()
-        if self._denoise_key != dc.key():
-            self.denoise_setup(dc)
-        B = len(lens)
-        res = self.denoise_raw(B, wav_ptr, False, lens, None, dev)
-        got = self.denoise_to_numpy(res, int16_only=int16_only, skip_wav=not last_stage)
-        if dc.report:
-            if np.array_equal(got["lens_out"], np.asarray(lens, np.int64)):      # the same packing on both sides: one call
-                cmp = self.compare_to_numpy(self.compare_raw(B, res.wav, wav_ptr, lens, dev))
-                got["removed_db"] = removed_db(cmp["sum_d2"], cmp["sum_y2"])
-            else:                                                                 # a length was cut to whole hops: utterance by utterance
-                offs_in, rd = np.concatenate([[0], np.cumsum(np.asarray(lens, np.int64))]), []
-                for b in range(B):
-                    cmp = self.compare_to_numpy(self.compare_raw(1, res.wav + 4 * int(got["offsets"][b]), wav_ptr + 4 * int(offs_in[b]),
-                                                                 got["lens_out"][b:b + 1], dev))
-                    rd.append(removed_db(cmp["sum_d2"], cmp["sum_y2"])[0])
-                got["removed_db"] = np.array(rd, np.float64)
-        return res, got
-
-    def _finish(self, wav_ptr: int, lens: np.ndarray, loudness, limiter, want_int16: bool, int16_only: bool, delivery=None, denoise=None):
-        """The output stages between the synthesis (or ev_stitch) and ev_flac, on a packed device fp32 waveform.  loudness / limiter: a
-        LoudnessConfig / LimiterConfig or None.  loudness alone: ev_loudness scales; limiter alone: ev_limit; both: ev_loudness measures only,
-        the pre-gain is worked out on the host (the gain rule without its sample-peak step) and ev_limit scales and limits in its one pass.
-        The last stage also writes the clamped int16 with ``want_int16``.  -> (the audio copied from the last stage: wav / wav_list and,
-        where the stage made it, wav_i16 / wav_i16_list, by ``int16_only`` as ``*_to_numpy`` reads it; the loudness figures or None; the
-        limiter's figures or None; the last stage's device int16 waveform or None; ev_deliver's result or None).
-        delivery: a DeliveryConfig or None.  With it ev_deliver runs last, on the fp32 device waveform of the stage before it (``wav_ptr`` when
-        there is none); the earlier stages then make no int16 and none of their audio is copied to the host: the delivered bytes are the audio
-        (delivered_list, delivered_rate and ``delivery`` = peak / clipped / n_samples in the returned audio)."""
-        import dataclasses
-        B, dev = len(lens), _ffi.EV_FLAG_DEVICE_INPUTS
-        last = figures = limited = gains = denoised = None
-        if delivery is not None:
-            want_int16 = False
-        if denoise is not None:      # first: the later stages measure and shape the audio that is delivered
-            last, denoised = self._denoise_stage(wav_ptr, lens, denoise, want_int16, int16_only, loudness is None and limiter is None and delivery is None)
-            wav_ptr, lens = last.wav, denoised["lens_out"]
-        if loudness is not None:
-            lc = (dataclasses.replace(loudness, want_int16=loudness.want_int16 or want_int16) if limiter is None else
-                  dataclasses.replace(loudness, target_lufs=float("nan"), want_int16=False))
-            last = self.loudness_raw(B, wav_ptr, False, lens, lc, dev)
-            figures = self.loudness_to_numpy(last, int16_only=int16_only, skip_wav=delivery is not None)
-        if limiter is not None:
-            if loudness is not None:
-                pairs = [pre_gain(float(l), loudness) for l in figures["loudness"]]
-                gains = np.array([g for g, _ in pairs], np.float32)
-                figures["gain"], figures["flags"] = gains.copy(), np.array([f for _, f in pairs], np.uint8)
-            last = self.limit_raw(B, wav_ptr, False, lens, gains, dataclasses.replace(limiter, want_int16=limiter.want_int16 or want_int16), dev)
-            limited = self.limit_to_numpy(last, int16_only=int16_only, skip_wav=delivery is not None)
-        src = limited if limited is not None else figures if figures is not None else denoised if denoised is not None else {}
-        audio = {k: src.pop(k) for k in ("wav", "wav_list", "wav_i16", "wav_i16_list") if k in src}
-        if denoised is not None:
-            audio["denoise"] = denoised
-        if delivery is None:
-            return audio, figures, limited, last.wav_i16 if last is not None else None, None
-        sr = int(self.shapes.sr)
-        if self._delivery_key != delivery.key(sr):
-            self.deliver_setup(delivery, sr)
-        dres = self.deliver_raw(B, last.wav if last is not None else wav_ptr, False, lens, None, dev)
-        got = self.deliver_to_numpy(dres, delivery)
-        audio = dict(delivered_list=got["delivered_list"], delivered_rate=int(delivery.sample_rate),
-                     delivery=dict(peak=got["peak"], clipped=got["clipped"], n_samples=got["n_samples"], encoding=delivery.encoding))
-        if denoised is not None:
-            audio["denoise"] = denoised
-        return audio, figures, limited, None, dres
-
-    def _flac_delivered(self, sel, dres, given, sample_rate: int, **kw) -> List[Optional[bytes]]:
-        """The selected utterances of an ev_deliver result (int16) as FLAC at the delivered rate: one ev_flac call per utterance, since every
-        utterance of the result starts on its own 16-byte boundary and ev_flac takes its segments back to back."""
-        fc = self._flac_config(given, int(sample_rate), **kw)
-        out: List[Optional[bytes]] = [None] * dres.batch
-        for b in range(dres.batch):
-            if sel[b]:
-                fr = self.flac_raw(1, dres.data + int(dres.byte_offsets[b]), True, [int(dres.n_samples[b])], fc, _ffi.EV_FLAG_DEVICE_INPUTS)
-                out[b] = self.flac_to_numpy(fr)["streams"][0]
-        return out
-
-    def _flac_config(self, given, sample_rate: int, **kw):
-        """The FlacConfig of a ``flac=`` argument: a given one with the engine's sample rate (and ``kw``), else the defaults."""
-        import dataclasses
-        from .flac import FlacConfig
-        if isinstance(given, FlacConfig):
-            return dataclasses.replace(given, sample_rate=int(sample_rate), **kw).validate()
-        return FlacConfig(sample_rate=int(sample_rate), **kw)
-
-    def _flac_runs(self, sel: np.ndarray, offsets: np.ndarray, wav_ptr: int, pcm_i16: Optional[int], given=None) -> List[Optional[bytes]]:
-        """The segments that ``sel`` selects of a packed device waveform, as FLAC: one ev_flac call per run of consecutive selected segments
-        (ev_flac takes its segments back to back), from the int16 waveform ``pcm_i16`` when there is one, else from the fp32 ``wav_ptr`` with
-        the wrapping conversion."""
-        fc = self._flac_config(given, int(self.shapes.sr), convert="wrap")
-        out: List[Optional[bytes]] = [None] * len(sel)
-        edges = np.flatnonzero(np.diff(np.concatenate([[0], sel, [0]]).astype(np.int8)))      # where a run begins, where it ends, ...
-        for b, e in zip(edges[::2].tolist(), edges[1::2].tolist()):
-            src = pcm_i16 + 2 * int(offsets[b]) if pcm_i16 else wav_ptr + 4 * int(offsets[b])
-            fr = self.flac_raw(e - b, src, bool(pcm_i16), np.diff(offsets[b:e + 1]), fc, _ffi.EV_FLAG_DEVICE_INPUTS)
-            out[b:e] = self.flac_to_numpy(fr)["streams"]
-        return out
-
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
                    forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None,
                    denoise=None) -> Dict[str, object]:
@@ -425,73 +317,38 @@ class EVEngine(EVAudio):
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
         for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
+        The five arguments below are the output chain on the device, denoise -> loudness -> limiter -> delivery -> flac; emotivoice_amd/output_chain.py
+        states once, for every combination, the order, which stage makes the int16, what is copied to the host and what a FLAC stream decodes to.
         flac: None, True, one boolean per utterance or an emotivoice_amd.flac.FlacConfig (every utterance, with its LPC / MD5 / block settings;
-        the sample rate is the engine's and the conversion stays the wrapping one): adds flac_list, the FLAC stream (``bytes``) of every selected utterance and None
-        for the others, encoded on the device from the fp32 waveform with the wrapping conversion -- a stream decodes to
-        wav_float_to_int16(wav_list[b]).
-        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every utterance is normalised on the device
-        (ev_loudness on the vocoder's waveform).  wav / wav_list then hold the normalised audio, want_int16 adds wav_i16 / wav_int16_list
-        by the clamping rule (not EV_FLAG_WANT_INT16's wrapping cast), ``loudness`` holds the per-utterance figures, and flac encodes the
-        normalised int16: a stream decodes to wav_int16_list[b].
+        the sample rate is the engine's and the conversion stays the wrapping one): adds flac_list, the FLAC stream (``bytes``) of every selected
+        utterance and None for the others.  Without another stage a stream decodes to wav_float_to_int16(wav_list[b]).
+        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every utterance is normalised on the device (ev_loudness).
+        wav / wav_list then hold the normalised audio, want_int16 adds wav_i16 / wav_int16_list by the clamping rule (not EV_FLAG_WANT_INT16's
+        wrapping cast) and ``loudness`` holds the per-utterance figures.
         limiter: None, True, a true-peak ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: every utterance goes through ev_limit
-        on the device.  With ``loudness`` the gain to the target is no longer cut by the utterance's largest sample: ev_loudness only measures,
-        the pre-gain (emotivoice_amd.limiter.pre_gain) goes into ev_limit, and the limiter holds the peaks sample by sample; ``loudness`` then
-        holds the measurement and the pre-gain, ``limiter`` the limiter's per-utterance figures, and the audio, the int16 (clamping rule) and
-        the FLAC streams are the limiter's.  The loudness is not measured again after the limiter: it sits at or slightly below the target.
+        on the device; ``limiter`` holds its per-utterance figures.  With ``loudness`` the gain to the target is no longer cut by the utterance's
+        largest sample: ev_loudness only measures and ``loudness`` holds the measurement and the pre-gain.  The loudness is not measured again
+        after the limiter: it sits at or slightly below the target.
         delivery: None, a sample rate in Hz (int16 at that rate) or an emotivoice_amd.delivery.DeliveryConfig: ev_deliver runs on the device
-        after the last of the stages above (on the vocoder's waveform when there is none) and the response is what it writes: delivered_list
-        (one float32 / int16 / uint8 array per utterance, at delivered_rate), ``delivery`` (peak, clipped, n_samples per utterance).  wav /
-        wav_list / wav_i16 are then not returned -- the 16 kHz waveform stays on the device -- and want_int16 is ignored.  With ``flac`` the
-        encoding must be "s16": ev_flac reads ev_deliver's int16 on the device at the delivered rate, a stream decodes to delivered_list[b].
+        after the last of the stages above and the response is what it writes: delivered_list (one float32 / int16 / uint8 array per utterance,
+        at delivered_rate), ``delivery`` (peak, clipped, n_samples per utterance).  wav / wav_list / wav_i16 are then not returned -- the 16 kHz
+        waveform stays on the device -- and want_int16 is ignored.  With ``flac`` the encoding must be "s16".
         denoise: None, True, a strength, a dict of DenoiseConfig's fields or an emotivoice_amd.denoise.DenoiseConfig: ev_denoise runs FIRST, on the
         vocoder's waveform -- strength times the magnitude spectrum of the vocoder's answer to an all-zero mel (measured once per engine, or
-        config.bias) is subtracted from every STFT cell -- so that loudness is measured on the audio that is delivered; the lengths do not change
-        (a waveform of whole frames).  Alone it is the last stage: wav / wav_list hold its output, want_int16 and flac its clamped int16.
-        ``denoise`` in the result holds lens_out and, with report=True, removed_db: per utterance the removed energy relative to the input
-        (ev_compare on the two device waveforms).  The default strength 0.01 is an unmeasured starting value (emotivoice_amd.denoise)."""
-        from .flac import FlacConfig
-        sel = None
-        if flac is not None and flac is not False:
-            sel = np.ones(len(utts), bool) if flac is True or isinstance(flac, FlacConfig) else np.asarray(flac, bool)
-            if sel.shape != (len(utts),):
-                raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (len(utts), sel.shape))
-        for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery), ("denoise", denoise)):
-            if given is not None and not vocoder:
-                raise ValueError("%s needs the vocoder's waveform" % name)
-        lc = None if loudness is None else loudness_config(loudness, int(self.shapes.sr))
-        mc = None if limiter is None else limiter_config(limiter, int(self.shapes.sr))
-        dc = delivery_config(delivery, int(self.shapes.sr))
-        nc = denoise_config(denoise, int(self.shapes.sr))
-        if dc is not None and sel is not None and dc.encoding != "s16":
-            raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
-        staged = lc is not None or mc is not None or dc is not None or nc is not None       # the audio is the last stage's: the synthesis makes no int16 and its waveform stays on the device
-        flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
-        self._denoise_ready(nc)
+        config.bias) is subtracted from every STFT cell; the lengths do not change (a waveform of whole frames).  ``denoise`` in the result holds
+        lens_out and, with report=True, removed_db.  The default strength 0.01 is an unmeasured starting value (emotivoice_amd.denoise)."""
+        plan = resolve_chain(self.shapes.sr, len(utts), denoise, loudness, limiter, delivery, flac, vocoder, flac_convert="wrap")
+        flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not plan.staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
+        self._denoise_ready(plan.denoise)
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
-        out = self.result_to_numpy(res, want_int16, skip_wav=staged)
+        out = self.result_to_numpy(res, want_int16, skip_wav=plan.staged)
         out["cu_seqlens"] = cu
-        offs = out["mel_offsets"] * self.shapes.upsample_factor
-        pcm_i16 = None
-        if staged:
-            audio, figures, limited, pcm_i16, dres = self._finish(res.wav, np.diff(offs), lc, mc, want_int16 or sel is not None, False, dc, nc)
-            if nc is not None:      # whole frames in, whole frames out: every offset above still holds
-                assert np.array_equal(audio["denoise"]["lens_out"], np.diff(offs)), "ev_denoise changed a length of whole frames"
-                out["denoise"] = audio.pop("denoise")
-            if dc is not None:
-                out.update(audio)
-            else:
-                out["wav"], out["wav_list"] = audio["wav"], audio["wav_list"]
-                if want_int16 or sel is not None:
-                    out["wav_i16"], out["wav_int16_list"] = audio.get("wav_i16"), audio.get("wav_i16_list")
-            if figures is not None:
-                out["loudness"] = figures
-            if limited is not None:
-                out["limiter"] = limited
-        if sel is not None and dc is not None:
-            out["flac_list"] = self._flac_delivered(sel, dres, flac, dc.sample_rate, convert="wrap")
-        elif sel is not None:
-            out["flac_list"] = self._flac_runs(sel, offs, res.wav, pcm_i16, flac)
-        return out
+        lens = np.diff(out["mel_offsets"] * self.shapes.upsample_factor)
+        want_i16 = want_int16 or plan.flac is not None
+        chain = run_chain(self, plan, res.wav, lens, want_i16)
+        if plan.denoise is not None:      # whole frames in, whole frames out: every offset above still holds
+            assert np.array_equal(chain.figures["denoise"]["lens_out"], lens), "ev_denoise changed a length of whole frames"
+        return chain.into(out, SYNTHESIZE_NAMES if want_i16 else SYNTHESIZE_NAMES[:2])
 
     def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None,
                         delivery=None, denoise=None) -> Dict[str, object]:
@@ -501,75 +358,53 @@ class EVEngine(EVAudio):
         documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
         config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
+        The five arguments below are the output chain, per document, after ev_stitch; emotivoice_amd/output_chain.py states its rules.
         flac=True or an emotivoice_amd.flac.FlacConfig (its LPC / MD5 / block settings; the sample rate is the engine's; ``md5`` costs one serial
-        chain per document) adds flac_list, one FLAC stream (``bytes``) per document, encoded on the device from ev_stitch's int16 documents (it turns
-        config.want_int16 on, so ``documents`` are the int16 ones a stream decodes to).
-        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every document is normalised on the device after ev_stitch
-        (ev_loudness: one gain per document, so the balance between its sentences stays) and before ev_flac; ``documents`` (int16 by the
-        clamping rule with config.want_int16) then hold the normalised audio and ``loudness`` the per-document figures.
-        limiter: as ``synthesize`` takes it, per document: ev_limit after ev_stitch (and after ev_loudness's measurement when ``loudness`` is
-        given, whose pre-gain it applies) and before ev_flac; ``documents`` hold the limited audio and ``limiter`` the per-document figures.
-        delivery: as ``synthesize`` takes it, per document, after the last of those stages: ``documents`` is then delivered_list (at
-        delivered_rate, in the delivery's encoding), ``delivery`` holds peak / clipped / n_samples, no 16 kHz audio is copied to the host,
-        config.want_int16 is ignored and flac (encoding "s16" only) reads ev_deliver's int16 at the delivered rate.  sentence_times are in
-        SECONDS and hold at any delivered rate; seg_pos / seg_start / seg_end / doc_lens and ``sample_rate`` stay on the engine's 16 kHz clock
-        (delivered_rate is returned next to them).
-        denoise: as ``synthesize`` takes it, per document: ev_denoise right after ev_stitch and before the other stages.  Its output has whole
-        hops: a document whose length is no multiple of the hop (256) loses the up to 255 samples after its last whole hop, doc_lens then holds
-        the new lengths and ``denoise`` lens_out (and removed_db with report=True)."""
+        chain per document) adds flac_list, one FLAC stream (``bytes``) per document (it turns config.want_int16 on, so
+        ``documents`` are the int16 ones a stream decodes to).
+        loudness: None, a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig: every document is normalised on the device (ev_loudness:
+        one gain per document, so the balance between its sentences stays); ``documents`` (int16 by the clamping rule with config.want_int16)
+        then hold the normalised audio and ``loudness`` the per-document figures.
+        limiter: as ``synthesize`` takes it, per document; ``documents`` hold the limited audio and ``limiter`` the per-document figures.
+        delivery: as ``synthesize`` takes it, per document: ``documents`` is then delivered_list (at delivered_rate, in the delivery's encoding),
+        ``delivery`` holds peak / clipped / n_samples, no 16 kHz audio is copied to the host, config.want_int16 is ignored and flac needs the
+        encoding "s16".  sentence_times are in SECONDS and hold at any delivered rate; seg_pos / seg_start / seg_end / doc_lens and
+        ``sample_rate`` stay on the engine's 16 kHz clock (delivered_rate is returned next to them).
+        denoise: as ``synthesize`` takes it, per document, right after ev_stitch.  Its output has whole hops: a document whose length is no
+        multiple of the hop (256) loses the up to 255 samples after its last whole hop, doc_lens then holds the new lengths and ``denoise``
+        lens_out (and removed_db with report=True)."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
-        dc = delivery_config(delivery, int(self.shapes.sr))
-        nc = denoise_config(denoise, int(self.shapes.sr))
-        if dc is not None and flac and dc.encoding != "s16":
-            raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
-        if dc is not None and sc.want_int16:
-            sc = dataclasses.replace(sc, want_int16=False).validate()
-        if flac and not sc.want_int16 and dc is None:
-            sc = dataclasses.replace(sc, want_int16=True).validate()
         if int(sc.sample_rate) != int(self.shapes.sr):
             raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
-        lc = None if loudness is None else loudness_config(loudness, int(sc.sample_rate))
-        mc = None if limiter is None else limiter_config(limiter, int(sc.sample_rate))
+        plan = resolve_chain(sc.sample_rate, None, denoise, loudness, limiter, delivery, flac)
+        stitch_i16 = bool(sc.want_int16 or plan.flac is not None) and plan.delivery is None      # a delivered response has no 16 kHz int16
+        if stitch_i16 != sc.want_int16:
+            sc = dataclasses.replace(sc, want_int16=stitch_i16).validate()
         utts, seg_doc, pauses = flatten_documents(documents)
         S = len(utts)
         if S > 65535:
             raise ValueError("%d sentences exceed the 65535 segments of one ev_stitch call; split the documents over several calls" % S)
         seg_doc, pause_after = plan_document(seg_doc, pauses, sc.sample_rate)
-        self._denoise_ready(nc)
+        self._denoise_ready(plan.denoise)
         res, _ = self._synthesize_call(utts, alpha, 0, None, prosody)
         mel_offs = host_array(res.mel_offsets, S + 1, np.int64) * self.shapes.upsample_factor
         st = self.stitch_raw(S, res.wav, mel_offs[:-1], np.diff(mel_offs), seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
-        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=lc is not None or mc is not None or dc is not None or nc is not None)
-        stage = ("denoise" if nc is not None else "limiter" if mc is not None else "loudness" if lc is not None else "delivery" if dc is not None else
-                 "flac" if flac else None)
+        out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=plan.staged)
+        reader = ("denoise" if plan.denoise is not None else "limiter" if plan.limiter is not None else "loudness" if plan.loudness is not None else
+                  "delivery" if plan.delivery is not None else "flac" if plan.flac is not None else None)
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
-        if empty and stage:
-            raise ValueError("%s: document %d is empty after the cut" % (stage, empty[0]))
-        audio, figures, limited, pcm_i16, dres = self._finish(st.wav, out["doc_lens"], lc, mc, sc.want_int16, sc.want_int16, dc, nc)
-        if nc is not None:
-            out["denoise"] = audio.pop("denoise")
+        if empty and reader:
+            raise ValueError("%s: document %d is empty after the cut" % (reader, empty[0]))
+        chain = run_chain(self, plan, st.wav, out["doc_lens"], sc.want_int16, sc.want_int16, st.wav_i16)
+        chain.into(out, SYNTHESIZE_LONG_NAMES)
+        if plan.denoise is not None:
             out["doc_lens"], out["doc_offsets"] = out["denoise"]["lens_out"], out["denoise"]["offsets"]
-        if dc is not None:
-            out.update(audio)
-        for k, name in (("wav", "wav"), ("wav_list", "docs"), ("wav_i16", "wav_i16"), ("wav_i16_list", "docs_i16")):
-            if k in audio:
-                out[name] = audio[k]
-        if figures is not None:
-            out["loudness"] = figures
-        if limited is not None:
-            out["limiter"] = limited
-        if flac and dc is not None:
-            out["flac_list"] = self._flac_delivered([True] * st.batch_docs, dres, flac, dc.sample_rate)
-        elif flac:
-            fr = self.flac_raw(st.batch_docs, pcm_i16 or st.wav_i16, True, out["doc_lens"], self._flac_config(flac, int(sc.sample_rate)),
-                               _ffi.EV_FLAG_DEVICE_INPUTS)
-            out["flac_list"] = self.flac_to_numpy(fr)["streams"]
         sr = float(sc.sample_rate)
         start = out["seg_pos"] / sr
         end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr
-        out["documents"] = out["delivered_list"] if dc is not None else out["docs_i16"] if sc.want_int16 else out["docs"]
+        out["documents"] = out["delivered_list"] if plan.delivery is not None else out["docs_i16"] if sc.want_int16 else out["docs"]
         out["seg_doc"] = seg_doc
         out["sentence_times"] = [[(float(start[s]), float(end[s])) for s in np.nonzero(seg_doc == d)[0]] for d in range(st.batch_docs)]
         out["sample_rate"] = int(sc.sample_rate)

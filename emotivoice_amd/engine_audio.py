@@ -50,6 +50,24 @@ class EVAudio:
     """The utilities' methods of EVEngine.  Every call leaves its result struct in ``last_<utility>``; the struct's arrays stay valid until the
     next call of the same utility on this engine."""
 
+    def __init__(self):
+        self.feature_config = self.resample_config = self.delivery_config = self.denoise_config = None      # set by the ``*_setup`` calls
+        self._setup_keys: Dict[str, tuple] = {}                   # "deliver" / "denoise" -> the key of the config the library is set up with
+        self._denoise_own_bias: Dict[tuple, np.ndarray] = {}      # the vocoder's own bias per (n_fft, hop), measured by denoise_setup on the loaded weights
+        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise"):
+            setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
+
+    def _setup_for(self, name: str, key: tuple, *args):
+        """``<name>_setup(*args)`` unless the library is set up with ``key`` already: the output chain and the host-array calls of one engine share
+        a setup, and set up again only when the key changed."""
+        if self._setup_keys.get(name) != key:
+            getattr(self, name + "_setup")(*args)
+
+    def _weights_changed(self):
+        """Other weights: the measured bias is the old vocoder's, and so is a denoise setup that may hold it."""
+        self._denoise_own_bias.clear()
+        self._setup_keys.pop("denoise", None)
+
     def _call(self, name: str, *args):
         """ev_<name>(handle, *args, &result): a fresh ev_<name>_result with its struct_size, the call, the error check, ``last_<name>``."""
         rt = getattr(_ffi, "ev_%s_result" % name)
@@ -374,7 +392,7 @@ class EVAudio:
             taps = np.ascontiguousarray(dc.taps, np.float32).reshape(-1)
             c.taps, c.half_len = taps.ctypes.data, (taps.size - 1) // 2
         self._check(self._lib.ev_deliver_setup(self._h, C.byref(c)))
-        self.delivery_config, self._delivery_key = dc, dc.key(sr_in)
+        self.delivery_config, self._setup_keys["deliver"] = dc, dc.key(sr_in)
 
     def deliver_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, seeds=None, flags: int = 0) -> _ffi.ev_deliver_result:
         """ev_deliver (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens and seeds (None: the
@@ -407,8 +425,7 @@ class EVAudio:
         dc = delivery_config(config, int(sample_rate))
         if dc is None:
             raise ValueError("deliver needs a DeliveryConfig or a sample rate")
-        if getattr(self, "_delivery_key", None) != dc.key(sample_rate):
-            self.deliver_setup(dc, sample_rate)
+        self._setup_for("deliver", dc.key(sample_rate), dc, sample_rate)
         flat, is16, lens = pack_segments(wavs)
         return self.deliver_to_numpy(self.deliver_raw(len(lens), flat.ctypes.data, is16, lens, seeds), dc)
 
@@ -424,12 +441,11 @@ class EVAudio:
         c = _ffi.ev_denoise_config()
         self._lib.ev_default_denoise_config(C.byref(c))
         c.n_fft, c.hop, c.strength, c.want_i16 = int(dc.n_fft), int(dc.hop), float(dc.strength), 1 if dc.want_int16 else 0
-        own = getattr(self, "_denoise_own_bias", None)      # (n_fft, hop) -> the bias measured on the loaded weights: measured once, then passed back
-        shape = (int(dc.n_fft), int(dc.hop))
-        bias = (own or {}).get(shape) if dc.bias is None else np.ascontiguousarray(dc.bias, np.float32)
+        own, shape = self._denoise_own_bias, (int(dc.n_fft), int(dc.hop))      # the bias measured on the loaded weights: measured once, then passed back
+        bias = own.get(shape) if dc.bias is None else np.ascontiguousarray(dc.bias, np.float32)
         self._check(self._lib.ev_denoise_setup(self._h, C.byref(c), _ptr(bias) if bias is not None else None))
-        self.denoise_config, self._denoise_key = dc, dc.key()
-        if dc.bias is None and bias is None and own is not None:
+        self.denoise_config, self._setup_keys["denoise"] = dc, dc.key()
+        if dc.bias is None and bias is None:
             own[shape] = self.denoise_bias()
 
     def denoise_bias(self) -> np.ndarray:
@@ -466,8 +482,7 @@ class EVAudio:
         the config's).  Every output has hop * (len // hop) samples."""
         from .denoise import DenoiseConfig, denoise_config
         dc = denoise_config(config) or DenoiseConfig().validate()
-        if getattr(self, "_denoise_key", None) != dc.key():
-            self.denoise_setup(dc)
+        self._setup_for("denoise", dc.key(), dc)
         flat, is16, lens = pack_segments(wavs, min_samples=int(dc.n_fft) // 2 + 1)
         return self.denoise_to_numpy(self.denoise_raw(len(lens), flat.ctypes.data, is16, lens, strengths))
 

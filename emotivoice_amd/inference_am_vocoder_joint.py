@@ -105,11 +105,12 @@ def synthesize_checkpoint(config, conf, checkpoint_path, out_dir, args, state_di
     eng = gen._ensure_engine()
     sr = int(getattr(config, "sampling_rate", gen.shapes.sr))
     written = 0
-    from .inference_tts import delivery_from_args, write_delivered
-    delivery = delivery_from_args(args)       # --sample-rate / --encoding / --dither: the files at that rate and encoding, converted on the device
+    from .inference_tts import chain_from_args, write_delivered
+    stages = chain_from_args(args)            # --sample-rate / --encoding / --dither: the files at that rate and encoding, converted on the device
+    delivery = stages.get("delivery")
     for s in range(0, len(todo), args.batch):
         chunk = todo[s:s + args.batch]
-        out = eng.synthesize([u for _, u in chunk]) if delivery is None else eng.synthesize([u for _, u in chunk], delivery=delivery)
+        out = eng.synthesize([u for _, u in chunk], **stages)
         os.makedirs(out_dir, exist_ok=True)
         for (i, _), wav in zip(chunk, out["wav_list" if delivery is None else "delivered_list"]):
             if delivery is None:

@@ -88,6 +88,17 @@ def delivery_from_args(args):
     return DeliveryConfig(sample_rate=int(rate) if rate is not None else 16000, encoding=enc or "s16", dither=dither).validate()
 
 
+def chain_from_args(args) -> dict:
+    """The output stages a command line asks for, as EVEngine.synthesize's keywords (emotivoice_amd/output_chain.py); a flag that is not given, or
+    that the parser does not have, leaves its keyword out.  --denoise: the vocoder's stationary bias removed (ev_denoise), before every other
+    stage; --loudness: every utterance normalised (ev_loudness); --true-peak: the true peak held at a ceiling (ev_limit; with --loudness it
+    replaces the sample-peak limit); --sample-rate / --encoding / --dither: the files at that rate and encoding (ev_deliver)."""
+    kw = {k: float(getattr(args, flag)) for k, flag in (("denoise", "denoise"), ("loudness", "loudness"), ("limiter", "true_peak"))
+          if getattr(args, flag, None) is not None}
+    delivery = delivery_from_args(args)
+    return kw if delivery is None else dict(kw, delivery=delivery)
+
+
 def add_delivery_arguments(p: argparse.ArgumentParser):
     p.add_argument("--sample-rate", type=int, default=None, metavar="HZ",
                    help="write the audio at this sample rate, converted on the device (ev_deliver: e.g. 8000, 24000, 44100, 48000); default: the model's 16000")
@@ -213,22 +224,10 @@ def main_worker(args, config, gpu_id: int, start_idx: int, chunk_num: int, state
     with open(args.text_file, "r", encoding="utf-8") as f:
         lines = f.readlines()
     eng = gen._ensure_engine()
-    synthesize = eng.synthesize
-    if getattr(args, "denoise", None) is not None:       # the vocoder's stationary bias removed on the device (ev_denoise), before every other output stage
-        import functools
-        synthesize = functools.partial(synthesize, denoise=float(args.denoise))
-    if getattr(args, "loudness", None) is not None:     # every utterance normalised on the device (ev_loudness) before it is written
-        import functools
-        synthesize = functools.partial(synthesize, loudness=float(args.loudness))
-    if getattr(args, "true_peak", None) is not None:     # the true peak held at a ceiling on the device (ev_limit); with --loudness it replaces the sample-peak limit
-        import functools
-        synthesize = functools.partial(synthesize, limiter=float(args.true_peak))
-    delivery = delivery_from_args(args)                   # the files at the client's rate and encoding, converted on the device (ev_deliver)
-    if delivery is not None:
-        import functools
-        synthesize = functools.partial(synthesize, delivery=delivery)
+    stages = chain_from_args(args)
+    delivery = stages.get("delivery")
     try:
-        stats = run_chunk(lines, start_idx, chunk_num, synthesize=synthesize, embed=embed, g2p=g2p, token2id=token2id,
+        stats = run_chunk(lines, start_idx, chunk_num, synthesize=lambda utts: eng.synthesize(utts, **stages), embed=embed, g2p=g2p, token2id=token2id,
                           id2speaker=id2speaker, output_dir=output_dir, sampling_rate=int(getattr(config, "sampling_rate", gen.shapes.sr)),
                           batch=args.batch, g2p_map=pool.map if pool is not None else None, n_speaker=int(config.speaker_n_labels),
                           **({} if delivery is None else dict(delivery=delivery)))

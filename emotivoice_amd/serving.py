@@ -310,56 +310,32 @@ def _resolve(future: Future, result=None, exception: Optional[BaseException] = N
         pass
 
 
-def _loudness_kw(loudness) -> dict:
-    """``loudness`` of the engine_*_synth_fn factories: a service-level setting (a target in LUFS or an emotivoice_amd.loudness.LoudnessConfig),
-    not a request field, so that a batch stays homogeneous and the request schema stays the reference's.  None: synthesize is called exactly
-    as before."""
-    return {} if loudness is None else dict(loudness=loudness)
-
-
-def _output_kw(loudness, limiter, denoise=None) -> dict:
-    """``loudness``, ``limiter`` (None, True, a ceiling in dBTP or an emotivoice_amd.limiter.LimiterConfig: ev_limit on every utterance) and
-    ``denoise`` (None, a strength or an emotivoice_amd.denoise.DenoiseConfig: ev_denoise on every utterance, before the other stages) of the
-    engine_*_synth_fn factories; like ``loudness`` service-level settings.  All None: synthesize is called exactly as before."""
-    kw = _loudness_kw(loudness)
-    if limiter is not None:
-        kw["limiter"] = limiter
-    if denoise is not None:
-        from .denoise import denoise_config
-        kw["denoise"] = denoise_config(denoise)
-    return kw
-
-
-def _delivered(delivery):
-    """``delivery`` of the engine_*_synth_fn factories (None, a sample rate in Hz or an emotivoice_amd.delivery.DeliveryConfig; like ``loudness``
-    a service-level setting, to be given to the DynamicBatcher as well) -> (the keyword for synthesize, the key of its result, what turns an
-    utterance of it into what the batcher resolves a Future with).  None: synthesize is called exactly as before."""
-    from .delivery import delivery_config
-    dc = delivery_config(delivery)
-    if dc is None:
-        return {}, "wav_list", lambda w: w
-    return dict(delivery=dc), "delivered_list", lambda w: w.tobytes()
+def _chain_settings(loudness, limiter, delivery, denoise, flac=None):
+    """The shared part of the engine_*_synth_fn factories.  ``loudness``, ``limiter``, ``delivery`` and ``denoise`` are what EVEngine.synthesize takes
+    (emotivoice_amd/output_chain.py): service-level settings, not request fields, so that a batch stays homogeneous and the request schema stays
+    the reference's (``delivery`` is to be given to the DynamicBatcher as well).  delivery, denoise and ``flac`` (a FlacConfig or True: the
+    service encodes FLAC) are checked here, when the service is built.  -> (the keywords for synthesize: the settings that are not None -- all
+    None: synthesize is called exactly as before; the key of its result that holds the audio; what turns an utterance of it into what the
+    batcher resolves a Future with)."""
+    from .output_chain import resolve
+    plan = resolve(16000, None, denoise=denoise, delivery=delivery, flac=flac)
+    kw = {k: v for k, v in (("loudness", loudness), ("limiter", limiter), ("denoise", plan.denoise), ("delivery", plan.delivery)) if v is not None}
+    return (kw, "wav_list", lambda w: w) if plan.delivery is None else (kw, "delivered_list", lambda w: w.tobytes())
 
 
 def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
     """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness); ``limiter``: its
     true peak held at a ceiling (ev_limit); ``delivery``: every utterance converted to the client's rate and encoding on the device (ev_deliver)
     and returned as ``bytes``; ``denoise``: the vocoder's stationary bias removed from every utterance on the device (ev_denoise), first in the chain."""
-    kw = _output_kw(loudness, limiter, denoise)
-    dkw, key, conv = _delivered(delivery)
-    if not dkw:
-        return lambda utts, alpha: engine.synthesize(utts, alpha=alpha, **kw)["wav_list"]
-    return lambda utts, alpha: [conv(w) for w in engine.synthesize(utts, alpha=alpha, **kw, **dkw)[key]]
+    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise)
+    return lambda utts, alpha: [conv(w) for w in engine.synthesize(utts, alpha=alpha, **kw)[key]]
 
 
 def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
     """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``,
     ``limiter``, ``delivery`` and ``denoise``: as ``engine_synth_fn``."""
-    kw = _output_kw(loudness, limiter, denoise)
-    dkw, key, conv = _delivered(delivery)
-    if not dkw:
-        return lambda utts, prosodies: engine.synthesize(utts, prosody=prosodies, **kw)["wav_list"]
-    return lambda utts, prosodies: [conv(w) for w in engine.synthesize(utts, prosody=prosodies, **kw, **dkw)[key]]
+    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise)
+    return lambda utts, prosodies: [conv(w) for w in engine.synthesize(utts, prosody=prosodies, **kw)[key]]
 
 
 def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None, denoise=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
@@ -371,18 +347,13 @@ def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, 
     a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms.
     ``delivery``: as ``engine_synth_fn``, with the encoding "s16": the streams carry ev_deliver's int16 at the delivered rate, the other
     utterances come back as its ``bytes``.  ``denoise``: as ``engine_synth_fn``; the streams carry the denoised audio."""
-    lkw = _output_kw(loudness, limiter, denoise)
     if flac_config is not None:
         flac_config.validate()
-    dkw, key, conv = _delivered(delivery)
-    if dkw and dkw["delivery"].encoding != "s16":
-        raise ValueError("flac needs delivery's encoding 's16', not %r" % dkw["delivery"].encoding)
-    lkw.update(dkw)
+    lkw, key, conv = _chain_settings(loudness, limiter, delivery, denoise, flac=flac_config or True)
 
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)
-        kw.update(lkw)
-        out = engine.synthesize(utts, flac=list(mask) if flac_config is None else flac_config, **kw)
+        out = engine.synthesize(utts, flac=list(mask) if flac_config is None else flac_config, **kw, **lkw)
         return [f if m else conv(w) for f, w, m in zip(out["flac_list"], out[key], mask)]
     return fn
 

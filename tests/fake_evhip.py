@@ -1,9 +1,15 @@
-"""A stand-in for the object ``emotivoice_amd._ffi.lib()`` returns, for CPU tests of the Python above the library (tests/test_engine_chain.py).
+"""A stand-in for the object ``emotivoice_amd._ffi.lib()`` returns, for CPU tests of the Python above the library (tests/test_engine_chain.py,
+test_deliver_chain.py, test_denoise.py, test_chain_transcripts.py).
 
-Only the entries of the output chain.  "Device" memory is host numpy memory kept alive in ``bufs``; every entry appends what it was given to
-``log`` (pointer arguments as (buffer, byte offset)) and fills the real _ffi result struct.  The arithmetic is trivial and tells the stages apart:
-the synthesis writes ``ramp``, ev_stitch negates, ev_loudness with a target doubles, ev_limit multiplies by gain * 3, every int16 is ``to_i16`` of
-its fp32, and a FLAC stream is b"fLaC" + the first 8 bytes of its segment.  One frame per token."""
+Only the entries of the output chain (emotivoice_amd/output_chain.py).  "Device" memory is host numpy memory kept alive in ``bufs``; every entry
+appends what it was given to ``log`` (pointer arguments as (buffer, byte offset)) and fills the real _ffi result struct.  The arithmetic is
+trivial and tells the stages apart: the synthesis writes ``ramp``, ev_stitch negates, ev_loudness with a target doubles, ev_limit multiplies by
+gain * 3, every int16 is ``to_i16`` of its fp32, and a FLAC stream is b"fLaC" + the first 8 bytes of its segment.  One frame per token.
+
+FakeLib has the synthesis, ev_stitch, ev_loudness, ev_limit and ev_flac, and raises (AttributeError) on any deliver or denoise call: two tests
+hold the chain without those stages to exactly the calls it made before they existed.  DeliverLib adds ev_deliver, which NEGATES and keeps
+every second sample; DenoiseLib adds ev_denoise, which ADDS 1/8 and cuts every utterance to whole hops, its setup and bias, and an ev_compare
+with fixed sums.  A test that needs both stages subclasses both."""
 import ctypes as C
 import math
 
@@ -164,3 +170,82 @@ class FakeLib:
         return self._fill("flac%d" % len(self.calls("ev_flac")), ref, bytes=np.frombuffer(b"".join(streams), np.uint8),
                           stream_offsets=np.concatenate([[0], np.cumsum([len(s) for s in streams])]).astype(np.int64), stream_frames=np.ones(B, np.int64),
                           frame_offsets=np.arange(B + 1, dtype=np.int64), frame_kind=np.full(B, 8, np.uint8), frame_porder=np.zeros(B, np.uint8))
+
+
+# -- the two later stages, each a subclass so that FakeLib itself keeps raising on any deliver or denoise call
+def encode(y, encoding):
+    """The stand-in's conversion: fp32, the stand-in's int16, or the int16's high byte."""
+    return y.astype(np.float32) if encoding == 0 else to_i16(y) if encoding == 1 else (to_i16(y).astype(np.int32) >> 8 & 0xFF).astype(np.uint8)
+
+
+class DeliverLib(FakeLib):
+    setup = None
+
+    def ev_deliver_setup(self, h, ref):
+        self.setup = _cfg(ref)
+        self.log.append(dict(name="ev_deliver_setup", cfg=dict(self.setup)))
+        return 0
+
+    def ev_deliver(self, h, B, wav, is_i16, lens, seeds, flags, ref):
+        ln = _host(lens, C.c_int64, B)
+        x, src = self._read(wav, is_i16, ln)
+        self.log.append(dict(name="ev_deliver", B=B, flags=int(flags), lens=ln.tolist(), is_i16=int(is_i16), src=src, seeds=seeds))
+        offs, parts, n, at = [0], [], [], 0
+        for L in ln:
+            y = encode(-x[at:at + L:2], self.setup["encoding"])
+            at += int(L)
+            raw = y.tobytes()
+            parts.append(raw + b"\0" * (-len(raw) % 16))
+            n.append(y.size)
+            offs.append(offs[-1] + len(parts[-1]))
+        res = ref._obj
+        res.batch, res.total_bytes = B, offs[-1]
+        return self._fill("deliver", ref, data=np.frombuffer(b"".join(parts), np.uint8), byte_offsets=np.array(offs, np.int64), n_samples=np.array(n, np.int64),
+                          peak=np.full(B, 0.25, np.float32), clipped=np.arange(B, dtype=np.int64))
+
+
+EIGHTH = np.float32(0.125)      # what the stand-in ev_denoise adds
+
+
+class DenoiseLib(FakeLib):
+    setup = None
+
+    def ev_default_denoise_config(self, ref):
+        c = ref._obj
+        c.struct_size, c.n_fft, c.hop, c.strength = C.sizeof(_ffi.ev_denoise_config), 1024, 256, 0.01
+
+    def ev_denoise_setup(self, h, ref, bias):
+        self.setup = _cfg(ref)
+        self.log.append(dict(name="ev_denoise_setup", cfg=dict(self.setup), bias=None if bias is None else _host(bias, C.c_float, 513).tolist()))
+        if bias is None:      # measuring runs the vocoder: whatever the synthesis left is gone
+            self.log.append(dict(name="ev_vocoder(zero mel)"))
+            if "synth.wav" in self.bufs:
+                self.bufs["synth.wav"][:] = np.nan
+        return 0
+
+    def ev_denoise_bias(self, h, out):
+        self.log.append(dict(name="ev_denoise_bias"))
+        half = np.full(513, 0.5, np.float32)
+        C.memmove(out, half.ctypes.data, half.nbytes)
+        return 0
+
+    def ev_denoise(self, h, B, wav, is_i16, lens, strengths, flags, ref):
+        ln = _host(lens, C.c_int64, B)
+        x, src = self._read(wav, is_i16, ln)
+        self.log.append(dict(name="ev_denoise", B=B, flags=int(flags), lens=ln.tolist(), is_i16=int(is_i16), src=src, strengths=strengths, cfg=dict(self.setup)))
+        offs = np.concatenate([[0], np.cumsum(ln)])
+        lo = ln // 256 * 256
+        out = np.concatenate([x[a:a + n] + EIGHTH for a, n in zip(offs[:-1], lo)])
+        res = ref._obj
+        res.batch, res.total = B, int(lo.sum())
+        return self._fill("denoise", ref, wav=out, wav_i16=to_i16(out) if self.setup["want_i16"] else None, lens_out=lo.astype(np.int64),
+                          offsets=np.concatenate([[0], np.cumsum(lo)]).astype(np.int64))
+
+    def ev_compare(self, h, B, a, b, lens, flags, ref):
+        ln = _host(lens, C.c_int64, B)
+        self.log.append(dict(name="ev_compare", B=B, flags=int(flags), lens=ln.tolist(), a=self.where(a), b=self.where(b)))
+        z, zi = np.zeros(B), np.zeros(B, np.int64)
+        res = ref._obj
+        res.batch, res.total = B, int(ln.sum())
+        return self._fill("compare", ref, sum_d=z, sum_d2=np.full(B, 1.0), sum_y=z, sum_y2=np.full(B, 100.0), rel_l2=z, rel_l2_ac=z, max_abs_d=np.zeros(B, np.float32),
+                          argmax_d=zi, peak_y=np.zeros(B, np.float32), nonfinite=zi, chunk_offsets=np.arange(B + 1, dtype=np.int64), chunk_d2=z, chunk_y2=z)

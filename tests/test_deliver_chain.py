@@ -17,35 +17,7 @@ OFFS = np.concatenate([[0], np.cumsum(LENS)])
 N = int(OFFS[-1])
 
 
-def encode(y, encoding):
-    """The stand-in's conversion: fp32, the stand-in's int16, or the int16's high byte."""
-    return y.astype(np.float32) if encoding == 0 else fk.to_i16(y) if encoding == 1 else (fk.to_i16(y).astype(np.int32) >> 8 & 0xFF).astype(np.uint8)
-
-
-class DeliverLib(fk.FakeLib):
-    setup = None
-
-    def ev_deliver_setup(self, h, ref):
-        self.setup = fk._cfg(ref)
-        self.log.append(dict(name="ev_deliver_setup", cfg=dict(self.setup)))
-        return 0
-
-    def ev_deliver(self, h, B, wav, is_i16, lens, seeds, flags, ref):
-        ln = fk._host(lens, C.c_int64, B)
-        x, src = self._read(wav, is_i16, ln)
-        self.log.append(dict(name="ev_deliver", B=B, flags=int(flags), lens=ln.tolist(), is_i16=int(is_i16), src=src, seeds=seeds))
-        offs, parts, n, at = [0], [], [], 0
-        for L in ln:
-            y = encode(-x[at:at + L:2], self.setup["encoding"])
-            at += int(L)
-            raw = y.tobytes()
-            parts.append(raw + b"\0" * (-len(raw) % 16))
-            n.append(y.size)
-            offs.append(offs[-1] + len(parts[-1]))
-        res = ref._obj
-        res.batch, res.total_bytes = B, offs[-1]
-        return self._fill("deliver", ref, data=np.frombuffer(b"".join(parts), np.uint8), byte_offsets=np.array(offs, np.int64), n_samples=np.array(n, np.int64),
-                          peak=np.full(B, 0.25, np.float32), clipped=np.arange(B, dtype=np.int64))
+encode, DeliverLib = fk.encode, fk.DeliverLib
 
 
 def utterances():

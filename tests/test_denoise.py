@@ -117,51 +117,7 @@ TOKENS = (3, 5, 2)
 LENS = [t * fk.UP for t in TOKENS]
 OFFS = np.concatenate([[0], np.cumsum(LENS)])
 N = int(OFFS[-1])
-EIGHTH = np.float32(0.125)
-
-
-class DenoiseLib(fk.FakeLib):
-    setup = None
-
-    def ev_default_denoise_config(self, ref):
-        c = ref._obj
-        c.struct_size, c.n_fft, c.hop, c.strength = C.sizeof(_ffi.ev_denoise_config), 1024, 256, 0.01
-
-    def ev_denoise_setup(self, h, ref, bias):
-        self.setup = fk._cfg(ref)
-        self.log.append(dict(name="ev_denoise_setup", cfg=dict(self.setup), bias=None if bias is None else fk._host(bias, C.c_float, 513).tolist()))
-        if bias is None:      # measuring runs the vocoder: whatever the synthesis left is gone
-            self.log.append(dict(name="ev_vocoder(zero mel)"))
-            if "synth.wav" in self.bufs:
-                self.bufs["synth.wav"][:] = np.nan
-        return 0
-
-    def ev_denoise_bias(self, h, out):
-        self.log.append(dict(name="ev_denoise_bias"))
-        half = np.full(513, 0.5, np.float32)
-        C.memmove(out, half.ctypes.data, half.nbytes)
-        return 0
-
-    def ev_denoise(self, h, B, wav, is_i16, lens, strengths, flags, ref):
-        ln = fk._host(lens, C.c_int64, B)
-        x, src = self._read(wav, is_i16, ln)
-        self.log.append(dict(name="ev_denoise", B=B, flags=int(flags), lens=ln.tolist(), is_i16=int(is_i16), src=src, strengths=strengths, cfg=dict(self.setup)))
-        offs = np.concatenate([[0], np.cumsum(ln)])
-        lo = ln // 256 * 256
-        out = np.concatenate([x[a:a + n] + EIGHTH for a, n in zip(offs[:-1], lo)])
-        res = ref._obj
-        res.batch, res.total = B, int(lo.sum())
-        return self._fill("denoise", ref, wav=out, wav_i16=fk.to_i16(out) if self.setup["want_i16"] else None, lens_out=lo.astype(np.int64),
-                          offsets=np.concatenate([[0], np.cumsum(lo)]).astype(np.int64))
-
-    def ev_compare(self, h, B, a, b, lens, flags, ref):
-        ln = fk._host(lens, C.c_int64, B)
-        self.log.append(dict(name="ev_compare", B=B, flags=int(flags), lens=ln.tolist(), a=self.where(a), b=self.where(b)))
-        z, zi = np.zeros(B), np.zeros(B, np.int64)
-        res = ref._obj
-        res.batch, res.total = B, int(ln.sum())
-        return self._fill("compare", ref, sum_d=z, sum_d2=np.full(B, 1.0), sum_y=z, sum_y2=np.full(B, 100.0), rel_l2=z, rel_l2_ac=z, max_abs_d=np.zeros(B, np.float32),
-                          argmax_d=zi, peak_y=np.zeros(B, np.float32), nonfinite=zi, chunk_offsets=np.arange(B + 1, dtype=np.int64), chunk_d2=z, chunk_y2=z)
+EIGHTH, DenoiseLib = fk.EIGHTH, fk.DenoiseLib
 
 
 def utterances():

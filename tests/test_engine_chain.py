@@ -1,7 +1,9 @@
-"""The output chain of EVEngine.synthesize / synthesize_long (synthesis -> [stitch] -> [loudness | limit | measure + limit] -> [flac]) on the
-CPU, against the stand-in library of tests/fake_evhip.py: which entries are called, in which order and with what, what is copied to the host,
-and which stage every returned value comes from.  The expectations are the behaviour of the code before the chain was unified; the two tests
-whose names end in ``new_check`` assert argument checks that were added with it (deselect them with ``-k "not new_check"``)."""
+"""The output chain of EVEngine.synthesize / synthesize_long (emotivoice_amd/output_chain.py: synthesis -> [stitch] -> [denoise] -> [loudness |
+limit | measure + limit] -> [deliver] -> [flac]) on the CPU, against the stand-in library of tests/fake_evhip.py: which entries are called, in
+which order and with what, what is copied to the host, and which stage every returned value comes from.  This file holds the stages the plain
+stand-in has -- loudness, limiter and FLAC; tests/test_denoise.py and tests/test_deliver_chain.py hold the first and the last but one, and
+tests/test_chain_transcripts.py the cross product of all five.  The expectations are the behaviour of the code before the chain was first
+unified; the two tests whose names end in ``new_check`` assert argument checks that were added with it (deselect them with ``-k "not new_check"``)."""
 import itertools
 
 import numpy as np
