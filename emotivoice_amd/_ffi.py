@@ -247,6 +247,22 @@ class ev_denoise_result(C.Structure):
     ]
 
 
+EV_STRETCH_FRAME, EV_STRETCH_HOP, EV_STRETCH_LAGS, EV_STRETCH_MAX_SAMPLES = 512, 256, 256, 1 << 30
+
+
+class ev_stretch_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("want_int16", C.c_int32)]
+
+
+class ev_stretch_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64), ("wav", C.c_void_p), ("wav_i16", C.c_void_p),
+        ("lens_out", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_int64)), ("frames", C.POINTER(C.c_int32)),
+        ("frame_offsets", C.POINTER(C.c_int64)), ("deltas", C.c_void_p), ("edge_frames", C.POINTER(C.c_int32)),
+        ("sum_dist", C.POINTER(C.c_uint64)), ("nonfinite", C.POINTER(C.c_int64)),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -341,6 +357,11 @@ SIGNATURES = {
     "ev_denoise_bias": (C.c_int, [_P, _P]),
     # lens and strengths are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_denoise": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_uint32, C.POINTER(ev_denoise_result)]),
+    "ev_default_stretch_config": (None, [C.POINTER(ev_stretch_config)]),
+    "ev_stretch_window": (C.c_int, [_P]),      # host only
+    "ev_stretch_plan": (C.c_int, [C.c_int, _P, _P, _P, _P]),      # host only; the message of a rejection: ev_last_error(None)
+    # lens and lens_out are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_stretch": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(ev_stretch_config), C.c_uint32, C.POINTER(ev_stretch_result)]),
     "ev_score_design": (C.c_int, [C.c_int, C.c_int, _P]),      # host only
     # lens is a HOST array; mel and f0_hz are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
     "ev_score_load": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_uint32]),

@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise, ev_stretch -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1439,6 +1439,112 @@ int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     reset_result(out);
     out->batch = B; out->total = total_out; out->wav = d_out; out->wav_i16 = d_i16;
     out->lens_out = h->dn.lens.data(); out->offsets = h->dn.offs.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- time-scale modification (include/evhip.h: ev_stretch)
+static_assert(EV_STRETCH_FRAME == STRETCH_FRAME && EV_STRETCH_HOP == STRETCH_HOP && EV_STRETCH_LAGS == STRETCH_LAGS,
+              "include/evhip.h states the frame, the hop and the lags of ev_stretch.hip");
+void ev_default_stretch_config(ev_stretch_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c;
+}
+
+int ev_stretch_window(float* w) {
+    if (!w) return -1;
+    const double pi = 3.14159265358979323846;
+    for (int j = 0; j < EV_STRETCH_HOP; ++j) w[j] = (float)(rint(8388608.0 * (0.5 - 0.5 * cos(2.0 * pi * (double)j / (double)EV_STRETCH_FRAME))) / 8388608.0);
+    return EV_STRETCH_HOP;
+}
+
+// the message of a pair of lengths that stretch_check rejects
+static int stretch_fail(ev_handle* h, const char* who, StretchBad bad, int b, int64_t len_in, int64_t len_out) {
+    switch (bad) {
+    case STRETCH_OK: return 0;
+    case STRETCH_IN_SHORT: return fail(h, "%s: lens[%d] = %lld < 1", who, b, (long long)len_in);
+    case STRETCH_OUT_SHORT: return fail(h, "%s: lens_out[%d] = %lld < 1", who, b, (long long)len_out);
+    case STRETCH_IN_LONG: return fail(h, "%s: lens[%d] = %lld > EV_STRETCH_MAX_SAMPLES = %d", who, b, (long long)len_in, EV_STRETCH_MAX_SAMPLES);
+    case STRETCH_OUT_LONG: return fail(h, "%s: lens_out[%d] = %lld > EV_STRETCH_MAX_SAMPLES = %d", who, b, (long long)len_out, EV_STRETCH_MAX_SAMPLES);
+    case STRETCH_RATIO: return fail(h, "%s: segment %d: %lld -> %lld samples lies outside the ratios [0.5, 2]", who, b, (long long)len_in, (long long)len_out);
+    case STRETCH_COUNT: return fail(h, "%s: lens_out[%d] = %lld: more than %d tiles in one call", who, b, (long long)len_out, INT_MAX);
+    }
+    return -1;
+}
+
+int ev_stretch_plan(int B, const int64_t* lens, const double* speeds, const int64_t* targets, int64_t* lens_out) {
+    if (!lens) return fail(nullptr, "ev_stretch_plan: lens is NULL");
+    if (!lens_out) return fail(nullptr, "ev_stretch_plan: lens_out is NULL");
+    if (B < 1 || B > 65535) return fail(nullptr, "ev_stretch_plan: B = %d outside [1, 65535]", B);
+    std::vector<int64_t> lo((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        if (targets && targets[b] != 0) lo[(size_t)b] = targets[b];
+        else {
+            const double s = speeds ? speeds[b] : 1.0;
+            if (!(std::isfinite(s) && s > 0.0)) return fail(nullptr, "ev_stretch_plan: speeds[%d] = %g is not finite and > 0", b, s);
+            const double v = nearbyint((double)lens[b] / s);      // ties to even (the default rounding mode)
+            lo[(size_t)b] = v >= 4e18 ? INT64_MAX : std::max<int64_t>(1, (int64_t)v);
+        }
+        const StretchBad bad = stretch_check(lens[b], lo[(size_t)b]);
+        if (bad != STRETCH_OK) return stretch_fail(nullptr, "ev_stretch_plan", bad, b, lens[b], lo[(size_t)b]);
+    }
+    std::copy(lo.begin(), lo.end(), lens_out);
+    return 0;
+}
+
+int ev_stretch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const int64_t* lens_out, const ev_stretch_config* cfg,
+               uint32_t flags, ev_stretch_result* out) {
+    if (!h) return -1;
+    if (!wav) return fail(h, "ev_stretch: wav is NULL");
+    if (!lens) return fail(h, "ev_stretch: lens is NULL");
+    if (!lens_out) return fail(h, "ev_stretch: lens_out is NULL");
+    if (!out) return fail(h, "ev_stretch: out is NULL");
+    if (check_struct_size(h, "ev_stretch", "out->struct_size", out->struct_size, "ev_stretch_result", sizeof(ev_stretch_result))) return -1;
+    ev_stretch_config dflt;
+    if (!cfg) { ev_default_stretch_config(&dflt); cfg = &dflt; }
+    if (check_struct_size(h, "ev_stretch", "cfg->struct_size", cfg->struct_size, "ev_stretch_config", sizeof(ev_stretch_config))) return -1;
+    if (B < 1 || B > 65535) return fail(h, "ev_stretch: B = %d outside [1, 65535]", B);
+    StretchPlan plan;
+    int at = 0;
+    const StretchBad bad = stretch_plan(B, lens, lens_out, plan, &at);
+    if (bad != STRETCH_OK) return stretch_fail(h, "ev_stretch", bad, at, lens[at], lens_out[at]);
+    const bool in16 = wav_is_i16 != 0, i16 = cfg->want_int16 != 0;
+    const int64_t total = plan.total_out, NF = plan.total_frames, NT = (int64_t)plan.tiles.size();
+    std::vector<float> win(EV_STRETCH_HOP);
+    ev_stretch_window(win.data());
+    WavIn in(wav, plan.total_in, wav_is_i16, flags);
+    if (call_begin(h)) return -1;
+    StretchSeg* d_segs = nullptr; StretchTile* d_tiles = nullptr; StretchFig* d_figs = nullptr; float *d_win = nullptr, *d_wav = nullptr;
+    int16_t *d_deltas = nullptr, *d_i16 = nullptr;
+    if (arena_plan(h, ARENA_STRETCH, [&](ArenaPlan& ap) {
+        in.plan(ap);
+        d_segs = ap.arr<StretchSeg>((size_t)B); d_tiles = ap.arr<StretchTile>((size_t)NT); d_figs = ap.arr<StretchFig>((size_t)B);
+        d_win = ap.arr<float>(EV_STRETCH_HOP); d_deltas = ap.arr<int16_t>((size_t)NF); d_wav = ap.arr<float>((size_t)total);
+        if (i16) d_i16 = ap.arr<int16_t>((size_t)total);
+    })) return -1;
+    if (in.copy(h) || upload(h, d_segs, plan.segs) || upload(h, d_tiles, plan.tiles) || upload(h, d_win, win)) return -1;
+    const double es = in16 ? 2.0 : 4.0;
+    region_begin(h, "total");
+    {      // per frame 256 lags of 512 terms, three operations a term; each frame stages 1023 samples
+        KScope ks(h, "wsola_search", 3.0 * STRETCH_LAGS * STRETCH_FRAME * (double)NF, (in16 ? 0.0 : (double)in.bytes) + 1023.0 * es * (double)NF + 2.0 * (double)NF);
+        if (launch_wsola_search(in.ptr(), in16, d_segs, B, d_deltas, d_figs, h->stream)) return fail(h, "ev_stretch: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {
+        KScope ks(h, "wsola_ola", 3.0 * (double)total, (2.0 * es + 4.0 + (i16 ? 2.0 : 0.0)) * (double)total + 2.0 * (double)NF);
+        if (launch_wsola_ola(in.ptr(), in16, d_segs, d_tiles, NT, d_deltas, d_win, d_wav, d_i16, h->stream)) return fail(h, "ev_stretch: the kernels do not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<StretchFig> figs((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(figs.data(), d_figs, (size_t)B * sizeof(StretchFig), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    std::vector<int32_t> edges((size_t)B); std::vector<uint64_t> sd((size_t)B); std::vector<int64_t> nonf((size_t)B);
+    for (int b = 0; b < B; ++b) { edges[(size_t)b] = figs[(size_t)b].edge_frames; sd[(size_t)b] = figs[(size_t)b].sum_dist; nonf[(size_t)b] = figs[(size_t)b].nonfinite; }
+    h->str.lens_out.swap(plan.lens_out); h->str.offs.swap(plan.offs); h->str.frame_offs.swap(plan.frame_offs); h->str.frames.swap(plan.frames);
+    h->str.edges.swap(edges); h->str.sum_dist.swap(sd); h->str.nonf.swap(nonf);
+    reset_result(out);
+    out->batch = B; out->total = total; out->wav = d_wav; out->wav_i16 = d_i16;
+    out->lens_out = h->str.lens_out.data(); out->offsets = h->str.offs.data(); out->frames = h->str.frames.data(); out->frame_offsets = h->str.frame_offs.data();
+    out->deltas = d_deltas; out->edge_frames = h->str.edges.data(); out->sum_dist = h->str.sum_dist.data(); out->nonfinite = h->str.nonf.data();
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // Device parts shared by the audio kernels (ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_loudness, ev_limit, ev_deliver, ev_score,
-// ev_denoise): wave reductions, the element rules that decide a bit, the polyphase filter of ev_resample and ev_deliver, and the windowed DFT of
+// ev_denoise, ev_stretch): wave reductions, the element rules that decide a bit, the polyphase filter of ev_resample and ev_deliver, and the windowed DFT of
 // ev_features and ev_denoise.  Everything is inline with internal
 // linkage: the library exports nothing from here.  Include it before a file-wide `#pragma clang fp contract`: it leaves contraction at the default
 // (fast), as a file without pragmas has it.
@@ -51,6 +51,16 @@ __device__ inline int64_t wave_min_i64(int64_t v) {
 __device__ inline int64_t wave_max_i64(int64_t v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v = max(v, (int64_t)__shfl_xor((long long)v, o, 64));
+    return v;
+}
+// the inclusive prefix sum over the wave: lane l ends with the sum of lanes 0 .. l (modulo 2^32, exact in any order)
+__device__ inline uint32_t wave_scan_u32(uint32_t v) {
+    const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+    for (int o = 1; o <= 32; o <<= 1) {
+        const uint32_t below = (uint32_t)__shfl_up((int)v, o, 64);
+        if (lane >= o) v += below;
+    }
     return v;
 }
 

@@ -41,6 +41,7 @@ enum Arena {
     ARENA_SCORE_B,     // ev_score_load(1) (likewise)
     ARENA_SCORE,       // ev_score (like ARENA_ALIGN; the distance and decision workspaces too)
     ARENA_DENOISE,     // ev_denoise (like ARENA_ALIGN; the spectrum scratch too)
+    ARENA_STRETCH,     // ev_stretch (like ARENA_ALIGN)
     ARENA_COUNT
 };
 
@@ -136,6 +137,7 @@ struct DenoiseState {       // ev_denoise.  basis, ibasis, env, bias: its own ta
     std::vector<int64_t> lens, offs;
 };
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
+struct StretchState { std::vector<int64_t> lens_out, offs, frame_offs, nonf; std::vector<int32_t> frames, edges; std::vector<uint64_t> sum_dist; };       // ev_stretch
 
 }  // namespace evh
 
@@ -170,7 +172,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score; evh::DenoiseState dn;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score; evh::DenoiseState dn; evh::StretchState str;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

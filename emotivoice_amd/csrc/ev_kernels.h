@@ -459,6 +459,20 @@ int launch_limit_peak(const void* wav, int is16, const float* gains, const Limit
 int launch_limit_apply(const void* wav, int is16, const float* gains, const LimitTile* tiles, int64_t n_tiles, const float* r, const double* win, int L,
                        int Hd, float* out, int16_t* out_i16, float* s_out, LimitApplyOut* outs, hipStream_t s);
 
+// ev_stretch (ev_stretch.hip): packed segments -> per segment the lag track of WSOLA (one block per segment, the frame loop inside), then, per
+// tile of STRETCH_OLA_FRAMES output frames, the two-term overlap-add.  Segment b has `frames` = ceil(len_out / STRETCH_HOP) lags at frame_off.
+constexpr int STRETCH_FRAME = 512, STRETCH_HOP = 256, STRETCH_LAGS = 256, STRETCH_OLA_FRAMES = 4;
+struct StretchSeg { int64_t in_off, len_in, out_off, len_out, frame_off; int32_t frames, pad; };
+struct StretchTile { int32_t seg, k0; };      // the segment, the tile's first frame
+struct StretchFig { uint64_t sum_dist; int64_t nonfinite; int32_t edge_frames, pad; };
+// the nominal read position of frame k: floor(k H L_in / L_out + 1/2); k H <= len_out + H and both lengths <= 2^30 keep it inside int64
+__host__ __device__ inline int64_t stretch_a(int64_t k, int64_t len_in, int64_t len_out) { return (2 * k * STRETCH_HOP * len_in + len_out) / (2 * len_out); }
+// deltas: device (total frames,) int16; figs: device (B,).  0, or -1 for a grid that does not exist.
+int launch_wsola_search(const void* wav, int is16, const StretchSeg* segs, int B, int16_t* deltas, StretchFig* figs, hipStream_t s);
+// win: device (STRETCH_HOP,) the rising half of the window; out_i16 may be null
+int launch_wsola_ola(const void* wav, int is16, const StretchSeg* segs, const StretchTile* tiles, int64_t n_tiles, const int16_t* deltas, const float* win,
+                     float* out, int16_t* out_i16, hipStream_t s);
+
 // ev_score (ev_score.hip): log-mel -> integer cepstra (one side at a time), then per pair the local distances, the time warp and the sums along
 // its path.  The distances and the 2-bit decisions are stored in the order the warp's wavefront visits them: lane l of the wave owns rows
 // [l * rm, (l + 1) * rm) of a and works on column s - l at step s, so cell (i, j) lives at step s = j + i / rm, run index r = i % rm, lane l = i / rm:

@@ -186,4 +186,46 @@ inline LenBad limit_plan(int B, const int64_t* lens, LimitPlan& p, int* at) {
     return LEN_OK;
 }
 
+// ---------------------------------------------------------------- frames of STRETCH_HOP outputs, tiles of STRETCH_OLA_FRAMES frames (ev_stretch)
+// the first rule of include/evhip.h's step 1 that a pair of lengths breaks
+enum StretchBad { STRETCH_OK = 0, STRETCH_IN_SHORT, STRETCH_OUT_SHORT, STRETCH_IN_LONG, STRETCH_OUT_LONG, STRETCH_RATIO, STRETCH_COUNT };
+inline StretchBad stretch_check(int64_t len_in, int64_t len_out) {
+    if (len_in < 1) return STRETCH_IN_SHORT;
+    if (len_out < 1) return STRETCH_OUT_SHORT;
+    if (len_in > EV_STRETCH_MAX_SAMPLES) return STRETCH_IN_LONG;
+    if (len_out > EV_STRETCH_MAX_SAMPLES) return STRETCH_OUT_LONG;
+    if (std::min(len_in, len_out) >= EV_STRETCH_FRAME && (len_in > 2 * len_out || len_out > 2 * len_in)) return STRETCH_RATIO;
+    return STRETCH_OK;
+}
+struct StretchPlan {
+    std::vector<ev::StretchSeg> segs; std::vector<ev::StretchTile> tiles; std::vector<int64_t> lens_out, offs, frame_offs; std::vector<int32_t> frames;
+    int64_t total_in = 0, total_out = 0, total_frames = 0;
+};
+// the segment and tile tables of a batch; a rejected pair leaves its index in *at (the tile table's size is judged before it is built)
+inline StretchBad stretch_plan(int B, const int64_t* lens, const int64_t* lens_out, StretchPlan& p, int* at) {
+    int64_t NT = 0;
+    for (int b = 0; b < B; ++b) {
+        *at = b;
+        const StretchBad bad = stretch_check(lens[b], lens_out[b]);
+        if (bad != STRETCH_OK) return bad;
+        const int64_t K = (lens_out[b] + ev::STRETCH_HOP - 1) / ev::STRETCH_HOP;
+        NT += (K + ev::STRETCH_OLA_FRAMES - 1) / ev::STRETCH_OLA_FRAMES;
+        if (NT > INT_MAX) return STRETCH_COUNT;
+    }
+    p.segs.resize((size_t)B); p.frames.resize((size_t)B); p.lens_out.assign(lens_out, lens_out + B);
+    p.offs.assign((size_t)B + 1, 0); p.frame_offs.assign((size_t)B + 1, 0);
+    p.tiles.clear(); p.tiles.reserve((size_t)NT);
+    int64_t io = 0, oo = 0, fo = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t K = (lens_out[b] + ev::STRETCH_HOP - 1) / ev::STRETCH_HOP;
+        p.segs[(size_t)b] = ev::StretchSeg{io, lens[b], oo, lens_out[b], fo, (int32_t)K, 0};
+        p.frames[(size_t)b] = (int32_t)K;
+        for (int64_t k0 = 0; k0 < K; k0 += ev::STRETCH_OLA_FRAMES) p.tiles.push_back(ev::StretchTile{b, (int32_t)k0});
+        io += lens[b]; oo += lens_out[b]; fo += K;
+        p.offs[(size_t)b + 1] = oo; p.frame_offs[(size_t)b + 1] = fo;
+    }
+    p.total_in = io; p.total_out = oo; p.total_frames = fo;
+    return STRETCH_OK;
+}
+
 }  // namespace evh

@@ -312,12 +312,12 @@ class EVEngine(EVAudio):
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
                    forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None,
-                   denoise=None) -> Dict[str, object]:
+                   denoise=None, stretch=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
         for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
-        The five arguments below are the output chain on the device, denoise -> loudness -> limiter -> delivery -> flac; emotivoice_amd/output_chain.py
+        The six arguments below are the output chain on the device, denoise -> stretch -> loudness -> limiter -> delivery -> flac; emotivoice_amd/output_chain.py
         states once, for every combination, the order, which stage makes the int16, what is copied to the host and what a FLAC stream decodes to.
         flac: None, True, one boolean per utterance or an emotivoice_amd.flac.FlacConfig (every utterance, with its LPC / MD5 / block settings;
         the sample rate is the engine's and the conversion stays the wrapping one): adds flac_list, the FLAC stream (``bytes``) of every selected
@@ -336,8 +336,13 @@ class EVEngine(EVAudio):
         denoise: None, True, a strength, a dict of DenoiseConfig's fields or an emotivoice_amd.denoise.DenoiseConfig: ev_denoise runs FIRST, on the
         vocoder's waveform -- strength times the magnitude spectrum of the vocoder's answer to an all-zero mel (measured once per engine, or
         config.bias) is subtracted from every STFT cell; the lengths do not change (a waveform of whole frames).  ``denoise`` in the result holds
-        lens_out and, with report=True, removed_db.  The default strength 0.01 is an unmeasured starting value (emotivoice_amd.denoise)."""
-        plan = resolve_chain(self.shapes.sr, len(utts), denoise, loudness, limiter, delivery, flac, vocoder, flac_convert="wrap")
+        lens_out and, with report=True, removed_db.  The default strength 0.01 is an unmeasured starting value (emotivoice_amd.denoise).
+        stretch: None, a speed, one speed per utterance or an emotivoice_amd.stretch.StretchConfig (speed, seconds or samples per utterance):
+        ev_stretch runs SECOND, after ev_denoise, and changes the length of every waveform at the same pitch (WSOLA; not the reference's Rubber
+        Band, see emotivoice_amd.stretch for what is not verified).  wav_list (and wav_int16_list, delivered_list) have the new lengths and
+        ``stretch`` holds lens_in, lens_out, speed and the search's figures.  durations, mel_lens and mel_offsets stay on the MODEL's clock: they
+        describe the mel the vocoder read, not the stretched waveform.  The packed ``wav`` is cut by stretch["offsets"], not by mel_offsets."""
+        plan = resolve_chain(self.shapes.sr, len(utts), denoise, loudness, limiter, delivery, flac, vocoder, flac_convert="wrap", stretch=stretch)
         flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not plan.staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
         self._denoise_ready(plan.denoise)
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
@@ -351,14 +356,14 @@ class EVEngine(EVAudio):
         return chain.into(out, SYNTHESIZE_NAMES if want_i16 else SYNTHESIZE_NAMES[:2])
 
     def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None,
-                        delivery=None, denoise=None) -> Dict[str, object]:
+                        delivery=None, denoise=None, stretch=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
         documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
         config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
-        The five arguments below are the output chain, per document, after ev_stitch; emotivoice_amd/output_chain.py states its rules.
+        The six arguments below are the output chain, per document, after ev_stitch; emotivoice_amd/output_chain.py states its rules.
         flac=True or an emotivoice_amd.flac.FlacConfig (its LPC / MD5 / block settings; the sample rate is the engine's; ``md5`` costs one serial
         chain per document) adds flac_list, one FLAC stream (``bytes``) per document (it turns config.want_int16 on, so
         ``documents`` are the int16 ones a stream decodes to).
@@ -372,17 +377,23 @@ class EVEngine(EVAudio):
         ``sample_rate`` stay on the engine's 16 kHz clock (delivered_rate is returned next to them).
         denoise: as ``synthesize`` takes it, per document, right after ev_stitch.  Its output has whole hops: a document whose length is no
         multiple of the hop (256) loses the up to 255 samples after its last whole hop, doc_lens then holds the new lengths and ``denoise``
-        lens_out (and removed_db with report=True)."""
+        lens_out (and removed_db with report=True).
+        stretch: as ``synthesize`` takes it, per DOCUMENT (a sequence has one entry per document), after ev_stitch and ev_denoise.  doc_lens and
+        doc_offsets become the stretched ones and ``stretch`` holds lens_in, lens_out, speed and the search's figures.  sentence_times are
+        scaled by L_out / L_in of their document: WSOLA follows that line only to within its lag range, so a time is off by up to 128 samples
+        (8 ms at 16 kHz) plus the rounding of the frame positions.  seg_pos, seg_start and seg_end stay on the clock BEFORE the stretch."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
         if int(sc.sample_rate) != int(self.shapes.sr):
             raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
-        plan = resolve_chain(sc.sample_rate, None, denoise, loudness, limiter, delivery, flac)
+        plan = resolve_chain(sc.sample_rate, None, denoise, loudness, limiter, delivery, flac, stretch=stretch)
         stitch_i16 = bool(sc.want_int16 or plan.flac is not None) and plan.delivery is None      # a delivered response has no 16 kHz int16
         if stitch_i16 != sc.want_int16:
             sc = dataclasses.replace(sc, want_int16=stitch_i16).validate()
         utts, seg_doc, pauses = flatten_documents(documents)
+        if plan.stretch is not None:
+            plan.stretch.per_segment(len(documents), sc.sample_rate)      # one entry per document, before any library call
         S = len(utts)
         if S > 65535:
             raise ValueError("%d sentences exceed the 65535 segments of one ev_stitch call; split the documents over several calls" % S)
@@ -392,7 +403,7 @@ class EVEngine(EVAudio):
         mel_offs = host_array(res.mel_offsets, S + 1, np.int64) * self.shapes.upsample_factor
         st = self.stitch_raw(S, res.wav, mel_offs[:-1], np.diff(mel_offs), seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
         out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=plan.staged)
-        reader = ("denoise" if plan.denoise is not None else "limiter" if plan.limiter is not None else "loudness" if plan.loudness is not None else
+        reader = ("denoise" if plan.denoise is not None else "stretch" if plan.stretch is not None else "limiter" if plan.limiter is not None else "loudness" if plan.loudness is not None else
                   "delivery" if plan.delivery is not None else "flac" if plan.flac is not None else None)
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
         if empty and reader:
@@ -401,13 +412,50 @@ class EVEngine(EVAudio):
         chain.into(out, SYNTHESIZE_LONG_NAMES)
         if plan.denoise is not None:
             out["doc_lens"], out["doc_offsets"] = out["denoise"]["lens_out"], out["denoise"]["offsets"]
+        scale = np.ones(st.batch_docs, np.float64)      # a sentence's time in its stretched document: its time before, times L_out / L_in
+        if plan.stretch is not None:
+            out["doc_lens"], out["doc_offsets"] = out["stretch"]["lens_out"], out["stretch"]["offsets"]
+            scale = out["stretch"]["lens_out"] / out["stretch"]["lens_in"]
         sr = float(sc.sample_rate)
-        start = out["seg_pos"] / sr
-        end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr
+        start = out["seg_pos"] / sr * scale[seg_doc]
+        end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr * scale[seg_doc]
         out["documents"] = out["delivered_list"] if plan.delivery is not None else out["docs_i16"] if sc.want_int16 else out["docs"]
         out["seg_doc"] = seg_doc
         out["sentence_times"] = [[(float(start[s]), float(end[s])) for s in np.nonzero(seg_doc == d)[0]] for d in range(st.batch_docs)]
         out["sample_rate"] = int(sc.sample_rate)
+        return out
+
+    def synthesize_fit(self, utts: Sequence[dict], seconds, prosody=None, **chain) -> Dict[str, object]:
+        """Every utterance in exactly its time slot: ``seconds`` (a scalar or one value per utterance) -> len(wav_list[b]) ==
+        round(seconds[b] * sample rate).  Three steps: an acoustic pass without the vocoder gives the natural mel_lens; a second synthesis runs
+        with alpha = target / natural per utterance, clamped to [0.5, 2] (the model's durations are whole frames and its own predictions, so
+        this only comes close); ``stretch=StretchConfig(samples=target)`` closes the rest on the waveform -- a few per cent, where a
+        time-domain stretch is cleanest.  prosody: as ``synthesize`` takes it, but without a speed or alpha of its own (ValueError): the
+        duration scale is this call's.  **chain: the other output-chain arguments and want_int16 of ``synthesize``.  Returns what ``synthesize``
+        returns and ``fit``: natural_samples, model_samples, target_samples and residual_speed (model / target, what the stretch closed) per
+        utterance.  A target outside [0.5, 2] of what the model reaches is refused by ev_stretch's ratio rule."""
+        import dataclasses
+        from .prosody import Prosody
+        from .stretch import StretchConfig, fit_alpha
+        B, sr, up = len(utts), int(self.shapes.sr), int(self.shapes.upsample_factor)
+        for k in ("stretch", "alpha", "vocoder", "forced_durations"):
+            if k in chain:
+                raise ValueError("synthesize_fit sets %s itself" % k)
+        plist = list(prosody) if isinstance(prosody, (list, tuple)) else [prosody] * B
+        if len(plist) != B:
+            raise ValueError("prosody: one entry per utterance (%d), got %d" % (B, len(plist)))
+        for b, p in enumerate(plist):
+            if p is not None and (p.speed is not None or p.alpha is not None):
+                raise ValueError("prosody[%d] has a speed or alpha of its own: synthesize_fit sets the duration scale" % b)
+        sc = StretchConfig(seconds=seconds if np.ndim(seconds) == 0 else list(seconds)).validate()
+        _, targets = sc.per_segment(B, sr)
+        natural = self.synthesize(utts, vocoder=False, prosody=prosody)["mel_lens"].astype(np.int64) * up
+        alphas = [fit_alpha(int(n), int(t)) for n, t in zip(natural, targets)]
+        fitted = [dataclasses.replace(p, alpha=a) if p is not None else Prosody(alpha=a) for p, a in zip(plist, alphas)]
+        out = self.synthesize(utts, prosody=fitted, stretch=StretchConfig(samples=[int(t) for t in targets]), **chain)
+        model = out["mel_lens"].astype(np.int64) * up
+        out["fit"] = dict(natural_samples=natural, model_samples=model, target_samples=np.array(targets, np.int64), alpha=np.array(alphas, np.float64),
+                          residual_speed=model / np.array(targets, np.float64))
         return out
 
     def vocoder(self, mels: Sequence[np.ndarray], want_int16: bool = False) -> Dict[str, object]:

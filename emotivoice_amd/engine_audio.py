@@ -1,5 +1,5 @@
 """The audio utilities of the libevhip.so handle (csrc/ev_audio.cpp): ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac,
-ev_loudness, ev_limit, ev_deliver, ev_score and ev_denoise as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
+ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise and ev_stretch as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
 handle, ``_check`` and ``d2h`` are its own."""
 from __future__ import annotations
 
@@ -54,7 +54,7 @@ class EVAudio:
         self.feature_config = self.resample_config = self.delivery_config = self.denoise_config = None      # set by the ``*_setup`` calls
         self._setup_keys: Dict[str, tuple] = {}                   # "deliver" / "denoise" -> the key of the config the library is set up with
         self._denoise_own_bias: Dict[tuple, np.ndarray] = {}      # the vocoder's own bias per (n_fft, hop), measured by denoise_setup on the loaded weights
-        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise"):
+        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise", "stretch"):
             setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
 
     def _setup_for(self, name: str, key: tuple, *args):
@@ -485,6 +485,44 @@ class EVAudio:
         self._setup_for("denoise", dc.key(), dc)
         flat, is16, lens = pack_segments(wavs, min_samples=int(dc.n_fft) // 2 + 1)
         return self.denoise_to_numpy(self.denoise_raw(len(lens), flat.ctypes.data, is16, lens, strengths))
+
+    # -- time-scale modification (ev_stretch): WSOLA per segment, another length at the same pitch, on the device
+    def stretch_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, lens_out: np.ndarray, config=None, flags: int = 0) -> _ffi.ev_stretch_result:
+        """ev_stretch (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens and lens_out (what
+        emotivoice_amd.stretch.plan_lengths or ev_stretch_plan gives) are host arrays.  config: an emotivoice_amd.stretch.StretchConfig (only its
+        want_int16 reaches the library), an _ffi.ev_stretch_config or None.  The returned struct's device arrays and host arrays stay valid until
+        the next stretch call on this engine."""
+        return self._call("stretch", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), _ptr(host_lens(lens_out, B, "lens_out")),
+                          config_ref(config), flags)
+
+    def stretch_to_numpy(self, res: _ffi.ev_stretch_result, int16_only: bool = False, skip_wav: bool = False, want_track: bool = False) -> Dict[str, object]:
+        """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
+        output only; without it both).  ``skip_wav``: the host arrays only.  ``want_track``: also deltas_list, one int16 array of lags per segment."""
+        B = res.batch
+        out: Dict[str, object] = dict(lens_out=host_array(res.lens_out, B, np.int64), offsets=host_array(res.offsets, B + 1, np.int64),
+                                      frames=host_array(res.frames, B, np.int32), frame_offsets=host_array(res.frame_offsets, B + 1, np.int64),
+                                      edge_frames=host_array(res.edge_frames, B, np.int32), sum_dist=host_array(res.sum_dist, B, np.uint64),
+                                      nonfinite=host_array(res.nonfinite, B, np.int64))
+        if want_track:
+            out["deltas_list"] = cut(self.d2h(res.deltas, (int(out["frame_offsets"][-1]),), np.int16), out["frame_offsets"])
+        if not skip_wav:
+            out.update(self._wav_pair(res, res.total, out["offsets"], int16_only))
+        return out
+
+    def stretch(self, wavs: Sequence[np.ndarray], speed=None, seconds=None, samples=None, sample_rate: int = 16000, want_int16: bool = False,
+                want_track: bool = False) -> Dict[str, object]:
+        """Host signals -> the same signals at another length and the same pitch (WSOLA; not the reference's Rubber Band).  wavs: one 1-D array per
+        segment, all int16 or all floating; speed, seconds, samples: the fields of emotivoice_amd.stretch.StretchConfig (a scalar or one entry
+        per segment, at most one of the three per segment; none: speed 1); sample_rate turns seconds into samples and nothing else: the frame
+        and the lag range are in samples.  Returns wav_list, lens_in, lens_out, speed (lens_in / lens_out) and the search's figures.  Needs no
+        weights."""
+        from .stretch import StretchConfig
+        sc = StretchConfig(speed, seconds, samples, want_int16).validate()
+        flat, is16, lens = pack_segments(wavs)
+        out = self.stretch_to_numpy(self.stretch_raw(len(lens), flat.ctypes.data, is16, lens, sc.lengths(lens, sample_rate), sc), want_track=want_track)
+        out["lens_in"] = np.asarray(lens, np.int64).copy()
+        out["speed"] = out["lens_in"] / out["lens_out"]
+        return out
 
     # -- objective scoring (ev_score): MCD, F0 error and voiced / unvoiced error of a signal against a yardstick of another length, on the device
     def score_load_raw(self, side: int, B: int, n_mels: int, n_ceps: int, mel_ptr: int, lens: np.ndarray, f0_ptr: int = 0, flags: int = 0) -> None:

@@ -91,12 +91,19 @@ def delivery_from_args(args):
 def chain_from_args(args) -> dict:
     """The output stages a command line asks for, as EVEngine.synthesize's keywords (emotivoice_amd/output_chain.py); a flag that is not given, or
     that the parser does not have, leaves its keyword out.  --denoise: the vocoder's stationary bias removed (ev_denoise), before every other
-    stage; --loudness: every utterance normalised (ev_loudness); --true-peak: the true peak held at a ceiling (ev_limit; with --loudness it
+    stage; --time-stretch: every utterance's duration divided by SPEED at the same pitch (ev_stretch, after --denoise); --loudness: every
+    utterance normalised (ev_loudness); --true-peak: the true peak held at a ceiling (ev_limit; with --loudness it
     replaces the sample-peak limit); --sample-rate / --encoding / --dither: the files at that rate and encoding (ev_deliver)."""
-    kw = {k: float(getattr(args, flag)) for k, flag in (("denoise", "denoise"), ("loudness", "loudness"), ("limiter", "true_peak"))
+    kw = {k: float(getattr(args, flag)) for k, flag in (("denoise", "denoise"), ("stretch", "time_stretch"), ("loudness", "loudness"), ("limiter", "true_peak"))
           if getattr(args, flag, None) is not None}
     delivery = delivery_from_args(args)
     return kw if delivery is None else dict(kw, delivery=delivery)
+
+
+def add_stretch_argument(p: argparse.ArgumentParser):
+    p.add_argument("--time-stretch", type=float, default=None, metavar="SPEED",
+                   help="stretch every finished waveform on the device to 1 / SPEED of its duration at the same pitch (ev_stretch: WSOLA, SPEED in "
+                        "[0.5, 2]; the waveform meaning of the reference's speed, but not its Rubber Band); default: off")
 
 
 def add_delivery_arguments(p: argparse.ArgumentParser):
@@ -267,6 +274,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--denoise", type=float, default=None, metavar="STRENGTH",
                    help="remove the vocoder's stationary bias on the device before the other output stages: STRENGTH times the magnitude spectrum of "
                         "its answer to an all-zero mel is subtracted from every STFT cell (e.g. 0.01, an unmeasured starting value); default: off")
+    add_stretch_argument(p)
     add_delivery_arguments(p)
     return p
 

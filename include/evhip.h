@@ -978,6 +978,73 @@ typedef struct ev_denoise_result {
  * ev_destroy -- the contract of ev_limit_result. */
 int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* strengths, uint32_t flags, ev_denoise_result* out);
 
+/* Time-scale modification (ev_stretch): a finished waveform at another length and the same pitch, per segment, on the device -- the waveform
+ * meaning of the reference's `speed` (openaiapi.py: pyrb.time_stretch) and the last few per cent of "this sentence in exactly 2.50 s".  It runs
+ * second in the output chain, after ev_denoise and before ev_loudness, so that the later stages measure and shape what is delivered.
+ * This is WSOLA (waveform-similarity overlap-add) with a squared-difference search on 12-bit samples.  It is NOT Rubber Band, which is a phase
+ * vocoder with transient handling; nobody has listened to it and it was compared to no other stretcher; N, H and the lag range are UNMEASURED
+ * starting values chosen for 16 kHz speech, in samples, and used as they are at any other rate.  Everything is integer except the last sum.
+ *   1 Lengths (host, ev_stretch_plan).  From a speed s: L_out = max(1, rint(L_in / s)) in fp64, ties to even; a target in samples is used as it
+ *     is.  Needed: L_in >= 1, L_out >= 1, both <= EV_STRETCH_MAX_SAMPLES, and L_in <= 2 L_out and L_out <= 2 L_in unless min(L_in, L_out) <
+ *     EV_STRETCH_FRAME (at a few samples the ratio means nothing).
+ *   2 Decision samples.  x[i]: the fp32 sample, or s / 32768 for int16; zero outside [0, L_in).  q[i] = clamp(rint(x[i] * 2048), -2047, 2047) as an
+ *     integer, ties to even; a non-finite sample gives 0 and counts in nonfinite.
+ *   3 Frames.  N = EV_STRETCH_FRAME, H = EV_STRETCH_HOP, K = ceil(L_out / H).  a_k = floor((2 k H L_in + L_out) / (2 L_out)) in int64, the nominal
+ *     read position.  p_(-1) = -H, delta_0 = 0.  For k >= 1 the template starts at t_k = p_(k-1) + H, the natural continuation of the previous frame;
+ *     D_k(d) = sum_(n < N) (q[t_k + n] - q[a_k + d + n])^2 for the lags d in [-EV_STRETCH_LAGS / 2, EV_STRETCH_LAGS / 2 - 1], an exact integer
+ *     (it reaches 8.6e9); delta_k = the lag of the smallest D_k, ties to the smallest |d|, then to the negative one.  p_k = a_k + delta_k.
+ *   4 Window (ev_stretch_window, host, fp64): w[j] = rint(2^23 (0.5 - 0.5 cos(2 pi j / N))) / 2^23, j < H, the rising half; the falling half is
+ *     1 - w[j].  Both are exact in fp32 and they sum to exactly 1.
+ *   5 Output.  For m < L_out, k = m / H, j = m % H: y[m] = (float)((double)w[j] (double)x[p_k + j] + (double)(1 - w[j]) (double)x[p_(k-1) + H + j]):
+ *     two products that are exact in fp64, one fp64 sum, one rounding to fp32.  A non-finite x reaches y by IEEE rules (0 * Inf = NaN).
+ *   6 int16 (want_int16): ev_loudness' rule -- t = y * 32768.0f (one fp32 product), clamped to [-32768, 32767], truncated toward zero; NaN -> 0.
+ *   7 Figures per segment: frames = K; edge_frames = the count of k >= 1 whose lag sits on either end of the range; sum_dist = the sum over
+ *     k >= 1 of D_k(delta_k); nonfinite; deltas, the track itself (delta_0 = 0 included).
+ * What follows from the rules: L_out == L_in returns a finite input bit for bit (distance 0 at lag 0 wins every tie; w x + (1 - w) x is exact);
+ * a segment gives the same bits alone or anywhere in a batch, as int16 or as the equal floats, from host or device memory; an input of integer
+ * period P <= EV_STRETCH_LAGS / 2 comes out as y[m] = x[m % P] away from its end.  A segment's last 896 / r + 256 output samples (r = L_in /
+ * L_out) read the zero extension: the search there is against silence.  The search of one segment is a serial chain of K steps on one compute
+ * unit; a batch runs its segments side by side.  No atomics.  Needs no setup call and no weights. */
+#define EV_STRETCH_FRAME 512                 /* N, samples */
+#define EV_STRETCH_HOP   256                 /* H, samples */
+#define EV_STRETCH_LAGS  256                 /* lags -128 .. 127 */
+#define EV_STRETCH_MAX_SAMPLES (1 << 30)     /* per segment, in and out */
+typedef struct ev_stretch_config {
+    uint32_t struct_size;          /* sizeof(ev_stretch_config); any other value is rejected */
+    int32_t  want_int16;           /* also write the clamped int16 waveform */
+} ev_stretch_config;
+void ev_default_stretch_config(ev_stretch_config* cfg);      /* no int16 */
+/* Host only: the EV_STRETCH_HOP values of the rising half of the window (step 4).  Returns EV_STRETCH_HOP, or -1 for a NULL w. */
+int ev_stretch_window(float* w);
+/* Host only: step 1 for B segments.  lens: (B,) L_in.  Segment b takes targets[b] samples where targets is given and targets[b] != 0, else the
+ * length that speeds[b] gives (speeds NULL: 1.0).  Writes lens_out (B,) and returns 0; or returns -1 with the message, which names the segment
+ * and the rule, in ev_last_error(NULL): a NULL lens or lens_out, B outside [1, 65535], a speed that is not finite and > 0, a broken rule of step 1. */
+int ev_stretch_plan(int B, const int64_t* lens, const double* speeds, const int64_t* targets, int64_t* lens_out);
+
+typedef struct ev_stretch_result {
+    uint32_t struct_size;          /* sizeof(ev_stretch_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* offsets[batch] */
+    const float*   wav;            /* DEVICE, (total,) segments back to back: what ev_loudness / ev_limit / ev_deliver / ev_flac take */
+    const int16_t* wav_i16;        /* DEVICE, the same layout; NULL without want_int16 */
+    const int64_t* lens_out;       /* (batch,) HOST: the call's lens_out */
+    const int64_t* offsets;        /* (batch+1,) HOST */
+    const int32_t* frames;         /* (batch,) HOST: K */
+    const int64_t* frame_offsets;  /* (batch+1,) HOST: segment b's lags are deltas[frame_offsets[b] .. frame_offsets[b+1]) */
+    const int16_t* deltas;         /* DEVICE, (frame_offsets[batch],) */
+    const int32_t* edge_frames;    /* (batch,) HOST */
+    const uint64_t* sum_dist;      /* (batch,) HOST */
+    const int64_t* nonfinite;      /* (batch,) HOST */
+} ev_stretch_result;
+/* wav / wav_is_i16 / lens / EV_FLAG_DEVICE_INPUTS as ev_limit (an ev_result.wav with lens = mel_lens * 256, an ev_denoise_result.wav or an
+ * ev_stitch_result.wav goes straight in).  lens_out: a HOST array (B,), what ev_stretch_plan wrote or the caller's own targets.  cfg NULL =
+ * ev_default_stretch_config.  Rejected before anything is launched (message naming the field or segment; the previous result stays valid): a NULL
+ * h, wav, lens, lens_out or out, a wrong struct_size, B outside [1, 65535], a pair (lens[b], lens_out[b]) that breaks a rule of step 1, more than
+ * INT_MAX output tiles in one call.  The result lives in a workspace of its own and is complete when the call returns; it stays valid across
+ * every other entry point until the next ev_stretch or ev_destroy -- the contract of ev_limit_result. */
+int ev_stretch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const int64_t* lens_out, const ev_stretch_config* cfg,
+               uint32_t flags, ev_stretch_result* out);
+
 /* Objective scoring (ev_score): how close a signal a (under test: a synthesised utterance) is to a signal b (the yardstick: a recording of the
  * same sentence) when the two differ in length and timing -- mel-cepstral distortion, F0 error in cents and the voiced / unvoiced error rate
  * along a dynamic-time-warping path, on the device.  ev_compare is the measure for signals of equal length; with EV_SCORE_LINEAR the same scores
