@@ -263,6 +263,29 @@ class ev_stretch_result(C.Structure):
     ]
 
 
+EV_WATERMARK_CHIPS, EV_WATERMARK_BANDS, EV_WATERMARK_MAX_BITS = 768, 48, 16
+
+
+class ev_watermark_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("key", C.c_uint32), ("want_i16", C.c_int32), ("nbits", C.c_int32), ("payload", C.c_uint32),
+                ("strength_db", C.c_float)]
+
+
+class ev_watermark_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("total", C.c_int64), ("wav", C.c_void_p), ("wav_i16", C.c_void_p),
+        ("lens_out", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_int64)),
+    ]
+
+
+class ev_watermark_detect_result(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("batch", C.c_int32), ("nbits", C.c_int32), ("reserved", C.c_int32),
+        ("offset", C.POINTER(C.c_int32)), ("C", C.POINTER(C.c_int32)), ("n", C.POINTER(C.c_int32)), ("bit_C", C.POINTER(C.c_int32)),
+        ("bit_n", C.POINTER(C.c_int32)), ("frames", C.POINTER(C.c_int32)), ("frame_offsets", C.POINTER(C.c_int64)), ("q", C.c_void_p),
+    ]
+
+
 class ev_bert_config(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
                 ("intermediate", C.c_int32), ("max_position", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float),
@@ -362,6 +385,11 @@ SIGNATURES = {
     "ev_stretch_plan": (C.c_int, [C.c_int, _P, _P, _P, _P]),      # host only; the message of a rejection: ev_last_error(None)
     # lens and lens_out are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
     "ev_stretch": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.POINTER(ev_stretch_config), C.c_uint32, C.POINTER(ev_stretch_result)]),
+    "ev_default_watermark_config": (None, [C.POINTER(ev_watermark_config)]),
+    "ev_watermark_pattern": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, _P]),      # host only
+    # lens, payloads, nbits and strengths_db are HOST arrays; wav is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS
+    "ev_watermark": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.POINTER(ev_watermark_config), _P, _P, _P, C.c_uint32, C.POINTER(ev_watermark_result)]),
+    "ev_watermark_detect": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(ev_watermark_detect_result)]),
     "ev_score_design": (C.c_int, [C.c_int, C.c_int, _P]),      # host only
     # lens is a HOST array; mel and f0_hz are host pointers, or device pointers with EV_FLAG_DEVICE_INPUTS
     "ev_score_load": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_uint32]),

@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["ev_gemm.hip", "ev_misc.hip", "ev_align.hip", "ev_features.hip", "ev_pitch.hip", "ev_resample.hip", "ev_stitch.hip", "ev_compare.hip", "ev_flac.hip", "ev_loudness.hip", "ev_limit.hip", "ev_deliver.hip", "ev_score.hip", "ev_denoise.hip", "ev_stretch.hip", "ev_engine.cpp", "ev_audio.cpp", "ev_ops.cpp"]
+SOURCES = ["ev_gemm.hip", "ev_misc.hip", "ev_align.hip", "ev_features.hip", "ev_pitch.hip", "ev_resample.hip", "ev_stitch.hip", "ev_compare.hip", "ev_flac.hip", "ev_loudness.hip", "ev_limit.hip", "ev_deliver.hip", "ev_score.hip", "ev_denoise.hip", "ev_stretch.hip", "ev_watermark.hip", "ev_engine.cpp", "ev_audio.cpp", "ev_ops.cpp"]
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + ["../../include/evhip.h", "../../include/evhip_ops.h"]      # every header in csrc/: a stale .so cost round 3 an hour of wrong measurements
 OUT = os.path.join(HERE, "libevhip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,4 +1,4 @@
-// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise, ev_stretch -- with
+// libevhip.so host side: the audio utilities of include/evhip.h -- ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac, ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise, ev_stretch, ev_watermark -- with
 // their config, setup, design and plan entry points, and the per-kernel test entry points (include/evhip_ops.h) of their kernels and of the aligner's.
 // Every utility call has the same shape: check the arguments, lay the batch out on the host (ev_layout.h), call_begin, plan its arena, upload, launch,
 // call_end, publish the result.  The result stays valid until the next call of the same utility: each has its own arena and its own host vectors.
@@ -1545,6 +1545,170 @@ int ev_stretch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64
     out->batch = B; out->total = total; out->wav = d_wav; out->wav_i16 = d_i16;
     out->lens_out = h->str.lens_out.data(); out->offsets = h->str.offs.data(); out->frames = h->str.frames.data(); out->frame_offsets = h->str.frame_offs.data();
     out->deltas = d_deltas; out->edge_frames = h->str.edges.data(); out->sum_dist = h->str.sum_dist.data(); out->nonfinite = h->str.nonf.data();
+    return 0;
+}
+
+// ------------------------------------------------------------------- audio watermark (include/evhip.h: ev_watermark, ev_watermark_detect)
+static_assert(EV_WATERMARK_NFFT == WM_NFFT && EV_WATERMARK_HOP == WM_HOP && EV_WATERMARK_BAND0 == WM_BAND0 && EV_WATERMARK_BANDS == WM_BANDS &&
+              EV_WATERMARK_TILE == WM_TILE && EV_WATERMARK_PERIOD == WM_PERIOD && EV_WATERMARK_CHIPS == WM_CHIPS && EV_WATERMARK_OFFSETS == WM_OFFSETS &&
+              EV_WATERMARK_MAX_BITS == WM_MAX_BITS, "include/evhip.h states the constants of ev_watermark.hip");
+void ev_default_watermark_config(ev_watermark_config* c) {
+    memset(c, 0, sizeof *c);
+    c->struct_size = sizeof *c;
+    c->strength_db = 1.0f;
+}
+
+static bool watermark_payload_ok(int nbits, uint32_t payload) { return nbits >= 0 && nbits <= WM_MAX_BITS && (uint64_t)payload < (1ull << nbits); }
+
+int ev_watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* signs) {
+    if (!signs || !watermark_payload_ok(nbits, payload)) return -1;
+    watermark_pattern(key, nbits, payload, signs, nullptr);
+    return 0;
+}
+
+// the checks the two entry points share, and the frame grid of the batch: 0, or -1 with the message set
+static int watermark_grid(ev_handle* h, const char* who, int B, const void* wav, const int64_t* lens, FrameGrid& g) {
+    if (!wav) return fail(h, "%s: wav is NULL", who);
+    if (!lens) return fail(h, "%s: lens is NULL", who);
+    if (B < 1 || B > 65535) return fail(h, "%s: B = %d outside [1, 65535]", who, B);
+    const int bad = frame_grid_layout(B, lens, WM_NFFT / 2 + 1, WM_HOP, 64, g);
+    if (bad > 0) return fail(h, "%s: lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", who, bad - 1, (long long)lens[bad - 1], WM_NFFT / 2 + 1);
+    if (bad < 0) return fail(h, "%s: segment %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", who, -bad - 1, (long long)(lens[-bad - 1] / WM_HOP + 1), EV_ALIGN_MAX_FRAMES);
+    return 0;
+}
+
+// ev_denoise's tables at the watermark's shape, once per handle
+static int watermark_tables(ev_handle* h, const char* who) {
+    if (h->wm.ready) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevMem basis, ibasis, env;
+    if (denoise_upload_tables(WM_NFFT, WM_HOP, nullptr, basis, ibasis, env)) return fail(h, "%s: uploading the tables failed", who);
+    h->wm.basis = std::move(basis); h->wm.ibasis = std::move(ibasis); h->wm.env = std::move(env);
+    h->wm.ready = true;
+    return 0;
+}
+
+int ev_watermark(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_watermark_config* cfg, const uint32_t* payloads,
+                 const int32_t* nbits, const float* strengths_db, uint32_t flags, ev_watermark_result* out) {
+    if (!h) return -1;
+    if (!out) return fail(h, "ev_watermark: out is NULL");
+    if (check_struct_size(h, "ev_watermark", "out->struct_size", out->struct_size, "ev_watermark_result", sizeof(ev_watermark_result))) return -1;
+    ev_watermark_config dflt;
+    if (!cfg) { ev_default_watermark_config(&dflt); cfg = &dflt; }
+    if (check_struct_size(h, "ev_watermark", "cfg->struct_size", cfg->struct_size, "ev_watermark_config", sizeof(ev_watermark_config))) return -1;
+    FrameGrid g;
+    if (watermark_grid(h, "ev_watermark", B, wav, lens, g)) return -1;
+    std::vector<int8_t> signs((size_t)B * WM_CHIPS);
+    std::vector<float> gains((size_t)B * 2);
+    for (int b = 0; b < B; ++b) {
+        const int nb = nbits ? nbits[b] : cfg->nbits;
+        const uint32_t pl = payloads ? payloads[b] : cfg->payload;
+        const float db = strengths_db ? strengths_db[b] : cfg->strength_db;
+        if (nb < 0 || nb > WM_MAX_BITS) return fail(h, "ev_watermark: nbits[%d] = %d outside [0, %d]", b, nb, WM_MAX_BITS);
+        if (!watermark_payload_ok(nb, pl)) return fail(h, "ev_watermark: payloads[%d] = %u does not fit %d bits", b, pl, nb);
+        if (!(db >= 0.f && db <= EV_WATERMARK_MAX_DB)) return fail(h, "ev_watermark: strengths_db[%d] = %g outside [0, %g]", b, (double)db, (double)EV_WATERMARK_MAX_DB);
+        watermark_pattern(cfg->key, nb, pl, signs.data() + (size_t)b * WM_CHIPS, nullptr);
+        const float a = (float)pow(10.0, (double)db / 20.0);
+        gains[2 * (size_t)b] = a;
+        gains[2 * (size_t)b + 1] = 1.0f / a;
+    }
+    const int n_fft = WM_NFFT, hop = WM_HOP, KP = denoise_k_pad(n_fft);
+    std::vector<IstftSeq> iseqs; std::vector<StftTile> itiles;
+    const int64_t total_out = istft_layout(B, g.lens.data(), n_fft, hop, iseqs, itiles);
+    const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    const bool want16 = cfg->want_i16 != 0;
+    WavIn in(wav, total_in, wav_is_i16, flags);
+    if (call_begin(h)) return -1;
+    if (watermark_tables(h, "ev_watermark")) return -1;
+    StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_gains = nullptr, *d_out = nullptr;
+    uint16_t *d_hi = nullptr, *d_lo = nullptr; int16_t* d_i16 = nullptr; int8_t* d_signs = nullptr;
+    if (arena_plan(h, ARENA_WATERMARK, [&](ArenaPlan& ap) {
+        in.plan(ap);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_iseqs = ap.arr<IstftSeq>(B); d_itiles = ap.arr<StftTile>(itiles.size());
+        d_gains = ap.arr<float>(gains.size()); d_signs = ap.arr<int8_t>(signs.size());
+        d_hi = ap.arr<uint16_t>((size_t)total_frames * KP); d_lo = ap.arr<uint16_t>((size_t)total_frames * KP);
+        d_out = ap.arr<float>((size_t)total_out); d_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
+    })) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) ||
+        upload(h, d_gains, gains) || upload(h, d_signs, signs)) return -1;
+    region_begin(h, "total");
+    {
+        WmEmbedParams p{};
+        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size(); p.basis = h->wm.basis.get();
+        p.ks = WM_NFFT / 32; p.n_btiles = stft_bin_tiles(WM_NFFT); p.signs = d_signs; p.gains = d_gains; p.spec_hi = d_hi; p.spec_lo = d_lo;
+        KScope ks(h, "wm_embed", 2.0 * 3.0 * 64.0 * (double)g.tiles.size() * n_fft * 2.0 * (n_fft / 2 + 1), (double)in.bytes + 4.0 * (double)total_frames * KP);
+        if (launch_wm_embed(p, h->stream)) return fail(h, "ev_watermark: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (!itiles.empty()) {
+        IstftParams p{};
+        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->wm.ibasis.get(); p.env = h->wm.env.as<float>();
+        p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = KP; p.out = d_out; p.out_i16 = d_i16;
+        KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)itiles.size() * (double)p.R * KP * hop,
+                  4.0 * (double)total_frames * KP + (double)total_out * (want16 ? 6.0 : 4.0));
+        if (launch_istft_ola(p, h->stream)) return fail(h, "ev_watermark: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    if (call_end(h)) return -1;
+    std::vector<int64_t> lo((size_t)B), offs((size_t)B + 1);
+    for (int b = 0; b < B; ++b) { lo[b] = iseqs[b].out_len; offs[b] = iseqs[b].out_off; }
+    offs[B] = total_out;
+    h->wm.lens.swap(lo); h->wm.offs.swap(offs);
+    reset_result(out);
+    out->batch = B; out->total = total_out; out->wav = d_out; out->wav_i16 = d_i16;
+    out->lens_out = h->wm.lens.data(); out->offsets = h->wm.offs.data();
+    return 0;
+}
+
+int ev_watermark_detect(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, uint32_t key, int nbits, uint32_t flags,
+                        ev_watermark_detect_result* out) {
+    if (!h) return -1;
+    if (!out) return fail(h, "ev_watermark_detect: out is NULL");
+    if (check_struct_size(h, "ev_watermark_detect", "out->struct_size", out->struct_size, "ev_watermark_detect_result", sizeof(ev_watermark_detect_result))) return -1;
+    FrameGrid g;
+    if (watermark_grid(h, "ev_watermark_detect", B, wav, lens, g)) return -1;
+    if (nbits < 0 || nbits > WM_MAX_BITS) return fail(h, "ev_watermark_detect: nbits = %d outside [0, %d]", nbits, WM_MAX_BITS);
+    std::vector<int8_t> tabs(3 * (size_t)WM_CHIPS);      // the pilots' signs (0 for a payload chip), every sign at payload 0, every role
+    watermark_pattern(key, nbits, 0, tabs.data() + WM_CHIPS, reinterpret_cast<uint8_t*>(tabs.data()) + 2 * WM_CHIPS);
+    for (int i = 0; i < WM_CHIPS; ++i) tabs[(size_t)i] = (uint8_t)tabs[2 * (size_t)WM_CHIPS + i] == WM_PILOT ? tabs[(size_t)WM_CHIPS + i] : (int8_t)0;
+    const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    WavIn in(wav, total_in, wav_is_i16, flags);
+    if (call_begin(h)) return -1;
+    if (watermark_tables(h, "ev_watermark_detect")) return -1;
+    StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; int32_t *d_q = nullptr, *d_win = nullptr; int8_t* d_tabs = nullptr; WmFig* d_figs = nullptr;
+    if (arena_plan(h, ARENA_WM_DETECT, [&](ArenaPlan& ap) {
+        in.plan(ap);
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_tabs = ap.arr<int8_t>(tabs.size()); d_figs = ap.arr<WmFig>(B);
+        d_q = ap.arr<int32_t>((size_t)total_frames * WM_BANDS); d_win = ap.arr<int32_t>((size_t)total_frames * WM_BANDS);
+    })) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_tabs, tabs)) return -1;
+    region_begin(h, "total");
+    {
+        WmBandParams p{};
+        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size(); p.basis = h->wm.basis.get(); p.ks = WM_NFFT / 32; p.n_btiles = stft_bin_tiles(WM_NFFT); p.q = d_q;
+        KScope ks(h, "wm_bands", 2.0 * 3.0 * 64.0 * (double)g.tiles.size() * WM_NFFT * 2.0 * (WM_NFFT / 2 + 1), (double)in.bytes + 4.0 * (double)total_frames * WM_BANDS);
+        if (launch_wm_bands(p, h->stream)) return fail(h, "ev_watermark_detect: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    {      // per (tile, band) one contrast, added into 16 offsets per phase, 8 phases
+        KScope ks(h, "wm_correlate", 2.0 * WM_OFFSETS * (double)total_frames / WM_TILE * WM_BANDS, 4.0 * 10.0 * (double)total_frames * WM_BANDS);
+        if (launch_wm_correlate(d_q, d_win, d_seqs, B, d_tabs, d_figs, h->stream)) return fail(h, "ev_watermark_detect: the kernel does not build this shape");
+    }
+    HIPCHK(h, hipGetLastError());
+    std::vector<WmFig> figs((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(figs.data(), d_figs, (size_t)B * sizeof(WmFig), hipMemcpyDeviceToHost, h->stream));
+    if (call_end(h)) return -1;
+    evh::WatermarkState& w = h->wm;
+    w.offset.resize((size_t)B); w.C.resize((size_t)B); w.n.resize((size_t)B); w.bit_C.resize((size_t)B * WM_MAX_BITS); w.bit_n.resize((size_t)B * WM_MAX_BITS);
+    for (int b = 0; b < B; ++b) {
+        w.offset[(size_t)b] = figs[(size_t)b].offset; w.C[(size_t)b] = figs[(size_t)b].C; w.n[(size_t)b] = figs[(size_t)b].n;
+        std::copy(figs[(size_t)b].bit_C, figs[(size_t)b].bit_C + WM_MAX_BITS, w.bit_C.begin() + (size_t)b * WM_MAX_BITS);
+        std::copy(figs[(size_t)b].bit_n, figs[(size_t)b].bit_n + WM_MAX_BITS, w.bit_n.begin() + (size_t)b * WM_MAX_BITS);
+    }
+    w.frames.swap(g.lens); w.frame_offs.swap(g.offs);
+    reset_result(out);
+    out->batch = B; out->nbits = nbits; out->offset = w.offset.data(); out->C = w.C.data(); out->n = w.n.data(); out->bit_C = w.bit_C.data(); out->bit_n = w.bit_n.data();
+    out->frames = w.frames.data(); out->frame_offsets = w.frame_offs.data(); out->q = d_q;
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Device parts shared by the audio kernels (ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_loudness, ev_limit, ev_deliver, ev_score,
-// ev_denoise, ev_stretch): wave reductions, the element rules that decide a bit, the polyphase filter of ev_resample and ev_deliver, and the windowed DFT of
-// ev_features and ev_denoise.  Everything is inline with internal
+// ev_denoise, ev_stretch, ev_watermark): wave reductions, the element rules that decide a bit, the polyphase filter of ev_resample and ev_deliver, and the windowed DFT of
+// ev_features, ev_denoise and ev_watermark.  Everything is inline with internal
 // linkage: the library exports nothing from here.  Include it before a file-wide `#pragma clang fp contract`: it leaves contraction at the default
 // (fast), as a file without pragmas has it.
 #pragma once
@@ -91,6 +91,13 @@ __device__ inline float load_sample(const void* wav, int is16, int64_t i) {
 // y -> int16: one rounded product, the clamp, truncation toward zero (the same integers as truncating first).  What a NaN becomes is the caller's rule.
 __device__ inline int16_t s16_trunc(float y) { return (int16_t)(int)fminf(fmaxf(mul_rn(y, 32768.0f), -32768.0f), 32767.0f); }
 
+// the keyed integer hash of ev_deliver's dither and ev_watermark's pattern (include/evhip.h states it): dl_mix(seed, c) is the value of counter c
+__host__ __device__ inline uint32_t dl_hash(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t dl_mix(uint32_t seed, uint64_t c) { return dl_hash(dl_hash((uint32_t)c + dl_hash(seed ^ (uint32_t)(c >> 32))) ^ seed); }
+
 __host__ __device__ inline int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && (a < 0)) ? q - 1 : q; }      // b > 0
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 
@@ -157,6 +164,14 @@ __device__ inline void stft_stage_planes(_Float16* sh, _Float16* sl, const void*
         sh[stft_spad(i)] = h;
         sl[stft_spad(i)] = (_Float16)((v - (float)h) * 2048.0f);
     }
+}
+
+// one gained cell (g Re, g Im) into the scratch planes of ev_denoise and ev_watermark: `at` = row k_pad + 2 bin, each value split as hi + 2^-11 lo
+__device__ inline void stft_store_cell(uint16_t* spec_hi, uint16_t* spec_lo, size_t at, float vr, float vi) {
+    const _Float16 hr = (_Float16)vr, hi = (_Float16)vi;
+    *reinterpret_cast<half2v*>(reinterpret_cast<_Float16*>(spec_hi) + at) = half2v{hr, hi};
+    *reinterpret_cast<half2v*>(reinterpret_cast<_Float16*>(spec_lo) + at) =
+        half2v{(_Float16)((vr - (float)hr) * 2048.0f), (_Float16)((vi - (float)hi) * 2048.0f)};
 }
 
 // One wave's share of one basis tile: its 32 frames (two 16-row tiles, A fragments at aoff[a] + 32 step) times the re and im columns of its 16

@@ -21,12 +21,6 @@ namespace ev {
 
 namespace {
 
-__device__ inline uint32_t dl_hash(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ inline uint32_t dl_mix(uint32_t seed, uint64_t c) { return dl_hash(dl_hash((uint32_t)c + dl_hash(seed ^ (uint32_t)(c >> 32))) ^ seed); }
-
 // y -> the int16 value s (as int) and whether t (with dither: t + d) fell outside [-32768, 32767]
 __device__ inline int dl_s16(float y, int dither, uint32_t seed, int64_t m, int* clipped) {
     float t = __fmul_rn(y, 32768.0f);

@@ -120,11 +120,7 @@ __global__ __launch_bounds__(256) void stft_gain_kernel(const StftGainParams p) 
                 if (2 * bin >= p.k_pad) continue;
                 const float gn = m > 0.f ? fmaxf(m - sb, 0.f) / m : 0.f;      // mag == 0 (and a NaN): the cell is zero
                 const float vr = gn * re, vi = gn * im;
-                const _Float16 hr = (_Float16)vr, hi = (_Float16)vi;
-                const size_t at = (size_t)row * p.k_pad + 2 * bin;
-                *reinterpret_cast<half2v*>(reinterpret_cast<_Float16*>(p.spec_hi) + at) = half2v{hr, hi};
-                *reinterpret_cast<half2v*>(reinterpret_cast<_Float16*>(p.spec_lo) + at) =
-                    half2v{(_Float16)((vr - (float)hr) * 2048.0f), (_Float16)((vi - (float)hi) * 2048.0f)};
+                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)row * p.k_pad + 2 * bin, vr, vi);
             }
     }
 }

@@ -42,6 +42,8 @@ enum Arena {
     ARENA_SCORE,       // ev_score (like ARENA_ALIGN; the distance and decision workspaces too)
     ARENA_DENOISE,     // ev_denoise (like ARENA_ALIGN; the spectrum scratch too)
     ARENA_STRETCH,     // ev_stretch (like ARENA_ALIGN)
+    ARENA_WATERMARK,   // ev_watermark (like ARENA_DENOISE)
+    ARENA_WM_DETECT,   // ev_watermark_detect (like ARENA_ALIGN; q and the window sums)
     ARENA_COUNT
 };
 
@@ -137,6 +139,10 @@ struct DenoiseState {       // ev_denoise.  basis, ibasis, env, bias: its own ta
     std::vector<int64_t> lens, offs;
 };
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
+struct WatermarkState {       // ev_watermark, ev_watermark_detect.  basis, ibasis, env: ev_denoise's tables at the watermark's shape, built by the first call
+    bool ready = false; DevMem basis, ibasis, env;
+    std::vector<int64_t> lens, offs, frame_offs; std::vector<int32_t> offset, C, n, bit_C, bit_n, frames;
+};
 struct StretchState { std::vector<int64_t> lens_out, offs, frame_offs, nonf; std::vector<int32_t> frames, edges; std::vector<uint64_t> sum_dist; };       // ev_stretch
 
 }  // namespace evh
@@ -172,7 +178,7 @@ struct ev_handle {
     const int64_t* last_dur_eff = nullptr;       // the durations the length regulator used (ev_synthesize_prosody: after the overrides)
     // per-utility state (the structs above)
     evh::AlignState aln; evh::FeaturesState feat; evh::PitchState pitch; evh::ResampleState rs;
-    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score; evh::DenoiseState dn; evh::StretchState str;
+    evh::StitchState stitch; evh::CompareState cmp; evh::FlacState flac; evh::LoudnessState loud; evh::LimitState lim; evh::DeliverState dlv; evh::ScoreState score; evh::DenoiseState dn; evh::StretchState str; evh::WatermarkState wm;
     // device maps (inside the arena)
     int32_t *d_tok_seq = nullptr, *d_tok_pos = nullptr, *d_tok_off = nullptr, *d_tok_len = nullptr, *d_cu = nullptr;
     uint8_t* d_tok_valid = nullptr;

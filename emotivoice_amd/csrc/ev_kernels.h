@@ -301,6 +301,39 @@ size_t stft_gain_lds_bytes(int n_fft, int hop);
 int launch_stft_gain(const StftGainParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
 int launch_istft_ola(const IstftParams& p, hipStream_t s);
 
+// ev_watermark / ev_watermark_detect (ev_watermark.hip), on ev_denoise's shapes at n_fft = WM_NFFT, hop = WM_HOP.  Embed: ev_denoise's forward
+// GEMM with the gain of a chip's sign, into the same scratch planes, then launch_istft_ola unchanged.  Detect: the forward GEMM again with a band
+// epilogue -- q[frame][WM_BANDS] int32, the quantised log2 of the floored band energies -- then wm_correlate_kernel, one block per segment.
+constexpr int WM_NFFT = 1024, WM_HOP = 256, WM_BAND0 = 20, WM_BAND_BINS = 4, WM_BANDS = 48, WM_TILE = 8, WM_PERIOD = 16, WM_CHIPS = WM_PERIOD * WM_BANDS,
+              WM_MAX_BITS = 16, WM_OFFSETS = WM_TILE * WM_PERIOD, WM_PILOT = 255;
+struct WmEmbedParams {
+    const void* wav; int wav_is_i16;
+    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
+    const void* basis;                                // stft_pack_basis(WM_NFFT), on the device
+    int ks, n_btiles;                                 // WM_NFFT / 32 and stft_bin_tiles(WM_NFFT), as RUNTIME values: with constants the compiler unrolls the GEMM's k loop whole and spills
+    const int8_t* signs;                              // (B, WM_CHIPS) device: watermark_pattern of the segment's key, payload and length
+    const float* gains;                               // (B, 2) device: a and float32(1 / a) of the segment
+    uint16_t *spec_hi, *spec_lo;                      // ev_denoise's scratch planes
+};
+struct WmBandParams {
+    const void* wav; int wav_is_i16;
+    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
+    const void* basis;
+    int ks, n_btiles;                                 // as WmEmbedParams has them
+    int32_t* q;                                       // (total frames, WM_BANDS) device; frame t of a segment is row frm_off + t
+};
+struct WmFig { int32_t offset, C, n, pad; int32_t bit_C[WM_MAX_BITS], bit_n[WM_MAX_BITS]; };
+// chip i = WM_BANDS u + v: h = dl_mix(key, i), sign (h & 1) ? +1 : -1, role (h >> 1) % (2 nbits); a role < nbits is that payload bit (the sign is
+// flipped where the bit of `payload` is 1), every other role -- and every chip at nbits == 0 -- is WM_PILOT.  roles may be null.
+void watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* signs /* host, WM_CHIPS */, uint8_t* roles /* host, WM_CHIPS, or null */);
+size_t wm_embed_lds_bytes();
+size_t wm_bands_lds_bytes();
+int launch_wm_embed(const WmEmbedParams& p, hipStream_t s);      // 0, or -1 for an empty grid
+int launch_wm_bands(const WmBandParams& p, hipStream_t s);
+// q as wm_bands wrote it; win: device scratch (total frames, WM_BANDS) int32; tabs: device 3 x WM_CHIPS bytes -- the pilot chips (sign, or 0 for a
+// payload chip), every chip's sign with payload 0, every chip's role; figs: device (B,)
+int launch_wm_correlate(const int32_t* q, int32_t* win, const StftSeq* seqs, int B, const int8_t* tabs, WmFig* figs, hipStream_t s);
+
 // ev_pitch (ev_pitch.hip): wav -> per-frame F0 (YIN), then the continuous fill and the standardisation.  The utterance and tile tables are the
 // StftSeq / StftTile of ev_features, with tiles of PITCH_TF frames.  Limits of the kernel: win <= PITCH_MAX_WIN, 1 <= hop <= win, 4 <= tau_min <
 // tau_max, tau_max + 1 <= win, and the tile's LDS (pitch_lds_bytes: its run of samples and three numbers per (frame, lag)) within PITCH_MAX_LDS.

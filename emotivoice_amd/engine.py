@@ -312,12 +312,12 @@ class EVEngine(EVAudio):
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,
                    forced_durations: Optional[np.ndarray] = None, prosody=None, flac=None, loudness=None, limiter=None, delivery=None,
-                   denoise=None, stretch=None) -> Dict[str, object]:
+                   denoise=None, stretch=None, watermark=None) -> Dict[str, object]:
         """utts: dicts with ling (N,) int64, speaker int, style (768,), content (768,) -- the four fields the
         reference builds per input line (inference_am_vocoder_joint.py:113-119).
         prosody: None (ev_synthesize), or one emotivoice_amd.prosody.Prosody per utterance (None entries = identity) or a single one
         for every utterance: ev_synthesize_prosody.  The returned pitch / energy / durations are the predictions either way.
-        The six arguments below are the output chain on the device, denoise -> stretch -> loudness -> limiter -> delivery -> flac; emotivoice_amd/output_chain.py
+        The seven arguments below are the output chain on the device, denoise -> stretch -> watermark -> loudness -> limiter -> delivery -> flac; emotivoice_amd/output_chain.py
         states once, for every combination, the order, which stage makes the int16, what is copied to the host and what a FLAC stream decodes to.
         flac: None, True, one boolean per utterance or an emotivoice_amd.flac.FlacConfig (every utterance, with its LPC / MD5 / block settings;
         the sample rate is the engine's and the conversion stays the wrapping one): adds flac_list, the FLAC stream (``bytes``) of every selected
@@ -341,8 +341,14 @@ class EVEngine(EVAudio):
         ev_stretch runs SECOND, after ev_denoise, and changes the length of every waveform at the same pitch (WSOLA; not the reference's Rubber
         Band, see emotivoice_amd.stretch for what is not verified).  wav_list (and wav_int16_list, delivered_list) have the new lengths and
         ``stretch`` holds lens_in, lens_out, speed and the search's figures.  durations, mel_lens and mel_offsets stay on the MODEL's clock: they
-        describe the mel the vocoder read, not the stretched waveform.  The packed ``wav`` is cut by stretch["offsets"], not by mel_offsets."""
-        plan = resolve_chain(self.shapes.sr, len(utts), denoise, loudness, limiter, delivery, flac, vocoder, flac_convert="wrap", stretch=stretch)
+        describe the mel the vocoder read, not the stretched waveform.  The packed ``wav`` is cut by stretch["offsets"], not by mel_offsets.
+        watermark: None, a key, 'KEY[:PAYLOAD:NBITS]', a dict or an emotivoice_amd.watermark.WatermarkConfig (payload, nbits and strength_db may
+        have one entry per utterance): ev_watermark runs THIRD, after ev_stretch and before ev_loudness, and marks every waveform with the keyed
+        pattern that EVEngine.watermark_detect finds again (see emotivoice_amd.watermark for what is not verified: nobody has listened to it, no
+        security claim).  Its output has whole hops, as ev_denoise's; ``watermark`` in the result holds lens_out, offsets, key, payload, nbits
+        and strength_db."""
+        plan = resolve_chain(self.shapes.sr, len(utts), denoise, loudness, limiter, delivery, flac, vocoder, flac_convert="wrap", stretch=stretch,
+                             watermark=watermark)
         flags = (_ffi.EV_FLAG_WANT_INT16 if want_int16 and not plan.staged else 0) | (0 if vocoder else _ffi.EV_FLAG_NO_VOCODER)
         self._denoise_ready(plan.denoise)
         res, cu = self._synthesize_call(utts, alpha, flags, forced_durations, prosody)
@@ -356,14 +362,14 @@ class EVEngine(EVAudio):
         return chain.into(out, SYNTHESIZE_NAMES if want_i16 else SYNTHESIZE_NAMES[:2])
 
     def synthesize_long(self, documents: Sequence, alpha: float = 1.0, prosody=None, config=None, flac=None, loudness=None, limiter=None,
-                        delivery=None, denoise=None, stretch=None) -> Dict[str, object]:
+                        delivery=None, denoise=None, stretch=None, watermark=None) -> Dict[str, object]:
         """Documents of several sentences each -> one waveform per document and the time of every sentence in it.  documents: each a
         dict(utts=[utt dicts as ``synthesize`` takes], pauses=[one per joint: a class of emotivoice_amd.longform.pauses_ms, milliseconds, or
         None]) or a pair (utts, pauses); pauses None = "sentence" everywhere.  prosody: as ``synthesize`` takes it, over the sentences of all
         documents in order.  config: an emotivoice_amd.longform.StitchConfig (None: its defaults, which have not been measured on a released
         checkpoint).  One ev_synthesize[_prosody] call, one ev_stitch call on its device waveform and one D2H copy (int16 with
         config.want_int16, else fp32).  All sentences go into one synthesize call: more than it takes raises; splitting is the caller's.
-        The six arguments below are the output chain, per document, after ev_stitch; emotivoice_amd/output_chain.py states its rules.
+        The seven arguments below are the output chain, per document, after ev_stitch; emotivoice_amd/output_chain.py states its rules.
         flac=True or an emotivoice_amd.flac.FlacConfig (its LPC / MD5 / block settings; the sample rate is the engine's; ``md5`` costs one serial
         chain per document) adds flac_list, one FLAC stream (``bytes``) per document (it turns config.want_int16 on, so
         ``documents`` are the int16 ones a stream decodes to).
@@ -381,19 +387,24 @@ class EVEngine(EVAudio):
         stretch: as ``synthesize`` takes it, per DOCUMENT (a sequence has one entry per document), after ev_stitch and ev_denoise.  doc_lens and
         doc_offsets become the stretched ones and ``stretch`` holds lens_in, lens_out, speed and the search's figures.  sentence_times are
         scaled by L_out / L_in of their document: WSOLA follows that line only to within its lag range, so a time is off by up to 128 samples
-        (8 ms at 16 kHz) plus the rounding of the frame positions.  seg_pos, seg_start and seg_end stay on the clock BEFORE the stretch."""
+        (8 ms at 16 kHz) plus the rounding of the frame positions.  seg_pos, seg_start and seg_end stay on the clock BEFORE the stretch.
+        watermark: as ``synthesize`` takes it, per DOCUMENT (a sequence has one entry per document), after ev_stretch.  Its output has whole
+        hops, so a document loses the up to 255 samples after its last whole hop, as under denoise; doc_lens and doc_offsets are the marked
+        ones."""
         import dataclasses
         from .longform import StitchConfig, flatten_documents, plan_document
         sc = (config or StitchConfig()).validate()
         if int(sc.sample_rate) != int(self.shapes.sr):
             raise ValueError("config.sample_rate %d is not the engine's %d" % (sc.sample_rate, self.shapes.sr))
-        plan = resolve_chain(sc.sample_rate, None, denoise, loudness, limiter, delivery, flac, stretch=stretch)
+        plan = resolve_chain(sc.sample_rate, None, denoise, loudness, limiter, delivery, flac, stretch=stretch, watermark=watermark)
         stitch_i16 = bool(sc.want_int16 or plan.flac is not None) and plan.delivery is None      # a delivered response has no 16 kHz int16
         if stitch_i16 != sc.want_int16:
             sc = dataclasses.replace(sc, want_int16=stitch_i16).validate()
         utts, seg_doc, pauses = flatten_documents(documents)
         if plan.stretch is not None:
             plan.stretch.per_segment(len(documents), sc.sample_rate)      # one entry per document, before any library call
+        if plan.watermark is not None:
+            plan.watermark.per_segment(len(documents))
         S = len(utts)
         if S > 65535:
             raise ValueError("%d sentences exceed the 65535 segments of one ev_stitch call; split the documents over several calls" % S)
@@ -403,7 +414,7 @@ class EVEngine(EVAudio):
         mel_offs = host_array(res.mel_offsets, S + 1, np.int64) * self.shapes.upsample_factor
         st = self.stitch_raw(S, res.wav, mel_offs[:-1], np.diff(mel_offs), seg_doc, pause_after, sc, _ffi.EV_FLAG_DEVICE_INPUTS)
         out = self.stitch_to_numpy(st, int16_only=sc.want_int16, skip_wav=plan.staged)
-        reader = ("denoise" if plan.denoise is not None else "stretch" if plan.stretch is not None else "limiter" if plan.limiter is not None else "loudness" if plan.loudness is not None else
+        reader = ("denoise" if plan.denoise is not None else "stretch" if plan.stretch is not None else "watermark" if plan.watermark is not None else "limiter" if plan.limiter is not None else "loudness" if plan.loudness is not None else
                   "delivery" if plan.delivery is not None else "flac" if plan.flac is not None else None)
         empty = [d for d in range(st.batch_docs) if out["doc_lens"][d] < 1]
         if empty and reader:
@@ -416,6 +427,8 @@ class EVEngine(EVAudio):
         if plan.stretch is not None:
             out["doc_lens"], out["doc_offsets"] = out["stretch"]["lens_out"], out["stretch"]["offsets"]
             scale = out["stretch"]["lens_out"] / out["stretch"]["lens_in"]
+        if plan.watermark is not None:
+            out["doc_lens"], out["doc_offsets"] = out["watermark"]["lens_out"], out["watermark"]["offsets"]
         sr = float(sc.sample_rate)
         start = out["seg_pos"] / sr * scale[seg_doc]
         end = (out["seg_pos"] + (out["seg_end"] - out["seg_start"])) / sr * scale[seg_doc]

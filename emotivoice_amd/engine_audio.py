@@ -1,10 +1,10 @@
 """The audio utilities of the libevhip.so handle (csrc/ev_audio.cpp): ev_features, ev_pitch, ev_resample, ev_stitch, ev_compare, ev_flac,
-ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise and ev_stretch as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
+ev_loudness, ev_limit, ev_deliver, ev_score, ev_denoise, ev_stretch and ev_watermark as ``*_setup`` / ``*_raw`` / ``*_to_numpy`` and a host-array call each.  EVEngine (engine.py) inherits them; the
 handle, ``_check`` and ``d2h`` are its own."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -54,7 +54,7 @@ class EVAudio:
         self.feature_config = self.resample_config = self.delivery_config = self.denoise_config = None      # set by the ``*_setup`` calls
         self._setup_keys: Dict[str, tuple] = {}                   # "deliver" / "denoise" -> the key of the config the library is set up with
         self._denoise_own_bias: Dict[tuple, np.ndarray] = {}      # the vocoder's own bias per (n_fft, hop), measured by denoise_setup on the loaded weights
-        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise", "stretch"):
+        for name in ("align", "features", "pitch", "resample", "stitch", "compare", "flac", "loudness", "limit", "deliver", "denoise", "stretch", "watermark", "watermark_detect"):
             setattr(self, "last_" + name, None)                # the ev_<name>_result of the last call (_call)
 
     def _setup_for(self, name: str, key: tuple, *args):
@@ -522,6 +522,82 @@ class EVAudio:
         out = self.stretch_to_numpy(self.stretch_raw(len(lens), flat.ctypes.data, is16, lens, sc.lengths(lens, sample_rate), sc), want_track=want_track)
         out["lens_in"] = np.asarray(lens, np.int64).copy()
         out["speed"] = out["lens_in"] / out["lens_out"]
+        return out
+
+    # -- audio watermark (ev_watermark, ev_watermark_detect): a keyed mark on the STFT magnitude and its detector, on the device
+    def watermark_pattern(self, key: int, nbits: int = 0, payload: int = 0) -> np.ndarray:
+        """ev_watermark_pattern: the 768 signs (int8, +1 / -1, payload flips applied) of the pattern, chip 48 u + v.  Host only."""
+        signs = np.zeros(_ffi.EV_WATERMARK_CHIPS, np.int8)
+        if self._lib.ev_watermark_pattern(C.c_uint32(int(key)), int(nbits), C.c_uint32(int(payload)), _ptr(signs)):
+            raise ValueError("ev_watermark_pattern: nbits %r outside [0, %d] or payload %r does not fit" % (nbits, _ffi.EV_WATERMARK_MAX_BITS, payload))
+        return signs
+
+    def watermark_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, config, flags: int = 0) -> _ffi.ev_watermark_result:
+        """ev_watermark (include/evhip.h).  wav_ptr is a host pointer, or a device pointer with EV_FLAG_DEVICE_INPUTS; lens is a host array.
+        config: an emotivoice_amd.watermark.WatermarkConfig; its payload, nbits and strength_db go in per segment.  The returned struct's device
+        waveforms and host arrays stay valid until the next watermark call on this engine."""
+        payloads, nbits, strengths = config.validate().per_segment(B)
+        return self._call("watermark", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), config_ref(config), _ptr(payloads),
+                          _ptr(nbits), _ptr(strengths), flags)
+
+    def watermark_to_numpy(self, res: _ffi.ev_watermark_result, int16_only: bool = False, skip_wav: bool = False) -> Dict[str, object]:
+        """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
+        output only; without it both).  ``skip_wav``: the host arrays only."""
+        B = res.batch
+        out: Dict[str, object] = dict(lens_out=host_array(res.lens_out, B, np.int64), offsets=host_array(res.offsets, B + 1, np.int64))
+        if not skip_wav:
+            out.update(self._wav_pair(res, res.total, out["offsets"], int16_only))
+        return out
+
+    def watermark(self, wavs: Sequence[np.ndarray], config) -> Dict[str, object]:
+        """Host signals at 16 kHz -> the marked signals.  wavs: one 1-D array per segment, all int16 or all floating, each of 513 samples or more;
+        config: a key, 'KEY[:PAYLOAD:NBITS]', a dict or an emotivoice_amd.watermark.WatermarkConfig.  Every output has 256 * (len // 256)
+        samples.  Needs no weights."""
+        from .watermark import N_FFT, watermark_config
+        wc = watermark_config(config)
+        if wc is None:
+            raise ValueError("watermark needs a key or a WatermarkConfig")
+        flat, is16, lens = pack_segments(wavs, min_samples=N_FFT // 2 + 1)
+        return self.watermark_to_numpy(self.watermark_raw(len(lens), flat.ctypes.data, is16, lens, wc))
+
+    def watermark_detect_raw(self, B: int, wav_ptr: int, wav_is_i16: bool, lens: np.ndarray, key: int, nbits: int = 0,
+                             flags: int = 0) -> _ffi.ev_watermark_detect_result:
+        """ev_watermark_detect (include/evhip.h).  The returned struct's host arrays and device q stay valid until the next detect call."""
+        return self._call("watermark_detect", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), C.c_uint32(int(key)), int(nbits), flags)
+
+    def watermark_detect_to_numpy(self, res: _ffi.ev_watermark_detect_result, want_q: bool = False) -> Dict[str, object]:
+        """The detector's integers per segment: offset, C, n (B,), bit_C, bit_n (B, 16), frames.  ``want_q``: also q_list, one (T_b, 48) int32
+        array per segment (a D2H copy)."""
+        B, nb = res.batch, _ffi.EV_WATERMARK_MAX_BITS
+        out: Dict[str, object] = dict(offset=host_array(res.offset, B, np.int32), C=host_array(res.C, B, np.int32), n=host_array(res.n, B, np.int32),
+                                      bit_C=host_array(res.bit_C, B * nb, np.int32).reshape(B, nb), bit_n=host_array(res.bit_n, B * nb, np.int32).reshape(B, nb),
+                                      frames=host_array(res.frames, B, np.int32), frame_offsets=host_array(res.frame_offsets, B + 1, np.int64))
+        if want_q:
+            nbands = _ffi.EV_WATERMARK_BANDS
+            q = self.d2h(res.q, (int(out["frame_offsets"][-1]) * nbands,), np.int32)
+            out["q_list"] = [a.reshape(-1, nbands) for a in cut(q, out["frame_offsets"] * nbands)]
+        return out
+
+    def watermark_detect(self, wavs: Sequence[np.ndarray], key: int, nbits: int = 0, sample_rate: int = 16000, threshold: Optional[float] = None,
+                         want_q: bool = False) -> Dict[str, object]:
+        """Host signals -> is the mark of ``key`` in them?  wavs: one 1-D array per segment, all int16 or all floating; sample_rate: theirs -- at
+        another rate than 16 kHz (one of ev_resample's) they are brought to 16 kHz by ev_resample on the device first.  Returns the detector's
+        integers and ``report``: per segment dict(z, present, offset, bits, payload) (emotivoice_amd.watermark.detect_report; threshold None:
+        6.25).  Needs no weights."""
+        from .watermark import N_FFT, SAMPLE_RATE, THRESHOLD, detect_report
+        if int(sample_rate) == SAMPLE_RATE:
+            flat, is16, lens = pack_segments(wavs, min_samples=N_FFT // 2 + 1)
+            res = self.watermark_detect_raw(len(lens), flat.ctypes.data, is16, lens, key, nbits)
+        else:
+            from .resample import ResampleConfig, pack_wavs
+            rc = ResampleConfig(sr_in=int(sample_rate), sr_out=SAMPLE_RATE).validate()
+            if self.resample_config is None or self.resample_config.key() != rc.key():
+                self.resample_setup(rc)
+            flat, is16, lens = pack_wavs(wavs, rc)
+            rs = self.resample_raw(len(wavs), flat.ctypes.data, is16, lens)
+            res = self.watermark_detect_raw(rs.batch, rs.wav, False, host_array(rs.wav_lens, rs.batch, np.int64), key, nbits, _ffi.EV_FLAG_DEVICE_INPUTS)
+        out = self.watermark_detect_to_numpy(res, want_q)
+        out["report"] = detect_report(out, int(nbits), THRESHOLD if threshold is None else float(threshold))
         return out
 
     # -- objective scoring (ev_score): MCD, F0 error and voiced / unvoiced error of a signal against a yardstick of another length, on the device

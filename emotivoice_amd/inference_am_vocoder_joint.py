@@ -106,7 +106,7 @@ def synthesize_checkpoint(config, conf, checkpoint_path, out_dir, args, state_di
     sr = int(getattr(config, "sampling_rate", gen.shapes.sr))
     written = 0
     from .inference_tts import chain_from_args, write_delivered
-    stages = chain_from_args(args)            # --time-stretch; --sample-rate / --encoding / --dither: the files at that rate and encoding, converted on the device
+    stages = chain_from_args(args)            # --time-stretch; --watermark; --sample-rate / --encoding / --dither: the files at that rate and encoding, converted on the device
     delivery = stages.get("delivery")
     for s in range(0, len(todo), args.batch):
         chunk = todo[s:s + args.batch]
@@ -138,8 +138,9 @@ def main(argv=None):
                    help="no checkpoint directory: synthesise with the seeded synthetic checkpoint (named 'synthetic')")
     p.add_argument("--verify-precision", action="store_true",
                    help="with --precision mx: measure the checkpoint against a strict engine at load time and run the cheapest mode within 1e-3 of it")
-    from .inference_tts import add_delivery_arguments, add_stretch_argument
+    from .inference_tts import add_delivery_arguments, add_stretch_argument, add_watermark_argument
     add_stretch_argument(p)
+    add_watermark_argument(p)
     add_delivery_arguments(p)
     args = p.parse_args(argv)
 

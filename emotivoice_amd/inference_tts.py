@@ -91,11 +91,15 @@ def delivery_from_args(args):
 def chain_from_args(args) -> dict:
     """The output stages a command line asks for, as EVEngine.synthesize's keywords (emotivoice_amd/output_chain.py); a flag that is not given, or
     that the parser does not have, leaves its keyword out.  --denoise: the vocoder's stationary bias removed (ev_denoise), before every other
-    stage; --time-stretch: every utterance's duration divided by SPEED at the same pitch (ev_stretch, after --denoise); --loudness: every
+    stage; --time-stretch: every utterance's duration divided by SPEED at the same pitch (ev_stretch, after --denoise); --watermark: every
+    utterance marked with the keyed pattern that tools/watermark_detect.py finds again (ev_watermark, after --time-stretch); --loudness: every
     utterance normalised (ev_loudness); --true-peak: the true peak held at a ceiling (ev_limit; with --loudness it
     replaces the sample-peak limit); --sample-rate / --encoding / --dither: the files at that rate and encoding (ev_deliver)."""
     kw = {k: float(getattr(args, flag)) for k, flag in (("denoise", "denoise"), ("stretch", "time_stretch"), ("loudness", "loudness"), ("limiter", "true_peak"))
           if getattr(args, flag, None) is not None}
+    if getattr(args, "watermark", None) is not None:
+        from .watermark import parse_flag
+        kw["watermark"] = parse_flag(args.watermark)
     delivery = delivery_from_args(args)
     return kw if delivery is None else dict(kw, delivery=delivery)
 
@@ -104,6 +108,13 @@ def add_stretch_argument(p: argparse.ArgumentParser):
     p.add_argument("--time-stretch", type=float, default=None, metavar="SPEED",
                    help="stretch every finished waveform on the device to 1 / SPEED of its duration at the same pitch (ev_stretch: WSOLA, SPEED in "
                         "[0.5, 2]; the waveform meaning of the reference's speed, but not its Rubber Band); default: off")
+
+
+def add_watermark_argument(p: argparse.ArgumentParser):
+    p.add_argument("--watermark", type=str, default=None, metavar="KEY[:PAYLOAD:NBITS]",
+                   help="mark every finished waveform on the device with the pattern of the integer KEY, optionally carrying the NBITS (up to 16) "
+                        "low bits of PAYLOAD (ev_watermark: 1 dB, unmeasured; nobody has listened to it and it is no defence against removal); "
+                        "tools/watermark_detect.py FILE.wav --key KEY finds it again; default: off")
 
 
 def add_delivery_arguments(p: argparse.ArgumentParser):
@@ -275,6 +286,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="remove the vocoder's stationary bias on the device before the other output stages: STRENGTH times the magnitude spectrum of "
                         "its answer to an all-zero mel is subtracted from every STFT cell (e.g. 0.01, an unmeasured starting value); default: off")
     add_stretch_argument(p)
+    add_watermark_argument(p)
     add_delivery_arguments(p)
     return p
 

@@ -1,14 +1,15 @@
-"""The output chain of EVEngine.synthesize / synthesize_long: denoise -> stretch -> loudness -> limiter -> delivery -> FLAC, as one plan and one
-runner.
+"""The output chain of EVEngine.synthesize / synthesize_long: denoise -> stretch -> watermark -> loudness -> limiter -> delivery -> FLAC, as one
+plan and one runner.
 
-``resolve`` turns the public arguments (``denoise=``, ``stretch=``, ``loudness=``, ``limiter=``, ``delivery=``, ``flac=``) into a ChainPlan and
+``resolve`` turns the public arguments (``denoise=``, ``stretch=``, ``watermark=``, ``loudness=``, ``limiter=``, ``delivery=``, ``flac=``) into a ChainPlan and
 makes every argument check, before any library call (what only the lengths can decide -- a stretch ratio outside [0.5, 2] -- is checked by the
 host rule once the source's lengths are known, still before ev_stretch is called).  ``run`` takes the packed fp32 device waveform of the SOURCE -- the synthesis, or ev_stitch in the long
 form -- through the stages of the plan and returns a ChainOutput.  The rules, which hold for every combination:
 
 Order.  ev_denoise first (on the source's waveform, so that the later stages measure and shape the audio that is delivered; its output has whole
-hops, so it may shorten a segment), then ev_stretch (it changes every length; the stages after it see the new ones), then ev_loudness, then
-ev_limit: the WAVEFORM stages, each reading the device fp32 output of the one before.
+hops, so it may shorten a segment), then ev_stretch (it changes every length; the stages after it see the new ones), then ev_watermark (a stretch would move its
+tiles, so it runs after it; loudness and the limiter then measure and bound what is delivered, and a gain does not change the detector's
+signs; its output has whole hops, like ev_denoise's), then ev_loudness, then ev_limit: the WAVEFORM stages, each reading the device fp32 output of the one before.
 ev_deliver follows them and ev_flac comes last.  loudness followed by a limiter is a MEASURE-only stage: ev_loudness runs with a NaN target and
 writes no audio, the pre-gain to the target is worked out on the host (emotivoice_amd.limiter.pre_gain: the gain rule without its sample-peak
 step) and goes into ev_limit, which scales and limits in its one pass; the ``loudness`` figures then hold the measurement and, as ``gain`` /
@@ -28,7 +29,8 @@ call each.
 
 The figures of every stage sit in ``ChainOutput.figures`` under the stage's argument name; ``denoise`` holds lens_out / offsets and, with
 ``report=True``, removed_db: the removed energy relative to the input, from ev_compare on the two device waveforms; ``stretch`` holds lens_in,
-lens_out, offsets, speed (lens_in / lens_out), frames, edge_frames and sum_dist."""
+lens_out, offsets, speed (lens_in / lens_out), frames, edge_frames and sum_dist; ``watermark`` holds lens_out, offsets, key, payload, nbits and
+strength_db."""
 from __future__ import annotations
 
 import dataclasses
@@ -44,6 +46,7 @@ from .flac import FlacConfig
 from .limiter import LimiterConfig, as_config as limiter_config, pre_gain
 from .loudness import LoudnessConfig, as_config as loudness_config
 from .stretch import StretchConfig, stretch_config
+from .watermark import WatermarkConfig, watermark_config
 
 AUDIO_KEYS = ("wav", "wav_list", "wav_i16", "wav_i16_list")      # what ``*_to_numpy`` calls the audio of a waveform stage
 
@@ -60,21 +63,22 @@ class ChainPlan:
     flac: object = None
     flac_config: Optional[FlacConfig] = None
     stretch: Optional[StretchConfig] = None
+    watermark: Optional[WatermarkConfig] = None
 
     @property
     def staged(self) -> bool:
         """The audio is a stage's: the source makes no int16 itself and its waveform stays on the device."""
-        return not (self.denoise is None and self.stretch is None and self.loudness is None and self.limiter is None and self.delivery is None)
+        return not (self.denoise is None and self.stretch is None and self.watermark is None and self.loudness is None and self.limiter is None and self.delivery is None)
 
     def waveform_stages(self) -> list:
         """(stage, config) in the order they run; loudness in front of a limiter is "measure"."""
-        stages = (("denoise", self.denoise), ("stretch", self.stretch), ("measure" if self.limiter is not None else "loudness", self.loudness),
+        stages = (("denoise", self.denoise), ("stretch", self.stretch), ("watermark", self.watermark), ("measure" if self.limiter is not None else "loudness", self.loudness),
                   ("limiter", self.limiter))
         return [(name, cfg) for name, cfg in stages if cfg is not None]
 
 
 def resolve(sample_rate: int, segments: Optional[int], denoise=None, loudness=None, limiter=None, delivery=None, flac=None, vocoder: bool = True,
-            flac_convert: Optional[str] = None, stretch=None) -> ChainPlan:
+            flac_convert: Optional[str] = None, stretch=None, watermark=None) -> ChainPlan:
     """The public stage arguments -> a ChainPlan, or ValueError.  sample_rate: the engine's; segments: how many a per-segment ``flac`` mask must
     have (None: ``flac`` is a switch, any true value selects every segment); flac_convert: overrides the ``convert`` of a given FlacConfig."""
     sr = int(sample_rate)
@@ -86,7 +90,8 @@ def resolve(sample_rate: int, segments: Optional[int], denoise=None, loudness=No
         sel = np.asarray(flac, bool)
         if sel.shape != (segments,):
             raise ValueError("flac: True or one entry per utterance (%d), got shape %s" % (segments, sel.shape))
-    for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery), ("denoise", denoise), ("stretch", stretch)):
+    for name, given in (("flac", sel), ("limiter", limiter), ("loudness", loudness), ("delivery", delivery), ("denoise", denoise), ("stretch", stretch),
+                        ("watermark", watermark)):
         if given is not None and not vocoder:
             raise ValueError("%s needs the vocoder's waveform" % name)
     lc = None if loudness is None else loudness_config(loudness, sr)
@@ -96,19 +101,22 @@ def resolve(sample_rate: int, segments: Optional[int], denoise=None, loudness=No
     tc = stretch_config(stretch, sr)
     if tc is not None and segments is not None:
         tc.per_segment(segments, sr)      # one entry per segment, at most one of speed / seconds / samples each
+    wc = watermark_config(watermark, sr)
+    if wc is not None and segments is not None:
+        wc.per_segment(segments)      # one payload, length and strength per segment
     if dc is not None and sel is not None and dc.encoding != "s16":
         raise ValueError("flac needs delivery's encoding 's16', not %r" % dc.encoding)
     fc = None
     if sel is not None:
         kw = dict(sample_rate=sr if dc is None else int(dc.sample_rate), **({} if flac_convert is None else dict(convert=flac_convert)))
         fc = dataclasses.replace(flac, **kw).validate() if isinstance(flac, FlacConfig) else FlacConfig(**kw)
-    return ChainPlan(sr, nc, lc, mc, dc, sel, fc, tc)
+    return ChainPlan(sr, nc, lc, mc, dc, sel, fc, tc, wc)
 
 
 @dataclasses.dataclass
 class ChainOutput:
     audio: Dict[str, object]                  # the last stage's, under AUDIO_KEYS; delivered: delivered_list, delivered_rate, delivery
-    figures: Dict[str, Dict[str, object]]     # "denoise" / "stretch" / "loudness" / "limiter" -> that stage's host figures
+    figures: Dict[str, Dict[str, object]]     # "denoise" / "stretch" / "watermark" / "loudness" / "limiter" -> that stage's host figures
     last: object = None                       # the result struct of the last waveform stage, whose int16 FLAC reads (None: the source's)
     delivered: object = None                  # the ev_deliver_result, which FLAC reads instead
     flac_list: Optional[List[Optional[bytes]]] = None
@@ -184,6 +192,12 @@ def run(eng, plan: ChainPlan, wav_ptr: int, lens, want_int16: bool = False, int1
             got = figures["stretch"] = eng.stretch_to_numpy(last, **copy)
             got["lens_in"], got["speed"] = lens_in, lens_in / got["lens_out"]
             wav_ptr, lens = last.wav, got["lens_out"]      # the later stages read the new lengths
+        elif stage == "watermark":
+            last = eng.watermark_raw(B, wav_ptr, False, lens, cfg, dev)
+            got = figures["watermark"] = eng.watermark_to_numpy(last, **copy)
+            payloads, nbits, strengths = cfg.per_segment(B)
+            got.update(key=int(cfg.key), payload=payloads, nbits=nbits, strength_db=strengths)
+            wav_ptr, lens = last.wav, got["lens_out"]      # whole hops: the mark may shorten a segment, as denoise may
         elif stage == "measure":      # no audio out: the limiter reads what this stage read
             res = eng.loudness_raw(B, wav_ptr, False, lens, dataclasses.replace(cfg, target_lufs=float("nan")), dev)
             got = figures["loudness"] = eng.loudness_to_numpy(res, **copy)

@@ -310,35 +310,38 @@ def _resolve(future: Future, result=None, exception: Optional[BaseException] = N
         pass
 
 
-def _chain_settings(loudness, limiter, delivery, denoise, flac=None):
-    """The shared part of the engine_*_synth_fn factories.  ``loudness``, ``limiter``, ``delivery`` and ``denoise`` are what EVEngine.synthesize takes
+def _chain_settings(loudness, limiter, delivery, denoise, flac=None, watermark=None):
+    """The shared part of the engine_*_synth_fn factories.  ``loudness``, ``limiter``, ``delivery``, ``denoise`` and ``watermark`` are what EVEngine.synthesize takes
     (emotivoice_amd/output_chain.py): service-level settings, not request fields, so that a batch stays homogeneous and the request schema stays
-    the reference's (``delivery`` is to be given to the DynamicBatcher as well).  delivery, denoise and ``flac`` (a FlacConfig or True: the
+    the reference's (``delivery`` is to be given to the DynamicBatcher as well).  delivery, denoise, watermark and ``flac`` (a FlacConfig or True: the
     service encodes FLAC) are checked here, when the service is built.  -> (the keywords for synthesize: the settings that are not None -- all
     None: synthesize is called exactly as before; the key of its result that holds the audio; what turns an utterance of it into what the
     batcher resolves a Future with)."""
     from .output_chain import resolve
-    plan = resolve(16000, None, denoise=denoise, delivery=delivery, flac=flac)
-    kw = {k: v for k, v in (("loudness", loudness), ("limiter", limiter), ("denoise", plan.denoise), ("delivery", plan.delivery)) if v is not None}
+    plan = resolve(16000, None, denoise=denoise, delivery=delivery, flac=flac, watermark=watermark)
+    kw = {k: v for k, v in (("loudness", loudness), ("limiter", limiter), ("denoise", plan.denoise), ("delivery", plan.delivery),
+                            ("watermark", plan.watermark)) if v is not None}
     return (kw, "wav_list", lambda w: w) if plan.delivery is None else (kw, "delivered_list", lambda w: w.tobytes())
 
 
-def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
+def engine_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None, watermark=None) -> Callable[[List[dict], float], Sequence[np.ndarray]]:
     """``synth_fn`` of a DynamicBatcher for an EVEngine.  ``loudness``: every utterance normalised on the device (ev_loudness); ``limiter``: its
     true peak held at a ceiling (ev_limit); ``delivery``: every utterance converted to the client's rate and encoding on the device (ev_deliver)
-    and returned as ``bytes``; ``denoise``: the vocoder's stationary bias removed from every utterance on the device (ev_denoise), first in the chain."""
-    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise)
+    and returned as ``bytes``; ``denoise``: the vocoder's stationary bias removed from every utterance on the device (ev_denoise), first in the chain;
+    ``watermark``: every utterance marked on the device with the service's key (ev_watermark, before ev_loudness; a key, 'KEY[:PAYLOAD:NBITS]' or
+    an emotivoice_amd.watermark.WatermarkConfig with one payload, length and strength for every utterance)."""
+    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise, watermark=watermark)
     return lambda utts, alpha: [conv(w) for w in engine.synthesize(utts, alpha=alpha, **kw)[key]]
 
 
-def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
+def engine_prosody_synth_fn(engine, loudness=None, limiter=None, delivery=None, denoise=None, watermark=None) -> Callable[[List[dict], List[Prosody]], Sequence[np.ndarray]]:
     """``synth_fn`` of a ``mixed_prosody=True`` DynamicBatcher for an EVEngine: one ev_synthesize_prosody call per batch.  ``loudness``,
-    ``limiter``, ``delivery`` and ``denoise``: as ``engine_synth_fn``."""
-    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise)
+    ``limiter``, ``delivery``, ``denoise`` and ``watermark``: as ``engine_synth_fn``."""
+    kw, key, conv = _chain_settings(loudness, limiter, delivery, denoise, watermark=watermark)
     return lambda utts, prosodies: [conv(w) for w in engine.synthesize(utts, prosody=prosodies, **kw)[key]]
 
 
-def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None, denoise=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
+def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, delivery=None, denoise=None, watermark=None) -> Callable[[List[dict], object, List[bool]], Sequence[object]]:
     """``flac_synth_fn`` of a DynamicBatcher for an EVEngine: one synthesize call per batch; the utterances ``mask`` selects are encoded on the
     device (ev_flac, from the fp32 waveform with the wrapping conversion) and come back as ``bytes``, the others as float waveforms.  The
     second argument is the batch's alpha, or with ``mixed_prosody=True`` its list of Prosody.  ``loudness``: as ``engine_synth_fn``; the
@@ -346,10 +349,11 @@ def engine_flac_synth_fn(engine, loudness=None, limiter=None, flac_config=None, 
     ``flac_config``: an emotivoice_amd.flac.FlacConfig for every stream of this service (LPC order, precision, MD5, block size), like ``loudness``
     a service-level setting; a batch is then encoded whole and the utterances outside ``mask`` still come back as waveforms.
     ``delivery``: as ``engine_synth_fn``, with the encoding "s16": the streams carry ev_deliver's int16 at the delivered rate, the other
-    utterances come back as its ``bytes``.  ``denoise``: as ``engine_synth_fn``; the streams carry the denoised audio."""
+    utterances come back as its ``bytes``.  ``denoise``: as ``engine_synth_fn``; the streams carry the denoised audio.  ``watermark``: as ``engine_synth_fn``;
+    the streams carry the marked audio."""
     if flac_config is not None:
         flac_config.validate()
-    lkw, key, conv = _chain_settings(loudness, limiter, delivery, denoise, flac=flac_config or True)
+    lkw, key, conv = _chain_settings(loudness, limiter, delivery, denoise, flac=flac_config or True, watermark=watermark)
 
     def fn(utts, control, mask):
         kw = dict(prosody=control) if isinstance(control, (list, tuple)) else dict(alpha=control)

@@ -1045,6 +1045,106 @@ typedef struct ev_stretch_result {
 int ev_stretch(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const int64_t* lens_out, const ev_stretch_config* cfg,
                uint32_t flags, ev_stretch_result* out);
 
+/* Audio watermark (ev_watermark, ev_watermark_detect): a keyed, machine-detectable mark in a finished waveform, so that the operator of the
+ * engine can answer "did this audio come from us?".  The embed runs third in the output chain, after ev_stretch (which would move the tiles) and
+ * before ev_loudness and ev_limit (a gain does not change the detector's signs).  It is a spread-spectrum mark on the STFT magnitude: every cell
+ * of a band is raised or lowered by a fraction of a dB according to a pseudo-random chip, and the detector correlates the sign of the local
+ * contrast of the log band energies with the chips.  Every constant below is an UNMEASURED starting value for 16 kHz speech.  Not verified:
+ * nobody has listened to it and no imperceptibility is claimed; it was compared with no other watermark (AudioSeal, WavMark: none installed); it
+ * was not tested against mp3, Opus or acoustic re-recording; the hash is not a proven source of independent bits and nothing here is a defence
+ * against someone who wants the mark gone -- no security claim.
+ * Shapes: n_fft = EV_WATERMARK_NFFT, hop = EV_WATERMARK_HOP, periodic hann: ev_denoise's frames, padding, limits and frame count at those values.
+ *   Pattern (host, ev_watermark_pattern).  Chip i = 48 u + v, tile u < EV_WATERMARK_PERIOD, band v < EV_WATERMARK_BANDS.  h = mix(key, i) with
+ *     hash(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 on uint32 and mix(key, c) = hash(hash((uint32)c +
+ *     hash(key ^ (uint32)(c >> 32))) ^ key) -- ev_deliver's dither hash.  sign = (h & 1) ? +1 : -1; role = (h >> 1) mod (2 nbits).  A role <
+ *     nbits carries that payload bit: its sign is flipped where the bit is 1.  Every other role is a pilot; with nbits = 0 every chip is.
+ *   Embed.
+ *   1, 2 ev_denoise's steps 1 and 2, word for word: input, reflect padding, T = L / hop + 1 frames, basis, split-precision GEMM.
+ *   3 Gain.  Band v holds the bins EV_WATERMARK_BAND0 + 4 v .. + 3.  mag = sqrtf(Re^2 + Im^2); for a cell (t, k) of band v, u = (t / 8) mod 16 and
+ *     g = a where chip 48 u + v has sign +1, float32(1 / a) (one fp32 division) where it has -1; g = 1 outside the bands; mag == 0 (and a NaN)
+ *     gives a zero cell.  a = float32(10^(strength_db / 20)), formed on the host in fp64.  The cell becomes g Re, g Im in ev_denoise's scratch.
+ *   4 .. 7 ev_denoise's steps 4 to 7, word for word: inverse GEMM, envelope, trim to hop (L / hop) samples, int16 rule.
+ *   Consequences: strength_db = 0 gives ev_denoise's output at strength 0 bit for bit; no atomics and nothing carried between blocks, so a segment
+ *   gives the same bits alone and in any batch.
+ *   Detect.
+ *   D1 Steps 1 and 2 again.  m2[t][k] = (Re Re) + (Im Im): two rounded fp32 products and one rounded sum, never fused.
+ *   D2 Band energy E[t][v] = (m2[k0] + m2[k0 + 1]) + (m2[k0 + 2] + m2[k0 + 3]), k0 = EV_WATERMARK_BAND0 + 4 v, rounded fp32 sums in that order.
+ *   D3 Floor.  M[t] = the largest m2[t][k] over ALL n_fft / 2 + 1 bins (carried through the GEMM's bin tiles before any band is written);
+ *     E = max(E, M * 2^-24).
+ *   D4 q[t][v] = bits(E) >> 17 as an integer: the float's exponent and its top six mantissa bits, a monotone piecewise-linear log2 in steps of
+ *     1 / 64 octave and an exact function of E.
+ *   D5 For every offset s in 0 .. EV_WATERMARK_OFFSETS - 1: tiles start at the frames f >= 0 with (f - s) mod 8 == 0 and f + 8 <= T (whole
+ *     tiles only); tile j (f = s mod 8 + 8 j) carries the chips of u = (j - s / 8) mod 16.  D[j][v] = the sum of q over the tile's 8 frames.
+ *     X = 2 D[j] - D[j - 1] - D[j + 1] for the interior tiles.  C(s) = the sum over the pilot chips of sign(chip) sign(X), n(s) = the count of
+ *     pilot chips with X != 0.
+ *   D6 The reported offset maximises C / sqrt(n) over the offsets with C > 0, compared exactly in int64 as C_a^2 n_b against C_b^2 n_a; a tie goes
+ *     to the smaller offset; without any C > 0 the offset is 0.  At that offset C_j, n_j are the same sums over the chips of payload bit j, with
+ *     the signs of payload 0.
+ *   D7 The device returns integers only.  The host forms z = C / sqrt(n) in fp64 (0 for n = 0), present = z >= threshold, bit j = C_j < 0.
+ *   Given q everything is integer: exact in any summation order.
+ *   Threshold: derived, not measured.  For fixed audio and independent +-1 chips Hoeffding gives P(z >= t) <= exp(-t^2 / 2); over 128 offsets
+ *   t = 6.25 bounds the false-alarm rate per segment and key at 128 exp(-19.5) < 5e-7 -- if the hash's bits were independent, which is not proven. */
+#define EV_WATERMARK_NFFT    1024
+#define EV_WATERMARK_HOP     256
+#define EV_WATERMARK_BAND0   20        /* first bin of band 0: 312.5 Hz at 16 kHz */
+#define EV_WATERMARK_BANDS   48        /* of 4 bins each: up to 3.3125 kHz, inside the telephone band */
+#define EV_WATERMARK_TILE    8         /* frames per time tile */
+#define EV_WATERMARK_PERIOD  16        /* tiles per pattern period: 128 frames, 2.048 s */
+#define EV_WATERMARK_CHIPS   768       /* PERIOD * BANDS */
+#define EV_WATERMARK_OFFSETS 128       /* TILE * PERIOD */
+#define EV_WATERMARK_MAX_BITS 16
+#define EV_WATERMARK_MAX_DB  6.0f      /* strength_db in [0, 6]: the scratch's fp16 range then holds for |x| <= 50 */
+#define EV_WATERMARK_THRESHOLD 6.25
+typedef struct ev_watermark_config {
+    uint32_t struct_size;          /* sizeof(ev_watermark_config); any other value is rejected */
+    uint32_t key;                  /* per call */
+    int32_t  want_i16;             /* also write the clamped int16 waveform */
+    int32_t  nbits;                /* 0 .. EV_WATERMARK_MAX_BITS: the payload length where ev_watermark is given no nbits */
+    uint32_t payload;              /* < 2^nbits: likewise */
+    float    strength_db;          /* in [0, EV_WATERMARK_MAX_DB]: likewise */
+} ev_watermark_config;
+void ev_default_watermark_config(ev_watermark_config* cfg);      /* key 0, no int16, nbits 0, payload 0, 1.0 dB */
+/* Host only: the EV_WATERMARK_CHIPS signs (+1 / -1) of the pattern, payload flips applied.  0, or -1 for a NULL signs, nbits outside
+ * [0, EV_WATERMARK_MAX_BITS] or payload >= 2^nbits. */
+int ev_watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* signs);
+
+typedef struct ev_watermark_result {
+    uint32_t struct_size;          /* sizeof(ev_watermark_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int64_t  total;                /* offsets[batch] */
+    const float*   wav;            /* DEVICE, (total,) segments back to back: what ev_loudness / ev_limit / ev_deliver / ev_flac take */
+    const int16_t* wav_i16;        /* DEVICE, the same layout; NULL without want_i16 */
+    const int64_t* lens_out;       /* (batch,) HOST: hop * (lens[b] / hop) */
+    const int64_t* offsets;        /* (batch+1,) HOST */
+} ev_watermark_result;
+/* wav / wav_is_i16 / lens / EV_FLAG_DEVICE_INPUTS as ev_denoise.  cfg NULL = ev_default_watermark_config.  payloads (uint32), nbits (int32) and
+ * strengths_db (float): HOST arrays (B,), or NULL = the config's value for every segment.  Needs no setup call and no weights (the tables are
+ * built on the first call).  Rejected before anything is launched (message naming the field or segment; the previous result stays valid): a
+ * NULL h, wav, lens or out, a wrong struct_size, B outside [1, 65535], lens[b] < n_fft / 2 + 1, a segment of more than EV_ALIGN_MAX_FRAMES
+ * frames, nbits outside [0, EV_WATERMARK_MAX_BITS], a payload >= 2^nbits, a strength outside [0, EV_WATERMARK_MAX_DB] or not finite.  The
+ * result lives in a workspace of its own and stays valid until the next ev_watermark or ev_destroy -- the contract of ev_limit_result. */
+int ev_watermark(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const ev_watermark_config* cfg, const uint32_t* payloads,
+                 const int32_t* nbits, const float* strengths_db, uint32_t flags, ev_watermark_result* out);
+
+typedef struct ev_watermark_detect_result {
+    uint32_t struct_size;          /* sizeof(ev_watermark_detect_result), set by the caller; any other value is rejected */
+    int32_t  batch;
+    int32_t  nbits;                /* the call's */
+    int32_t  reserved;
+    const int32_t* offset;         /* (batch,) HOST: D6 */
+    const int32_t* C;              /* (batch,) HOST */
+    const int32_t* n;              /* (batch,) HOST */
+    const int32_t* bit_C;          /* (batch, EV_WATERMARK_MAX_BITS) HOST; zero from nbits on */
+    const int32_t* bit_n;          /* (batch, EV_WATERMARK_MAX_BITS) HOST */
+    const int32_t* frames;         /* (batch,) HOST: T */
+    const int64_t* frame_offsets;  /* (batch+1,) HOST: segment b's rows of q */
+    const int32_t* q;              /* DEVICE, (frame_offsets[batch], EV_WATERMARK_BANDS): D4 */
+} ev_watermark_detect_result;
+/* Inputs as ev_watermark; key and nbits are per call.  Rejected as ev_watermark rejects.  The result stays valid until the next
+ * ev_watermark_detect or ev_destroy. */
+int ev_watermark_detect(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, uint32_t key, int nbits, uint32_t flags,
+                        ev_watermark_detect_result* out);
+
 /* Objective scoring (ev_score): how close a signal a (under test: a synthesised utterance) is to a signal b (the yardstick: a recording of the
  * same sentence) when the two differ in length and timing -- mel-cepstral distortion, F0 error in cents and the voiced / unvoiced error rate
  * along a dynamic-time-warping path, on the device.  ev_compare is the measure for signals of equal length; with EV_SCORE_LINEAR the same scores
