@@ -118,8 +118,9 @@ __global__ __launch_bounds__(256) void stft_gain_kernel(const StftGainParams p) 
                     continue;
                 }
                 if (2 * bin >= p.k_pad) continue;
-                const float gn = m > 0.f ? fmaxf(m - sb, 0.f) / m : 0.f;      // mag == 0 (and a NaN): the cell is zero
-                const float vr = gn * re, vi = gn * im;
+                const bool live = m > 0.f;      // mag == 0 (and a NaN): the cell is zero -- selected, since 0 * NaN is NaN
+                const float gn = live ? fmaxf(m - sb, 0.f) / m : 0.f;
+                const float vr = live ? gn * re : 0.f, vi = live ? gn * im : 0.f;
                 stft_store_cell(p.spec_hi, p.spec_lo, (size_t)row * p.k_pad + 2 * bin, vr, vi);
             }
     }

@@ -91,8 +91,8 @@ __global__ __launch_bounds__(256) void wm_embed_kernel(const WmEmbedParams p) {
                 const float m = sqrtf(re * re + im * im);
                 const int t = t0 + mh * 32 + a * 16 + g * 4 + r;
                 if (t >= T || 2 * bin >= WM_KPAD) continue;
-                const float gn = m > 0.f ? gw : 0.f;      // mag == 0 (and a NaN): the cell is zero, as ev_denoise has it
-                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)(sq.frm_off + t) * WM_KPAD + 2 * bin, gn * re, gn * im);
+                const bool live = m > 0.f;      // mag == 0 (and a NaN): the cell is zero, selected as ev_denoise selects it (0 * NaN is NaN)
+                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)(sq.frm_off + t) * WM_KPAD + 2 * bin, live ? gw * re : 0.f, live ? gw * im : 0.f);
             }
         }
     }

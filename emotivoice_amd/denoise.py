@@ -27,6 +27,7 @@ class DenoiseConfig:
     bias: Optional[np.ndarray] = None      # (n_fft / 2 + 1,) magnitudes >= 0, or None: the engine measures its own vocoder's
     want_int16: bool = False               # also the int16 output, clamped (ev_loudness' rule), never wrapped
     report: bool = False                   # adds, per utterance, the removed energy in dB relative to the input (ev_compare)
+    window: Optional[np.ndarray] = None    # (n_fft,) float32 analysis / synthesis window, or None: periodic hann
 
     def validate(self) -> "DenoiseConfig":
         s = self.strength
@@ -46,12 +47,20 @@ class DenoiseConfig:
             b = np.asarray(self.bias)
             if b.shape != (n_fft // 2 + 1,) or not np.all(np.isfinite(b)) or np.any(b < 0):
                 raise ValueError("bias must hold n_fft / 2 + 1 = %d finite magnitudes >= 0" % (n_fft // 2 + 1))
+        if self.window is not None:
+            w = np.asarray(self.window)
+            if w.shape != (n_fft,) or not np.all(np.isfinite(w)):
+                raise ValueError("window must hold n_fft = %d finite values" % n_fft)
         return self
+
+    def tables_key(self):
+        """What the vocoder's measured bias depends on besides the weights: the frame shape and the window."""
+        return (int(self.n_fft), int(self.hop), None if self.window is None else np.ascontiguousarray(self.window, np.float32).tobytes())
 
     def key(self):
         """What a setup depends on: a changed key means ev_denoise_setup again."""
         b = None if self.bias is None else np.ascontiguousarray(self.bias, np.float32).tobytes()
-        return (int(self.n_fft), int(self.hop), float(np.float32(self.strength)), bool(self.want_int16), b)
+        return self.tables_key() + (float(np.float32(self.strength)), bool(self.want_int16), b)
 
 
 def denoise_config(x, sr: int = 16000) -> Optional[DenoiseConfig]:

@@ -307,7 +307,7 @@ class EVEngine(EVAudio):
     def _denoise_ready(self, denoise):
         """Before a synthesis whose waveform ev_denoise will read: measure the vocoder's own bias now if the config asks for it and none is
         kept, because measuring runs the vocoder and would replace that waveform."""
-        if denoise is not None and denoise.bias is None and (int(denoise.n_fft), int(denoise.hop)) not in self._denoise_own_bias:
+        if denoise is not None and denoise.bias is None and denoise.tables_key() not in self._denoise_own_bias:
             self.denoise_setup(denoise)
 
     def synthesize(self, utts: Sequence[dict], alpha: float = 1.0, want_int16: bool = False, vocoder: bool = True,

@@ -441,7 +441,9 @@ class EVAudio:
         c = _ffi.ev_denoise_config()
         self._lib.ev_default_denoise_config(C.byref(c))
         c.n_fft, c.hop, c.strength, c.want_i16 = int(dc.n_fft), int(dc.hop), float(dc.strength), 1 if dc.want_int16 else 0
-        own, shape = self._denoise_own_bias, (int(dc.n_fft), int(dc.hop))      # the bias measured on the loaded weights: measured once, then passed back
+        win = None if dc.window is None else np.ascontiguousarray(dc.window, np.float32)      # copied by the library; kept alive across the call
+        c.window = win.ctypes.data if win is not None else None
+        own, shape = self._denoise_own_bias, dc.tables_key()      # the bias measured on the loaded weights: measured once, then passed back
         bias = own.get(shape) if dc.bias is None else np.ascontiguousarray(dc.bias, np.float32)
         self._check(self._lib.ev_denoise_setup(self._h, C.byref(c), _ptr(bias) if bias is not None else None))
         self.denoise_config, self._setup_keys["denoise"] = dc, dc.key()

@@ -213,7 +213,10 @@ int ev_op_align_mas(const float* log_p, int B, const int32_t* tokens, const int3
  * T_b = wav_lens[b] / hop + 1, packed in utterance order), energy (sum_b T_b,) and, unless NULL, mag (sum_b T_b, n_fft / 2 + 1); semantics as ev_features
  * (include/evhip.h).  wav_lens, mel_basis (n_mels, n_fft / 2 + 1) and window (n_fft,) or NULL are HOST arrays: the call packs the basis planes, waits for
  * the stream and frees them.  -2 for what the kernel would mishandle: n_fft not a multiple of 128 or above 2048, hop not a multiple of 8 or above n_fft,
- * 63 hop + n_fft > 24576, n_mels outside [1, 128], wav_lens[b] < n_fft / 2 + 1, T_b > 16384, B outside [1, 65535]. */
+ * 63 hop + n_fft > 24576, n_mels outside [1, 128], wav_lens[b] < n_fft / 2 + 1, T_b > 16384, B outside [1, 65535].
+ * Held on the device (tests/test_gpu_stft_shapes.py) at 128 / 8, 128 / 128, 384 / 48, 640 / 320, 2048 / 352 (n_mels 128 and 80) and 2048 / 256 besides the
+ * default 1024 / 256, with the hann window and an asymmetric one, to 4 x the error of a plain float32 evaluation (floor 2^-22); a non-finite sample
+ * stays inside its utterance (no rule is stated for the utterance itself). */
 int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* mel_basis, const float* window, int n_fft, int hop,
                    int n_mels, float mel_clip, float energy_floor, float energy_mean, float energy_std, float* mel, float* energy, float* mag,
                    void* hip_stream);
@@ -224,7 +227,11 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
  * zero.  With mag not NULL it writes the fp32 magnitudes (sum_b T_b, n_fft / 2 + 1) instead and reads neither bias nor strengths nor the planes.
  * ev_op_istft: steps 4-7, the planes of T_b = frames[b] frames per utterance -> out (sum_b hop (T_b - 1),) fp32 and, unless NULL, out_i16.  wav_lens,
  * frames and window (n_fft,) or NULL are HOST arrays: the calls pack their tables, wait for the stream and free them.  -2 for what a kernel would
- * mishandle: a shape outside ev_denoise's limits, wav_lens[b] < n_fft / 2 + 1, T_b outside [1, 16384], B outside [1, 65535]. */
+ * mishandle: a shape outside ev_denoise's limits, wav_lens[b] < n_fft / 2 + 1, T_b outside [1, 16384], B outside [1, 65535].
+ * Held on the device (tests/test_gpu_stft_shapes.py): both modes of ev_op_stft_gain and ev_op_istft at R = n_fft / hop = 1 (128 / 128), 2 (640 / 320), 4 and
+ * 8 (384 / 48, 2048 / 256), T_b < R and a second chunk tile included, with the hann window, an asymmetric window and one with a run of zeros; the
+ * rejections of 128 / 8 (R = 16) and 2048 / 352 (-2, nothing written); peaks of 2^-12 and 8.0 and +-2 LSB of int16 at the same relative bars; a
+ * NaN or an infinity in an utterance gives zero cells in the frames that hold it (step 3) and leaves every other frame and utterance alone. */
 int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_lens, const float* window, int n_fft, int hop, const float* bias,
                     const float* strengths, void* spec_hi, void* spec_lo, float* mag, void* hip_stream);
 int ev_op_istft(const void* spec_hi, const void* spec_lo, int B, const int32_t* frames, const float* window, int n_fft, int hop, float* out,

@@ -90,12 +90,15 @@ def stft64(wav, n_fft=1024, hop=256, window=None):
 
 
 def gain64(re, im, bias, strength):
-    """Step 3: (g re, g im, mag) float64; bias (n_bins,) and strength as the float32 values the device holds."""
-    mag = np.sqrt(re * re + im * im)
+    """Step 3: (g re, g im, mag) float64; bias (n_bins,) and strength as the float32 values the device holds.  A cell whose mag is not greater
+    than 0 -- zero, or a NaN -- is a zero cell: selected, not multiplied by 0 (0 * NaN is NaN)."""
+    with np.errstate(invalid="ignore"):
+        mag = np.sqrt(re * re + im * im)
+        live = mag > 0
     sb = float(np.float32(strength)) * np.asarray(bias, np.float32).astype(np.float64)[None, :]
     with np.errstate(divide="ignore", invalid="ignore"):
-        g = np.where(mag > 0, np.maximum(mag - sb, 0.0) / np.where(mag > 0, mag, 1.0), 0.0)
-    return g * re, g * im, mag
+        g = np.where(live, np.maximum(mag - sb, 0.0) / np.where(live, mag, 1.0), 0.0)
+        return np.where(live, g * re, 0.0), np.where(live, g * im, 0.0), mag
 
 
 def istft64(gre, gim, n_fft=1024, hop=256, window=None, all_two=False):

@@ -10,7 +10,10 @@ against the float64 oracle (tests/denoise_oracle.py).  The GPU test's bar is 4 x
 Signal: the tests' synthetic voiced signal (24 harmonics of 120 Hz under a 3 Hz envelope) plus a 3.1 kHz tone and a noise floor; the bias is the
 magnitude of frame 0 of the reference's transform of that tone and noise alone, 88 x 256 samples long.
 
-Usage:  python tests/golden/make_golden_denoise.py
+dn_shape_<n_fft>_<hop>.npz tie the oracle to the same class at the other frame shapes the GPU tests run (SHAPES below): the reference takes named
+windows only, so these are hann too.
+
+Usage:  python tests/golden/make_golden_denoise.py [--shapes]      (--shapes: the shape fixtures alone)
 """
 import os
 import sys
@@ -66,6 +69,35 @@ def save(name, wav, bias, strength, stft):
     return err
 
 
+SHAPES = ((384, 48), (640, 320), (128, 128))      # a non-power-of-two n_fft with R = 8, R = 2, R = 1: the shapes the GPU shape table adds
+
+
+def save_shape(n_fft, hop, STFT, window_sumsquare):
+    """dn_shape_<n_fft>_<hop>.npz: the reference's STFT class at another frame shape on a 2000-sample signal -- its transform's magnitudes, its
+    transform -> clamp -> inverse, its window_sumsquare -- and ref_err of that output against the float64 oracle at the same shape."""
+    stft = STFT(n_fft, hop, n_fft, "hann")
+    R = n_fft // hop
+    wav = signal(2000, 20 + n_fft // 128)
+    with torch.no_grad():
+        bias = stft.transform(torch.from_numpy(hum(88 * hop, 7).astype(np.float32)).unsqueeze(0))[0][0, :, 0].numpy().astype(np.float32).copy()
+        ref_mag = stft.transform(torch.from_numpy(wav).unsqueeze(0))[0].squeeze(0).t().contiguous().numpy().astype(np.float32)
+    ref, _ = reference_denoise(stft, wav, bias, 0.1)
+    y64 = do.denoise64(wav, bias, 0.1, n_fft, hop)
+    assert ref.size == y64.size == hop * (2000 // hop) and ref_mag.shape == (2000 // hop + 1, n_fft // 2 + 1)
+    err = do.peak_error(ref, y64)
+    envs = {"env_T%d" % T: window_sumsquare("hann", T, hop_length=hop, win_length=n_fft, n_fft=n_fft, dtype=np.float32) for T in sorted({1, 2, R, R + 1, 2 * R + 3})}
+    for key, ws in envs.items():
+        assert np.array_equal(ws, do.envelope_f32(int(key[5:]), n_fft, hop)), (n_fft, hop, key)
+    path = os.path.join(HERE, "denoise", "dn_shape_%d_%d.npz" % (n_fft, hop))
+    np.savez_compressed(path, wav=wav, bias=bias, strength=np.float32(0.1), n_fft=np.int64(n_fft), hop=np.int64(hop), ref_mag=ref_mag, ref_out=ref,
+                        ref_err=np.float64(err), **envs)
+    re, im = do.stft64(wav, n_fft, hop)
+    print("%-20s T %3d out %5d  E(ref) %.3e  E_mag(ref) %.3e  %d bytes"
+          % (os.path.basename(path)[:-4], ref_mag.shape[0], ref.size, err, fo.mag_error(ref_mag, np.sqrt(re * re + im * im)), os.path.getsize(path)))
+    assert os.path.getsize(path) < 100_000, path
+    return err
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -73,6 +105,11 @@ def main():
     sys.modules["librosa.util"].normalize = lambda x, norm=None, **kw: x if norm is None else (_ for _ in ()).throw(NotImplementedError("norm"))
     sys.path.insert(0, REF)
     from models.prompt_tts_modified.stft import STFT
+    if "--shapes" in sys.argv:      # the shape fixtures alone: the others keep their bytes
+        from models.prompt_tts_modified.audio_processing import window_sumsquare
+        for n_fft, hop in SHAPES:
+            save_shape(n_fft, hop, STFT, window_sumsquare)
+        return
     stft = STFT(1024, 256, 1024, "hann")
     os.makedirs(os.path.join(HERE, "denoise"), exist_ok=True)
     with torch.no_grad():
@@ -114,6 +151,8 @@ def main():
     np.savez_compressed(os.path.join(HERE, "denoise", "dn_envelope.npz"),
                         **{"T%d" % T: window_sumsquare("hann", T, hop_length=256, win_length=1024, n_fft=1024, dtype=np.float32) for T in (1, 3, 4, 9, 79)})
     print("largest E(ref) %.3e -> the bar is 4 x that = %.3e" % (max(errs), 4 * max(errs)))
+    for n_fft, hop in SHAPES:
+        save_shape(n_fft, hop, STFT, window_sumsquare)
 
 
 if __name__ == "__main__":

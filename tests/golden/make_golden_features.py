@@ -14,7 +14,10 @@ a seed whose case has one is skipped for the next.
 Cases: (a) the reference's own synthesis of a 48-phoneme utterance, (b) the same wav as int16, (c) a chirp at 0.99 full scale followed by 0.3 s
 of exact zeros and by 1e-4 noise, (d) L = 513 and an L that is not a multiple of 256.
 
-Usage:  python tests/golden/make_golden_features.py
+stft_<n_fft>_<hop>.npz tie the oracle to the same class built at the other frame shapes the GPU tests run (SHAPES below), with the hann window the
+reference's named windows allow.
+
+Usage:  python tests/golden/make_golden_features.py [--shapes]      (--shapes: the shape fixtures alone)
 """
 import os
 import sys
@@ -87,10 +90,41 @@ def save(name, wav, stft, extra=None):
     return mel, energy
 
 
+SHAPES = ((384, 48), (640, 320))      # the non-power-of-two frame shapes the GPU shape table adds
+
+
+def save_shape(n_fft, hop, TacotronSTFT):
+    """stft_<n_fft>_<hop>.npz: the reference's TacotronSTFT built at another frame shape, on a 2000-sample signal: mel, magnitudes, energy."""
+    stft = TacotronSTFT(n_fft, hop, n_fft, 80, 16000, 0.0, 8000.0)
+    rng = np.random.default_rng(1000 + n_fft)
+    t = np.arange(2000) / 16000.0
+    wav = (0.3 * np.sin(2 * np.pi * 310.0 * t) * (0.6 + 0.4 * np.sin(2 * np.pi * 9.0 * t)) + 0.02 * rng.standard_normal(2000)).astype(np.float32)
+    y = torch.from_numpy(wav).unsqueeze(0)
+    with torch.no_grad():
+        mel = stft.mel_spectrogram(y).squeeze(0).numpy()
+        mag = stft.stft_fn.transform(y)[0].squeeze(0).t().contiguous().numpy()
+    energy = np.sqrt(np.maximum((mag.astype(np.float32) ** 2).sum(axis=1, dtype=np.float32), np.float32(1e-10))).astype(np.float32)
+    T = 2000 // hop + 1
+    assert mel.shape == (80, T) and mag.shape == (T, n_fft // 2 + 1)
+    o = fo.features64(wav, mel_filterbank(16000, n_fft, 80, 0.0, 8000.0), n_fft=n_fft, hop=hop)
+    path = os.path.join(HERE, "features", "stft_%d_%d.npz" % (n_fft, hop))
+    np.savez_compressed(path, wav=wav, n_fft=np.int64(n_fft), hop=np.int64(hop), ref_mel=mel, ref_mag=mag, ref_energy=energy)
+    print("%-22s T %4d  E_mel(ref) %.3e  E_energy(ref) %.3e  E_mag(ref) %.3e  %d bytes"
+          % (os.path.basename(path)[:-4], T, fo.mel_error(mel, o["mel"]), fo.energy_error(energy, o["energy"]), fo.mag_error(mag, o["mag"]), os.path.getsize(path)))
+    assert os.path.getsize(path) < 100_000, path
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     stub_librosa()
+    if "--shapes" in sys.argv:      # the shape fixtures alone: the others keep their bytes
+        from make_golden import REF
+        sys.path.insert(0, REF)
+        from models.prompt_tts_modified.tacotron_stft import TacotronSTFT
+        for n_fft, hop in SHAPES:
+            save_shape(n_fft, hop, TacotronSTFT)
+        return
     gen = load_reference()
     from models.prompt_tts_modified.tacotron_stft import TacotronSTFT
     stft = TacotronSTFT(1024, 256, 1024, 80, 16000, 0.0, 8000.0)
@@ -138,6 +172,8 @@ def main():
     # (d) the shortest utterance and a length that is not a multiple of the hop
     save("feat_d_l513", (0.5 * rng.standard_normal(513)).clip(-1, 1).astype(np.float32), stft)
     save("feat_d_l20011", (0.3 * np.sin(2 * np.pi * 440.0 * np.arange(20011) / 16000.0) + 0.05 * rng.standard_normal(20011)).clip(-1, 1).astype(np.float32), stft)
+    for n_fft, hop in SHAPES:
+        save_shape(n_fft, hop, TacotronSTFT)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,7 @@ import pytest
 
 import denoise_oracle as do
 import fake_evhip as fk
+import features_oracle as fo
 from conftest import GOLDEN_DIR
 from emotivoice_amd import _ffi
 from emotivoice_amd.denoise import DEFAULT_STRENGTH, DenoiseConfig, denoise_config, out_len, removed_db
@@ -80,6 +81,77 @@ def test_envelope_table_is_the_references_window_sumsquare():
     t2 = do.envelope_table(512, 128)
     for T in (1, 2, 5, 11):
         assert np.array_equal(do.envelope_from_table(t2, T, 512, 128), do.envelope_f32(T, 512, 128))
+
+
+SHAPE_FIXTURES = sorted(glob.glob(os.path.join(DN_DIR, "dn_shape_*.npz")))
+
+
+def test_the_shape_fixtures_are_the_three_shapes():
+    assert [os.path.basename(p)[:-4] for p in SHAPE_FIXTURES] == ["dn_shape_128_128", "dn_shape_384_48", "dn_shape_640_320"]
+    assert all(os.path.getsize(p) < 100_000 and np.load(p)["wav"].size == 2000 for p in SHAPE_FIXTURES)
+
+
+@pytest.mark.parametrize("path", SHAPE_FIXTURES, ids=lambda p: os.path.basename(p)[:-4])
+def test_oracle_against_the_reference_at_other_shapes(path):
+    """The reference's STFT class built at 384 / 48 (R = 8), 640 / 320 (R = 2) and 128 / 128 (R = 1): its transform's magnitudes, its transform ->
+    clamp -> inverse and its window_sumsquare against the oracle at the same shape.  The float32 rounding REF_BOUND describes is that of the
+    overlap-added sum, before the division by the envelope; the division multiplies it by 1 / env.  For R >= 2 the envelope of the trimmed signal
+    stays near its mean and the plain error is inside the bound.  At R = 1 a lone hann^2 comes down to sin^4(pi / 128) = 3.6e-7 next to every chunk
+    edge, so there the bound is held on the error times env / max env, and the plain error (recorded: 1.6e-4) is the conditioning of that shape, which
+    the reference's float32 run shows like any other float32 run."""
+    g = dict(np.load(path))
+    n_fft, hop = int(g["n_fft"]), int(g["hop"])
+    T = 2000 // hop + 1
+    re, im = do.stft64(g["wav"], n_fft, hop)
+    assert g["ref_mag"].shape == re.shape == (T, n_fft // 2 + 1)
+    e_mag = fo.mag_error(g["ref_mag"], np.sqrt(re * re + im * im))
+    y64 = do.denoise64(g["wav"], g["bias"], float(g["strength"]), n_fft, hop)
+    assert y64.size == g["ref_out"].size == out_len(2000, hop) == hop * (T - 1)
+    e = do.peak_error(g["ref_out"], y64)
+    env = do.envelope_f32(T, n_fft, hop).astype(np.float64)[n_fft // 2:n_fft // 2 + y64.size]
+    e_sum = float((np.abs(g["ref_out"] - y64) * env / env.max()).max() / np.abs(y64).max())
+    print(os.path.basename(path), "E_mag(ref) %.3e E(ref) %.3e before the division %.3e" % (e_mag, e, e_sum))
+    assert e == pytest.approx(float(g["ref_err"]), rel=1e-6) and e_mag <= REF_BOUND and e_sum <= REF_BOUND
+    assert e <= REF_BOUND or n_fft == hop
+    # window_sumsquare, bit for bit, T < R included: both ends reach into the same chunk
+    tab = do.envelope_table(n_fft, hop)
+    keys = [k for k in g if k.startswith("env_T")]
+    assert len(keys) >= 3 and (n_fft == hop or any(int(k[5:]) < n_fft // hop for k in keys))
+    for k in keys:
+        assert np.array_equal(do.envelope_f32(int(k[5:]), n_fft, hop), g[k]) and np.array_equal(do.envelope_from_table(tab, int(k[5:]), n_fft, hop), g[k]), k
+
+
+def test_gain64_selects_a_zero_cell_where_mag_is_not_greater_than_zero():
+    """Step 3 of include/evhip.h: mag == 0 and a NaN give a zero cell -- 0, not 0 * NaN; every other cell is untouched by the rule."""
+    rng = np.random.default_rng(2)
+    re, im = rng.standard_normal((4, 9)), rng.standard_normal((4, 9))
+    bias = np.abs(rng.standard_normal(9)).astype(np.float32)
+    want = do.gain64(re, im, bias, 0.5)
+    re2, im2 = re.copy(), im.copy()
+    re2[1, 3], im2[2, :] = np.nan, np.nan
+    re2[3, 4] = im2[3, 4] = 0.0
+    gre, gim, mag = do.gain64(re2, im2, bias, 0.5)
+    dead = np.zeros((4, 9), bool)
+    dead[1, 3] = dead[2, :] = dead[3, 4] = True
+    assert np.all(gre[dead] == 0) and np.all(gim[dead] == 0) and np.all(np.isfinite(gre)) and np.all(np.isfinite(gim))
+    assert np.array_equal(gre[~dead], want[0][~dead]) and np.array_equal(gim[~dead], want[1][~dead]) and np.isnan(mag[1, 3])
+    # and through the inverse: a frame of NaN cells contributes nothing
+    w = (0.3 * rng.standard_normal(2048)).astype(np.float32)
+    r, i = do.stft64(w)
+    r[4], i[4] = np.nan, np.nan
+    r0, i0 = np.where(np.isnan(r), 0.0, r), np.where(np.isnan(i), 0.0, i)
+    b513 = np.full(513, 0.01, np.float32)
+    y = do.istft64(*do.gain64(r, i, b513, 0.1)[:2])
+    assert np.all(np.isfinite(y)) and np.array_equal(y, do.istft64(*do.gain64(r0, i0, b513, 0.1)[:2]))
+
+
+def test_config_window_is_part_of_the_setup_key():
+    w = np.hanning(1024).astype(np.float32)
+    assert DenoiseConfig(window=w).validate().key() != DenoiseConfig().key() and DenoiseConfig(window=w).key() == DenoiseConfig(window=w.copy()).key()
+    assert DenoiseConfig(window=w).tables_key() != DenoiseConfig().tables_key() == DenoiseConfig(strength=0.3).tables_key()
+    for bad in (DenoiseConfig(window=w[:512]), DenoiseConfig(window=np.full(1024, np.nan))):
+        with pytest.raises(ValueError):
+            bad.validate()
 
 
 def test_config_validation():

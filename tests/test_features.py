@@ -49,6 +49,28 @@ def test_oracle_reproduces_the_reference_features(path):
     assert np.allclose(g["ref_energy"][floor], 1e-5, rtol=1e-6)
 
 
+SHAPE_FIXTURES = sorted(glob.glob(os.path.join(FEAT_DIR, "stft_*.npz")))
+
+
+def test_the_shape_fixtures_are_the_two_shapes():
+    assert [os.path.basename(p)[:-4] for p in SHAPE_FIXTURES] == ["stft_384_48", "stft_640_320"]
+    assert all(os.path.getsize(p) < 100_000 and np.load(p)["wav"].size == 2000 for p in SHAPE_FIXTURES)
+
+
+@pytest.mark.parametrize("path", SHAPE_FIXTURES, ids=lambda p: os.path.basename(p)[:-4])
+def test_oracle_reproduces_the_reference_features_at_other_shapes(path):
+    """The reference's TacotronSTFT built at 384 / 48 and 640 / 320 (n_fft not a power of two): the same bound as at the default shape, whose
+    sqrt(1024) covers these shorter sums."""
+    g = np.load(path)
+    n_fft, hop = int(g["n_fft"]), int(g["hop"])
+    o = fo.features64(g["wav"], ft.mel_filterbank(16000, n_fft, 80, 0.0, 8000.0), n_fft=n_fft, hop=hop)
+    T = 2000 // hop + 1
+    assert g["ref_mel"].shape == (80, T) == o["mel"].shape and g["ref_mag"].shape == (T, n_fft // 2 + 1) == o["mag"].shape and g["ref_energy"].shape == (T,)
+    e_mel, e_en, e_mag = fo.mel_error(g["ref_mel"], o["mel"]), fo.energy_error(g["ref_energy"], o["energy"]), fo.mag_error(g["ref_mag"], o["mag"])
+    print(os.path.basename(path), "E_mel(ref) %.3e E_energy(ref) %.3e E_mag(ref) %.3e" % (e_mel, e_en, e_mag))
+    assert e_mel <= REF_F32_BOUND and e_en <= REF_F32_BOUND and e_mag <= REF_F32_BOUND
+
+
 def test_chirp_fixture_exercises_both_clamps():
     o = fo.features64(np.load(os.path.join(FEAT_DIR, "feat_c_chirp_zeros.npz"))["wav"])
     assert (o["mel_lin"] < 0.5e-5).sum() > 1000 and ((o["mag"] ** 2).sum(axis=1) < 0.5e-10).sum() >= 10

@@ -120,6 +120,32 @@ def test_strength_zero_is_ev_denoise_at_strength_zero_bit_for_bit(ctx):
     assert np.array_equal(marked["wav_i16"], clean["wav_i16"])
 
 
+@pytest.mark.parametrize("kind", ("nan", "inf"))
+def test_embed_gives_zero_cells_for_a_non_finite_sample(ctx, kind):
+    """include/evhip.h, Embed step 3: mag == 0 (and a NaN) gives a zero cell.  One NaN (or +inf, whose lo plane is inf - inf) in segment 0: the four
+    frames that hold it contribute nothing, the output is finite and is the oracle's with those frames zeroed; segment 1 keeps its bits."""
+    eng = ctx["eng"]
+    i0 = 2400
+    clean, other = ctx["speech"][:4869].copy(), ctx["rich"][5000:5700]
+    bad = clean.copy()
+    bad[i0] = np.float32(np.nan if kind == "nan" else np.inf)
+    clean[i0] = 0.0
+    re, im = do.stft64(clean, wo.N_FFT, wo.HOP)
+    g = wo.gain_map(re.shape[0], wo.pattern(KEY, 8, 0x5A)[0], 2.0)
+    dead = np.arange((i0 - wo.N_FFT // 2) // wo.HOP + 1, (i0 + wo.N_FFT // 2) // wo.HOP + 1)
+    assert dead.tolist() == [8, 9, 10, 11]
+    g[dead] = 0.0
+    want = do.istft64(g * re, g * im, wo.N_FFT, wo.HOP)
+    cfg = _cfg(payload=0x5A, nbits=8, strength_db=2.0, want_int16=True)
+    out = eng.watermark([bad, other], cfg)
+    y = out["wav_list"][0]
+    e, a = do.peak_error(y, want), float(wo.gains_f32(2.0)[0])
+    print(kind, "E %.3e bar %.3e non-finite outputs %d" % (e, ctx["bar"] * a, int((~np.isfinite(out["wav"])).sum())))
+    assert np.all(np.isfinite(out["wav"])) and e <= ctx["bar"] * a and np.array_equal(out["wav_i16"], do.to_i16(out["wav"]))
+    alone = eng.watermark([other], cfg)["wav_list"][0]
+    assert np.array_equal(_bits(alone), _bits(out["wav_list"][1]))
+
+
 def _oracle_side(wav, key, nbits, marked=True):
     """The oracle's decisions, its intervals and the CPU-side conditions on a fixture.  An unmarked fixture has one decision, absent: the offset
     and the bits of an absent mark are the argmax of noise and mean nothing, so nothing is asked of them."""
