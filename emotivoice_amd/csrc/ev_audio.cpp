@@ -36,6 +36,60 @@ struct WavIn {
     const void* ptr() const { return dev ? src : stage; }
 };
 
+// what every forward STFT kernel takes (StftFront, ev_kernels.h)
+StftFront stft_front(const void* wav, int wav_is_i16, const StftSeq* seqs, const StftTile* tiles, size_t n_tiles, const void* basis, int n_fft, int hop) {
+    return StftFront{wav, wav_is_i16 != 0, seqs, tiles, (int)n_tiles, basis, n_fft, hop, stft_bin_tiles(n_fft)};
+}
+
+// the checks ev_denoise, ev_watermark and ev_watermark_detect share, and the frame grid of the batch: 0, or -1 with the message set.  `unit` is what
+// the caller's messages call an element of the batch
+int stft_grid(ev_handle* h, const char* who, const char* unit, int n_fft, int hop, int B, const void* wav, const int64_t* lens, FrameGrid& g) {
+    if (!wav) return fail(h, "%s: wav is NULL", who);
+    if (!lens) return fail(h, "%s: lens is NULL", who);
+    if (B < 1 || B > 65535) return fail(h, "%s: B = %d outside [1, 65535]", who, B);
+    const int bad = frame_grid_layout(B, lens, n_fft / 2 + 1, hop, 64, g);
+    if (bad > 0) return fail(h, "%s: lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", who, bad - 1, (long long)lens[bad - 1], n_fft / 2 + 1);
+    if (bad < 0) return fail(h, "%s: %s %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", who, unit, -bad - 1, (long long)(lens[-bad - 1] / hop + 1), EV_ALIGN_MAX_FRAMES);
+    return 0;
+}
+
+// The second half of ev_denoise and ev_watermark: the scratch planes that the caller's forward kernel fills, their inverse STFT and the packed result.
+// Used like WavIn: built from the grid, plan() inside the arena's plan, copy() with the uploads, then -- after the forward launch into hi / lo --
+// inverse(), and finish() once the call has ended.
+struct IstftTrip {
+    std::vector<IstftSeq> seqs; std::vector<StftTile> tiles;
+    int n_fft, hop, KP; bool want16; int64_t total_frames, total_out;
+    IstftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; uint16_t *hi = nullptr, *lo = nullptr; float* out = nullptr; int16_t* out_i16 = nullptr;
+    IstftTrip(const FrameGrid& g, int n_fft_, int hop_, bool want16_)
+        : n_fft(n_fft_), hop(hop_), KP(denoise_k_pad(n_fft_)), want16(want16_), total_frames(g.offs.back()),
+          total_out(istft_layout((int)g.lens.size(), g.lens.data(), n_fft_, hop_, seqs, tiles)) {}
+    void plan(ArenaPlan& ap) {
+        d_seqs = ap.arr<IstftSeq>(seqs.size()); d_tiles = ap.arr<StftTile>(tiles.size());
+        hi = ap.arr<uint16_t>((size_t)total_frames * KP); lo = ap.arr<uint16_t>((size_t)total_frames * KP);
+        out = ap.arr<float>((size_t)total_out); out_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
+    }
+    int copy(ev_handle* h) const { return upload(h, d_seqs, seqs) || upload(h, d_tiles, tiles); }
+    double plane_bytes() const { return 4.0 * (double)total_frames * KP; }      // both planes, as the forward kernel writes them
+    int inverse(ev_handle* h, const char* who, const StftTables& t) const {
+        if (!tiles.empty()) {
+            const IstftParams p{hi, lo, d_seqs, d_tiles, (int)tiles.size(), t.ibasis.get(), t.env.as<float>(), n_fft, hop, n_fft / hop, KP, out, out_i16};
+            KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)tiles.size() * (double)p.R * KP * hop, plane_bytes() + (double)total_out * (want16 ? 6.0 : 4.0));
+            if (launch_istft_ola(p, h->stream)) return fail(h, "%s: the kernel does not build this shape", who);
+        }
+        HIPCHK(h, hipGetLastError());
+        return 0;
+    }
+    template <typename R> void finish(WavOut& keep, R* res) const {      // R: ev_denoise_result or ev_watermark_result
+        const size_t B = seqs.size();
+        keep.lens.resize(B); keep.offs.resize(B + 1);
+        for (size_t b = 0; b < B; ++b) { keep.lens[b] = seqs[b].out_len; keep.offs[b] = seqs[b].out_off; }
+        keep.offs[B] = total_out;
+        reset_result(res);
+        res->batch = (int)B; res->total = total_out; res->wav = out; res->wav_i16 = out_i16;
+        res->lens_out = keep.lens.data(); res->offsets = keep.offs.data();
+    }
+};
+
 // The device side of a per-kernel test entry point (the end of this file): ONE allocation that holds the host tables appended with add() and the
 // scratch reserved with room(), each at an aligned offset.  commit() allocates and uploads, at<T>() turns an offset into its pointer, and the end
 // of the scope frees -- after the wrapper has waited for the stream.
@@ -145,11 +199,8 @@ int ev_features(ev_handle* h, int B, const void* wav, int wav_is_i16, const int6
     if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles)) return -1;
     region_begin(h, "total");
     {
-        StftParams p{};
-        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size();
-        p.basis = h->feat.basis.get(); p.melT = h->feat.melT.as<float>(); p.n_fft = fc.n_fft; p.hop = fc.hop; p.n_mels = fc.n_mels; p.nmi = stft_mels_per_group(fc.n_mels);
-        p.n_bins = n_bins; p.n_btiles = stft_bin_tiles(fc.n_fft); p.mel_clip = fc.mel_clip; p.energy_floor = fc.energy_floor;
-        p.energy_mean = energy_mean; p.energy_std = energy_std; p.mel = d_mel; p.energy = d_energy; p.mag = d_mag;
+        const StftParams p{stft_front(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->feat.basis.get(), fc.n_fft, fc.hop), h->feat.melT.as<float>(),
+                           fc.n_mels, fc.mel_clip, fc.energy_floor, energy_mean, energy_std, d_mel, d_energy, d_mag};
         const double tile_frames = 64.0 * (double)g.tiles.size();
         KScope ks(h, "stft_mel", 2.0 * 3.0 * tile_frames * fc.n_fft * 2.0 * n_bins + 2.0 * tile_frames * n_bins * fc.n_mels,
                   (double)in.bytes + (double)total_frames * (fc.n_mels + 1) * 4.0);
@@ -1301,22 +1352,14 @@ static int denoise_check_shape(ev_handle* h, const char* who, int n_fft, int hop
     return 0;
 }
 
-// the three tables of a shape, packed on the host and uploaded, one allocation each: 0, or -1 (the caller's locals free what was built)
-static int denoise_upload_tables(int n_fft, int hop, const float* window, DevMem& basis, DevMem& ibasis, DevMem& env) {
+// the three tables of a shape, packed on the host and uploaded, one allocation each: 0, or -1 (the caller's local frees what was built)
+static int denoise_upload_tables(int n_fft, int hop, const float* window, StftTables& t) {
     std::vector<uint16_t> hb(stft_basis_halfs(n_fft)), hi(istft_basis_halfs(n_fft, hop));
     std::vector<float> he(istft_envelope_floats(n_fft, hop));
     stft_pack_basis(n_fft, window, hb.data());
     istft_pack_basis(n_fft, hop, window, hi.data());
     istft_pack_envelope(n_fft, hop, window, he.data());
-    return dev_upload(basis, hb) == hipSuccess && dev_upload(ibasis, hi) == hipSuccess && dev_upload(env, he) == hipSuccess ? 0 : -1;
-}
-
-static StftGainParams stft_gain_params(const void* wav, int wav_is_i16, const StftSeq* seqs, const StftTile* tiles, size_t n_tiles, const void* basis, int n_fft,
-                                       int hop) {
-    StftGainParams p{};
-    p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = seqs; p.tiles = tiles; p.n_tiles = (int)n_tiles; p.basis = basis;
-    p.n_fft = n_fft; p.hop = hop; p.n_bins = n_fft / 2 + 1; p.n_btiles = stft_bin_tiles(n_fft); p.k_pad = denoise_k_pad(n_fft);
-    return p;
+    return dev_upload(t.basis, hb) == hipSuccess && dev_upload(t.ibasis, hi) == hipSuccess && dev_upload(t.env, he) == hipSuccess ? 0 : -1;
 }
 
 static int denoise_bad_value(int n, const float* v) {      // -1, or the first index of a value that is negative, NaN or infinite
@@ -1339,8 +1382,8 @@ int ev_denoise_setup(ev_handle* h, const ev_denoise_config* cfg, const float* bi
     }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    DevMem basis, ibasis, env, d_bias;
-    if (denoise_upload_tables(cfg->n_fft, cfg->hop, cfg->window, basis, ibasis, env)) return fail(h, "ev_denoise_setup: uploading the tables failed");
+    StftTables tab; DevMem d_bias;
+    if (denoise_upload_tables(cfg->n_fft, cfg->hop, cfg->window, tab)) return fail(h, "ev_denoise_setup: uploading the tables failed");
     if (bias) {
         if (dev_upload(d_bias, bias, (size_t)n_bins * 4) != hipSuccess) return fail(h, "ev_denoise_setup: uploading the bias failed");
     } else {      // the vocoder's answer to a zero mel; the magnitudes of its frame 0 go straight into d_bias
@@ -1356,12 +1399,12 @@ int ev_denoise_setup(ev_handle* h, const ev_denoise_config* cfg, const float* bi
         DevTable dt;
         const size_t so = dt.add(&sq, sizeof sq), to = dt.add(&tile, sizeof tile);
         if (dt.commit()) return fail(h, "ev_denoise_setup: no memory for the bias measurement");
-        StftGainParams p = stft_gain_params(r.wav, 0, dt.at<StftSeq>(so), dt.at<StftTile>(to), 1, basis.get(), cfg->n_fft, cfg->hop);
+        StftGainParams p{stft_front(r.wav, 0, dt.at<StftSeq>(so), dt.at<StftTile>(to), 1, tab.basis.get(), cfg->n_fft, cfg->hop)};
         p.mag = d_bias.as<float>(); p.mag_frames = 1;
         if (launch_stft_gain(p, h->stream)) return fail(h, "ev_denoise_setup: the kernel does not build this shape");
         if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, "ev_denoise_setup: measuring the bias failed");
     }
-    h->dn.basis = std::move(basis); h->dn.ibasis = std::move(ibasis); h->dn.env = std::move(env); h->dn.bias = std::move(d_bias);
+    h->dn.tab = std::move(tab); h->dn.bias = std::move(d_bias);
     h->dn.cfg = *cfg; h->dn.cfg.window = nullptr;
     h->dn.ready = true;
     return 0;
@@ -1379,66 +1422,41 @@ int ev_denoise_bias(ev_handle* h, float* out) {
 
 int ev_denoise(ev_handle* h, int B, const void* wav, int wav_is_i16, const int64_t* lens, const float* strengths, uint32_t flags, ev_denoise_result* out) {
     if (!h) return -1;
-    if (!wav) return fail(h, "ev_denoise: wav is NULL");
-    if (!lens) return fail(h, "ev_denoise: lens is NULL");
     if (!out) return fail(h, "ev_denoise: out is NULL");
     if (check_struct_size(h, "ev_denoise", "out->struct_size", out->struct_size, "ev_denoise_result", sizeof(ev_denoise_result))) return -1;
     if (!h->dn.ready) return fail(h, "ev_denoise: ev_denoise_setup has not been called");
-    if (B < 1 || B > 65535) return fail(h, "ev_denoise: B = %d outside [1, 65535]", B);
     const ev_denoise_config& c = h->dn.cfg;
-    const int n_fft = c.n_fft, hop = c.hop, KP = denoise_k_pad(n_fft);
+    const int n_fft = c.n_fft, hop = c.hop;
+    FrameGrid g;
+    if (stft_grid(h, "ev_denoise", "utterance", n_fft, hop, B, wav, lens, g)) return -1;
     if (strengths) {
         const int bad = denoise_bad_value(B, strengths);
         if (bad >= 0) return fail(h, "ev_denoise: strengths[%d] must be >= 0 and finite", bad);
     }
-    FrameGrid g;
-    const int bad = frame_grid_layout(B, lens, n_fft / 2 + 1, hop, 64, g);
-    if (bad > 0) return fail(h, "ev_denoise: lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", bad - 1, (long long)lens[bad - 1], n_fft / 2 + 1);
-    if (bad < 0) return fail(h, "ev_denoise: utterance %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", -bad - 1, (long long)(lens[-bad - 1] / hop + 1), EV_ALIGN_MAX_FRAMES);
-    std::vector<IstftSeq> iseqs; std::vector<StftTile> itiles;
-    const int64_t total_out = istft_layout(B, g.lens.data(), n_fft, hop, iseqs, itiles);
-    const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
+    IstftTrip trip(g, n_fft, hop, c.want_i16 != 0);
     std::vector<float> st((size_t)B);
     for (int b = 0; b < B; ++b) st[b] = strengths ? strengths[b] : c.strength;
-    const bool want16 = c.want_i16 != 0;
-    WavIn in(wav, total_in, wav_is_i16, flags);
+    WavIn in(wav, g.seqs[B - 1].wav_off + g.seqs[B - 1].len, wav_is_i16, flags);
     if (call_begin(h)) return -1;
-    StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_st = nullptr, *d_out = nullptr;
-    uint16_t *d_hi = nullptr, *d_lo = nullptr; int16_t* d_i16 = nullptr;
+    StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float* d_st = nullptr;
     if (arena_plan(h, ARENA_DENOISE, [&](ArenaPlan& ap) {
         in.plan(ap);
-        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_iseqs = ap.arr<IstftSeq>(B); d_itiles = ap.arr<StftTile>(itiles.size());
-        d_st = ap.arr<float>(B);
-        d_hi = ap.arr<uint16_t>((size_t)total_frames * KP); d_lo = ap.arr<uint16_t>((size_t)total_frames * KP);
-        d_out = ap.arr<float>((size_t)total_out); d_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_st = ap.arr<float>(B);
+        trip.plan(ap);
     })) return -1;
-    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) || upload(h, d_st, st)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_st, st) || trip.copy(h)) return -1;
     region_begin(h, "total");
     {
-        StftGainParams p = stft_gain_params(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->dn.basis.get(), n_fft, hop);
-        p.bias = h->dn.bias.as<float>(); p.strengths = d_st; p.spec_hi = d_hi; p.spec_lo = d_lo;
+        StftGainParams p{stft_front(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->dn.tab.basis.get(), n_fft, hop)};
+        p.bias = h->dn.bias.as<float>(); p.strengths = d_st; p.spec_hi = trip.hi; p.spec_lo = trip.lo;
         const double tile_frames = (double)64 * (double)g.tiles.size();
-        KScope ks(h, "stft_gain", 2.0 * 3.0 * tile_frames * n_fft * 2.0 * p.n_bins, (double)in.bytes + 4.0 * (double)total_frames * KP);
+        KScope ks(h, "stft_gain", 2.0 * 3.0 * tile_frames * n_fft * 2.0 * (n_fft / 2 + 1), (double)in.bytes + trip.plane_bytes());
         if (launch_stft_gain(p, h->stream)) return fail(h, "ev_denoise: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
-    if (!itiles.empty()) {
-        IstftParams p{};
-        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->dn.ibasis.get(); p.env = h->dn.env.as<float>();
-        p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = KP; p.out = d_out; p.out_i16 = d_i16;
-        KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)itiles.size() * (double)p.R * KP * hop,
-                  4.0 * (double)total_frames * KP + (double)total_out * (want16 ? 6.0 : 4.0));
-        if (launch_istft_ola(p, h->stream)) return fail(h, "ev_denoise: the kernel does not build this shape");
-    }
-    HIPCHK(h, hipGetLastError());
+    if (trip.inverse(h, "ev_denoise", h->dn.tab)) return -1;
     if (call_end(h)) return -1;
-    std::vector<int64_t> lo((size_t)B), offs((size_t)B + 1);
-    for (int b = 0; b < B; ++b) { lo[b] = iseqs[b].out_len; offs[b] = iseqs[b].out_off; }
-    offs[B] = total_out;
-    h->dn.lens.swap(lo); h->dn.offs.swap(offs);
-    reset_result(out);
-    out->batch = B; out->total = total_out; out->wav = d_out; out->wav_i16 = d_i16;
-    out->lens_out = h->dn.lens.data(); out->offsets = h->dn.offs.data();
+    trip.finish(h->dn.res, out);
     return 0;
 }
 
@@ -1566,24 +1584,13 @@ int ev_watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* sign
     return 0;
 }
 
-// the checks the two entry points share, and the frame grid of the batch: 0, or -1 with the message set
-static int watermark_grid(ev_handle* h, const char* who, int B, const void* wav, const int64_t* lens, FrameGrid& g) {
-    if (!wav) return fail(h, "%s: wav is NULL", who);
-    if (!lens) return fail(h, "%s: lens is NULL", who);
-    if (B < 1 || B > 65535) return fail(h, "%s: B = %d outside [1, 65535]", who, B);
-    const int bad = frame_grid_layout(B, lens, WM_NFFT / 2 + 1, WM_HOP, 64, g);
-    if (bad > 0) return fail(h, "%s: lens[%d] = %lld < n_fft / 2 + 1 = %d (reflect padding needs that many samples)", who, bad - 1, (long long)lens[bad - 1], WM_NFFT / 2 + 1);
-    if (bad < 0) return fail(h, "%s: segment %d has %lld frames > EV_ALIGN_MAX_FRAMES %d", who, -bad - 1, (long long)(lens[-bad - 1] / WM_HOP + 1), EV_ALIGN_MAX_FRAMES);
-    return 0;
-}
-
 // ev_denoise's tables at the watermark's shape, once per handle
 static int watermark_tables(ev_handle* h, const char* who) {
     if (h->wm.ready) return 0;
     HIPCHK(h, hipSetDevice(h->device));
-    DevMem basis, ibasis, env;
-    if (denoise_upload_tables(WM_NFFT, WM_HOP, nullptr, basis, ibasis, env)) return fail(h, "%s: uploading the tables failed", who);
-    h->wm.basis = std::move(basis); h->wm.ibasis = std::move(ibasis); h->wm.env = std::move(env);
+    StftTables tab;
+    if (denoise_upload_tables(WM_NFFT, WM_HOP, nullptr, tab)) return fail(h, "%s: uploading the tables failed", who);
+    h->wm.tab = std::move(tab);
     h->wm.ready = true;
     return 0;
 }
@@ -1597,7 +1604,7 @@ int ev_watermark(ev_handle* h, int B, const void* wav, int wav_is_i16, const int
     if (!cfg) { ev_default_watermark_config(&dflt); cfg = &dflt; }
     if (check_struct_size(h, "ev_watermark", "cfg->struct_size", cfg->struct_size, "ev_watermark_config", sizeof(ev_watermark_config))) return -1;
     FrameGrid g;
-    if (watermark_grid(h, "ev_watermark", B, wav, lens, g)) return -1;
+    if (stft_grid(h, "ev_watermark", "segment", WM_NFFT, WM_HOP, B, wav, lens, g)) return -1;
     std::vector<int8_t> signs((size_t)B * WM_CHIPS);
     std::vector<float> gains((size_t)B * 2);
     for (int b = 0; b < B; ++b) {
@@ -1612,51 +1619,27 @@ int ev_watermark(ev_handle* h, int B, const void* wav, int wav_is_i16, const int
         gains[2 * (size_t)b] = a;
         gains[2 * (size_t)b + 1] = 1.0f / a;
     }
-    const int n_fft = WM_NFFT, hop = WM_HOP, KP = denoise_k_pad(n_fft);
-    std::vector<IstftSeq> iseqs; std::vector<StftTile> itiles;
-    const int64_t total_out = istft_layout(B, g.lens.data(), n_fft, hop, iseqs, itiles);
-    const int64_t total_frames = g.offs[B], total_in = g.seqs[B - 1].wav_off + g.seqs[B - 1].len;
-    const bool want16 = cfg->want_i16 != 0;
-    WavIn in(wav, total_in, wav_is_i16, flags);
+    IstftTrip trip(g, WM_NFFT, WM_HOP, cfg->want_i16 != 0);
+    WavIn in(wav, g.seqs[B - 1].wav_off + g.seqs[B - 1].len, wav_is_i16, flags);
     if (call_begin(h)) return -1;
     if (watermark_tables(h, "ev_watermark")) return -1;
-    StftSeq* d_seqs = nullptr; StftTile *d_tiles = nullptr, *d_itiles = nullptr; IstftSeq* d_iseqs = nullptr; float *d_gains = nullptr, *d_out = nullptr;
-    uint16_t *d_hi = nullptr, *d_lo = nullptr; int16_t* d_i16 = nullptr; int8_t* d_signs = nullptr;
+    StftSeq* d_seqs = nullptr; StftTile* d_tiles = nullptr; float* d_gains = nullptr; int8_t* d_signs = nullptr;
     if (arena_plan(h, ARENA_WATERMARK, [&](ArenaPlan& ap) {
         in.plan(ap);
-        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_iseqs = ap.arr<IstftSeq>(B); d_itiles = ap.arr<StftTile>(itiles.size());
-        d_gains = ap.arr<float>(gains.size()); d_signs = ap.arr<int8_t>(signs.size());
-        d_hi = ap.arr<uint16_t>((size_t)total_frames * KP); d_lo = ap.arr<uint16_t>((size_t)total_frames * KP);
-        d_out = ap.arr<float>((size_t)total_out); d_i16 = want16 ? ap.arr<int16_t>((size_t)total_out) : nullptr;
+        d_seqs = ap.arr<StftSeq>(B); d_tiles = ap.arr<StftTile>(g.tiles.size()); d_gains = ap.arr<float>(gains.size()); d_signs = ap.arr<int8_t>(signs.size());
+        trip.plan(ap);
     })) return -1;
-    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_iseqs, iseqs) || upload(h, d_itiles, itiles) ||
-        upload(h, d_gains, gains) || upload(h, d_signs, signs)) return -1;
+    if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_gains, gains) || upload(h, d_signs, signs) || trip.copy(h)) return -1;
     region_begin(h, "total");
     {
-        WmEmbedParams p{};
-        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size(); p.basis = h->wm.basis.get();
-        p.ks = WM_NFFT / 32; p.n_btiles = stft_bin_tiles(WM_NFFT); p.signs = d_signs; p.gains = d_gains; p.spec_hi = d_hi; p.spec_lo = d_lo;
-        KScope ks(h, "wm_embed", 2.0 * 3.0 * 64.0 * (double)g.tiles.size() * n_fft * 2.0 * (n_fft / 2 + 1), (double)in.bytes + 4.0 * (double)total_frames * KP);
+        const WmEmbedParams p{stft_front(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->wm.tab.basis.get(), WM_NFFT, WM_HOP), d_signs, d_gains, trip.hi, trip.lo};
+        KScope ks(h, "wm_embed", 2.0 * 3.0 * 64.0 * (double)g.tiles.size() * WM_NFFT * 2.0 * (WM_NFFT / 2 + 1), (double)in.bytes + trip.plane_bytes());
         if (launch_wm_embed(p, h->stream)) return fail(h, "ev_watermark: the kernel does not build this shape");
     }
     HIPCHK(h, hipGetLastError());
-    if (!itiles.empty()) {
-        IstftParams p{};
-        p.spec_hi = d_hi; p.spec_lo = d_lo; p.seqs = d_iseqs; p.tiles = d_itiles; p.n_tiles = (int)itiles.size(); p.ibasis = h->wm.ibasis.get(); p.env = h->wm.env.as<float>();
-        p.n_fft = n_fft; p.hop = hop; p.R = n_fft / hop; p.k_pad = KP; p.out = d_out; p.out_i16 = d_i16;
-        KScope ks(h, "istft_ola", 2.0 * 3.0 * (double)DN_TJ * (double)itiles.size() * (double)p.R * KP * hop,
-                  4.0 * (double)total_frames * KP + (double)total_out * (want16 ? 6.0 : 4.0));
-        if (launch_istft_ola(p, h->stream)) return fail(h, "ev_watermark: the kernel does not build this shape");
-    }
-    HIPCHK(h, hipGetLastError());
+    if (trip.inverse(h, "ev_watermark", h->wm.tab)) return -1;
     if (call_end(h)) return -1;
-    std::vector<int64_t> lo((size_t)B), offs((size_t)B + 1);
-    for (int b = 0; b < B; ++b) { lo[b] = iseqs[b].out_len; offs[b] = iseqs[b].out_off; }
-    offs[B] = total_out;
-    h->wm.lens.swap(lo); h->wm.offs.swap(offs);
-    reset_result(out);
-    out->batch = B; out->total = total_out; out->wav = d_out; out->wav_i16 = d_i16;
-    out->lens_out = h->wm.lens.data(); out->offsets = h->wm.offs.data();
+    trip.finish(h->wm.res, out);
     return 0;
 }
 
@@ -1666,7 +1649,7 @@ int ev_watermark_detect(ev_handle* h, int B, const void* wav, int wav_is_i16, co
     if (!out) return fail(h, "ev_watermark_detect: out is NULL");
     if (check_struct_size(h, "ev_watermark_detect", "out->struct_size", out->struct_size, "ev_watermark_detect_result", sizeof(ev_watermark_detect_result))) return -1;
     FrameGrid g;
-    if (watermark_grid(h, "ev_watermark_detect", B, wav, lens, g)) return -1;
+    if (stft_grid(h, "ev_watermark_detect", "segment", WM_NFFT, WM_HOP, B, wav, lens, g)) return -1;
     if (nbits < 0 || nbits > WM_MAX_BITS) return fail(h, "ev_watermark_detect: nbits = %d outside [0, %d]", nbits, WM_MAX_BITS);
     std::vector<int8_t> tabs(3 * (size_t)WM_CHIPS);      // the pilots' signs (0 for a payload chip), every sign at payload 0, every role
     watermark_pattern(key, nbits, 0, tabs.data() + WM_CHIPS, reinterpret_cast<uint8_t*>(tabs.data()) + 2 * WM_CHIPS);
@@ -1684,8 +1667,7 @@ int ev_watermark_detect(ev_handle* h, int B, const void* wav, int wav_is_i16, co
     if (in.copy(h) || upload(h, d_seqs, g.seqs) || upload(h, d_tiles, g.tiles) || upload(h, d_tabs, tabs)) return -1;
     region_begin(h, "total");
     {
-        WmBandParams p{};
-        p.wav = in.ptr(); p.wav_is_i16 = wav_is_i16 != 0; p.seqs = d_seqs; p.tiles = d_tiles; p.n_tiles = (int)g.tiles.size(); p.basis = h->wm.basis.get(); p.ks = WM_NFFT / 32; p.n_btiles = stft_bin_tiles(WM_NFFT); p.q = d_q;
+        const WmBandParams p{stft_front(in.ptr(), wav_is_i16, d_seqs, d_tiles, g.tiles.size(), h->wm.tab.basis.get(), WM_NFFT, WM_HOP), d_q};
         KScope ks(h, "wm_bands", 2.0 * 3.0 * 64.0 * (double)g.tiles.size() * WM_NFFT * 2.0 * (WM_NFFT / 2 + 1), (double)in.bytes + 4.0 * (double)total_frames * WM_BANDS);
         if (launch_wm_bands(p, h->stream)) return fail(h, "ev_watermark_detect: the kernel does not build this shape");
     }
@@ -1974,11 +1956,8 @@ int ev_op_stft_mel(const void* wav, int wav_is_i16, int B, const int64_t* wav_le
     DevTable t;
     const size_t so = t.add(g.seqs), to = t.add(g.tiles);
     if (features_upload_tables(nullptr, n_fft, n_mels, mel_basis, window, basis, melT) || t.commit()) return -1;
-    StftParams p{};
-    p.wav = wav; p.wav_is_i16 = wav_is_i16 != 0; p.seqs = t.at<StftSeq>(so); p.tiles = t.at<StftTile>(to); p.n_tiles = (int)g.tiles.size();
-    p.basis = basis.get(); p.melT = melT.as<float>(); p.n_fft = n_fft; p.hop = hop; p.n_mels = n_mels; p.nmi = stft_mels_per_group(n_mels); p.n_bins = n_fft / 2 + 1;
-    p.n_btiles = stft_bin_tiles(n_fft); p.mel_clip = mel_clip; p.energy_floor = energy_floor; p.energy_mean = energy_mean; p.energy_std = energy_std;
-    p.mel = mel; p.energy = energy; p.mag = mag;
+    const StftParams p{stft_front(wav, wav_is_i16, t.at<StftSeq>(so), t.at<StftTile>(to), g.tiles.size(), basis.get(), n_fft, hop), melT.as<float>(),
+                       n_mels, mel_clip, energy_floor, energy_mean, energy_std, mel, energy, mag};
     return op_finish(launch_stft_mel(p, (hipStream_t)stream), (hipStream_t)stream);
 }
 
@@ -1993,7 +1972,7 @@ int ev_op_stft_gain(const void* wav, int wav_is_i16, int B, const int64_t* wav_l
     DevTable t;
     const size_t so = t.add(g.seqs), to = t.add(g.tiles), bo = t.add(hb);
     if (t.commit()) return -1;
-    StftGainParams p = stft_gain_params(wav, wav_is_i16, t.at<StftSeq>(so), t.at<StftTile>(to), g.tiles.size(), t.at<char>(bo), n_fft, hop);
+    StftGainParams p{stft_front(wav, wav_is_i16, t.at<StftSeq>(so), t.at<StftTile>(to), g.tiles.size(), t.at<char>(bo), n_fft, hop)};
     p.bias = bias; p.strengths = strengths; p.spec_hi = (uint16_t*)spec_hi; p.spec_lo = (uint16_t*)spec_lo;
     p.mag = mag; p.mag_frames = EV_ALIGN_MAX_FRAMES;
     return op_finish(launch_stft_gain(p, (hipStream_t)stream), (hipStream_t)stream);

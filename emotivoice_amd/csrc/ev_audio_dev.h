@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ev_kernels.h"
+
 namespace ev {
 
 namespace {
@@ -137,17 +139,11 @@ __device__ inline void stage_run(D dst, const void* wav, int is16, int64_t in_of
 }
 
 // ---- the windowed DFT of ev_features and ev_denoise: a GEMM with overlapping rows.  Row t of the A operand is padded[hop t .. hop t + n_fft), so a
-// tile of STFT_TF frames is ONE run of (STFT_TF - 1) hop + n_fft samples, kept in LDS as fp16 hi / lo planes (x = hi + 2^-11 lo).
+// tile of STFT_TF frames is ONE run of (STFT_TF - 1) hop + n_fft samples, kept in LDS as fp16 hi / lo planes (x = hi + 2^-11 lo); ev_kernels.h states
+// the layout (stft_spad, stft_plane_halfs).  A forward kernel is stft_begin, its own staging, __syncthreads(), then stft_tile_loop with its epilogue.
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int STFT_TF = 64;      // frames per block
-constexpr int STFT_TB = 32;      // bins per basis tile (64 GEMM columns: re and im of the same bins)
-
-// LDS index of sample i of the block's run: 8 halfs of padding after every 256 samples, so that the 16 frames of an A fragment (hop apart:
-// 512 bytes at hop 256) start 16 bytes apart modulo the bank width.  A fragment's 8 samples start at a multiple of 8 and never straddle a pad.
-__host__ __device__ inline int stft_spad(int i) { return i + 8 * (i >> 8); }
 
 // a block of 256 threads stages samples first .. first + NS - 1 of the utterance wav[wav_off .. wav_off + L) as the two planes: reflected at
 // both ends, int16 converted (x / 32768), zero where the reflection still falls outside (frames of the tile that are never written)
@@ -207,6 +203,70 @@ __device__ inline void stft_tile_gemm(const _Float16* sh, const _Float16* sl, co
         }
     }
 }
+
+// A thread's place in a forward block of 4 waves: wave (nb, mh) multiplies frames 32 mh .. + 31 of the tile (two 16-row tiles a) into the re and im
+// columns of bins 16 nb .. + 15 of each basis tile, and lane (fr, g) ends with bin fr of the frames 4 g + r.
+struct StftLane {
+    StftSeq sq; int seq, t0;      // the utterance, its index, the tile's first frame
+    int fr, g, nb, mh;
+    const _Float16 *sh, *sl;      // the staged planes
+    __device__ int frame(int a, int r) const { return mh * 32 + a * 16 + g * 4 + r; }      // the frame of the tile that re[a][r], im[a][r] belong to
+};
+
+// The start of a forward block of 256 threads: looks its tile up, carves the two planes from the dynamic LDS at `smem` and stages them.  *tail is
+// what follows the planes, 16-byte aligned; the planes may be read after the kernel's next __syncthreads().
+__device__ inline StftLane stft_begin(const StftFront& f, char* smem, char** tail) {
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const StftTile tl = f.tiles[blockIdx.x];
+    const int NSP = stft_plane_halfs(f.n_fft, f.hop);
+    _Float16* sh = reinterpret_cast<_Float16*>(smem);
+    _Float16* sl = sh + NSP;
+    *tail = reinterpret_cast<char*>(sl + NSP);
+    const StftLane L{f.seqs[tl.seq], tl.seq, tl.t0, lane & 15, lane >> 4, w & 1, w >> 1, sh, sl};
+    stft_stage_planes(sh, sl, f.wav, f.wav_is_i16, L.sq.wav_off, L.sq.len, (int64_t)L.t0 * f.hop - f.n_fft / 2, stft_run_samples(f.n_fft, f.hop));
+    return L;
+}
+
+// The loop over the basis tiles: the wave's share of tile nt (stft_tile_gemm), hi and cross terms recombined, then cell(nt, bin, re, im) with
+// re[a][r], im[a][r] of the lane's bin = 32 nt + 16 nb + fr at frame L.frame(a, r).  Every thread calls `cell` for every tile: it may hold barriers.
+template <class Cell>
+__device__ inline void stft_tile_loop(const StftFront& f, const StftLane& L, Cell cell) {
+    const int KS = f.n_fft / 32;
+    int aoff[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) aoff[a] = (L.mh * 32 + a * 16 + L.fr) * f.hop + 8 * L.g;
+    const half8* basis = reinterpret_cast<const half8*>(f.basis) + (threadIdx.x & 63);
+    for (int nt = 0; nt < f.n_btiles; ++nt) {
+        f4 acc[2][2], accl[2][2];
+        stft_tile_gemm(L.sh, L.sl, basis + (size_t)(nt * 2 + L.nb) * KS * 256, KS, aoff, acc, accl);
+        float re[2][4], im[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                re[a][r] = acc[a][0][r] + accl[a][0][r] * (1.0f / 2048.0f);
+                im[a][r] = acc[a][1][r] + accl[a][1][r] * (1.0f / 2048.0f);
+            }
+        cell(nt, nt * STFT_TB + L.nb * 16 + L.fr, re, im);
+    }
+}
+
+// |re + i im| as every forward kernel has rounded it: im * im, then one fma.  Spelled as the fma, not left to contraction: with re * re + im * im the
+// vectoriser packed the two squares of some cells of stft_mel_kernel and left them unfused, an ulp away from stft_gain_kernel's.
+__device__ inline float stft_mag(float re, float im) { return sqrtf(fmaf(re, re, im * im)); }
+
+// Launches a forward kernel over the front's tiles, 256 threads each, with the two planes and `tail_bytes` of its own as dynamic LDS: 0, or -1 for
+// a shape the kernels do not build
+template <class P>
+inline int stft_launch(void (*kernel)(P), const P& p, size_t tail_bytes, hipStream_t s) {
+    const StftFront& f = p.f;
+    if (!stft_shape_ok(f.n_fft, f.hop, 1) || f.n_tiles <= 0 || f.n_btiles != stft_bin_tiles(f.n_fft)) return -1;
+    const size_t lds = (size_t)stft_plane_halfs(f.n_fft, f.hop) * 2 * sizeof(_Float16) + tail_bytes;
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)f.n_tiles), dim3(256), lds, s, p);
+    return 0;
+}
+
 
 }  // namespace
 

@@ -26,21 +26,13 @@ namespace ev {
 int denoise_shape_ok(int n_fft, int hop) {
     return stft_shape_ok(n_fft, hop, 1) && n_fft % hop == 0 && n_fft / hop <= DN_MAX_R;
 }
-int denoise_k_pad(int n_fft) { return (2 * (n_fft / 2 + 1) + 31) / 32 * 32; }
 static int istft_col_tiles(int hop) { return (hop + 15) / 16; }
 size_t istft_basis_halfs(int n_fft, int hop) { return (size_t)istft_col_tiles(hop) * ((size_t)(n_fft / hop) * denoise_k_pad(n_fft) / 32) * 2 * 64 * 8; }
 size_t istft_envelope_floats(int n_fft, int hop) { const size_t R = n_fft / hop; return R * R * hop; }
-size_t stft_gain_lds_bytes(int n_fft, int hop) { return (size_t)(stft_spad((STFT_TF - 1) * hop + n_fft) + 8) * 2 * sizeof(_Float16); }
-
-static void host_window(int n_fft, const float* window, std::vector<float>& win) {
-    win.resize((size_t)n_fft);
-    for (int n = 0; n < n_fft; ++n) win[n] = window ? window[n] : (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)n_fft));
-}
 
 void istft_pack_basis(int n_fft, int hop, const float* window, uint16_t* out) {
     const int n_bins = n_fft / 2 + 1, R = n_fft / hop, KP = denoise_k_pad(n_fft), KS = R * KP / 32, NT = istft_col_tiles(hop);
-    std::vector<float> win;
-    host_window(n_fft, window, win);
+    const std::vector<double> win = host_window(n_fft, window);
     _Float16* o = reinterpret_cast<_Float16*>(out);
     for (int nt = 0; nt < NT; ++nt)
         for (int ks = 0; ks < KS; ++ks)
@@ -53,7 +45,7 @@ void istft_pack_basis(int n_fft, int hop, const float* window, uint16_t* out) {
                         const int m = (R - 1 - q) * hop + n;
                         const double ang = 2.0 * M_PI * (double)(((int64_t)bin * m) % n_fft) / (double)n_fft;
                         const double ck = (bin == 0 || bin == n_fft / 2) ? 1.0 : 2.0;
-                        v = (float)(part ? -ck * sin(ang) : ck * cos(ang)) * win[m];
+                        v = (float)(part ? -ck * sin(ang) : ck * cos(ang)) * (float)win[m];
                     }
                     const _Float16 hi = (_Float16)v;
                     const size_t at = ((((size_t)nt * KS + ks) * 2) * 64 + lane) * 8 + j;
@@ -64,11 +56,8 @@ void istft_pack_basis(int n_fft, int hop, const float* window, uint16_t* out) {
 
 void istft_pack_envelope(int n_fft, int hop, const float* window, float* out) {
     const int R = n_fft / hop;
-    std::vector<double> w2((size_t)n_fft);      // the squares in float64: of the float64 hann for window == null, as the reference squares scipy's
-    for (int n = 0; n < n_fft; ++n) {
-        const double w = window ? (double)window[n] : 0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)n_fft);
-        w2[n] = w * w;
-    }
+    std::vector<double> w2 = host_window(n_fft, window);      // the squares in float64: of the float64 hann for window == null, as the reference squares scipy's
+    for (double& w : w2) w = w * w;
     for (int qa = 0; qa < R; ++qa)
         for (int qb = 0; qb < R; ++qb)
             for (int n = 0; n < hop; ++n) {
@@ -78,63 +67,42 @@ void istft_pack_envelope(int n_fft, int hop, const float* window, float* out) {
             }
 }
 
-// One block = 64 frames of one utterance, 4 waves; wave w multiplies frames 32 (w >> 1) .. + 31 into the re and im columns of bins
-// 16 (w & 1) .. + 15 of each 32-bin basis tile (stft_tile_gemm).  Lane (fr, g) then holds re and im of bin fr of frames 4 g + r.
+// The forward GEMM of ev_features (stft_begin, stft_tile_loop) with the gain epilogue: one block = 64 frames of one utterance, and lane (fr, g)
+// holds re and im of bin fr of the frames 4 g + r (StftLane).
 __global__ __launch_bounds__(256) void stft_gain_kernel(const StftGainParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const StftTile tl = p.tiles[blockIdx.x];
-    const StftSeq sq = p.seqs[tl.seq];
-    const int t0 = tl.t0, n_fft = p.n_fft, hop = p.hop;
-    const int T = p.mag ? min(sq.frames, p.mag_frames) : sq.frames;
-    const int NS = (STFT_TF - 1) * hop + n_fft, NSP = stft_spad(NS) + 8;
-    _Float16* sh = reinterpret_cast<_Float16*>(smem);
-    _Float16* sl = sh + NSP;
-    stft_stage_planes(sh, sl, p.wav, p.wav_is_i16, sq.wav_off, sq.len, (int64_t)t0 * hop - n_fft / 2, NS);
+    char* tail;
+    const StftLane L = stft_begin(p.f, smem, &tail);
     __syncthreads();
-    const int fr = lane & 15, g = lane >> 4, nb = w & 1, mh = w >> 1;
-    const int KS = n_fft / 32;
-    int aoff[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) aoff[a] = (mh * 32 + a * 16 + fr) * hop + 8 * g;
-    const float s = p.mag ? 0.f : p.strengths[tl.seq];
-    const half8* basis = reinterpret_cast<const half8*>(p.basis);
-    for (int nt = 0; nt < p.n_btiles; ++nt) {
-        f4 acc[2][2], accl[2][2];
-        stft_tile_gemm(sh, sl, basis + (size_t)(nt * 2 + nb) * KS * 256 + lane, KS, aoff, acc, accl);
-        const int bin = nt * STFT_TB + nb * 16 + fr;
-        const float sb = (!p.mag && bin < p.n_bins) ? s * p.bias[bin] : 0.f;
+    const int T = p.mag ? min(L.sq.frames, p.mag_frames) : L.sq.frames, n_bins = p.f.n_fft / 2 + 1, k_pad = denoise_k_pad(p.f.n_fft);
+    const float s = p.mag ? 0.f : p.strengths[L.seq];
+    stft_tile_loop(p.f, L, [&](int, int bin, const float (&re)[2][4], const float (&im)[2][4]) {
+        const float sb = (!p.mag && bin < n_bins) ? s * p.bias[bin] : 0.f;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float re = acc[a][0][r] + accl[a][0][r] * (1.0f / 2048.0f), im = acc[a][1][r] + accl[a][1][r] * (1.0f / 2048.0f);
-                const float m = sqrtf(re * re + im * im);
-                const int t = t0 + mh * 32 + a * 16 + g * 4 + r;
+                const float m = stft_mag(re[a][r], im[a][r]);
+                const int t = L.t0 + L.frame(a, r);
                 if (t >= T) continue;
-                const int64_t row = sq.frm_off + t;
+                const int64_t row = L.sq.frm_off + t;
                 if (p.mag) {
-                    if (bin < p.n_bins) p.mag[row * p.n_bins + bin] = m;
+                    if (bin < n_bins) p.mag[row * n_bins + bin] = m;
                     continue;
                 }
-                if (2 * bin >= p.k_pad) continue;
+                if (2 * bin >= k_pad) continue;
                 const bool live = m > 0.f;      // mag == 0 (and a NaN): the cell is zero -- selected, since 0 * NaN is NaN
                 const float gn = live ? fmaxf(m - sb, 0.f) / m : 0.f;
-                const float vr = live ? gn * re : 0.f, vi = live ? gn * im : 0.f;
-                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)row * p.k_pad + 2 * bin, vr, vi);
+                const float vr = live ? gn * re[a][r] : 0.f, vi = live ? gn * im[a][r] : 0.f;
+                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)row * k_pad + 2 * bin, vr, vi);
             }
-    }
+    });
 }
 
 int launch_stft_gain(const StftGainParams& p, hipStream_t s) {
-    if (!denoise_shape_ok(p.n_fft, p.hop) || p.n_tiles <= 0 || p.k_pad != denoise_k_pad(p.n_fft) || p.n_bins != p.n_fft / 2 + 1 ||
-        p.n_btiles != stft_bin_tiles(p.n_fft))
-        return -1;
+    if (!denoise_shape_ok(p.f.n_fft, p.f.hop)) return -1;
     if (p.mag ? p.mag_frames < 1 : (!p.spec_hi || !p.spec_lo || !p.bias || !p.strengths)) return -1;
-    const size_t lds = stft_gain_lds_bytes(p.n_fft, p.hop);
-    if (hipFuncSetAttribute((const void*)stft_gain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(stft_gain_kernel, dim3((unsigned)p.n_tiles), dim3(256), lds, s, p);
-    return 0;
+    return stft_launch(stft_gain_kernel, p, 0, s);
 }
 
 // One block = DN_TJ chunks of one utterance times DN_TN output columns, 4 waves: wave w multiplies chunks 32 (w >> 1) .. + 31 (two 16-row tiles)

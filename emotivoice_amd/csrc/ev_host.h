@@ -134,14 +134,15 @@ struct ScoreState {       // ev_score: the two sides and the host halves of the 
     std::vector<int64_t> sum_dist, path_offs; std::vector<int32_t> K, cnt[7], lens_a, lens_b, nonf_a, nonf_b;
     std::vector<double> sum_c, sum_c2, mcd, rmse, bias, vuv, warp;
 };
-struct DenoiseState {       // ev_denoise.  basis, ibasis, env, bias: its own tables on the device (one allocation each), never ev_features'
-    ev_denoise_config cfg{}; bool ready = false; DevMem basis, ibasis, env, bias;
-    std::vector<int64_t> lens, offs;
+struct StftTables { DevMem basis, ibasis, env; };       // the three tables of an (n_fft, hop, window), one allocation each (denoise_upload_tables)
+struct WavOut { std::vector<int64_t> lens, offs; };       // the host half of a result of packed waveforms
+struct DenoiseState {       // ev_denoise.  tab, bias: its own tables on the device, never ev_features'
+    ev_denoise_config cfg{}; bool ready = false; StftTables tab; DevMem bias; WavOut res;
 };
 struct LimitState { std::vector<float> tp_in, sp_in, tp_out, sp_out, min_gain; std::vector<int64_t> limited, nonf; };       // ev_limit
-struct WatermarkState {       // ev_watermark, ev_watermark_detect.  basis, ibasis, env: ev_denoise's tables at the watermark's shape, built by the first call
-    bool ready = false; DevMem basis, ibasis, env;
-    std::vector<int64_t> lens, offs, frame_offs; std::vector<int32_t> offset, C, n, bit_C, bit_n, frames;
+struct WatermarkState {       // ev_watermark, ev_watermark_detect.  tab: ev_denoise's tables at the watermark's shape, built by the first call
+    bool ready = false; StftTables tab; WavOut res;
+    std::vector<int64_t> frame_offs; std::vector<int32_t> offset, C, n, bit_C, bit_n, frames;
 };
 struct StretchState { std::vector<int64_t> lens_out, offs, frame_offs, nonf; std::vector<int32_t> frames, edges; std::vector<uint64_t> sum_dist; };       // ev_stretch
 

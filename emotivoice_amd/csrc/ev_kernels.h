@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <vector>
+
 namespace ev {
 
 // A/B switches of the kernel launchers (EV_GEMM_TILE, EV_ATTN_X3_NW, ...: tools/bench_*.py) exist only in tuning builds
@@ -243,21 +245,41 @@ void launch_align_mas(const float* log_p, const AlignSeq* seqs, int B, int max_t
 constexpr int STFT_MAX_NFFT = 2048, STFT_MAX_MELS = 128, STFT_MAX_RUN = 24576;
 struct StftSeq { int64_t wav_off, len, frm_off; int32_t frames, reserved; };   // sample offset / length of the utterance, its packed frame offset, T
 struct StftTile { int32_t seq, t0; };                                           // one block: utterance and first frame
-struct StftParams {
+// Layout facts of the windowed-DFT kernels, each stated once for host and device.  A block multiplies STFT_TF frames by basis tiles of STFT_TB bins
+// (64 GEMM columns: re and im of the same bins); the frames are ONE run of samples, kept in LDS as two fp16 planes.
+constexpr int STFT_TF = 64, STFT_TB = 32;
+// LDS index of sample i of the block's run: 8 halfs of padding after every 256 samples, so that the 16 frames of an A fragment (hop apart:
+// 512 bytes at hop 256) start 16 bytes apart modulo the bank width.  A fragment's 8 samples start at a multiple of 8 and never straddle a pad.
+constexpr int stft_spad(int i) { return i + 8 * (i >> 8); }
+constexpr int stft_run_samples(int n_fft, int hop) { return (STFT_TF - 1) * hop + n_fft; }                  // the samples a block stages
+constexpr int stft_plane_halfs(int n_fft, int hop) { return stft_spad(stft_run_samples(n_fft, hop)) + 8; }   // one plane
+constexpr int stft_bin_tiles(int n_fft) { return (n_fft / 2 + 1 + STFT_TB - 1) / STFT_TB; }
+constexpr int stft_mels_per_group(int n_mels) { return (n_mels + 3) / 4; }
+constexpr int denoise_k_pad(int n_fft) { return (2 * (n_fft / 2 + 1) + 31) / 32 * 32; }                      // the width of a scratch row (ev_denoise, below)
+
+// What every forward kernel takes, the first member of its parameters.  n_fft and n_btiles reach the kernels as RUNTIME values, at the watermark's
+// fixed shape too: with constants the compiler unrolls the GEMM's k loop whole and spills.
+struct StftFront {
     const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
     const StftSeq* seqs; const StftTile* tiles; int n_tiles;
-    const void* basis; const float* melT;             // stft_pack_basis / stft_pack_mel, on the device
-    int n_fft, hop, n_mels, nmi, n_bins, n_btiles;    // nmi = stft_mels_per_group, n_bins = n_fft / 2 + 1, n_btiles = stft_bin_tiles
+    const void* basis;                                // stft_pack_basis, on the device
+    int n_fft, hop, n_btiles;                         // n_btiles = stft_bin_tiles
+};
+struct StftParams {
+    StftFront f;
+    const float* melT;                                // stft_pack_mel, on the device
+    int n_mels;
     float mel_clip, energy_floor, energy_mean, energy_std;
     float* mel;                                       // per utterance (n_mels, T) row-major at frm_off * n_mels: log(max(mel_basis @ mag, mel_clip))
     float* energy;                                    // (total_frames,): (sqrt(max(sum_k mag^2, energy_floor)) - energy_mean) / energy_std
     float* mag;                                       // (total_frames, n_bins) or null
 };
 int stft_shape_ok(int n_fft, int hop, int n_mels);
-int stft_bin_tiles(int n_fft);
-int stft_mels_per_group(int n_mels);
 size_t stft_basis_halfs(int n_fft);
 size_t stft_melT_floats(int n_fft);
+// the window of the three packers in float64: window (host, n_fft), or the periodic hann for null.  The bases multiply by its float32 rounding, the
+// envelope squares it as it is.
+std::vector<double> host_window(int n_fft, const float* window);
 void stft_pack_basis(int n_fft, const float* window /* host (n_fft,) or null = periodic hann */, uint16_t* out /* host, stft_basis_halfs */);
 void stft_pack_mel(int n_fft, int n_mels, const float* mel_basis /* host (n_mels, n_bins) */, float* out /* host, stft_melT_floats */);
 int launch_stft_mel(const StftParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
@@ -268,12 +290,9 @@ int launch_stft_mel(const StftParams& p, hipStream_t s);      // 0, or -1 for a 
 // R = n_fft / hop <= DN_MAX_R.
 constexpr int DN_MAX_R = 8, DN_TJ = 64, DN_TN = 128;      // chunks (of hop output samples) and output columns per block of the inverse
 struct StftGainParams {
-    const void* wav; int wav_is_i16;                  // utterances back to back, fp32 or int16 (x / 32768)
-    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
-    const void* basis;                                // stft_pack_basis, on the device
+    StftFront f;
     const float* bias;                                // (n_bins,) device
     const float* strengths;                           // (B,) device
-    int n_fft, hop, n_bins, n_btiles, k_pad;
     uint16_t *spec_hi, *spec_lo;                      // the scratch planes; frame t of an utterance is row frm_off + t
     float* mag; int mag_frames;                       // not null: the other mode -- fp32 magnitudes (row frm_off + t, n_bins columns) of frames t < mag_frames
 };
@@ -287,7 +306,6 @@ struct IstftParams {
     float* out; int16_t* out_i16;                     // packed at out_off; out_i16 may be null
 };
 int denoise_shape_ok(int n_fft, int hop);
-int denoise_k_pad(int n_fft);
 size_t istft_basis_halfs(int n_fft, int hop);
 size_t istft_envelope_floats(int n_fft, int hop);
 // Inverse basis planes.  Row q k_pad + 2 k + part (q = 0 .. R - 1: the frame j - R + 1 + q of chunk j), column n: float32(c_k cos / -c_k sin(2 pi k m / n_fft))
@@ -297,7 +315,6 @@ void istft_pack_basis(int n_fft, int hop, const float* window /* host (n_fft,) o
 // env[(qa R + qb) hop + n]: the float32 window-sum envelope at phase n of a chunk that the frames q = qa .. qb reach, summed in ascending q as the
 // reference's window_sumsquare sums it (float32 accumulator, float64 squares); 0 for qa > qb
 void istft_pack_envelope(int n_fft, int hop, const float* window, float* out /* host, istft_envelope_floats */);
-size_t stft_gain_lds_bytes(int n_fft, int hop);
 int launch_stft_gain(const StftGainParams& p, hipStream_t s);      // 0, or -1 for a shape the kernel does not build
 int launch_istft_ola(const IstftParams& p, hipStream_t s);
 
@@ -307,27 +324,19 @@ int launch_istft_ola(const IstftParams& p, hipStream_t s);
 constexpr int WM_NFFT = 1024, WM_HOP = 256, WM_BAND0 = 20, WM_BAND_BINS = 4, WM_BANDS = 48, WM_TILE = 8, WM_PERIOD = 16, WM_CHIPS = WM_PERIOD * WM_BANDS,
               WM_MAX_BITS = 16, WM_OFFSETS = WM_TILE * WM_PERIOD, WM_PILOT = 255;
 struct WmEmbedParams {
-    const void* wav; int wav_is_i16;
-    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
-    const void* basis;                                // stft_pack_basis(WM_NFFT), on the device
-    int ks, n_btiles;                                 // WM_NFFT / 32 and stft_bin_tiles(WM_NFFT), as RUNTIME values: with constants the compiler unrolls the GEMM's k loop whole and spills
+    StftFront f;                                      // at n_fft = WM_NFFT, hop = WM_HOP
     const int8_t* signs;                              // (B, WM_CHIPS) device: watermark_pattern of the segment's key, payload and length
     const float* gains;                               // (B, 2) device: a and float32(1 / a) of the segment
     uint16_t *spec_hi, *spec_lo;                      // ev_denoise's scratch planes
 };
 struct WmBandParams {
-    const void* wav; int wav_is_i16;
-    const StftSeq* seqs; const StftTile* tiles; int n_tiles;
-    const void* basis;
-    int ks, n_btiles;                                 // as WmEmbedParams has them
+    StftFront f;                                      // as WmEmbedParams has it
     int32_t* q;                                       // (total frames, WM_BANDS) device; frame t of a segment is row frm_off + t
 };
 struct WmFig { int32_t offset, C, n, pad; int32_t bit_C[WM_MAX_BITS], bit_n[WM_MAX_BITS]; };
 // chip i = WM_BANDS u + v: h = dl_mix(key, i), sign (h & 1) ? +1 : -1, role (h >> 1) % (2 nbits); a role < nbits is that payload bit (the sign is
 // flipped where the bit of `payload` is 1), every other role -- and every chip at nbits == 0 -- is WM_PILOT.  roles may be null.
 void watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* signs /* host, WM_CHIPS */, uint8_t* roles /* host, WM_CHIPS, or null */);
-size_t wm_embed_lds_bytes();
-size_t wm_bands_lds_bytes();
 int launch_wm_embed(const WmEmbedParams& p, hipStream_t s);      // 0, or -1 for an empty grid
 int launch_wm_bands(const WmBandParams& p, hipStream_t s);
 // q as wm_bands wrote it; win: device scratch (total frames, WM_BANDS) int32; tabs: device 3 x WM_CHIPS bytes -- the pilot chips (sign, or 0 for a

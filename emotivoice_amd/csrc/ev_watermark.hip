@@ -1,7 +1,7 @@
 // Audio watermark (ev_watermark, ev_watermark_detect): a keyed pattern of small gains on the STFT magnitude, and the detector that finds it again.
 // include/evhip.h states the scheme.
 //
-// wm_embed_kernel is stft_gain_kernel (ev_denoise.hip) with another gain: the same staging, the same tile GEMM (ev_audio_dev.h), the same cell
+// wm_embed_kernel is stft_gain_kernel (ev_denoise.hip) with another gain: the same begin and tile loop (ev_audio_dev.h), the same cell
 // store into the same scratch planes, from which launch_istft_ola rebuilds the waveform unchanged.  The gain of cell (t, k) in band v is a or
 // float32(1 / a) by the sign of chip 48 ((t / 8) mod 16) + v, read from the segment's 768 signs in LDS; 1 outside the bands.
 //
@@ -42,110 +42,77 @@ void watermark_pattern(uint32_t key, int nbits, uint32_t payload, int8_t* signs,
 
 namespace {
 
-constexpr int WM_NS = (STFT_TF - 1) * WM_HOP + WM_NFFT;      // the samples a block stages
-constexpr int WM_NSP = WM_NS + 8 * (WM_NS >> 8) + 8;         // stft_spad(WM_NS) + 8: one plane, in halfs
-constexpr int WM_KS = WM_NFFT / 32, WM_BINS = WM_NFFT / 2 + 1, WM_BTILES = (WM_BINS + STFT_TB - 1) / STFT_TB;
-constexpr int WM_KPAD = (2 * WM_BINS + 31) / 32 * 32;
+constexpr int WM_BINS = WM_NFFT / 2 + 1, WM_KPAD = denoise_k_pad(WM_NFFT);
 constexpr int WM_WAVES = WM_TILE;      // wm_correlate_kernel: one wave per phase of the tile grid
 static_assert(WM_BAND0 % WM_BAND_BINS == 0, "a band is four neighbouring lanes that start at a multiple of four");
-static_assert((4 * WM_NSP) % 16 == 0, "what follows the planes in LDS stays aligned");
+
+// the checks the two forward launchers share: the one shape the kernels' constants describe
+bool wm_front_ok(const StftFront& f) { return f.n_fft == WM_NFFT && f.hop == WM_HOP; }
 
 }  // namespace
-
-size_t wm_embed_lds_bytes() { return (size_t)WM_NSP * 2 * sizeof(_Float16) + WM_CHIPS; }
-size_t wm_bands_lds_bytes() { return (size_t)WM_NSP * 2 * sizeof(_Float16) + (size_t)(STFT_TF * WM_BANDS + 2 * STFT_TF) * sizeof(float); }
 
 // One block = 64 frames of one segment, 4 waves, laid out as stft_gain_kernel: lane (fr, g) of wave (nb, mh) holds re and im of bin
 // 32 nt + 16 nb + fr of frames t0 + 32 mh + 16 a + 4 g + r.  t0 is a multiple of 64, so the tile of those four frames is one value per (a, g).
 __global__ __launch_bounds__(256) void wm_embed_kernel(const WmEmbedParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const StftTile tl = p.tiles[blockIdx.x];
-    const StftSeq sq = p.seqs[tl.seq];
-    const int t0 = tl.t0, T = sq.frames;
-    _Float16* sh = reinterpret_cast<_Float16*>(smem);
-    _Float16* sl = sh + WM_NSP;
-    int8_t* sg = reinterpret_cast<int8_t*>(sl + WM_NSP);
-    for (int i = tid; i < WM_CHIPS; i += 256) sg[i] = p.signs[(size_t)tl.seq * WM_CHIPS + i];
-    stft_stage_planes(sh, sl, p.wav, p.wav_is_i16, sq.wav_off, sq.len, (int64_t)t0 * WM_HOP - WM_NFFT / 2, WM_NS);
+    char* tail;
+    const StftLane L = stft_begin(p.f, smem, &tail);
+    int8_t* sg = reinterpret_cast<int8_t*>(tail);
+    for (int i = threadIdx.x; i < WM_CHIPS; i += 256) sg[i] = p.signs[(size_t)L.seq * WM_CHIPS + i];
     __syncthreads();
-    const int fr = lane & 15, g = lane >> 4, nb = w & 1, mh = w >> 1;
-    int aoff[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) aoff[a] = (mh * 32 + a * 16 + fr) * WM_HOP + 8 * g;
-    const float ga = p.gains[2 * tl.seq], gi = p.gains[2 * tl.seq + 1];
-    const half8* basis = reinterpret_cast<const half8*>(p.basis);
-    for (int nt = 0; nt < p.n_btiles; ++nt) {
-        f4 acc[2][2], accl[2][2];
-        stft_tile_gemm(sh, sl, basis + (size_t)(nt * 2 + nb) * p.ks * 256 + lane, p.ks, aoff, acc, accl);
-        const int bin = nt * STFT_TB + nb * 16 + fr;
+    const int T = L.sq.frames;
+    const float ga = p.gains[2 * L.seq], gi = p.gains[2 * L.seq + 1];
+    stft_tile_loop(p.f, L, [&](int, int bin, const float (&re)[2][4], const float (&im)[2][4]) {
         const bool banded = bin >= WM_BAND0 && bin < WM_BAND0 + WM_BAND_BINS * WM_BANDS;
         const int v = banded ? (bin - WM_BAND0) / WM_BAND_BINS : 0;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-            const int u = ((t0 + mh * 32 + a * 16 + g * 4) / WM_TILE) & (WM_PERIOD - 1);
+            const int u = ((L.t0 + L.frame(a, 0)) / WM_TILE) & (WM_PERIOD - 1);
             const float gw = banded ? (sg[WM_BANDS * u + v] > 0 ? ga : gi) : 1.0f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float re = acc[a][0][r] + accl[a][0][r] * (1.0f / 2048.0f), im = acc[a][1][r] + accl[a][1][r] * (1.0f / 2048.0f);
-                const float m = sqrtf(re * re + im * im);
-                const int t = t0 + mh * 32 + a * 16 + g * 4 + r;
+                const float m = stft_mag(re[a][r], im[a][r]);
+                const int t = L.t0 + L.frame(a, r);
                 if (t >= T || 2 * bin >= WM_KPAD) continue;
                 const bool live = m > 0.f;      // mag == 0 (and a NaN): the cell is zero, selected as ev_denoise selects it (0 * NaN is NaN)
-                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)(sq.frm_off + t) * WM_KPAD + 2 * bin, live ? gw * re : 0.f, live ? gw * im : 0.f);
+                stft_store_cell(p.spec_hi, p.spec_lo, (size_t)(L.sq.frm_off + t) * WM_KPAD + 2 * bin, live ? gw * re[a][r] : 0.f, live ? gw * im[a][r] : 0.f);
             }
         }
-    }
+    });
 }
 
 int launch_wm_embed(const WmEmbedParams& p, hipStream_t s) {
-    if (p.n_tiles <= 0 || p.ks != WM_KS || p.n_btiles != WM_BTILES || !p.signs || !p.gains || !p.spec_hi || !p.spec_lo) return -1;
-    const size_t lds = wm_embed_lds_bytes();
-    if (hipFuncSetAttribute((const void*)wm_embed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(wm_embed_kernel, dim3((unsigned)p.n_tiles), dim3(256), lds, s, p);
-    return 0;
+    if (!wm_front_ok(p.f) || !p.signs || !p.gains || !p.spec_hi || !p.spec_lo) return -1;
+    return stft_launch(wm_embed_kernel, p, WM_CHIPS, s);      // the tail: the segment's signs
 }
 
 __global__ __launch_bounds__(256) void wm_bands_kernel(const WmBandParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const StftTile tl = p.tiles[blockIdx.x];
-    const StftSeq sq = p.seqs[tl.seq];
-    const int t0 = tl.t0, T = sq.frames;
-    _Float16* sh = reinterpret_cast<_Float16*>(smem);
-    _Float16* sl = sh + WM_NSP;
-    float* eb = reinterpret_cast<float*>(sl + WM_NSP);      // [frame of the tile][band]: the unfloored band energies
-    float* fm = eb + STFT_TF * WM_BANDS;                     // [nb][frame of the tile]: the largest mag^2 of each half of the bins
-    stft_stage_planes(sh, sl, p.wav, p.wav_is_i16, sq.wav_off, sq.len, (int64_t)t0 * WM_HOP - WM_NFFT / 2, WM_NS);
+    char* tail;
+    const StftLane L = stft_begin(p.f, smem, &tail);
+    float* eb = reinterpret_cast<float*>(tail);      // [frame of the tile][band]: the unfloored band energies
+    float* fm = eb + STFT_TF * WM_BANDS;             // [nb][frame of the tile]: the largest mag^2 of each half of the bins
     __syncthreads();
-    const int fr = lane & 15, g = lane >> 4, nb = w & 1, mh = w >> 1;
-    int aoff[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) aoff[a] = (mh * 32 + a * 16 + fr) * WM_HOP + 8 * g;
-    const half8* basis = reinterpret_cast<const half8*>(p.basis);
+    const int T = L.sq.frames;
     float mx[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx[a][r] = 0.f;
-    for (int nt = 0; nt < p.n_btiles; ++nt) {
-        f4 acc[2][2], accl[2][2];
-        stft_tile_gemm(sh, sl, basis + (size_t)(nt * 2 + nb) * p.ks * 256 + lane, p.ks, aoff, acc, accl);
-        const int bin = nt * STFT_TB + nb * 16 + fr;
-        const bool owner = (fr & (WM_BAND_BINS - 1)) == 0 && bin >= WM_BAND0 && bin < WM_BAND0 + WM_BAND_BINS * WM_BANDS;
+    stft_tile_loop(p.f, L, [&](int, int bin, const float (&re)[2][4], const float (&im)[2][4]) {
+        const bool owner = (L.fr & (WM_BAND_BINS - 1)) == 0 && bin >= WM_BAND0 && bin < WM_BAND0 + WM_BAND_BINS * WM_BANDS;
         const int v = (bin - WM_BAND0) / WM_BAND_BINS;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float re = acc[a][0][r] + accl[a][0][r] * (1.0f / 2048.0f), im = acc[a][1][r] + accl[a][1][r] * (1.0f / 2048.0f);
-                const float m2 = bin < WM_BINS ? add_rn(mul_rn(re, re), mul_rn(im, im)) : 0.f;
+                const float m2 = bin < WM_BINS ? add_rn(mul_rn(re[a][r], re[a][r]), mul_rn(im[a][r], im[a][r])) : 0.f;
                 mx[a][r] = fmaxf(mx[a][r], m2);
                 float e = add_rn(m2, __shfl_xor(m2, 1, 64));      // (m0 + m1) and (m2 + m3) ...
                 e = add_rn(e, __shfl_xor(e, 2, 64));               // ... and their sum: the same value in all four lanes of the band
-                if (owner) eb[(mh * 32 + a * 16 + g * 4 + r) * WM_BANDS + v] = e;
+                if (owner) eb[L.frame(a, r) * WM_BANDS + v] = e;
             }
-    }
+    });
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -153,24 +120,21 @@ __global__ __launch_bounds__(256) void wm_bands_kernel(const WmBandParams p) {
             float m = mx[a][r];
 #pragma unroll
             for (int o = 1; o <= 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));      // over the 16 lanes (bins) of the frame
-            if (fr == 0) fm[nb * STFT_TF + mh * 32 + a * 16 + g * 4 + r] = m;
+            if (L.fr == 0) fm[L.nb * STFT_TF + L.frame(a, r)] = m;
         }
     __syncthreads();
-    for (int i = tid; i < STFT_TF * WM_BANDS; i += 256) {
-        const int f = i / WM_BANDS, t = t0 + f;
+    for (int i = threadIdx.x; i < STFT_TF * WM_BANDS; i += 256) {
+        const int f = i / WM_BANDS, t = L.t0 + f;
         if (t >= T) continue;
         const float peak = fmaxf(fm[f], fm[STFT_TF + f]);
         const float e = fmaxf(eb[i], mul_rn(peak, 0x1p-24f));
-        p.q[(size_t)(sq.frm_off + t) * WM_BANDS + (i - f * WM_BANDS)] = (int32_t)(__float_as_uint(e) >> 17);
+        p.q[(size_t)(L.sq.frm_off + t) * WM_BANDS + (i - f * WM_BANDS)] = (int32_t)(__float_as_uint(e) >> 17);
     }
 }
 
 int launch_wm_bands(const WmBandParams& p, hipStream_t s) {
-    if (p.n_tiles <= 0 || p.ks != WM_KS || p.n_btiles != WM_BTILES || !p.q) return -1;
-    const size_t lds = wm_bands_lds_bytes();
-    if (hipFuncSetAttribute((const void*)wm_bands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(wm_bands_kernel, dim3((unsigned)p.n_tiles), dim3(256), lds, s, p);
-    return 0;
+    if (!wm_front_ok(p.f) || !p.q) return -1;
+    return stft_launch(wm_bands_kernel, p, (size_t)(STFT_TF * WM_BANDS + 2 * STFT_TF) * sizeof(float), s);      // the tail: eb and fm
 }
 
 namespace {

@@ -542,14 +542,7 @@ class EVAudio:
         return self._call("watermark", B, C.c_void_p(wav_ptr), 1 if wav_is_i16 else 0, _ptr(host_lens(lens, B)), config_ref(config), _ptr(payloads),
                           _ptr(nbits), _ptr(strengths), flags)
 
-    def watermark_to_numpy(self, res: _ffi.ev_watermark_result, int16_only: bool = False, skip_wav: bool = False) -> Dict[str, object]:
-        """Copies of the result's host arrays and one D2H copy of the fp32 output (with ``int16_only`` and a result that has it, of the int16
-        output only; without it both).  ``skip_wav``: the host arrays only."""
-        B = res.batch
-        out: Dict[str, object] = dict(lens_out=host_array(res.lens_out, B, np.int64), offsets=host_array(res.offsets, B + 1, np.int64))
-        if not skip_wav:
-            out.update(self._wav_pair(res, res.total, out["offsets"], int16_only))
-        return out
+    watermark_to_numpy = denoise_to_numpy      # an ev_watermark_result has the fields of an ev_denoise_result
 
     def watermark(self, wavs: Sequence[np.ndarray], config) -> Dict[str, object]:
         """Host signals at 16 kHz -> the marked signals.  wavs: one 1-D array per segment, all int16 or all floating, each of 513 samples or more;

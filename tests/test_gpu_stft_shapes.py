@@ -471,6 +471,35 @@ def test_features_keeps_a_non_finite_sample_inside_its_utterance():
         assert fo.mag_error(both[0][2][ok], o["mag"][ok]) <= 4 * FLOOR
 
 
+# ---------------------------------------------------------------- 5: the two forward kernels share one front end
+@pytest.mark.parametrize("i16", (False, True), ids=("f32", "i16"))
+@pytest.mark.parametrize("n_fft,hop,T", ((128, 128, 3), (384, 48, 70)), ids=("128_128", "384_48"))
+def test_mel_and_gain_kernels_give_the_same_magnitude_bits(n_fft, hop, T, i16):
+    """stft_mel_kernel's mag output and stft_gain_kernel's magnitude mode are the same code up to and including sqrtf(re * re + im * im)
+    (stft_begin, stft_tile_loop): through ev_op_stft_mel and ev_op_stft_gain the two arrays are equal bit for bit.  B = 2, window A; 3 frames, and
+    70 frames (a partial second tile).  The small shape is 128 / 128: at 128 / 8 an utterance has 9 frames or more (n_fft / 2 + 1 = 65 samples)
+    and ev_op_stft_gain answers -2 (R = 16), so no shape with hop 8 reaches both kernels."""
+    from emotivoice_amd.features import mel_filterbank
+    window = window_of("A", n_fft, hop)
+    wavs = _pair(T, n_fft, hop, T)
+    if i16:
+        wavs = [np.round(w * 32767.0).astype(np.int16) for w in wavs]
+    lens = np.array([len(w) for w in wavs], np.int64)
+    TT, nb, n_mels = int((lens // hop + 1).sum()), n_fft // 2 + 1, 20
+    assert int(lens[0]) // hop + 1 == T
+    mb = np.ascontiguousarray(mel_filterbank(16000, n_fft, n_mels, 0.0, 8000.0), np.float32)
+    d_wav = torch.from_numpy(np.concatenate(wavs)).cuda()
+    d_mel, d_en = torch.zeros(TT * n_mels, device="cuda"), torch.zeros(TT, device="cuda")
+    d_mag = torch.full((TT, nb), float("nan"), device="cuda")
+    rc = _lib().ev_op_stft_mel(d_wav.data_ptr(), int(i16), len(wavs), lens.ctypes.data, mb.ctypes.data, _wp(window), n_fft, hop, n_mels, 1e-5, 1e-10,
+                               0.0, 1.0, d_mel.data_ptr(), d_en.data_ptr(), d_mag.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0
+    from_mel = d_mag.cpu().numpy()
+    from_gain = _gain(wavs, None, None, n_fft, hop, window, mag=True)
+    assert from_mel.shape == from_gain.shape and np.all(np.isfinite(from_mel)) and from_mel.max() > 0
+    assert np.array_equal(tgd._bits(from_mel), tgd._bits(from_gain))
+
+
 # ---------------------------------------------------------------- 2: the public configurations with a real window
 def test_public_configs_take_a_real_window_and_forget_it():
     """EVEngine.features with FeatureConfig(window=A) and EVEngine.denoise with DenoiseConfig(window=A) at the default shape against the oracle
