@@ -596,7 +596,8 @@ int make_voc_plan(ev_handle* h, int Rf, VocPlan& vp) {
                 // EV_PREC_MX at C = 32: the whole pair in one persistent kernel (ev_pair_mx.h), x fp32 in, fp32 out
                 else if (mx && cout == 32 && k3711(k) && (k - 1) * (dil + 1) <= 64 && has_wt(c1 + ".wpmx") && has_wt(c2 + ".wpmx") && c.fused_pairs == 0) pk = PairKind::FusedC32Mx;
                 // fused fp16 pair kernels: C = 32 (every k) and C = 64 with k = 3 (the HBM-bound end of the generator)
-                else if (!st.stage_mx) pk = !x3 && ((cout == 32 && k3711(k)) || (cout == 64 && k == 3)) && c.fused_pairs == 0 ? PairKind::Fused : PairKind::Layers;
+                // (C = 64: the kernel's 272-row slab holds conv1's 256 rows + 2 dil <= 16: a wider dilation read past it and gave wrong rows at every tile's end)
+                else if (!st.stage_mx) pk = !x3 && ((cout == 32 && k3711(k)) || (cout == 64 && k == 3 && dil <= PAIR64_MAX_DIL)) && c.fused_pairs == 0 ? PairKind::Fused : PairKind::Layers;
                 else if (!has_mx(c1) || !has_mx(c2)) return fail(h, "MX stage: %s has no fp4 planes", (has_mx(c1) ? c2 : c1).c_str());
                 else pk = PairKind::MxLayers;
             }

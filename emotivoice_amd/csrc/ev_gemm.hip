@@ -2356,7 +2356,7 @@ __global__ __launch_bounds__(512, 1) void resblock_pair_c64_kernel(const ResPair
     constexpr int WPL = K * C * 64, WBYTES = 2 * WPL;                    // per conv: 2 planes of [(tap, co)][64 B]
     constexpr int EPITCH = C * 4 + 16, EBYTES = 16 * EPITCH;             // per-wave transpose scratch: 16 rows x 64 fp32
     constexpr int XCH = (XROWS * 8 + 511) / 512;
-    static_assert(8 * EBYTES <= XBYTES && 256 + 2 * 5 * H2 + 2 * H2 <= XROWS && XCH == 5, "LDS aliasing / slab geometry");
+    static_assert(8 * EBYTES <= XBYTES && 256 + 2 * PAIR64_MAX_DIL * H2 <= XROWS && XCH == 5, "LDS aliasing / slab geometry");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* W1s = smem;
     char* W2s = smem + WBYTES;
@@ -2699,6 +2699,7 @@ int launch_resblock_pair_c32_mx(const ResPairParams& p, hipStream_t s) {
 }
 
 void launch_resblock_pair_c64(const ResPairParams& p, hipStream_t s) {
+    if (p.dil < 1 || p.dil > PAIR64_MAX_DIL) return;          // (the planner and ev_op_resblock_pair_c64 refuse it before)
     const size_t bytes = PAIR64_LDS_BYTES;
     const int n_cu = device_cus();
     const int bmo = 256 - 2;

@@ -123,6 +123,8 @@ int launch_resblock_pair_c32_mx(const ResPairParams& p, hipStream_t s);
 // (epi.res_inv_slope); outputs epi.out32 and / or the plane set epi.mxo_*.  Returns 0, or -1 for an unsupported call.
 int launch_resblock_pair_c64_mx(const ResPairParams& p, hipStream_t s);
 // same pair at C = 64 (stage 2), k = 3 only: both weight sets (48 KB) stationary in LDS, x as two 64-byte K-chunk planes
+// dil <= PAIR64_MAX_DIL: the slab of a tile has 272 rows, conv1's 256 output rows read rows up to 255 + 2 dil (callers check: nothing is launched beyond it)
+constexpr int PAIR64_MAX_DIL = 8;
 void launch_resblock_pair_c64(const ResPairParams& p, hipStream_t s);
 
 // LayerNorm over the channel dim (eps 1e-12, reference modules/encoder.py:112-127), fp32 in.

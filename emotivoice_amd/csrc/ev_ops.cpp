@@ -72,7 +72,7 @@ int ev_op_resblock_pair_c64_mx(const ev_res_pair_desc* d, void* stream) {
 int ev_op_resblock_pair_c64(const ev_res_pair_desc* d, void* stream) {
     ResPairParams p;
     memcpy(&p, d, sizeof p);
-    if (p.k != 3) return -2;
+    if (p.k != 3 || p.dil < 1 || p.dil > PAIR64_MAX_DIL) return -2;
     if (p.epi.post_lrelu && !(p.epi.post_slope >= 0.f && p.epi.post_slope <= 1.f)) return -2;
     launch_resblock_pair_c64(p, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -109,7 +109,7 @@ int ev_op_resblock_pair_c32_mx(const ev_res_pair_desc* d, void* hip_stream);
  * res_inv_slope, out_scale, acc32 (optional), row_valid, out32 and / or the output plane set mxo_* (mxo_logC = 6).  Bit-identical to the two layer-wise
  * ev_op_conv_gemm launches it replaces. */
 int ev_op_resblock_pair_c64_mx(const ev_res_pair_desc* d, void* hip_stream);
-/* the same pair at C = 64 (HiFi-GAN stage 2), k = 3 only (both weight sets stay in LDS) */
+/* the same pair at C = 64 (HiFi-GAN stage 2), k = 3 only (both weight sets stay in LDS), dil <= 8 (the tile's slab); -2 otherwise */
 int ev_op_resblock_pair_c64(const ev_res_pair_desc* d, void* hip_stream);
 
 /* LayerNorm(eps) over channels, optional fused Linear(C,1) head (reference modules/encoder.py:112-127,
